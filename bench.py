@@ -6,21 +6,28 @@ section 8d): initialise the framebuffers (z = 1e6, colour = normal = 0), project
 triangles, rasterize — `AdvancedPixelBufferFiller.render_model` on cleared buffers.
 Default workload: T-Rex.obj at 1024x1024, fov 45 (configs[1], the README benchmark).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (frames/s and
+`ms_per_step`).  `--dump-outputs DIR` writes what the last timed step computed — the planes a caller
+of the timed path receives — as DIR/<name>.npy in float32: the whole frame, or a fixed, seeded sample
+of its pixels where the frame holds more than 64 MB (`outputs` in the line says which).  `--full`
+measures everything else the line used to carry: per-kernel durations, roofline, CPU baseline,
+api_call, and for N > 1 the step without exchange, the one-GPU reference and the weak-scaling point.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU), two modes:
   --mode strips (default)  north_star's layout: ONE frame per step, sharded into row strips, the
                            finished strips exchanged with RCCL: "strong" scaling.  Default workload
                            for N > 1 is T-Rex 8192x8192 (configs[3]).  --exchange picks what is
                            gathered (planes 28 B/pixel, color 12, present 3), --chunks N gathers
-                           sub-strips on a second stream while the next one is rasterized.  The same
-                           JSON line carries the step time without the exchange;
+                           sub-strips on a second stream while the next one is rasterized.  With
+                           --full the same JSON line carries the step time without the exchange;
   --mode frames            every rank renders its own full frames, no collective in the data
                            path: "weak" scaling, value = frames of all ranks per second.
 
-Rank 0 prints ONE JSON line.  `roofline` prices the kernel that rasterizes the timed region's
-frames — `k_frame` (raster pass + the next frame's binning wavefronts in one launch) when the
-swap chain runs with look-ahead, else `k_raster` — against HBM bandwidth with the algorithmic
+Rank 0 prints ONE JSON line.  With --full, `roofline` prices the kernel that rasterizes the timed
+region's frames — `k_frame` (raster pass + the next frame's binning wavefronts in one launch) when
+the swap chain runs with look-ahead, else `k_raster` — against HBM bandwidth with the algorithmic
 bytes of SURVEY.md section 8d (108 B per triangle read once + 28 B per pixel written once); its
 launch duration is measured with HIP events on the frame's own stream in a pass of its own
 (frames one after another on ONE stream, so that a launch's duration is its own), and is never
@@ -308,6 +315,32 @@ def api_calls(tri, col, nrm, H, W, fov, device, budget_s=3.0):
     return out
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, planes, seed=0):
+    """--dump-outputs: `planes` (name -> tensor [H, W] or [H, W, C], what a caller of the timed path
+    receives) as out_dir/<name>.npy in float32.  A frame of more than DUMP_LIMIT_BYTES in all is
+    written as a sample: the same n pixels of every plane ([n] or [n, C], in raster order), chosen
+    by numpy's default_rng(seed) and so the same from run to run.  Returns what the line says of it."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    H, W = next(iter(planes.values())).shape[:2]
+    bytes_per_pixel = sum(4 * p[0, 0].numel() for p in planes.values())
+    n = min(H * W, (DUMP_LIMIT_BYTES - 4096) // bytes_per_pixel)      # (room for the .npy headers)
+    idx = None if n == H * W else np.sort(np.random.default_rng(seed).choice(H * W, n, replace=False))
+    shapes = {}
+    for name, p in planes.items():
+        if idx is not None:
+            p = p.reshape(H * W, *p.shape[2:])[torch.from_numpy(idx).to(p.device)]
+        a = p.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return {"dir": out_dir, "arrays": shapes, "dtype": "float32",
+            "pixels": "all" if idx is None else
+            f"{n} of {H * W}: numpy default_rng({seed}).choice without replacement, in raster order"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -323,9 +356,15 @@ def main():
                     help="A/B knob: tile size of the swap chain's plans (default: the chain's own choice, 32)")
     ap.add_argument("--max-triangles", type=int, default=-1,
                     help="experiment knob: keep only the first N triangles (0 = pure clear)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure per-kernel durations, roofline, CPU baseline, "
+                         "api_call and (N > 1) the strips' other figures; a plain run prints the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; a fixed, "
+                         "seeded sample of pixels where the frame holds more than 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-api-calls", action="store_true",
-                    help="skip the api_call block (the reference's own calls, PCIe included)")
+                    help="--full: skip the api_call block (the reference's own calls, PCIe included)")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="do not overlap the next frame's bin pass with this frame's raster pass")
     ap.add_argument("--no-gather", action="store_true", help="N>1: skip the RCCL all-gather")
@@ -453,178 +492,167 @@ def main():
         "bin lists overflowed inside the timed region"
     if filler._pipe is not None:
         filler._pipe.n = 0
-
-    # ---- per-kernel durations: the same K steps again with HIP events on the frame's stream
-    # around the binning passes and around the raster kernel (single stream, not pipelined, so
-    # each kernel's duration is its own).  Kept out of the timed region
-    # above because the three event records cost ~11 us per frame on a ~35 us frame (measured:
-    # scripts/hostoverhead.py vs this loop); the events loop's own frame time is reported too.
-    elapsed_render_only = None
-    if strips:
-        # the same K steps without the exchange: what the rasterization of the sharded frame costs
-        barrier()
-        t3 = time.perf_counter()
-        for _ in range(args.steps):
-            step(gather=False)
-        barrier()
-        elapsed_render_only = time.perf_counter() - t3
     if sr is not None and sr.empty:
         raise SystemExit("more ranks than rows")
-    step(pipelined=False, gather=False)            # also makes sure the single-stream plan exists
-    barrier()
-    t2 = time.perf_counter()         # the same K frames one at a time on one stream: frame latency
-    for _ in range(args.steps):
-        filler.render_frame(pipelined=False)
-    barrier()
-    elapsed_single = time.perf_counter() - t2
-    filler.timing_begin(args.steps)
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        filler.render_frame(pipelined=False)
-    barrier()
-    elapsed_events = time.perf_counter() - t1
-    n_timed, bin_ms, raster_ms = filler.timing_end()
-    need, cap = filler.bin_usage()
-    assert need <= cap, "bin lists overflowed inside the timing pass"
 
-    # ---- the kernel of the timed region.  With look-ahead the swap chain's frames are ONE launch
-    # each, k_frame (this frame's raster workgroups + the next frame's binning wavefronts), not the
-    # k_setup_wave -> k_raster pair timed above.  Its duration is its own only when launches do not
-    # overlap: a chain of depth 1 (same kernel, same arguments, frames one after another on one
-    # stream), K frames back to back on the wall clock and K frames with HIP events around each launch.
-    lookahead = filler._pipe is not None and filler._pipe.lookahead
-    kframe_events_ms = kframe_b2b_ms = None
-    if lookahead:
-        probe = AdvancedPixelBufferFiller(H, W, fov=fov, device=device, tile=filler._pipe.tile, pipeline=True,
-                                          pipeline_depth=1, lookahead=True, raster_path=rpath,
-                                          row_strip=(y0, y1) if strips else None)
-        probe.render_arrays(tri, col, nrm, clear=True)
-        probe.synchronize()
-        for _ in range(max(3, args.warmup)):
-            probe.render_frame()
-        probe.synchronize()
-        assert probe._pipe.lookahead
-        barrier()
-        t4 = time.perf_counter()
-        for _ in range(args.steps):
-            probe.render_frame()
-        probe.join()
-        barrier()
-        kframe_b2b_ms = (time.perf_counter() - t4) / args.steps * 1e3
-        probe._pipe.timing_begin(args.steps)
-        for _ in range(args.steps):
-            probe.render_frame()
-        n_k, kframe_events_ms = probe._pipe.timing_end()
-        assert n_k == args.steps and not probe._pipe.overflowed(probe)
-        probe_paths = probe.last_raster_paths()
-        del probe
+    # ---- --dump-outputs: what the last timed step computed, as a caller of the timed path receives
+    # it (rank 0): the filler's planes, or the tensors StripRenderer.render_frame returns
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if sr is None:
+            planes = {"z": filler.get_z_tensor(), "color": filler.get_color_tensor(),
+                      "normals": filler.get_normals_tensor()}
+        else:
+            names = {"planes": ("z", "color", "normals"), "color": ("color",), "present": ("image",)}[args.exchange]
+            planes = dict(zip(names, sr._payload(sr.filler)))
+        dumped = dump_outputs(args.dump_outputs, planes)
 
-    # ---- strips: the SAME frame on ONE GPU, in the same run (rank 0; the others wait at the next
-    # collective): the denominator of this line's strong-scaling speedup.  The N = 1 line of bench.py
-    # is the headline workload (T-Rex 1024x1024), not this one, so a speedup computed from the two
-    # lines' values would compare different frames.
-    one_gpu = None
-    if strips and rank == 0:
-        solo = AdvancedPixelBufferFiller(H, W, fov=fov, device=device, tile=args.tile, pipeline=not args.no_pipeline)
-        solo.render_arrays(tri, col, nrm, clear=True)
-        solo.synchronize()
-        for _ in range(max(2, args.warmup)):
-            solo.render_frame()
-        solo.synchronize()
-        t5 = time.perf_counter()
-        for _ in range(args.steps):
-            solo.render_frame()
-        solo.join()
-        torch.cuda.synchronize(device)
-        dt1 = (time.perf_counter() - t5) / args.steps
-        assert not (solo._pipe is not None and solo._pipe.overflowed(solo))
-        one_gpu = {"n_gpus": 1, "value": 1.0 / dt1, "unit": "frames/s", "ms_per_step": dt1 * 1e3,
-                   "what": "the whole frame of this workload on rank 0's GPU alone, same process, same K "
-                           "(no exchange: the frame is complete in its memory)"}
-        del solo
-
-    # ---- strips: and the WEAK-scaling curve of BASELINE.json's metric ("frames/sec, T-Rex.obj 1024x1024 at
-    # 1/2/4/8 GPUs") from the same run: every rank renders K full frames of the headline workload on its own GPU,
-    # no collective (what --mode frames times), between the same barriers; value = world x K / slowest rank.
-    weak = None
-    if strips:
-        w_tri, w_col, w_nrm, (wH, wW), w_fov = scenes.scene("trex1024")
-        wf = AdvancedPixelBufferFiller(wH, wW, fov=w_fov, device=device, pipeline=not args.no_pipeline, raster_path=rpath)
-        wf.render_arrays(w_tri, w_col, w_nrm, clear=True)
-        wf.synchronize()
-        for _ in range(max(3, args.warmup)):
-            wf.render_frame()
-        wf.synchronize()
+    # ---- --full: everything else the line reports, each figure from passes of its own after the timed
+    # region (none of it when the run is plain)
+    elapsed_render_only = weak = one_gpu = None
+    lookahead = False
+    if args.full:
+        # ---- per-kernel durations: the same K steps again with HIP events on the frame's stream
+        # around the binning passes and around the raster kernel (single stream, not pipelined, so
+        # each kernel's duration is its own).  Kept out of the timed region
+        # above because the three event records cost ~11 us per frame on a ~35 us frame (measured:
+        # scripts/hostoverhead.py vs this loop); the events loop's own frame time is reported too.
+        if strips:
+            # the same K steps without the exchange: what the rasterization of the sharded frame costs
+            barrier()
+            t3 = time.perf_counter()
+            for _ in range(args.steps):
+                step(gather=False)
+            barrier()
+            elapsed_render_only = time.perf_counter() - t3
+        step(pipelined=False, gather=False)            # also makes sure the single-stream plan exists
         barrier()
-        t6 = time.perf_counter()
+        t2 = time.perf_counter()         # the same K frames one at a time on one stream: frame latency
         for _ in range(args.steps):
-            wf.render_frame()
-        wf.join()
+            filler.render_frame(pipelined=False)
         barrier()
-        weak_elapsed = time.perf_counter() - t6
-        assert not (wf._pipe is not None and wf._pipe.overflowed(wf))
-        del wf
-        weak = weak_elapsed
+        elapsed_single = time.perf_counter() - t2
+        filler.timing_begin(args.steps)
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            filler.render_frame(pipelined=False)
+        barrier()
+        elapsed_events = time.perf_counter() - t1
+        n_timed, bin_ms, raster_ms = filler.timing_end()
+        need, cap = filler.bin_usage()
+        assert need <= cap, "bin lists overflowed inside the timing pass"
 
-    # CPUs the thread that submits the frames may run on, NOW (after torch / libgomp are loaded): a
-    # runtime that bound it would show here — smallest over the ranks
-    try:
-        affinity = len(os.sched_getaffinity(0))
-    except AttributeError:
-        affinity = os.cpu_count() or 1
-    if world > 1:
-        t = torch.tensor([elapsed, raster_ms, bin_ms, elapsed_render_only or 0.0, kframe_events_ms or 0.0,
-                          kframe_b2b_ms or 0.0, -float(affinity), weak or 0.0], dtype=torch.float64,
-                         device=device if args.backend == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, raster_ms, bin_ms, ero, ke, kb, naff, weak_max = (float(v) for v in t.cpu())
-        if weak is not None:
-            weak = weak_max
-        affinity = int(-naff)
-        if elapsed_render_only is not None:
-            elapsed_render_only = ero
+        # ---- the kernel of the timed region.  With look-ahead the swap chain's frames are ONE launch
+        # each, k_frame (this frame's raster workgroups + the next frame's binning wavefronts), not the
+        # k_setup_wave -> k_raster pair timed above.  Its duration is its own only when launches do not
+        # overlap: a chain of depth 1 (same kernel, same arguments, frames one after another on one
+        # stream), K frames back to back on the wall clock and K frames with HIP events around each launch.
+        lookahead = filler._pipe is not None and filler._pipe.lookahead
+        kframe_events_ms = kframe_b2b_ms = None
         if lookahead:
-            kframe_events_ms, kframe_b2b_ms = ke, kb
+            probe = AdvancedPixelBufferFiller(H, W, fov=fov, device=device, tile=filler._pipe.tile, pipeline=True,
+                                              pipeline_depth=1, lookahead=True, raster_path=rpath,
+                                              row_strip=(y0, y1) if strips else None)
+            probe.render_arrays(tri, col, nrm, clear=True)
+            probe.synchronize()
+            for _ in range(max(3, args.warmup)):
+                probe.render_frame()
+            probe.synchronize()
+            assert probe._pipe.lookahead
+            barrier()
+            t4 = time.perf_counter()
+            for _ in range(args.steps):
+                probe.render_frame()
+            probe.join()
+            barrier()
+            kframe_b2b_ms = (time.perf_counter() - t4) / args.steps * 1e3
+            probe._pipe.timing_begin(args.steps)
+            for _ in range(args.steps):
+                probe.render_frame()
+            n_k, kframe_events_ms = probe._pipe.timing_end()
+            assert n_k == args.steps and not probe._pipe.overflowed(probe)
+            probe_paths = probe.last_raster_paths()
+            del probe
+
+        # ---- strips: the SAME frame on ONE GPU, in the same run (rank 0; the others wait at the next
+        # collective): the denominator of this line's strong-scaling speedup.  The N = 1 line of bench.py
+        # is the headline workload (T-Rex 1024x1024), not this one, so a speedup computed from the two
+        # lines' values would compare different frames.
+        if strips and rank == 0:
+            solo = AdvancedPixelBufferFiller(H, W, fov=fov, device=device, tile=args.tile, pipeline=not args.no_pipeline)
+            solo.render_arrays(tri, col, nrm, clear=True)
+            solo.synchronize()
+            for _ in range(max(2, args.warmup)):
+                solo.render_frame()
+            solo.synchronize()
+            t5 = time.perf_counter()
+            for _ in range(args.steps):
+                solo.render_frame()
+            solo.join()
+            torch.cuda.synchronize(device)
+            dt1 = (time.perf_counter() - t5) / args.steps
+            assert not (solo._pipe is not None and solo._pipe.overflowed(solo))
+            one_gpu = {"n_gpus": 1, "value": 1.0 / dt1, "unit": "frames/s", "ms_per_step": dt1 * 1e3,
+                       "what": "the whole frame of this workload on rank 0's GPU alone, same process, same K "
+                               "(no exchange: the frame is complete in its memory)"}
+            del solo
+
+        # ---- strips: and the WEAK-scaling curve of BASELINE.json's metric ("frames/sec, T-Rex.obj 1024x1024 at
+        # 1/2/4/8 GPUs") from the same run: every rank renders K full frames of the headline workload on its own GPU,
+        # no collective (what --mode frames times), between the same barriers; value = world x K / slowest rank.
+        if strips:
+            w_tri, w_col, w_nrm, (wH, wW), w_fov = scenes.scene("trex1024")
+            wf = AdvancedPixelBufferFiller(wH, wW, fov=w_fov, device=device, pipeline=not args.no_pipeline, raster_path=rpath)
+            wf.render_arrays(w_tri, w_col, w_nrm, clear=True)
+            wf.synchronize()
+            for _ in range(max(3, args.warmup)):
+                wf.render_frame()
+            wf.synchronize()
+            barrier()
+            t6 = time.perf_counter()
+            for _ in range(args.steps):
+                wf.render_frame()
+            wf.join()
+            barrier()
+            weak_elapsed = time.perf_counter() - t6
+            assert not (wf._pipe is not None and wf._pipe.overflowed(wf))
+            del wf
+            weak = weak_elapsed
+
+        # CPUs the thread that submits the frames may run on, NOW (after torch / libgomp are loaded): a
+        # runtime that bound it would show here — smallest over the ranks
+        try:
+            affinity = len(os.sched_getaffinity(0))
+        except AttributeError:
+            affinity = os.cpu_count() or 1
+
+    if world > 1:
+        # the slowest rank's figures
+        t = torch.tensor([elapsed] + ([raster_ms, bin_ms, elapsed_render_only or 0.0, kframe_events_ms or 0.0,
+                                       kframe_b2b_ms or 0.0, -float(affinity), weak or 0.0] if args.full else []),
+                         dtype=torch.float64, device=device if args.backend == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t[0])
+        if args.full:
+            raster_ms, bin_ms, ero, ke, kb, naff, weak_max = (float(v) for v in t[1:].cpu())
+            if weak is not None:
+                weak = weak_max
+            affinity = int(-naff)
+            if elapsed_render_only is not None:
+                elapsed_render_only = ero
+            if lookahead:
+                kframe_events_ms, kframe_b2b_ms = ke, kb
 
     if rank == 0:
         frames_per_step = 1 if (world == 1 or strips) else world
         fps = frames_per_step * args.steps / elapsed
-        rows = filler.y1 - filler.y0                 # rows the measured launches rasterize: this rank's strip
-        abytes = algorithmic_bytes(T, rows, W)       # (ranks are symmetric), its first sub-strip with --chunks
-        # Two views of the raster kernel's launch duration:
-        #   raster_ms      HIP events right around the launch (second pass).  The event records
-        #                  open idle bubbles in which the previous frame's dirty lines drain, so a
-        #                  write-heavy launch looks up to ~10 % shorter than it is back to back;
-        #   raster_b2b_ms  single-stream frame time (no events inside the loop) minus the event-
-        #                  measured bin passes: the launch as it runs in a continuous stream.  This
-        #                  is what rocprofv3's AverageNs of the same command shows (profiles/).
-        # The roofline uses the LONGER of the two, i.e. never the flattering one.
-        single_ms = elapsed_single / args.steps * 1e3
-        raster_b2b_ms = max(single_ms - bin_ms, 0.0)
-        ts = (filler._pipe.tile if lookahead else filler.tile) or (16 if H * W <= 1024 * 1024 else 32)
         # (32-pixel plans have two raster kernels, both exact; which one these launches were: the plans say)
         paths = filler.last_raster_paths()
-        kpath = (probe_paths[-1] if lookahead else paths[0]) if ts == 32 else 0
-        if lookahead:
-            kernel = f"k_frame<{ts},true,{kpath}>"
-            views = {"hip_events_around_each_launch": kframe_events_ms, "frames_back_to_back_on_one_stream": kframe_b2b_ms}
-            prof = load_rocprof_avg_ms(args.workload, profile_key(kernel) + "_one_stream") if rows == H else None
-        else:
-            kernel = f"k_raster<{ts},true,{kpath}>"
-            views = {"hip_events_around_each_launch": raster_ms,
-                     "single_stream_frame_minus_event_measured_bin_passes": raster_b2b_ms}
-            prof = load_rocprof_avg_ms(args.workload, profile_key(kernel)) if rows == H else None
-        if prof is not None:
-            views["committed_rocprofv3_average"] = prof
-        launch_ms = max(v for v in views.values() if v is not None)
-        achieved = abytes / (launch_ms * 1e-3) / 1e9 if launch_ms > 0 else 0.0
         out = {
             "metric": "frames/sec", "value": fps, "unit": "frames/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
-            "ms_per_step_without_exchange": (elapsed_render_only / args.steps * 1e3
-                                             if elapsed_render_only is not None else None),
             "higher_is_better": True,
             # strips: the job is ONE frame however many GPUs share its rows; frames: one per rank
             "scaling": "strong" if strips else "weak",
@@ -658,83 +686,116 @@ def main():
             "mtris_per_sec": T * fps / 1e6,
             "frame_algorithmic_bytes": algorithmic_bytes(T, H, W),
             "whole_frame_gbps": algorithmic_bytes(T, H, W) * fps / 1e9,
-            "kernel_ms": {"binning_passes": bin_ms, "raster": raster_ms,
-                          "raster_back_to_back": raster_b2b_ms, "timed_frames": n_timed,
-                          "how": "HIP events on the frame's stream, second pass of K steps",
-                          "ms_per_step_with_events": elapsed_events / args.steps * 1e3},
-            "ms_per_frame_single_stream": elapsed_single / args.steps * 1e3,
-            "roofline": {"kernel": kernel, "bound": "hbm", "achieved": achieved,
-                         "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
-                         "algorithmic_bytes_per_launch": abytes,
-                         "avg_launch_ms": launch_ms,
-                         "avg_launch_ms_views": views,
-                         "avg_launch_ms_how": "the LONGEST of the views: the kernel the timed region's frames "
-                                              "run, launches one after another on one stream",
-                         # what the overlapped stream of frames achieves with the same launches
-                         "overlapped_frames_gbps": abytes * (args.steps / elapsed) / 1e9,
-                         # PMC bytes of the committed profile are per WHOLE-frame launch: a strip's
-                         # launch was not profiled
-                         "traffic": load_traffic(args.workload, kernel) if rows == H else None},
-            "bin_entries": {"needed": need, "capacity": cap},
-            # the kernels' sources; profiles/*.json figures are quoted only if they were measured on these
-            "csrc_sha16": csrc_sha16(),
-            "submit_thread_affinity_cpus_min_over_ranks": affinity,
         }
-        if strips:
-            # what the exchange moves and what it costs: the line explains its own scaling
-            step_ms = elapsed / args.steps * 1e3
-            bare_ms = elapsed_render_only / args.steps * 1e3
-            gathered = not args.no_gather
-            out["exchange"] = {
-                "kind": args.exchange if gathered else None,
-                "exchange_bytes_received_per_rank": D.exchange_bytes_received(args.exchange, H, W, world, 0) if gathered else 0,
-                "exchange_ms": step_ms - bare_ms,
-                "ms_per_step": step_ms, "ms_per_step_without_exchange": bare_ms,
-                "bytes_received_per_rank_by_choice": {k: D.exchange_bytes_received(k, H, W, world, 0) for k in D.EXCHANGES},
-                "projection_broadcast_bytes_per_rank": 36 * T if args.project == "broadcast" else 0,
-                "expectation": ("DESIGN.md section 5: with exchange = planes every rank receives 28 B/pixel x (N-1)/N "
-                                "of the frame over xGMI, several times the time ONE GPU needs to render the whole "
-                                "frame — a speed-up below 1x is the predicted outcome of north_star's layout; "
-                                "'present' moves 9x less"),
-            }
-            out["config"]["multi_gpu"] += ("; predicted by DESIGN.md section 5 to be SLOWER than one GPU with exchange = "
-                                           "planes (the exchange, not the rasterization, bounds the sharded frame)"
-                                           if args.exchange == "planes" and gathered else "")
-        if weak is not None:
-            out["weak_scaling_frames"] = {
-                "metric": "frames/sec", "workload": "trex1024", "n_gpus": world, "scaling": "weak",
-                "value": world * args.steps / weak, "ms_per_step": weak / args.steps * 1e3, "steps": args.steps,
-                "what": "measured in this same run after the strips: every rank K full frames of BASELINE.json's "
-                        "headline workload on its own GPU, no collective (bench.py --mode frames), barrier to barrier, "
-                        "slowest rank; divide by the N = 1 line's value for the weak-scaling efficiency"}
-        if one_gpu is not None:
-            one_gpu["speedup_of_this_line"] = fps / one_gpu["value"]
-            out["strong_scaling_reference"] = one_gpu
         if args.workload == "synth10m":
             out["config"]["resident_model"] = (
                 "sorted ONCE at upload into tile-coherent order (Morton code of the 4-pixel cell of each "
                 "triangle's projected centroid: key kernel + device radix sort + three gathers, about 1 GB of "
                 "traffic, ~2 ms, outside the timed region); depth ties and the winner plane keep the caller's indices")
-        want_api = not args.no_api_calls and world == 1 and H * W <= 4096 * 4096 and T <= 1_000_000
-        child = None
-        if not args.no_cpu_baseline:
-            # (rank 0, beside every N: the other ranks wait at the closing barrier meanwhile)
-            child = cpu_baseline(args.workload, args.synth_triangles, args.max_triangles, api=want_api)
-            cb = out["cpu_baseline"] = child["cpu_baseline"]
-            # north_star's denominator is the 16-thread column; the best column is beside it
-            out["speedup_vs_cpu_baseline"] = fps / cb["value"]
-            out["speedup_vs_best_cpu_column"] = fps / cb["best"]["frames_per_s"]
-            lone = 1e3 / (elapsed_single / args.steps * 1e3)       # frames/s of frames one at a time on one stream
-            out["speedup_lone_frame"] = {"frames_per_s": lone, "vs_16_threads": lone / cb["value"],
-                                         "vs_best_cpu_column": lone / cb["best"]["frames_per_s"],
-                                         "what": "ms_per_frame_single_stream (no frames in flight together) "
-                                                 "against the CPU columns"}
-        if want_api:
-            out["api_call"] = api_calls(tri, col, nrm, H, W, fov, device)
-            if child is not None and "api_cpu_oracle" in child:
-                out["api_call"]["cpu_oracle"] = child["api_cpu_oracle"]
+        if strips and args.exchange == "planes" and not args.no_gather:
+            out["config"]["multi_gpu"] += ("; predicted by DESIGN.md section 5 to be SLOWER than one GPU with exchange = "
+                                           "planes (the exchange, not the rasterization, bounds the sharded frame)")
+        if dumped is not None:
+            out["outputs"] = dumped
+        if args.full:
+            rows = filler.y1 - filler.y0                 # rows the measured launches rasterize: this rank's strip
+            abytes = algorithmic_bytes(T, rows, W)       # (ranks are symmetric), its first sub-strip with --chunks
+            # Two views of the raster kernel's launch duration:
+            #   raster_ms      HIP events right around the launch (second pass).  The event records
+            #                  open idle bubbles in which the previous frame's dirty lines drain, so a
+            #                  write-heavy launch looks up to ~10 % shorter than it is back to back;
+            #   raster_b2b_ms  single-stream frame time (no events inside the loop) minus the event-
+            #                  measured bin passes: the launch as it runs in a continuous stream.  This
+            #                  is what rocprofv3's AverageNs of the same command shows (profiles/).
+            # The roofline uses the LONGER of the two, i.e. never the flattering one.
+            single_ms = elapsed_single / args.steps * 1e3
+            raster_b2b_ms = max(single_ms - bin_ms, 0.0)
+            ts = (filler._pipe.tile if lookahead else filler.tile) or (16 if H * W <= 1024 * 1024 else 32)
+            kpath = (probe_paths[-1] if lookahead else paths[0]) if ts == 32 else 0
+            if lookahead:
+                kernel = f"k_frame<{ts},true,{kpath}>"
+                views = {"hip_events_around_each_launch": kframe_events_ms, "frames_back_to_back_on_one_stream": kframe_b2b_ms}
+                prof = load_rocprof_avg_ms(args.workload, profile_key(kernel) + "_one_stream") if rows == H else None
+            else:
+                kernel = f"k_raster<{ts},true,{kpath}>"
+                views = {"hip_events_around_each_launch": raster_ms,
+                         "single_stream_frame_minus_event_measured_bin_passes": raster_b2b_ms}
+                prof = load_rocprof_avg_ms(args.workload, profile_key(kernel)) if rows == H else None
+            if prof is not None:
+                views["committed_rocprofv3_average"] = prof
+            launch_ms = max(v for v in views.values() if v is not None)
+            achieved = abytes / (launch_ms * 1e-3) / 1e9 if launch_ms > 0 else 0.0
+            out.update({
+                "ms_per_step_without_exchange": (elapsed_render_only / args.steps * 1e3
+                                                 if elapsed_render_only is not None else None),
+                "kernel_ms": {"binning_passes": bin_ms, "raster": raster_ms,
+                              "raster_back_to_back": raster_b2b_ms, "timed_frames": n_timed,
+                              "how": "HIP events on the frame's stream, second pass of K steps",
+                              "ms_per_step_with_events": elapsed_events / args.steps * 1e3},
+                "ms_per_frame_single_stream": elapsed_single / args.steps * 1e3,
+                "roofline": {"kernel": kernel, "bound": "hbm", "achieved": achieved,
+                             "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
+                             "algorithmic_bytes_per_launch": abytes,
+                             "avg_launch_ms": launch_ms,
+                             "avg_launch_ms_views": views,
+                             "avg_launch_ms_how": "the LONGEST of the views: the kernel the timed region's frames "
+                                                  "run, launches one after another on one stream",
+                             # what the overlapped stream of frames achieves with the same launches
+                             "overlapped_frames_gbps": abytes * (args.steps / elapsed) / 1e9,
+                             # PMC bytes of the committed profile are per WHOLE-frame launch: a strip's
+                             # launch was not profiled
+                             "traffic": load_traffic(args.workload, kernel) if rows == H else None},
+                "bin_entries": {"needed": need, "capacity": cap},
+                # the kernels' sources; profiles/*.json figures are quoted only if they were measured on these
+                "csrc_sha16": csrc_sha16(),
+                "submit_thread_affinity_cpus_min_over_ranks": affinity,
+            })
+            if strips:
+                # what the exchange moves and what it costs: the line explains its own scaling
+                step_ms = elapsed / args.steps * 1e3
+                bare_ms = elapsed_render_only / args.steps * 1e3
+                gathered = not args.no_gather
+                out["exchange"] = {
+                    "kind": args.exchange if gathered else None,
+                    "exchange_bytes_received_per_rank": D.exchange_bytes_received(args.exchange, H, W, world, 0) if gathered else 0,
+                    "exchange_ms": step_ms - bare_ms,
+                    "ms_per_step": step_ms, "ms_per_step_without_exchange": bare_ms,
+                    "bytes_received_per_rank_by_choice": {k: D.exchange_bytes_received(k, H, W, world, 0) for k in D.EXCHANGES},
+                    "projection_broadcast_bytes_per_rank": 36 * T if args.project == "broadcast" else 0,
+                    "expectation": ("DESIGN.md section 5: with exchange = planes every rank receives 28 B/pixel x (N-1)/N "
+                                    "of the frame over xGMI, several times the time ONE GPU needs to render the whole "
+                                    "frame — a speed-up below 1x is the predicted outcome of north_star's layout; "
+                                    "'present' moves 9x less"),
+                }
+            if weak is not None:
+                out["weak_scaling_frames"] = {
+                    "metric": "frames/sec", "workload": "trex1024", "n_gpus": world, "scaling": "weak",
+                    "value": world * args.steps / weak, "ms_per_step": weak / args.steps * 1e3, "steps": args.steps,
+                    "what": "measured in this same run after the strips: every rank K full frames of BASELINE.json's "
+                            "headline workload on its own GPU, no collective (bench.py --mode frames), barrier to barrier, "
+                            "slowest rank; divide by the N = 1 line's value for the weak-scaling efficiency"}
+            if one_gpu is not None:
+                one_gpu["speedup_of_this_line"] = fps / one_gpu["value"]
+                out["strong_scaling_reference"] = one_gpu
+            want_api = not args.no_api_calls and world == 1 and H * W <= 4096 * 4096 and T <= 1_000_000
+            child = None
+            if not args.no_cpu_baseline:
+                # (rank 0, beside every N: the other ranks wait at the closing barrier meanwhile)
+                child = cpu_baseline(args.workload, args.synth_triangles, args.max_triangles, api=want_api)
+                cb = out["cpu_baseline"] = child["cpu_baseline"]
+                # north_star's denominator is the 16-thread column; the best column is beside it
+                out["speedup_vs_cpu_baseline"] = fps / cb["value"]
+                out["speedup_vs_best_cpu_column"] = fps / cb["best"]["frames_per_s"]
+                lone = 1e3 / (elapsed_single / args.steps * 1e3)       # frames/s of frames one at a time on one stream
+                out["speedup_lone_frame"] = {"frames_per_s": lone, "vs_16_threads": lone / cb["value"],
+                                             "vs_best_cpu_column": lone / cb["best"]["frames_per_s"],
+                                             "what": "ms_per_frame_single_stream (no frames in flight together) "
+                                                     "against the CPU columns"}
+            if want_api:
+                out["api_call"] = api_calls(tri, col, nrm, H, W, fov, device)
+                if child is not None and "api_cpu_oracle" in child:
+                    out["api_call"]["cpu_oracle"] = child["api_cpu_oracle"]
         print(json.dumps(out), flush=True)
-
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

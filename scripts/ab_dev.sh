@@ -10,11 +10,11 @@ print('%-14s %-10s fps=%9.1f ms=%7.4f single_ms=%7.4f bin_ms=%7.4f raster_ms=%7.
 for c in ${CONFIGS:-base:0:5}; do
   IFS=: read name dbg cell <<< "$c"
   export ABNAME=$name CRENDER_DEBUG=$dbg CRENDER_ORDER_CELL_SHIFT=$cell
-  for rep in 1 2; do python bench.py --no-cpu-baseline --no-api-calls --workload ${WORKLOAD:-synth10m} --steps ${STEPS:-20} --warmup ${WARMUP:-5} ${EXTRA:-} 2>/dev/null | line; done
+  for rep in 1 2; do python bench.py --full --no-cpu-baseline --no-api-calls --workload ${WORKLOAD:-synth10m} --steps ${STEPS:-20} --warmup ${WARMUP:-5} ${EXTRA:-} 2>/dev/null | line; done
   if [ -n "${PMC:-}" ]; then
     for cn in FETCH_SIZE; do
       out=/tmp/pmcd_${name}_$cn; rm -rf $out
-      (cd /tmp && TMPDIR=/tmp rocprofv3 --pmc $cn --output-format csv -d $out -- python3 $OLDPWD/bench.py --workload ${WORKLOAD:-synth10m} --steps 10 --warmup 2 --no-cpu-baseline --no-api-calls --no-pipeline > $out.log 2>&1)
+      (cd /tmp && TMPDIR=/tmp rocprofv3 --pmc $cn --output-format csv -d $out -- python3 $OLDPWD/bench.py --full --workload ${WORKLOAD:-synth10m} --steps 10 --warmup 2 --no-cpu-baseline --no-api-calls --no-pipeline > $out.log 2>&1)
       python - $out $name $cn <<'PY'
 import csv, glob, sys
 d, g, c = sys.argv[1:4]

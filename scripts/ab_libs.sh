@@ -12,7 +12,7 @@ for w in ${WORKLOADS:-synth10m}; do
     for v in ${LIBS:-base cur}; do
       export ABNAME=$v
       if [ $v = cur ]; then unset CRENDER_LIB; else export CRENDER_LIB=$(pwd)/scripts/ab/$v.so; fi
-      for rep in 1 2; do python bench.py --no-cpu-baseline --no-api-calls --workload $w --tile $t --steps ${STEPS:-20} --warmup ${WARMUP:-5} 2>/dev/null | line; done
+      for rep in 1 2; do python bench.py --full --no-cpu-baseline --no-api-calls --workload $w --tile $t --steps ${STEPS:-20} --warmup ${WARMUP:-5} 2>/dev/null | line; done
     done
   done
 done

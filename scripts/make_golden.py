@@ -95,7 +95,67 @@ def synth10m_record():
     return rec
 
 
+def bar_cases(n=4000, seed=7):
+    """Barycentric test cases: random triangles and pixels, with zero-area triangles (division by zero:
+    inf / NaN), vertices on pixel centres (exact zeros) and vertices 1e-30 apart among them."""
+    rng = np.random.default_rng(seed)
+    tris = np.empty((n, 9), np.float32)
+    xy = np.empty((n, 2), np.int32)
+    for i in range(n):
+        tri = rng.uniform(-50, 300, 9).astype(np.float32)
+        if i % 7 == 0:
+            tri[6:8] = tri[0:2]
+        if i % 11 == 0:
+            tri = np.round(tri)
+        if i % 13 == 0:
+            tri[3:5] = tri[0:2] + np.float32(1e-30)
+        tris[i] = tri
+        xy[i] = rng.integers(-5, 300, 2)
+    return tris, xy
+
+
+def reference_checks():
+    """What two CPU tests pin the oracle to, recorded from the reference's own code so that the tests
+    need no reference checkout (tests/test_oracle_cpu.py):
+      ref_bar.npz        cases and results of the barycentric function of math_utils.pyx as
+                         oracle/build_ref.sh builds it (oracle/_ref/math_utils.so);
+      ref_backface.json  the type of the division in the back-face test of
+                         advanced_pixel_buffer_filler.pyx:202, read off the C that Cython generates for
+                         that line (code generation only: nothing of it is compiled, run or stored)."""
+    import re
+    import subprocess
+    import tempfile
+    from oracle import ref_bar
+    assert ref_bar.available(), "oracle/_ref/math_utils.so is not built (oracle/build_ref.sh)"
+    tris, xy = bar_cases()
+    bar = np.stack([ref_bar.bar(t, x, y) for t, (x, y) in zip(tris, xy)])
+    np.savez_compressed(os.path.join(OUT, "ref_bar.npz"), tri=tris, xy=xy, bar=bar)
+    pyx = os.path.join(REF, "crender", "cy", "pixel_buffer_filler", "advanced_pixel_buffer_filler.pyx")
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "filler.c")
+        subprocess.check_call([shutil.which("cython"), "-3", "-X", "legacy_implicit_noexcept=True", pyx, "-o", out],
+                              stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        with open(out) as fh:
+            lines = fh.read().splitlines()
+    # the C statement(s) generated under the source-line marker of .pyx:202
+    marks = [i for i, l in enumerate(lines) if 'advanced_pixel_buffer_filler.pyx":202' in l]
+    assert marks, "no code generated for .pyx:202"
+    stmt = [l for i in marks for l in lines[i:i + 80] if ">= 0.0)" in l and "__pyx_v_normals.data" in l]
+    assert stmt, "the cull test of .pyx:202 was not found in the generated C"
+    double = all(re.search(r"\)\s*/\s*3\.0\)\s*>=\s*0\.0\)", l) and "(float)3" not in l and "3.0f" not in l
+                 for l in stmt)
+    assert double or all("(float)3" in l or "3.0f" in l for l in stmt), ("division of unknown type", stmt)
+    with open(os.path.join(OUT, "ref_backface.json"), "w") as fh:
+        json.dump({"_comment": "advanced_pixel_buffer_filler.pyx:202 culls when the sum of the three normals' z "
+                               "divided by 3 is >= 0; 'division' is the type Cython divides in there",
+                   "line": 202, "division": "double" if double else "float"}, fh, indent=1, sort_keys=True)
+    print("wrote ref_bar.npz and ref_backface.json, division:", "double" if double else "float")
+
+
 def main():
+    if "--only-reference-checks" in sys.argv:   # refresh ref_bar.npz / ref_backface.json alone
+        reference_checks()
+        return
     if "--only-synth10m" in sys.argv:       # add / refresh that one entry (needs no reference checkout)
         path = os.path.join(OUT, "golden.json")
         with open(path) as fh:
@@ -168,6 +228,7 @@ def main():
     # Model -> filler -> GuroIllumination -> flip -> uint8 (reference: run.py:20-26)
     shutil.copyfile(os.path.join(REF, "output", "T-Rex.png"),
                     os.path.join(OUT, "reference_output_T-Rex.png"))
+    reference_checks()
     print("wrote", OUT)
 
 

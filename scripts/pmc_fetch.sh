@@ -8,7 +8,7 @@ for g in ${DBGS:-0}; do
   export CRENDER_DEBUG=$g
   for c in FETCH_SIZE WRITE_SIZE; do
     out=/tmp/pmcf_${g}_$c; rm -rf $out
-    (cd /tmp && TMPDIR=/tmp rocprofv3 --pmc $c --output-format csv -d $out -- python3 $REPO/bench.py --workload $W --steps 10 --warmup 2 --no-cpu-baseline --no-api-calls --no-pipeline > $out.log 2>&1)
+    (cd /tmp && TMPDIR=/tmp rocprofv3 --pmc $c --output-format csv -d $out -- python3 $REPO/bench.py --full --workload $W --steps 10 --warmup 2 --no-cpu-baseline --no-api-calls --no-pipeline > $out.log 2>&1)
     python - $out $g $c <<'PY'
 import csv, glob, sys
 d, g, c = sys.argv[1:4]

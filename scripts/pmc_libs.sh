@@ -7,7 +7,7 @@ for v in ${LIBS:-cur}; do
   if [ $v = cur ]; then unset CRENDER_LIB; else export CRENDER_LIB=$REPO/scripts/ab/$v.so; fi
   for c in ${COUNTERS:-FETCH_SIZE WRITE_SIZE}; do
     out=/tmp/pmcl_${v}_$c; rm -rf $out
-    (cd /tmp && TMPDIR=/tmp rocprofv3 --pmc $c --output-format csv -d $out -- python3 $REPO/bench.py --workload $W --steps 10 --warmup 2 --no-cpu-baseline --no-api-calls --no-pipeline "$@" > $out.log 2>&1)
+    (cd /tmp && TMPDIR=/tmp rocprofv3 --pmc $c --output-format csv -d $out -- python3 $REPO/bench.py --full --workload $W --steps 10 --warmup 2 --no-cpu-baseline --no-api-calls --no-pipeline "$@" > $out.log 2>&1)
     python - $out $v $c <<'PY'
 import csv, glob, sys
 d, g, c = sys.argv[1:4]

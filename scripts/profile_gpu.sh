@@ -19,7 +19,7 @@ OUT=$REPO/gpurun_out/prof_$WL${SUFFIX:-}; [ $MODE = pipelined ] && OUT=$REPO/gpu
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 NOPIPE=--no-pipeline; [ $MODE = pipelined ] && NOPIPE=
-ARGS="$REPO/bench.py --workload $WL --steps $STEPS --warmup 3 --no-cpu-baseline --no-api-calls $NOPIPE $*"
+ARGS="$REPO/bench.py --full --workload $WL --steps $STEPS --warmup 3 --no-cpu-baseline --no-api-calls $NOPIPE $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 $ARGS > "$OUT/trace.log" 2>&1
 echo "trace rc=$?"
 [ -n "${TRACE_ONLY:-}" ] && exit 0

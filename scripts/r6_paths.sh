@@ -20,6 +20,6 @@ for spec in ${BENCH:-bunny4096:0,1,auto trex8192:0,1,auto synth10m:0,auto trex10
   s=200; [ $w = bunny4096 ] && s=50; [ $w = trex8192 ] && s=30; [ $w = synth10m ] && s=30
   for rep in 1 2; do for p in $ps; do
     export ABP=$p
-    timeout -k 10 300 python bench.py --no-cpu-baseline --no-api-calls --workload $w --steps $s --warmup 10 --raster-path $p 2>$OUT/bench_err.log | line | tee -a $OUT/ab_paths.txt
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-api-calls --workload $w --steps $s --warmup 10 --raster-path $p 2>$OUT/bench_err.log | line | tee -a $OUT/ab_paths.txt
   done; done
 done

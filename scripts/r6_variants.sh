@@ -15,7 +15,7 @@ for w in ${WORKLOADS:-bunny4096}; do
     v=${arm%%:*}; p=${arm#*:}
     export ABNAME=$v ABP=$p
     if [ $v = cur ]; then unset CRENDER_LIB; else export CRENDER_LIB=$REPO/scripts/ab/$v.so; fi
-    timeout -k 10 300 python bench.py --no-cpu-baseline --no-api-calls --workload $w --steps $s --warmup ${WARMUP:-10} --raster-path $p 2>$OUT/bench_err.log | line | tee -a $OUT/ab_variants.txt
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-api-calls --workload $w --steps $s --warmup ${WARMUP:-10} --raster-path $p 2>$OUT/bench_err.log | line | tee -a $OUT/ab_variants.txt
   done; done
 done
 unset CRENDER_LIB

@@ -44,11 +44,11 @@ python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "
 timeout -k 10 1100 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -2 $OUT/pytest_gpu.log
 fi
 if [ $PART = a ] || [ $PART = c ] || [ $PART = all ]; then      # (c: the bench lines alone)
-python bench.py > $OUT/bench_trex1024.json 2> $OUT/bench_trex1024.err; echo "bench rc=$?"
-python bench.py --steps 20 --warmup 5 > $OUT/bench_trex1024_k20.json 2>/dev/null       # the driver's command line
-python bench.py --workload bunny4096 --steps 50 --warmup 5 > $OUT/bench_bunny4096.json 2>/dev/null
-python bench.py --workload trex8192 --steps 30 --warmup 3 > $OUT/bench_trex8192.json 2>/dev/null
-python bench.py --workload synth10m --steps 40 --warmup 10 > $OUT/bench_synth10m.json 2>/dev/null     # (the first ~20 frames after the 1.5 GB upload run up to 15 % slower: K = 10, W = 2 gave 1 062-1 104 frames/s)
-python bench.py --workload cube256 --steps 200 > $OUT/bench_cube256.json 2>/dev/null
+python bench.py --full > $OUT/bench_trex1024.json 2> $OUT/bench_trex1024.err; echo "bench rc=$?"
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_trex1024_k20.json 2>/dev/null       # the driver's K and W
+python bench.py --full --workload bunny4096 --steps 50 --warmup 5 > $OUT/bench_bunny4096.json 2>/dev/null
+python bench.py --full --workload trex8192 --steps 30 --warmup 3 > $OUT/bench_trex8192.json 2>/dev/null
+python bench.py --full --workload synth10m --steps 40 --warmup 10 > $OUT/bench_synth10m.json 2>/dev/null     # (the first ~20 frames after the 1.5 GB upload run up to 15 % slower: K = 10, W = 2 gave 1 062-1 104 frames/s)
+python bench.py --full --workload cube256 --steps 200 > $OUT/bench_cube256.json 2>/dev/null
 fi
 ls $OUT

@@ -2559,8 +2559,8 @@ def test_bench_launch_contract_two_ranks_strips():
     """The N > 1 contract of bench.py end to end, so that the first multi-GPU scaling run measures
     RCCL and not argument parsing: two ranks on the one GPU (gloo carries the timings; --no-gather
     because gloo cannot all-gather device strips in place), north_star's layout (row strips of
-    T-Rex 8192^2, strong scaling), the CPU baseline beside it."""
-    d = _bench_line(["--backend", "gloo", "--no-gather", "--steps", "3", "--warmup", "1"], 2)
+    T-Rex 8192^2, strong scaling), the CPU baseline beside it (--full)."""
+    d = _bench_line(["--full", "--backend", "gloo", "--no-gather", "--steps", "3", "--warmup", "1"], 2)
     assert d["n_gpus"] == 2 and d["steps"] == 3 and d["warmup"] == 1
     assert d["scaling"] == "strong" and d["config"]["workload"] == "trex8192"
     assert d["metric"].startswith("frames") and d["unit"] == "frames/s" and d["higher_is_better"] is True
@@ -2588,13 +2588,43 @@ def test_bench_launch_contract_two_ranks_strips():
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_bench_launch_contract_two_ranks_frames():
-    """--mode frames: every rank its own full frames, no collective in the data path (weak scaling)."""
-    d = _bench_line(["--backend", "gloo", "--mode", "frames", "--workload", "trex1024", "--steps", "5",
+    """--mode frames: every rank its own full frames, no collective in the data path (weak scaling); --full."""
+    d = _bench_line(["--full", "--backend", "gloo", "--mode", "frames", "--workload", "trex1024", "--steps", "5",
                      "--warmup", "2", "--no-api-calls"], 2)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["workload"] == "trex1024"
     assert d["value"] > 0 and "cpu_baseline" in d and "roofline" in d
     assert d["submit_thread_affinity_cpus_min_over_ranks"] > 2, "a rank's submitting thread was bound to a core"
     assert "exchange" not in d and d["speedup_vs_best_cpu_column"] <= d["speedup_vs_cpu_baseline"] * 1.0000001
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_bench_plain_line_and_dumped_outputs(oracle, tmp_path):
+    """The driver's command, `bench.py --gpus 1 --steps K --warmup W`, prints the headline alone (no figure
+    that takes passes of its own), and with --dump-outputs writes what the last timed step computed: the
+    whole T-Rex 1024^2 frame in float32, bit for bit the oracle's."""
+    import json, subprocess, sys
+    from cython3dmodelrenderer_amd import scenes
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+           "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=540)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "frames/sec" and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == 7 and d["warmup"] == 2 and d["config"]["workload"] == "trex1024"
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-6
+    for key in ("kernel_ms", "ms_per_frame_single_stream", "roofline", "cpu_baseline", "api_call"):
+        assert key not in d, key
+    assert d["outputs"]["pixels"] == "all" and d["outputs"]["arrays"]["color"] == [1024, 1024, 3]
+    ref = oracle.OracleFiller(1024, 1024, fov=45)
+    ref.render_arrays(*scenes.load_fixture("trex_inputs.npz"))
+    for name, want in (("z", ref.z_buffer), ("color", ref.color_buffer), ("normals", ref.normals_buffer)):
+        got = np.load(tmp_path / f"{name}.npy")
+        assert got.dtype == np.float32
+        assert_bit_equal(got, want, name)
 
 
 @pytest.mark.gpu

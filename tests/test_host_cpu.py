@@ -421,6 +421,39 @@ def test_profile_figures_are_quoted_only_for_the_sources_they_were_measured_on(t
     assert _build.source_sha16() != sha
 
 
+def test_bench_dump_outputs_whole_frames_and_a_fixed_sample_of_large_ones(tmp_path):
+    """bench.py --dump-outputs writes float32 .npy files of at most 64 MB in all: a small frame whole, a
+    larger one as the same seeded sample of pixels in every plane, identical from run to run."""
+    import torch
+    import bench
+    z = torch.arange(12, dtype=torch.float32).reshape(3, 4)
+    img = torch.full((3, 4, 3), 7, dtype=torch.uint8)
+    d = bench.dump_outputs(str(tmp_path / "small"), {"z": z, "image": img})
+    assert d["pixels"] == "all" and d["arrays"] == {"z": [3, 4], "image": [3, 4, 3]}
+    got = np.load(tmp_path / "small" / "z.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, z.numpy())
+    got = np.load(tmp_path / "small" / "image.npy")
+    assert got.dtype == np.float32 and (got == 7).all() and got.shape == (3, 4, 3)
+    # 2400 x 1200 pixels x 28 B (z, colour, normal) = 80.6 MB: sampled; the z plane holds each pixel's index
+    H, W = 2400, 1200
+    z = torch.arange(H * W, dtype=torch.float32).reshape(H, W)
+    color = z[..., None].expand(H, W, 3).contiguous()
+    planes = {"z": z, "color": color, "normals": -color}
+    runs = [tmp_path / "a", tmp_path / "b"]
+    for r in runs:
+        d = bench.dump_outputs(str(r), planes)
+    assert d["pixels"] != "all"
+    assert sum(f.stat().st_size for f in runs[0].iterdir()) <= bench.DUMP_LIMIT_BYTES <= 64_000_000
+    idx = np.load(runs[0] / "z.npy")
+    n = idx.shape[0]
+    assert n > 2_000_000 and d["arrays"] == {"z": [n], "color": [n, 3], "normals": [n, 3]}
+    assert (np.diff(idx) > 0).all() and idx[-1] < H * W             # distinct pixels, in raster order
+    c = np.load(runs[0] / "color.npy")
+    assert (c == idx[:, None]).all() and (np.load(runs[0] / "normals.npy") == -c).all()   # the same pixels in every plane
+    for name in planes:
+        assert (runs[0] / f"{name}.npy").read_bytes() == (runs[1] / f"{name}.npy").read_bytes(), name
+
+
 def test_strip_rows_partition():
     from cython3dmodelrenderer_amd.distributed import strip_rows
     for H, n in [(8192, 8), (1024, 8), (1000, 3), (7, 8), (64, 1)]:
