@@ -69,7 +69,7 @@ def needs_build() -> bool:
 def compile_library(out: str, extra_flags=(), sources=None, src_dir: str = SRC_DIR, verbose: bool = False,
                     quiet: bool = False) -> str:
     """hipcc -c every translation unit (side by side), then link them into `out`.  `extra_flags`:
-    defines of development / diagnostic builds (-DCRENDER_DEV_KNOBS, -DCRENDER_STAMPS, ...)."""
+    defines of diagnostic builds (-DCRENDER_STAMPS, ...)."""
     import tempfile
     from concurrent.futures import ThreadPoolExecutor
     sources = list(sources or SOURCES)

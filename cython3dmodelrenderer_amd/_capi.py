@@ -108,12 +108,6 @@ def load():
     got = L.crender_abi_version()
     if got != ABI_VERSION:
         raise CrenderError(f"libcrender_hip.so ABI {got}, binding expects {ABI_VERSION}")
-    # CRENDER_RASTER_PATH=0|1: every plan that has not been told otherwise renders with that kernel
-    # (crender_set_default_raster_path) — how the parity suite is run once per kernel
-    forced = os.environ.get("CRENDER_RASTER_PATH")
-    if forced not in (None, ""):
-        if L.crender_set_default_raster_path(int(forced)) != OK:
-            raise CrenderError(f"CRENDER_RASTER_PATH={forced}: expected -1, 0 or 1")
     _lib = L
     return L
 

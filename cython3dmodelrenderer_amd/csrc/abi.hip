@@ -67,10 +67,8 @@ bool make_layout(int H, int W, int y0, int y1, int64_t max_T, int64_t cap, int t
     }
     L.pair_cap = 0;
     if (L.direct_cap == 0 && max_T > 0) {
-#ifndef CRENDER_PAIR_MULT
-#define CRENDER_PAIR_MULT 3
-#endif
-        int64_t pc = (CRENDER_PAIR_MULT * max_T / L.g.ntiles + 64 + 63) / 64 * 64;
+        constexpr int64_t kPairMult = 3;     // slabs of three times the mean list (plan.h)
+        int64_t pc = (kPairMult * max_T / L.g.ntiles + 64 + 63) / 64 * 64;
         // (a scene whose MEAN list — 1.3 entries per triangle — already fills the clamped slab would overflow
         // it on its first frame and leave up to 2 GB allocated and dead: such plans get no slabs at all)
         const bool hopeless = pc > 8192 && 13 * max_T / 10 / L.g.ntiles > 8192;

@@ -9,10 +9,6 @@
 // parity with the reference depends on them.
 #include "plan.h"
 
-#ifndef CRENDER_BIN_PER
-#define CRENDER_BIN_PER 1
-#endif
-
 using namespace crender_detail;
 
 namespace {
@@ -229,7 +225,7 @@ __global__ __launch_bounds__(kWave) void k_count_wave(const float *__restrict__ 
 // Groups of 64 triangles a wavefront takes through the chain together.  One: more groups lengthen the runs
 // of neighbouring positions in the lists (the raster launch gathers its records faster: 0.559 / 0.552 / 0.524 ms
 // with 1 / 2 / 4) but slow this pass down by more (0.176 / 0.195 / 0.279 ms; profiles/r05/ab_pair_bins_synth10m.txt).
-constexpr int kBinPer = CRENDER_BIN_PER;
+constexpr int kBinPer = 1;
 template <int TS, bool PROJECT>
 __global__ __launch_bounds__(kWave) void k_bin_wave(const float *__restrict__ tri_in,
                                                     const float *__restrict__ nrm,
@@ -583,14 +579,12 @@ int run_bin_pass(crender_plan *plan, bool project, const float *d_tri, const flo
 {
     const Layout &L = plan->L;
     const Geom G = L.g;
-    const int dbg = dev_knobs();
-    const bool direct = L.direct_cap > 0 && plan->direct_ok && !(flags & CRENDER_NO_DIRECT_BINS) &&
-                        !(dbg & 16);
+    const bool direct = L.direct_cap > 0 && plan->direct_ok && !(flags & CRENDER_NO_DIRECT_BINS);
     plan->last_frame_direct = direct;
     plan->last_T = T;
     const int par = (int)(plan->frame_no++ & 1u);
     plan->parity = par;
-    plan->frame_lone = !(flags & CRENDER_OVERLAPPED_FRAMES) || (dbg & 16384);
+    plan->frame_lone = !(flags & CRENDER_OVERLAPPED_FRAMES);
     // Which lists are split among several workgroups (binning.h, "heavy tiles"): on a frame rendered alone the
     // plan's own thresholds (32-pixel plans of small frames: every covered tile, in quadrants); on a frame of a
     // swap chain — whose tiles are one workgroup each — only the long ones, from 32 records in halves and from 64
@@ -599,16 +593,12 @@ int run_bin_pass(crender_plan *plan, bool project, const float *d_tri, const flo
     // (T-Rex 1024^2: +2.7 % at the driver's 20 steps, +1.9 % at 200; profiles/r06/ab_split_overlapped.txt).
     plan->frame_hmax = 0;
     plan->frame_heavy_at = plan->frame_quad_at = 0;
-    if (direct && L.hmax > 0 && !(dbg & 2048)) {
+    if (direct && L.hmax > 0) {
         plan->frame_hmax = plan->frame_lone || L.hmax < kMaxHeavyHelped ? L.hmax : kMaxHeavyHelped;
         plan->frame_heavy_at = plan->frame_lone ? heavy_at(TS) : kHeavyAt;
         plan->frame_quad_at = plan->frame_lone ? quad_at(TS) : kQuadAt;
     }
-#if defined(CRENDER_FAULT) && CRENDER_FAULT == 2     // (round 5's defect back in, for the state check's own test: scripts/r6_faults.sh)
-    if (plan->awaiting[par]) {
-#else
     if (plan->awaiting[par] || plan->unrastered[par ^ 1]) {
-#endif
         // this parity was binned into and not zeroed since, or the other one was binned into and never
         // rasterized (the swap chain binned ahead for inputs that then changed; crender_prepare twice in a
         // row): start over from the state crender_plan_create leaves.  (The second case was missed until
@@ -637,10 +627,10 @@ int run_bin_pass(crender_plan *plan, bool project, const float *d_tri, const flo
     // Scan path: one wavefront per 64 triangles (k_count_wave / k_fill_wave) where neighbouring
     // triangles can be expected to share tiles — a mesh, or a large model kept in tile-coherent
     // order; a large triangle soup in arbitrary order keeps the block histograms.
-    const bool wave_scan = (plan->orig_of != nullptr || T < kWaveScanBelow) && !(dbg & 4);
+    const bool wave_scan = plan->orig_of != nullptr || T < kWaveScanBelow;
     // large scenes: ONE binning pass into fixed-capacity slabs of (position, index) pairs (k_bin_wave)
     const bool pairbins = !direct && wave_scan && T > 0 && L.pair_cap > 0 && plan->pairbins_ok &&
-                          !(flags & CRENDER_NO_DIRECT_BINS) && !(dbg & 16);
+                          !(flags & CRENDER_NO_DIRECT_BINS);
     plan->last_frame_pairbins = pairbins;
     plan->last_frame_pairs = pairbins || (!direct && wave_scan && plan->orig_of != nullptr && T > 0);
     if (T > 0 && direct) {

@@ -44,15 +44,9 @@ constexpr int kThreads = 256;           // 4 wavefronts per workgroup
 constexpr int kWavesPerSimd16 = 7, kWavesPerSimd32 = 6;   // (32-pixel tiles: 28.7 KB of LDS = 5 workgroups per CU)
 // the 32-pixel kernel with the pixel owners alone (raster.hip, kPathOwners): seven wavefronts (70 registers,
 // 19.5 KB of LDS)
-#ifndef CRENDER_WAVES_OWNERS
-#define CRENDER_WAVES_OWNERS 7
-#endif
-constexpr int kWavesPerSimdOwners = CRENDER_WAVES_OWNERS;
+constexpr int kWavesPerSimdOwners = 7;
 constexpr int kItemPixels = 2;      // samples per work item of the per-pixel sweep of 16-pixel tiles
-#ifndef CRENDER_ITEM32
-#define CRENDER_ITEM32 2
-#endif
-constexpr int kItemPixels32 = CRENDER_ITEM32;    // the same for the small-record batches of 32-pixel tiles
+constexpr int kItemPixels32 = 2;    // the same for the small-record batches of 32-pixel tiles
 constexpr uint32_t kPixelPathRecords = 8;   // k_raster<16>: batches this short go pixel-parallel
 constexpr uint32_t kNoTiles = 0xFFFFFFFFu;
 
@@ -248,17 +242,6 @@ inline int grid_for(size_t items, int cap)
     if (b < 1) b = 1;
     if (b > (size_t)cap) b = (size_t)cap;
     return (int)b;
-}
-
-// CRENDER_DEBUG of a development build (-DCRENDER_DEV_KNOBS; see raster.hip), read once; 0 in the product
-inline int dev_knobs()
-{
-#ifdef CRENDER_DEV_KNOBS
-    static const int dbg = std::getenv("CRENDER_DEBUG") ? std::atoi(std::getenv("CRENDER_DEBUG")) : 0;
-    return dbg;
-#else
-    return 0;
-#endif
 }
 
 }  // namespace crender_detail

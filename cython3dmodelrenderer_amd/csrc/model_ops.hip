@@ -330,10 +330,7 @@ int crender_tile_order_keys(const float *d_tri, int64_t T, const float *P16, int
     if (T < 0 || !P16 || w <= 0 || h <= 0 || (T > 0 && (!d_tri || !d_keys)))
         return fail(CRENDER_EINVAL, "crender_tile_order_keys: bad argument");
     if (T == 0) return CRENDER_OK;
-    int cell_shift = 2;      // 4-pixel cells
-#ifdef CRENDER_DEV_KNOBS
-    if (std::getenv("CRENDER_ORDER_CELL_SHIFT")) cell_shift = std::atoi(std::getenv("CRENDER_ORDER_CELL_SHIFT"));
-#endif
+    const int cell_shift = 2;      // 4-pixel cells
     hipLaunchKernelGGL(k_tile_order_keys, dim3(grid_for((size_t)T, 4096)), dim3(kThreads), 0,
                        static_cast<hipStream_t>(stream), d_tri, T, make_proj(P16, w, h), w, h, d_keys, cell_shift);
     CR_LAUNCH_CHECK("k_tile_order_keys");

@@ -19,18 +19,6 @@
 // No HBM atomics on the framebuffer and every framebuffer byte is written once per frame.
 // Build flags (see _build.py): -ffp-contract=off, correctly rounded division, denormals on —
 // float parity with the reference depends on them.
-//
-// Measurement knobs exist only in a development build (-DCRENDER_DEV_KNOBS, scripts/dev_build.sh):
-// there CRENDER_DEBUG (environment, read once) is a bit mask; the product library is compiled
-// without them (every `dbg & bit` below folds to 0):
-//   1 no coverage work, 2 no shading (both produce WRONG images: ablation timing only),
-//   4 block-histogram count / fill passes on every scan-path frame, 8 XCD-banded tile map, 16 never use direct bins, 32 no sign rejection, 64 no hoisted
-//   reciprocal, 128 small-record block sweep for every batch (64-pixel tiles), 256 invert the
-//   scatter-dispatch rule, 512 no row rotation of the tile map, 4096 coarse pass keeps every
-//   block, 8192 large-record sweep for every batch (32/64-pixel tiles), bits 16..23 = n + 1:
-//   pixel-parallel path of 16-pixel tiles for batches <= n records (n = 0 disables it; default
-//   kPixelPathRecords), 16384 frames of a swap chain are treated as lone frames (ordered dispatch
-//   and split tiles although they overlap), 32768 no pixel-owner sweep on 32-pixel tiles.
 #include "plan.h"
 
 using namespace crender_detail;
@@ -38,17 +26,6 @@ using namespace crender_detail;
 namespace {
 
 // ---- tile rasterizer --------------------------------------------------------------
-// Alternative block -> tile map (debug knob 8): one contiguous band of tiles per XCD.
-// Measured SLOWER than the identity map on every workload (r01: T-Rex 8192^2 0.60 vs 0.42 ms):
-// the covered tiles cluster, so banding piles the work onto a few XCDs.  The identity map
-// deals neighbouring tiles round-robin over the XCDs and is the default.
-CR_DEV int xcd_band_tile(int b, int n)
-{
-    const int per = n >> 3, rem = n & 7;
-    const int xcd = b & 7, k = b >> 3;
-    return xcd * per + (xcd < rem ? xcd : rem) + k;
-}
-
 // Slot of tile-local pixel (dx, dy) in the LDS key plane.  On 32-pixel tiles a row of the plane (32 keys of
 // 8 bytes) is exactly one sweep of the 64 LDS banks, so lanes that work on the same columns of different
 // rows — the 16 lanes of a 4x4 block, the rows of one wide box, the lanes of a run-wise sweep that sit a
@@ -58,9 +35,7 @@ CR_DEV int xcd_band_tile(int b, int n)
 template <int TS>
 CR_DEV int key_slot(int dx, int dy)
 {
-#ifndef CRENDER_NO_KEY_SWIZZLE
     if constexpr (TS == 32) return dy * 32 + (dx ^ ((dy << 1) & 30));
-#endif
     return dy * TS + dx;
 }
 
@@ -170,7 +145,7 @@ CR_DEV bool fragment16(const Rec16Regs &R, int X, int Y, unsigned long long &key
     float n1, n2, n3;
     numerators(s, X, Y, n1, n2, n3);
     float b1, b2, b3;
-    quotients(s, n1, n2, n3, true, b1, b2, b3);
+    quotients(s, n1, n2, n3, b1, b2, b3);
     if (b1 < 0.0f || b2 < 0.0f || b3 < 0.0f) return false;     // .pyx:215-216 (NaN passes)
     const float z = interp(s.z0, s.z1, s.z2, b1, b2, b3);
     if (z != z) return false;                                  // .pyx:220
@@ -201,7 +176,7 @@ CR_DEV void shade16_store(const Rec16Regs &R, const float *__restrict__ col, con
     s.fast = (__float_as_uint(R.c.w) & kRecFast) != 0;
     float n1, n2, n3, b1, b2, b3;
     numerators(s, X, Y, n1, n2, n3);
-    quotients(s, n1, n2, n3, true, b1, b2, b3);
+    quotients(s, n1, n2, n3, b1, b2, b3);
     store_fragment(interp(s.z0, s.z1, s.z2, b1, b2, b3), c, n, b1, b2, b3, Lt, pix, zb, cb, nb);
 }
 
@@ -297,8 +272,7 @@ CR_DEV bool rect_surely_missed(const TriSetup &s, int xa, int xb, int ya, int yb
 
 // Coarse pass of a large-record batch: one lane per dense 4x4 block; surviving blocks are
 // recorded in q.big.mask.
-CR_DEV void coarse_cull(WorkQueue &q, const uint32_t *wo, int total, int tid, int X0, int Y0,
-                                                      bool keep_all)
+CR_DEV void coarse_cull(WorkQueue &q, const uint32_t *wo, int total, int tid, int X0, int Y0)
 {
     for (int p = tid; p < total; p += kThreads) {
         uint32_t first;
@@ -321,7 +295,7 @@ CR_DEV void coarse_cull(WorkQueue &q, const uint32_t *wo, int total, int tid, in
         const bool o1 = worst(s.l01, s.l02, s.y2, s.x2, s.rej1) < -kRejTiny;
         const bool o2 = worst(s.l11, s.l12, s.y0, s.x0, s.rej2) < -kRejTiny;
         const bool o3 = worst(s.l21, s.l22, s.y1, s.x1, s.rej3) < -kRejTiny;
-        if (keep_all || !(o1 || o2 || o3)) atomicOr(&q.big.mask[r], 1ull << b);
+        if (!(o1 || o2 || o3)) atomicOr(&q.big.mask[r], 1ull << b);
     }
 }
 
@@ -671,7 +645,7 @@ CR_DEV void owner_tile(const Q &q, const float *pre, int nrec, const float *__re
             if (wave_any(live)) {                                 // wavefront-uniform
                 if (live) {
                     float b1, b2, b3;
-                    quotients(st, n1, n2, n3, true, b1, b2, b3);
+                    quotients(st, n1, n2, n3, b1, b2, b3);
                     if (!(b1 < 0.0f || b2 < 0.0f || b3 < 0.0f)) {          // .pyx:215-216 (NaN passes)
                         const float z = interp(st.z0, st.z1, st.z2, b1, b2, b3);
                         if (z == z) {                                      // .pyx:220
@@ -756,7 +730,6 @@ struct Tile {
     const Geom &G;
     unsigned long long *key;     // LDS: the key plane (the pixel owners' per-record words instead)
     unsigned char *qraw;         // LDS: the batch queue (Rec16 records on 16-pixel tiles, else a WorkQueue)
-    int dbg;                     // CRENDER_DEBUG of a development build, 0 in the product
     int X0, Y0, X1, Y1;          // the rectangle
     int rw, quad;                // its width in the key plane's terms; -1 = whole tile, 0..3 = part of a heavy one
     uint32_t beg, end;           // the tile's list
@@ -764,11 +737,6 @@ struct Tile {
     size_t stamp_base;
 #endif
 };
-#ifdef CRENDER_DEV_KNOBS
-#define CR_TILE_DBG(c) [[maybe_unused]] const int dbg = (c).dbg
-#else
-#define CR_TILE_DBG(c) [[maybe_unused]] constexpr int dbg = 0
-#endif
 #ifdef CRENDER_STAMPS
 #define CR_TILE_STAMPS(c) [[maybe_unused]] const size_t stamp_base = (c).stamp_base
 #else
@@ -790,7 +758,6 @@ struct Tile {
     [[maybe_unused]] const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;                              \
     [[maybe_unused]] const int X0 = (c).X0, Y0 = (c).Y0, X1 = (c).X1, Y1 = (c).Y1, rw = (c).rw, quad = (c).quad; \
     [[maybe_unused]] const uint32_t beg = (c).beg, end = (c).end;                                                \
-    CR_TILE_DBG(c);                                                                                              \
     CR_TILE_STAMPS(c)
 
 // the batch: records array-of-structures on 16-pixel tiles (Rec16), else the WorkQueue
@@ -812,7 +779,6 @@ CR_DEV bool pick_tile(const Tile<TS> &c, int b, int &b_out, int &tile, int &quad
     int32_t *const win = c.win;
     unsigned char *const qraw = c.qraw;
     const int tid = threadIdx.x;
-    CR_TILE_DBG(c);
     // ---- which tile, and which part of it --------------------------------------------------
     // grid = [order builder, if ordered][3 * hmax helpers][ntiles main workgroups, one tile each]; an ordered
     // launch reads it as [builder][covered tiles, longest lists first][helpers][groups of empty tiles]
@@ -840,18 +806,14 @@ CR_DEV bool pick_tile(const Tile<TS> &c, int b, int &b_out, int &tile, int &quad
     // without a look at their slot word: it is zero, nobody registered there.
     int lead = 0;                                               // own workgroups ahead of the helpers
     int used = L.nhelp;                                         // helper slots in front of the other own workgroups
-#ifndef CRENDER_HELPERS_FIRST
     if constexpr (TS == 32) {
         const bool ordered_now = L.nhelp > 0 && L.order && L.hint[0] && !*L.hint_bad;
         if (ordered_now) {
             lead = (int)L.hint[3];
-#ifndef CRENDER_ALL_HELPER_SLOTS
             const uint32_t reg = *L.heavy_ctr, hmax = (uint32_t)L.nhelp / 3u;
             used = 3 * (int)(reg < hmax ? reg : hmax);
-#endif
         }
     }
-#endif
     if (b >= G.ntiles + used) return false;                     // (an unused helper slot)
     const bool helper = b >= lead && b < lead + used;
     quad = -1;                   // -1 = the whole tile, 0..3 = one part of a heavy tile (half or quadrant)
@@ -918,7 +880,10 @@ CR_DEV bool pick_tile(const Tile<TS> &c, int b, int &b_out, int &tile, int &quad
                 return false;
             }
         } else {
-            tile = (dbg & 8) ? xcd_band_tile(m, G.ntiles) : m;
+            // Identity map: neighbouring tiles are dealt round-robin over the XCDs.  One contiguous band of
+            // tiles per XCD measured slower on every workload (r01: T-Rex 8192^2 0.60 vs 0.42 ms): the covered
+            // tiles cluster, so banding piles the work onto a few XCDs.
+            tile = m;
             // Tile-coherent triangle order (lists of (position, index) pairs: millions of small triangles):
             // neighbouring tiles read the same records along their common border — a sixth of a list —
             // and workgroup m runs on XCD m % 8, each XCD with an L2 of its own: dealt round-robin, the
@@ -929,7 +894,7 @@ CR_DEV bool pick_tile(const Tile<TS> &c, int b, int &b_out, int &tile, int &quad
             // +1 % (blocks of 2 / 4 / 8 tiles: 1 738 / 1 700 / 1 667 MB, +3.5 / +2 / +2.5 %;
             // profiles/r05/ab_block_map_synth10m.txt).  Needs whole blocks, eight at a time.
             constexpr uint32_t SL = 4, SB = 1u << SL;
-            const bool super_map = (L.pairs != 0) != ((dbg & (1 << 27)) != 0) && (G.ntx & (SB - 1)) == 0 &&
+            const bool super_map = L.pairs != 0 && (G.ntx & (SB - 1)) == 0 &&
                                    (G.nty & (SB - 1)) == 0 && (((uint32_t)G.ntiles >> (2 * SL)) & 7u) == 0;
             if (super_map) {
                 const uint32_t xcd = (uint32_t)m & 7u, j = (uint32_t)m >> 3;
@@ -942,7 +907,7 @@ CR_DEV bool pick_tile(const Tile<TS> &c, int b, int &b_out, int &tile, int &quad
             // that a band of covered tiles is spread over the whole launch instead of arriving
             // together (T-Rex 8192^2: 0.446 -> 0.402 ms).  Small grids are faster in raster order
             // (T-Rex 1024^2: 24.7 vs 29.1 us), so the scatter starts at 32768 tiles.
-            if (!super_map && (G.ntiles >= 32768) != ((dbg & 256) != 0)) {
+            if (!super_map && G.ntiles >= 32768) {
                 // (b * stride) mod ntiles, the product below 2^48: quotient from a double multiply
                 // (exact product, at most one off after rounding), remainder fixed up
                 const unsigned long long P = (unsigned long long)m * (unsigned)G.tile_stride;
@@ -959,7 +924,7 @@ CR_DEV bool pick_tile(const Tile<TS> &c, int b, int &b_out, int &tile, int &quad
             // the whole dispatch while a third of the chip's workgroup slots stand free.  Rotating
             // row ty by 9 * ty columns walks every pair through every column (T-Rex 1024^2 raster
             // 24.0 -> 21.6 us; the larger frames gain 0-2 %).
-            if (!(dbg & 512) && !super_map) {
+            if (!super_map) {
                 const int ty = G.ntx_magic ? (int)__umulhi((uint32_t)tile, G.ntx_magic) : tile / G.ntx;
                 const int t = tile - ty * G.ntx + 9 * ty;
                 const int tx = G.ntx_magic ? t - (int)__umulhi((uint32_t)t, G.ntx_magic) * G.ntx : t % G.ntx;
@@ -1020,16 +985,16 @@ CR_DEV void pixel_path16(const Tile<16> &c, uint32_t left, bool first, const Tri
     key[tid] = best;
 }
 
-// Per-pixel sweep: every pixel of every clipped box is one work item; thread t takes
+// Per-pixel sweep of 16-pixel tiles: every pixel of every clipped box is one work item; thread t takes
 // items t, t + 256, ...  All lanes work on a sample that lies in its box (a 4x4 block
 // of a small box is mostly empty: 71 % of T-Rex 1024^2's block lanes were inside their
 // box, 40-50 % on its busiest tiles, 35 % for the 10 M small triangles), and there is
 // no per-group record walk.  The item's record comes from a two-level search of the
 // prefix sums (most batches fit the first wavefront's 64 slots: then no wavefront
 // selection and only log2 of the record count steps).
-template <int TS>
-CR_DEV void sweep_items(const Tile<TS> &c, const uint32_t *scan, const uint32_t *wo_, int total_, int nrec)
+CR_DEV void sweep_items(const Tile<16> &c, const uint32_t *scan, const uint32_t *wo_, int total_, int nrec)
 {
+    constexpr int TS = 16;
     CR_TILE_LOCALS(c);
     const int first_n = nrec <= 1 ? 1 : (nrec > 64 ? 64 : 1 << (32 - __clz(nrec - 1)));
     for (int e = tid; e < total_; e += kThreads) {
@@ -1047,70 +1012,35 @@ CR_DEV void sweep_items(const Tile<TS> &c, const uint32_t *scan, const uint32_t 
         } else {
             r = find_record(scan, wo_, e, i);
         }
-        if constexpr (TS == 16) {
-            const Rec16Regs R = load_rec16(&recs[r]);
-            const uint32_t xy = __float_as_uint(R.c.z);
-            const int bw = box_w(__float_as_uint(R.c.w));
-            // kItemPixels samples per item — x-neighbours of one box row — share the
-            // item's record search, its six LDS reads and its decode (a third of a
-            // sample's instructions and most of an iteration's dependent LDS round
-            // trips); a box width that is no multiple wastes part of an item per row.
-            const int bwn = (bw + kItemPixels - 1) / kItemPixels;
-            const int dy = (int)(((float)i + 0.5f) * __builtin_amdgcn_rcpf((float)bwn));
-            const int px0 = ((int)i - dy * bwn) * kItemPixels;
-            const int x = (int)(xy & 0xFFFF) + px0, y = (int)(xy >> 16) + dy;
-            unsigned long long *kp = &key[key_slot<TS>(x - X0, y - Y0)];
+        const Rec16Regs R = load_rec16(&recs[r]);
+        const uint32_t xy = __float_as_uint(R.c.z);
+        const int bw = box_w(__float_as_uint(R.c.w));
+        // kItemPixels samples per item — x-neighbours of one box row — share the
+        // item's record search, its six LDS reads and its decode (a third of a
+        // sample's instructions and most of an iteration's dependent LDS round
+        // trips); a box width that is no multiple wastes part of an item per row.
+        const int bwn = (bw + kItemPixels - 1) / kItemPixels;
+        const int dy = (int)(((float)i + 0.5f) * __builtin_amdgcn_rcpf((float)bwn));
+        const int px0 = ((int)i - dy * bwn) * kItemPixels;
+        const int x = (int)(xy & 0xFFFF) + px0, y = (int)(xy >> 16) + dy;
+        unsigned long long *kp = &key[key_slot<TS>(x - X0, y - Y0)];
 #pragma unroll
-            for (int j = 0; j < kItemPixels; ++j) {
-                unsigned long long k;
-                if (fragment16(R, x + j, y, k) && (j == 0 || px0 + j < bw)) lds_key_min(kp + j, k);
-            }
-        } else {
-            const uint32_t xy = packed_xy(q.box[r], X0, Y0);
-            const int bw = box_w(packed_wh(q.box[r]));
-            const TriXYZ t{q.x0[r], q.y0[r], q.z0[r], q.x1[r], q.y1[r], q.z1[r],
-                           q.x2[r], q.y2[r], q.z2[r]};
-            const uint32_t id = q.tri[r];
-            // the item's samples share its record search, its twelve LDS reads, the nine
-            // edge constants and the refined reciprocals (raster_math.h (2)): per sample
-            // that was 150 vector instructions, a pair costs 175
-            TriSetup st;
-            {
-                st.x0 = t.x0; st.y0 = t.y0; st.z0 = t.z0; st.x1 = t.x1; st.y1 = t.y1; st.z1 = t.z1;
-                st.x2 = t.x2; st.y2 = t.y2; st.z2 = t.z2;
-                st.l01 = t.x1 - t.x2; st.l02 = t.y1 - t.y2;
-                st.l11 = t.x2 - t.x0; st.l12 = t.y2 - t.y0;
-                st.l21 = t.x0 - t.x1; st.l22 = t.y0 - t.y1;
-                st.l03 = q.pre.l03[r]; st.l13 = q.pre.l13[r]; st.l23 = q.pre.l23[r];
-                st.r1 = q.pre.r1[r]; st.r2 = q.pre.r2[r]; st.r3 = q.pre.r3[r];
-                st.fast = st.r1 != 0.0f;
-                st.rej1 = st.rej2 = st.rej3 = 0.0f;
-            }
-            const int bwn = (bw + kItemPixels32 - 1) / kItemPixels32;
-            // i / bwn for i < 1024, bwn <= 32: the approximate reciprocal is exact enough
-            const int dy = (int)(((float)i + 0.5f) * __builtin_amdgcn_rcpf((float)bwn));
-            const int px0 = ((int)i - dy * bwn) * kItemPixels32;
-            const int x = (int)(xy & 0xFFFF) + px0, y = (int)(xy >> 16) + dy;
-#pragma unroll
-            for (int j = 0; j < kItemPixels32; ++j) {
-                float n1, n2, n3;
-                numerators(st, x + j, y, n1, n2, n3);
-                unsigned long long k;
-                if (fragment_from(st, id, n1, n2, n3, true, k) && (j == 0 || px0 + j < bw))
-                    lds_key_min(&key[key_slot<TS>(x + j - X0, y - Y0)], k);
-            }
+        for (int j = 0; j < kItemPixels; ++j) {
+            unsigned long long k;
+            if (fragment16(R, x + j, y, k) && (j == 0 || px0 + j < bw)) lds_key_min(kp + j, k);
         }
     }
 }
 
-// The same items — pairs of x-neighbours of the clipped boxes' rows — in RUNS: thread t takes
-// items [t c, (t + 1) c) of the batch (c = ceil(total / 256)), finds the record of its first
-// item by the search above ONCE and then walks: next pair of the row, next row, next record.
-// Per item that is no search (6 dependent LDS reads and ~55 of ~230 vector instructions on
-// batches of more than 64 records) and no division for the row; the record is re-read
-// from LDS per item as before (registers: the 32-pixel kernel has none to spare), one round
-// trip.  Lanes of a wavefront hold neighbouring records (consecutive LDS banks), every lane
-// makes the same number of trips.
+// Small records of 32-pixel tiles, per pixel.  The work items are pairs of x-neighbours of the clipped
+// boxes' rows, walked in RUNS: thread t takes items [t c, (t + 1) c) of the batch (c = ceil(total / 256)),
+// finds the record of its first item by the two-level search of the prefix sums ONCE and then walks: next
+// pair of the row, next row, next record.  Per item that is no search (6 dependent LDS reads and ~55 of
+// ~230 vector instructions on batches of more than 64 records) and no division for the row: faster than a
+// sweep item by item, with a search per item, on every workload once the key plane is swizzled (T-Rex
+// 1024^2 pipelined +12 %, 10 M small triangles' raster launch -4 %).  The record is re-read from LDS per
+// item (registers: the 32-pixel kernel has none to spare), one round trip.  Lanes of a wavefront hold
+// neighbouring records (consecutive LDS banks), every lane makes the same number of trips.
 CR_DEV void sweep_runs32(const Tile<32> &c, const uint32_t *wo_, int total_)
 {
     constexpr int TS = 32;
@@ -1124,6 +1054,7 @@ CR_DEV void sweep_runs32(const Tile<32> &c, const uint32_t *wo_, int total_)
     int dy, px0;             // the item within its record: row of the box, first pixel of the pair
     {
         const int bwn = (box_w(packed_wh(q.box[r])) + kItemPixels32 - 1) / kItemPixels32;
+        // (i / bwn for i < 1024, bwn <= 32: the approximate reciprocal is exact enough)
         dy = (int)(((float)i + 0.5f) * __builtin_amdgcn_rcpf((float)bwn));
         px0 = ((int)i - dy * bwn) * kItemPixels32;
     }
@@ -1138,6 +1069,8 @@ CR_DEV void sweep_runs32(const Tile<32> &c, const uint32_t *wo_, int total_)
         const int bw = box_w(wh), bh = box_h(wh);
         const TriXYZ t{q.x0[r], q.y0[r], q.z0[r], q.x1[r], q.y1[r], q.z1[r], q.x2[r], q.y2[r], q.z2[r]};
         const uint32_t id = q.tri[r];
+        // the item's samples share its twelve LDS reads, the nine edge constants and the refined
+        // reciprocals (raster_math.h (2)): per sample that was 150 vector instructions, a pair costs 175
         TriSetup st;
         {
             st.x0 = t.x0; st.y0 = t.y0; st.z0 = t.z0; st.x1 = t.x1; st.y1 = t.y1; st.z1 = t.z1;
@@ -1156,7 +1089,7 @@ CR_DEV void sweep_runs32(const Tile<32> &c, const uint32_t *wo_, int total_)
             float n1, n2, n3;
             numerators(st, x + j, y, n1, n2, n3);
             unsigned long long k;
-            if (fragment_from(st, id, n1, n2, n3, true, k) && px0 + j < bw)
+            if (fragment_from(st, id, n1, n2, n3, k) && px0 + j < bw)
                 lds_key_min(&key[key_slot<TS>(x + j - X0, y - Y0)], k);
         }
         left -= bw != 0 ? 1 : 0;
@@ -1367,7 +1300,7 @@ CR_DEV void owners_batches(const Tile<32> &c)
                 if (!wave_any(live)) continue;
                 if (live) {
                     float b1, b2, b3;
-                    quotients(st, n1, n2, n3, true, b1, b2, b3);
+                    quotients(st, n1, n2, n3, b1, b2, b3);
                     if (!(b1 < 0.0f || b2 < 0.0f || b3 < 0.0f)) {          // .pyx:215-216 (NaN passes)
                         const float z = interp(st.z0, st.z1, st.z2, b1, b2, b3);
                         if (z == z) {                                      // .pyx:220
@@ -1466,7 +1399,6 @@ CR_DEV void sweep_blocks_culled(const Tile<TS> &c, uint32_t (&wo)[kThreads / 64 
     static_assert(TS <= 32, "a record has at most 64 blocks: one mask word");
     CR_TILE_LOCALS(c);
     const int l = tid & 15, lx = l & 3, ly = l >> 2;
-    [[maybe_unused]] const bool allow_rej = !(dbg & 32), allow_fast = !(dbg & 64);
     q.big.mask[tid] = 0;
     if constexpr (TS == 32) q.big.blk_scan[tid] = blk_excl;
     __syncthreads();
@@ -1474,7 +1406,7 @@ CR_DEV void sweep_blocks_culled(const Tile<TS> &c, uint32_t (&wo)[kThreads / 64 
     // rounding step is), so its extreme over the block sits on a corner; a block
     // goes only if all four corners are "surely outside" the SAME edge, which is
     // then true of every pixel in it (raster_math.h (1)).
-    coarse_cull(q, wo, total, tid, X0, Y0, (dbg & 4096) != 0);
+    coarse_cull(q, wo, total, tid, X0, Y0);
     __syncthreads();
     // survivors per record -> the same two-level prefix as the block counts
     const uint32_t mine = (uint32_t)__popcll(q.big.mask[tid]);
@@ -1505,7 +1437,7 @@ CR_DEV void sweep_blocks_culled(const Tile<TS> &c, uint32_t (&wo)[kThreads / 64 
             float n1, n2, n3;
             numerators(wk.s, x, y, n1, n2, n3);
             unsigned long long k;
-            if (x < wk.bx1 && y < wk.by1 && fragment_from(wk.s, wk.id, n1, n2, n3, allow_fast, k))
+            if (x < wk.bx1 && y < wk.by1 && fragment_from(wk.s, wk.id, n1, n2, n3, k))
                 lds_key_min(&key[key_slot<TS>(x - X0, y - Y0)], k);
             if (++p >= pend) break;   // (p < pend guarantees another survivor)
             m &= m - 1;
@@ -1524,7 +1456,6 @@ CR_DEV void walk64_dense(const Tile<64> &c, const uint32_t *wo, int total)
     constexpr int TS = 64;
     CR_TILE_LOCALS(c);
     const int l = tid & 15, lx = l & 3, ly = l >> 2;
-    const bool allow_rej = !(dbg & 32), allow_fast = !(dbg & 64);
     const int wchunk = (total + kThreads / 64 - 1) / (kThreads / 64);
     int p = wave * wchunk + ((tid >> 4) & 3);
     const int pend = ((wave + 1) * wchunk < total) ? ((wave + 1) * wchunk) : total;
@@ -1540,10 +1471,10 @@ CR_DEV void walk64_dense(const Tile<64> &c, const uint32_t *wo, int total)
             float n1, n2, n3;
             numerators(wk.s, x, y, n1, n2, n3);
             const bool live = x < wk.bx1 && y < wk.by1 &&
-                              !(allow_rej && surely_outside(wk.s, n1, n2, n3));
+                              !surely_outside(wk.s, n1, n2, n3);
             if (wave_any(live)) {   // wavefront-uniform
                 unsigned long long k;
-                if (live && fragment_from(wk.s, wk.id, n1, n2, n3, allow_fast, k))
+                if (live && fragment_from(wk.s, wk.id, n1, n2, n3, k))
                     lds_key_min(&key[key_slot<TS>(x - X0, y - Y0)], k);
             }
             p += 4;
@@ -1578,7 +1509,7 @@ CR_DEV void resolve_tile(const Tile<TS> &c, bool slotted)
     constexpr uint32_t kHashSlots = (QBYTES / sizeof(uint2)) >= 2048 ? 2048u : 1024u;
     static_assert(kHashSlots * sizeof(uint2) <= QBYTES, "the table takes the batch queue's place");
     uint2 *hash_tab = reinterpret_cast<uint2 *>(qraw);
-    const bool hashed = L.pos_of && L.pairs && end - beg <= kHashSlots / 2 && !(dbg & (1 << 21));
+    const bool hashed = L.pos_of && L.pairs && end - beg <= kHashSlots / 2;
     auto hash_of = [](uint32_t orig) { return (orig * 2654435761u) >> (kHashSlots == 2048u ? 21 : 22); };
     if (hashed) {
         for (uint32_t i = (uint32_t)tid; i < kHashSlots; i += kThreads) hash_tab[i] = make_uint2(0u, 0u);
@@ -1628,7 +1559,7 @@ CR_DEV void resolve_tile(const Tile<TS> &c, bool slotted)
         uint32_t id = 0xFFFFFFFEu - low;
         if (slotted) {
             id = 0xFFFFu - (low >> 16);
-            if (((low >> 8) & 0xFFu) == (((end - beg - 1) / kBatch) & 0xFFu) && !(dbg & 2)) {
+            if (((low >> 8) & 0xFFu) == (((end - beg - 1) / kBatch) & 0xFFu)) {
                 // the winner's record is still in LDS (it came with the last batch)
                 shade16_store(load_rec16(&recs[low & 0xFFu]), col, nrm, L.pos_of ? L.pos_of[id] : id, x, y, pix,
                               zb, cb, nb, L.light);
@@ -1636,14 +1567,7 @@ CR_DEV void resolve_tile(const Tile<TS> &c, bool slotted)
                 continue;
             }
         }
-        if (dbg & 2) {   // ablation: no shading (development build)
-            *elem(zb, pix) = (float)id;
-            float *cp = elem(cb, (I)(pix * 3)), *np_ = elem(nb, (I)(pix * 3));
-            cp[0] = 1.0f; cp[1] = 1.0f; cp[2] = 1.0f;
-            np_[0] = 1.0f; np_[1] = 1.0f; np_[2] = 1.0f;
-            continue;
-        }
-        shade_and_store(proj, col, nrm, position_of(id), x, y, pix, zb, cb, nb, L.light, (dbg >> 28) & 3);
+        shade_and_store(proj, col, nrm, position_of(id), x, y, pix, zb, cb, nb, L.light);
         if (win) *reinterpret_cast<int32_t *>(elem(reinterpret_cast<float *>(win), pix)) = (int32_t)id;
     }
     };
@@ -1657,20 +1581,14 @@ template <int TS, bool CLEAR, int PATH = kPathGeneral>
 CR_DEV void raster_body(const float *__restrict__ proj, const float *__restrict__ col,
                         const float *__restrict__ nrm, const TileLists &L,
                         float *__restrict__ zb, float *__restrict__ cb, float *__restrict__ nb,
-                        int32_t *__restrict__ win, const Geom &G, int dbg_arg, int b,
+                        int32_t *__restrict__ win, const Geom &G, [[maybe_unused]] int stamp_slot, int b,
                         unsigned long long *key, unsigned char *qraw)
 {
-    Tile<TS> c{proj, col, nrm, L, zb, cb, nb, win, G, key, qraw, 0, 0, 0, 0, 0, TS, -1, 0u, 0u};
-#ifdef CRENDER_DEV_KNOBS
-    c.dbg = dbg_arg;
-#else
-    (void)dbg_arg;
-#endif
+    Tile<TS> c{proj, col, nrm, L, zb, cb, nb, win, G, key, qraw, 0, 0, 0, 0, TS, -1, 0u, 0u};
 #ifdef CRENDER_STAMPS
-    // frames of a swap chain stamp into a region of their slot (bits 24..26 of dbg_arg), 8192 workgroups each
-    c.stamp_base = ((size_t)((dbg_arg >> 24) & 7) * 8192 + blockIdx.x) * 16;
+    // frames of a swap chain stamp into a region of their slot, 8192 workgroups each
+    c.stamp_base = ((size_t)stamp_slot * 8192 + blockIdx.x) * 16;
 #endif
-    CR_TILE_DBG(c);
     CR_TILE_STAMPS(c);
     [[maybe_unused]] WorkQueue &q = *reinterpret_cast<WorkQueue *>(qraw);                 // (TS != 16 only)
     [[maybe_unused]] Rec16 *recs = reinterpret_cast<Rec16 *>(qraw);                       // (TS == 16 only)
@@ -1743,7 +1661,6 @@ CR_DEV void raster_body(const float *__restrict__ proj, const float *__restrict_
         if (X1 < X0) X1 = X0;
         if (Y1 < Y0) Y1 = Y0;
     }
-    if (dbg & 1) end = beg;   // ablation: no coverage work (development build)
 
     const bool work = beg != end && X0 < X1 && Y0 < Y1;     // (uniform over the workgroup)
     if (!work) {
@@ -1831,8 +1748,7 @@ CR_DEV void raster_body(const float *__restrict__ proj, const float *__restrict_
         if constexpr (TS == 16) {
             // a short last batch goes pixel-parallel
             const uint32_t left = end - base;
-            const uint32_t pix_max = (dbg >> 16) & 0xFF ? (uint32_t)((dbg >> 16) & 0xFF) - 1u : kPixelPathRecords;
-            if (left <= pix_max) {
+            if (left <= kPixelPathRecords) {
                 pixel_path16(c, left, base == beg, cur_t, key_low, box_xy, box_wh);
                 cur_ok = false;
                 continue;   // (this was the list's last batch)
@@ -1905,7 +1821,7 @@ CR_DEV void raster_body(const float *__restrict__ proj, const float *__restrict_
             const int nrec = (int)((end - base) < (uint32_t)kBatch ? (end - base) : (uint32_t)kBatch);
             const uint32_t blk_excl = incl - my_blocks;
             bool small_by_pixel = false;    // 32-pixel tiles: small records go per pixel too
-            if constexpr (either) small_by_pixel = total < 16 * nrec && !(dbg & 8192);
+            if constexpr (either) small_by_pixel = total < 16 * nrec;
 #ifdef CRENDER_STAMPS
             if (base == beg) CR_STAMP(13);
 #endif
@@ -1915,18 +1831,16 @@ CR_DEV void raster_body(const float *__restrict__ proj, const float *__restrict_
             if (cur_ok) cur_ok = load_record(L, proj, G, nxt, cur_id, cur_t, cur_bx, cur_by);
             if constexpr (TS == 32) {
                 // the whole list is this one batch of large records: the pixels' owners take it from here
-                if (base == beg && end - beg <= (uint32_t)kBatch && !small_by_pixel && !(dbg & 32768)) {
+                if (base == beg && end - beg <= (uint32_t)kBatch && !small_by_pixel) {
                     // (a heavy tile's hand-off words go back to zero HERE: this path returns, and every wavefront
                     // read them before the queue's barrier.  Without it a frame of large triangles on a split
                     // 32-pixel plan left its flags up, and the next frame cleared only the upper half of the
                     // tiles it no longer covered: test_dispatch_order_hint_never_changes_pixels[True-32].
                     // A `break` to the common exit instead costs 76 spilled registers.)
-#if !defined(CRENDER_FAULT) || CRENDER_FAULT != 1      // (-DCRENDER_FAULT=1: round 4's defect back in, for the state check's own test)
                     if (quad >= 0 && tid == 0) {
                         if (!helper) L.heavy_flag[tile] = 0;
                         else L.heavy_slots[b] = 0;
                     }
-#endif
                     owner_path32<CLEAR>(c, nrec);
                     if (tid == 0) count_tile_class(L, tile_class);
                     return;
@@ -1940,24 +1854,16 @@ CR_DEV void raster_body(const float *__restrict__ proj, const float *__restrict_
 #endif
             }
             if constexpr (per_pixel) {
-                sweep_items<TS>(c, scan16, wo, total, nrec);
+                sweep_items(c, scan16, wo, total, nrec);
             } else if (small_by_pixel) {
                 if constexpr (TS == 32) {
                     uint32_t wop[kThreads / 64 + 1];
                     wop[0] = 0;
 #pragma unroll
                     for (int w = 0; w < kThreads / 64; ++w) wop[w + 1] = wop[w] + q.wave_px[w];
-                    // (item by item — thread t takes items t, t + 256, ... with a search per item — only as a
-                    // development knob: the run-wise walk is faster on every workload once the key plane is
-                    // swizzled, T-Rex 1024^2 pipelined +12 %, 10 M small triangles' raster launch -4 %)
                     const int items = (int)wop[kThreads / 64];
 #ifdef CRENDER_STAMPS
                     if (g_stamps && base == beg && tid == 0) g_stamps[stamp_base + 12] = (unsigned long long)items;
-#endif
-#ifdef CRENDER_RUNS_MAX_AVG
-                    if ((dbg & (1 << 30)) || items > CRENDER_RUNS_MAX_AVG * nrec) sweep_items<TS>(c, q.pre.px_scan, wop, items, nrec); else
-#else
-                    if (dbg & (1 << 30)) sweep_items<TS>(c, q.pre.px_scan, wop, items, nrec); else
 #endif
                     sweep_runs32(c, wop, items);
 #ifdef CRENDER_STAMPS
@@ -1965,7 +1871,7 @@ CR_DEV void raster_body(const float *__restrict__ proj, const float *__restrict_
 #endif
                 }
             } else if constexpr (TS == 64) {
-                if ((total < 16 * nrec && !(dbg & 8192)) || (dbg & 128)) walk64_small(c, wo, total);
+                if (total < 16 * nrec) walk64_small(c, wo, total);
                 else walk64_dense(c, wo, total);
             } else {
 #ifdef CRENDER_STAMPS
@@ -2011,12 +1917,12 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(path_w
 void k_raster(const float *__restrict__ proj, const float *__restrict__ col,
               const float *__restrict__ nrm, TileLists L,
               float *__restrict__ zb, float *__restrict__ cb, float *__restrict__ nb,
-              int32_t *__restrict__ win, Geom G, int dbg_arg)
+              int32_t *__restrict__ win, Geom G, int stamp_slot)
 {
     // (the pixel owners read the plane as float4: their eight words per record — the whole of it in kPathOwners)
     __shared__ __attribute__((aligned(16))) unsigned long long key[TS * TS];
     __shared__ __attribute__((aligned(16))) unsigned char qraw[path_queue_bytes<TS, PATH>()];
-    raster_body<TS, CLEAR, PATH>(proj, col, nrm, L, zb, cb, nb, win, G, dbg_arg, (int)blockIdx.x, key, qraw);
+    raster_body<TS, CLEAR, PATH>(proj, col, nrm, L, zb, cb, nb, win, G, stamp_slot, (int)blockIdx.x, key, qraw);
 }
 
 // One launch per frame for a stream of frames (crender_pipeline_*, direct bins): the raster pass of
@@ -2031,7 +1937,7 @@ struct RasterArgs {
     float *zb, *cb, *nb;
     int32_t *win;
     Geom G;
-    int dbg;
+    int stamp_slot;
 };
 static_assert(kSetupWaveLds <= raster_queue_bytes<16>() && kSetupWaveLds <= raster_queue_bytes<32>() &&
               kSetupWaveLds <= sizeof(OwnerQueue),
@@ -2054,7 +1960,7 @@ void k_frame(FrameArgs A)
                                       A.S.hv, A.S.T, A.S.P, A.S.G, (int64_t)blockIdx.x, qraw);
         return;
     }
-    raster_body<TS, CLEAR, PATH>(A.R.proj, A.R.col, A.R.nrm, A.R.L, A.R.zb, A.R.cb, A.R.nb, A.R.win, A.R.G, A.R.dbg,
+    raster_body<TS, CLEAR, PATH>(A.R.proj, A.R.col, A.R.nrm, A.R.L, A.R.zb, A.R.cb, A.R.nb, A.R.win, A.R.G, A.R.stamp_slot,
                                  (int)blockIdx.x - A.nsetup, key, qraw);
 }
 
@@ -2184,11 +2090,6 @@ int run_raster_pass(crender_plan *plan, const float *proj, const float *d_col, c
 {
     const Layout &L = plan->L;
     const Geom G = L.g;
-#ifdef CRENDER_STAMPS
-    const int dbg = dev_knobs() | (plan->stamp_slot << 24);
-#else
-    const int dbg = dev_knobs();
-#endif
     const bool direct = plan->last_frame_direct;          // direct bins of 48-byte entries (small scenes)
     const bool pairbins = plan->last_frame_pairbins;      // fixed-capacity slabs of (position, index) pairs (k_bin_wave)
     const int par = plan->parity;
@@ -2203,7 +2104,7 @@ int run_raster_pass(crender_plan *plan, const float *proj, const float *d_col, c
     tl.T = (uint32_t)plan->last_T;
     tl.orig_of = plan->orig_of;
     tl.pos_of = plan->pos_of;
-    const bool split = direct && plan->frame_hmax > 0 && !(dbg & 2048);    // (lone frames: the plan's thresholds; frames in flight: long lists only)
+    const bool split = direct && plan->frame_hmax > 0;    // (lone frames: the plan's thresholds; frames in flight: long lists only)
     tl.heavy_flag = split ? plan->hflag() : nullptr;
     tl.heavy_slots = split ? plan->hslots() : nullptr;
     tl.heavy_ctr_next = plan->hdr() + 2 + (par ^ 1);
@@ -2211,7 +2112,7 @@ int run_raster_pass(crender_plan *plan, const float *proj, const float *d_col, c
     tl.nhelp = split ? 3 * plan->frame_hmax : 0;
     tl.quad_at = plan->frame_quad_at;
     // ordered launches: read the order the previous launch left, leave one for the next
-    const bool ordered = direct && L.ordered && plan->frame_lone && !(dbg & 1024);
+    const bool ordered = direct && L.ordered && plan->frame_lone;
     const int hp = plan->hint_par;
     tl.order = ordered ? plan->order(hp) : nullptr;
     tl.hint = plan->hint(hp);
@@ -2262,15 +2163,15 @@ int run_raster_pass(crender_plan *plan, const float *proj, const float *d_col, c
 #define CR_LAUNCH_RASTER(P)                                                                                             \
     do {                                                                                                                \
         if (clear) hipLaunchKernelGGL((k_raster<TS, true, P>), dim3(grid), dim3(kThreads), 0, s, proj, d_col, d_nrm,    \
-                                      tl, d_z, d_color, d_normal, d_winner, G, dbg);                                    \
+                                      tl, d_z, d_color, d_normal, d_winner, G, plan->stamp_slot);                       \
         else hipLaunchKernelGGL((k_raster<TS, false, P>), dim3(grid), dim3(kThreads), 0, s, proj, d_col, d_nrm,         \
-                                tl, d_z, d_color, d_normal, d_winner, G, dbg);                                          \
+                                tl, d_z, d_color, d_normal, d_winner, G, plan->stamp_slot);                             \
     } while (0)
     if constexpr (TS <= 32) {
         if (with_setup) {
             // this frame's raster pass and another plan's binning pass in one launch (k_frame)
             const int nsetup = (int)((with_setup->T + kWave - 1) / kWave);
-            const RasterArgs ra{proj, d_col, d_nrm, tl, d_z, d_color, d_normal, d_winner, G, dbg};
+            const RasterArgs ra{proj, d_col, d_nrm, tl, d_z, d_color, d_normal, d_winner, G, plan->stamp_slot};
             const FrameArgs fa{ra, *with_setup, nsetup};
             if constexpr (TS == 32) {
                 if (path == kPathOwners) CR_LAUNCH_FRAME(kPathOwners);

@@ -1,7 +1,6 @@
 #!/bin/bash
-# Development build of the HIP library with the measurement knobs compiled in
-# (CRENDER_DEBUG bit mask, see csrc/raster.hip) -> /tmp/libcrender_hip_dev.so.
-# Use with CRENDER_LIB=/tmp/libcrender_hip_dev.so.  The product library has none of them.
+# A copy of the HIP library built from the working tree with extra defines (e.g. -DCRENDER_STAMPS)
+# -> /tmp/libcrender_hip_dev.so.  Use with CRENDER_LIB=/tmp/libcrender_hip_dev.so.
 #   scripts/dev_build.sh [-DNAME=VALUE ...] [--out PATH]
 cd ${GRAFT_REPO_ROOT:-$(dirname $0)/..}
 python - "$@" <<'PY'
@@ -11,8 +10,6 @@ args = sys.argv[1:]
 out = "/tmp/libcrender_hip_dev.so"
 if "--out" in args:
     i = args.index("--out"); out = args[i + 1]; del args[i:i + 2]
-nodev = "--no-dev-knobs" in args
-args = [a for a in args if a != "--no-dev-knobs"]
-_build.compile_library(out, ([] if nodev else ["-DCRENDER_DEV_KNOBS"]) + args, quiet=True)
+_build.compile_library(out, args, quiet=True)
 print(out)
 PY

@@ -9,7 +9,7 @@ several ways, one way per process:
   python scripts/placement_probe.py late   [K]   the same arena, taken AFTER the plan's workspace and the model
   python scripts/placement_probe.py reuse  [K]   torch sets; then all freed and made again (the caching allocator hands the blocks back)
   python scripts/placement_probe.py pmc    [K]   torch sets, 6 clears into each in turn and nothing else: run under
-                                                 rocprofv3 --kernel-trace --pmc ... (scripts/r6_placement.sh correlates)
+                                                 rocprofv3 --kernel-trace --pmc ... (round 6: profiles/r06/placement_trex8192.txt)
 """
 import os
 import sys

@@ -2657,7 +2657,6 @@ def test_normal_z_array_feeds_the_back_face_test(oracle):
 
 
 # ---- the raster kernels of a 32-pixel plan (crender_plan_set_raster_path): each exact on every tile ----------
-# (scripts/r6_paths.sh also runs this whole file once per kernel, CRENDER_RASTER_PATH = 0 / 1)
 @pytest.mark.parametrize("path", [0, 1])
 @pytest.mark.parametrize("name,fixture,res", SCENES)
 @pytest.mark.parametrize("mode", ["fused", "fused-scan", "split"])
@@ -2703,8 +2702,6 @@ def test_plans_pick_their_raster_kernel_from_what_their_frames_count(hip, oracle
     the launch before it).  bunny 2048^2 — 7 triangles per tile, but large ones — starts on the general kernel
     and moves to the pixel owners with its third frame; T-Rex 1024^2 on 32-pixel tiles stays; the cube (12
     triangles) starts with the owners.  Whatever the kernel, the pixels are the oracle's."""
-    if os.environ.get("CRENDER_RASTER_PATH"):
-        pytest.skip("the suite is being run with one kernel for every plan (CRENDER_RASTER_PATH)")
     for fixture, res, want in (("bunny_inputs.npz", 2048, [0, 0, 1, 1]), ("trex_inputs.npz", 1024, [0, 0, 0, 0]),
                                ("cube_inputs.npz", 256, [1, 1, 1, 1])):
         tri, col, nrm = scene(fixture)
@@ -2736,8 +2733,6 @@ def test_a_swap_chain_shares_what_one_plan_learnt(oracle):
     of them has read from its records is every plan's from its next launch on (crender_pipeline_frame).  (A plan
     learns with its third launch: its second launch's record carries what its first counted.  Six plans take
     turns: the first of them knows at the chain's thirteenth frame, all of them one round later.)"""
-    if os.environ.get("CRENDER_RASTER_PATH"):
-        pytest.skip("the suite is being run with one kernel for every plan (CRENDER_RASTER_PATH)")
     from cython3dmodelrenderer_amd.pixel_buffer_filler import AdvancedPixelBufferFiller
     tri, col, nrm = scene("bunny_inputs.npz")
     res = 2048
