@@ -17,6 +17,11 @@ LIB_PATH = os.path.join(_HERE, "libcrender_hip.so")
 # model_ops.hip  rows f1-f4 of SURVEY 8f     abi.hip  plans, frames, swap chain (no kernels)
 SOURCES = ["abi.hip", "binning.hip", "raster.hip", "model_ops.hip"]
 HEADERS = ["common.h", "binning.h", "plan.h", "raster_math.h", os.path.join("..", "..", "include", "crender_hip.h")]
+# wireframe.hip  EdgeOnlyPixelBufferFiller (include/crender_wire.h).  Linked into the same library but
+# kept out of source_sha16(): that fingerprint names the kernels the committed profiles/*.json were
+# measured on, and the wireframe kernels are none of them.
+WIRE_SOURCES = ["wireframe.hip"]
+WIRE_HEADERS = [os.path.join("..", "..", "include", "crender_wire.h")]
 
 # Float parity with the reference depends on these (DESIGN.md "Numerics"):
 #   -ffp-contract=off                           no FMA contraction (hipcc defaults to fast)
@@ -62,7 +67,8 @@ def needs_build() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     built = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(SRC_DIR, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
+    deps = [os.path.join(SRC_DIR, s) for s in SOURCES + HEADERS + WIRE_SOURCES + WIRE_HEADERS] + \
+        [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > built for d in deps)
 
 
@@ -72,7 +78,7 @@ def compile_library(out: str, extra_flags=(), sources=None, src_dir: str = SRC_D
     defines of diagnostic builds (-DCRENDER_STAMPS, ...)."""
     import tempfile
     from concurrent.futures import ThreadPoolExecutor
-    sources = list(sources or SOURCES)
+    sources = list(sources or SOURCES + WIRE_SOURCES)
     err = subprocess.DEVNULL if quiet else None
     with tempfile.TemporaryDirectory(prefix="crender_build_") as tmp:
         objs = [os.path.join(tmp, os.path.splitext(s)[0] + ".o") for s in sources]

@@ -78,6 +78,13 @@ SIGNATURES = {
     "crender_model_texture_colors": (_i32, [_vp, _i32, _i64, _vp, _i32, _i32, _vp, _vp]),
 }
 
+# the wireframe filler's entry points (include/crender_wire.h), bound from a table of their own
+WIRE_DOTS, WIRE_FORCE_COLORS, WIRE_CLEAR = 1, 2, 4
+WIRE_SIGNATURES = {
+    "crender_wire_key_bytes": (_sz, [_i32, _i32]),
+    "crender_wire_draw": (_i32, [_vp, _vp, _i64, _f32p, _vp, _vp, _vp, _vp, _i32, _i32, _u32, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -101,7 +108,7 @@ def load():
             f"{path} is missing: build it with `python -m cython3dmodelrenderer_amd._build` "
             "(or __graft_entry__.build()).  There is no CPU fallback for the rasterizer.")
     L = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(WIRE_SIGNATURES.items()):
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

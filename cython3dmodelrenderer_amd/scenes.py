@@ -33,6 +33,23 @@ def fit_model(m):
     m.shift(shift=[0, 0, 1])
 
 
+def fit_soup_to_frame(tri, h, w):
+    """Vertices of the triangle soup `tri` (float32 [T,3,3]) fitted into an h x w frame as the
+    reference's ``Renderer.render(normalize_model=True)`` fits a model (py/renderer.py:41-46), the
+    soup taken as a ``Model`` whose vertices are the 3 T corners.  The inputs of the wireframe
+    fixtures (scripts/make_wire_golden.py), which draw raw x / y with no projection."""
+    from .data_structures.model import Model
+    T = tri.shape[0]
+    corners = np.asarray(tri, np.float32).reshape(3 * T, 3)
+    faces = np.arange(3 * T, dtype=np.int32).reshape(T, 3)
+    m = Model(corners, faces, normals=np.zeros_like(corners), triangles_normals=faces, recalculate_normals=False)
+    centre = (h // 2, w // 2)
+    span = min(centre)
+    m.scale(span / m.get_max_span())
+    m.shift(-m.get_mean_vertex() + [centre[0], centre[1], -span])
+    return np.ascontiguousarray(m._vertices_by_triangles)
+
+
 def load_fixture(name):
     """(tri, col, nrm) float32 [T,3,3] from tests/golden/<name>."""
     with np.load(os.path.join(GOLDEN_DIR, name)) as z:

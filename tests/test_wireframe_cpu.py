@@ -1,0 +1,217 @@
+"""The wireframe filler without a GPU: its imports, the host line and the host filler against fixtures
+made by the reference's own code (scripts/make_wire_golden.py), the C ABI's argument checks, and the
+host model the GPU tests compare with (tests/wire_ref.py)."""
+import ctypes as C
+import hashlib
+import json
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from util import sha
+from wire_ref import HostImage, line_pixels, wire_plane
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+@pytest.fixture(scope="module")
+def capi():
+    from cython3dmodelrenderer_amd import _build, _capi
+    _build.build()           # hipcc cross-compiles for gfx950 without a GPU
+    return _capi
+
+
+@pytest.fixture(scope="module")
+def lines():
+    with np.load(os.path.join(GOLDEN, "wire_lines.npz")) as z:
+        return {k: z[k] for k in z.files}
+
+
+@pytest.fixture(scope="module")
+def wire_golden():
+    with open(os.path.join(GOLDEN, "wire_golden.json")) as fh:
+        return json.load(fh)
+
+
+class _Log:
+    def __init__(self):
+        self.px = []
+
+    def set_pixel(self, x, y, value):
+        self.px.append((x, y))
+
+
+def test_the_reference_import_paths_exist():
+    from cython3dmodelrenderer_amd.pixel_buffer_filler import EdgeOnlyPixelBufferFiller, LineBresenham, LineDrawer
+    from cython3dmodelrenderer_amd.pixel_buffer_filler.edge_only import EdgeOnlyPixelBufferFiller as E2
+    from cython3dmodelrenderer_amd.pixel_buffer_filler.edge_only.line_drawer import LineBresenham as L2, LineDrawer as D2
+    from cython3dmodelrenderer_amd.pixel_buffer_filler.edge_only.line_drawer.bresenham.line_bresenham import \
+        LineBresenham as L3
+    from cython3dmodelrenderer_amd.pixel_buffer_filler.edge_only.edge_only_pixel_buffer_filler import \
+        EdgeOnlyPixelBufferFiller as E3
+    assert EdgeOnlyPixelBufferFiller is E2 is E3 and LineBresenham is L2 is L3 and LineDrawer is D2
+    assert issubclass(LineBresenham, LineDrawer)
+
+
+def test_host_bresenham_reproduces_the_reference_lines(lines):
+    from cython3dmodelrenderer_amd.pixel_buffer_filler import LineBresenham
+    drawer = LineBresenham()
+    full = {int(i): n for n, i in enumerate(lines["full_index"])}
+    off = lines["full_offsets"]
+    for n in range(len(lines["p1"])):
+        p1, p2 = [int(v) for v in lines["p1"][n]], [int(v) for v in lines["p2"][n]]
+        log = _Log()
+        drawer.draw_line(p1, p2, log, None)
+        seq = np.asarray(log.px, np.int32)
+        assert len(seq) == lines["length"][n], (n, p1, p2)
+        if n in full:
+            j = full[n]
+            assert np.array_equal(seq, lines["full_xy"][off[j]:off[j + 1]]), (n, p1, p2)
+        assert hashlib.sha256(seq.tobytes()).digest() == lines["sha"][n].tobytes(), (n, p1, p2)
+    assert len(lines["p1"]) >= 3000 and lines["length"].max() > 5000
+
+
+def test_closed_form_reproduces_the_reference_lines(lines):
+    """The form the kernel evaluates (and tests/wire_ref.py with it), on every line of the fixture."""
+    for n in range(len(lines["p1"])):
+        seq = line_pixels(tuple(int(v) for v in lines["p1"][n]), tuple(int(v) for v in lines["p2"][n]))
+        assert hashlib.sha256(seq.astype(np.int32).tobytes()).digest() == lines["sha"][n].tobytes(), n
+
+
+def _fitted(entry):
+    from cython3dmodelrenderer_amd import scenes
+    tri, col, _ = scenes.load_fixture(entry["fixture"])
+    fitted = scenes.fit_soup_to_frame(tri, entry["h"], entry["w"])
+    assert hashlib.sha256(fitted.tobytes()).hexdigest() == entry["vertices_sha"]
+    return fitted, col
+
+
+@pytest.mark.parametrize("name", ["cube256", "trex1024", "bunny1024"])
+def test_host_filler_reproduces_the_reference_planes(name, wire_golden):
+    from cython3dmodelrenderer_amd.pixel_buffer_filler import EdgeOnlyPixelBufferFiller, LineBresenham
+    entry = wire_golden["scenes"][name]
+    tri, col = _fitted(entry)
+    H, W = entry["h"], entry["w"]
+    for key, want in entry["planes"].items():
+        edges, forced = key.startswith("edges"), key.endswith("forced")
+        f = EdgeOnlyPixelBufferFiller(LineBresenham(), wire_golden["line_color"], draw_edges=edges,
+                                      force_triangle_colors=forced)
+        img = HostImage(H, W)
+        for i in range(len(tri)):
+            f.compute_triangle_statistics(tri[i], col[i] if forced else None, None, img, None, None)
+        assert sha(img.a) == want, (name, key)
+        # and the vectorised model of the GPU tests
+        got = wire_plane(tri, H, W, wire_golden["line_color"], edges, col if forced else None)
+        assert sha(got) == want, (name, key, "wire_ref")
+
+
+def test_host_model_equals_the_host_loop_on_random_soups():
+    """tests/wire_ref.py (clipping before expansion, last writer per pixel) against the per-pixel loop,
+    on soups that reach far off a small frame and pile many triangles on the same pixels."""
+    from cython3dmodelrenderer_amd.pixel_buffer_filler import EdgeOnlyPixelBufferFiller, LineBresenham
+    rng = np.random.default_rng(7)
+    H, W = 48, 64
+    for trial in range(12):
+        T = int(rng.integers(1, 60))
+        tri = rng.uniform(-300, 300, (T, 3, 3)).astype(np.float32)
+        if trial % 3 == 0:
+            tri[:, :, :2] = rng.uniform(-2, 70, (T, 3, 2)).astype(np.float32)
+        if trial % 4 == 1:
+            tri[:, 1] = tri[:, 0]            # degenerate
+        col = rng.uniform(0, 255, (T, 3, 3)).astype(np.float32)
+        base = rng.uniform(0, 9, (H, W, 3)).astype(np.float32)
+        for edges in (True, False):
+            for forced in (False, True):
+                f = EdgeOnlyPixelBufferFiller(LineBresenham(), (1.5, 2, 3), draw_edges=edges,
+                                              force_triangle_colors=forced)
+                img = HostImage(H, W, base)
+                for i in range(T):
+                    f.compute_triangle_statistics(tri[i], col[i], None, img, None, None)
+                got = wire_plane(tri, H, W, (1.5, 2, 3), edges, col if forced else None, base=base)
+                assert np.array_equal(got.view(np.uint32), img.a.view(np.uint32)), (trial, edges, forced)
+
+
+def test_wire_header_symbols_are_exported_and_bound(capi):
+    header = open(os.path.join(ROOT, "include", "crender_wire.h")).read()
+    declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
+    assert declared == set(capi.WIRE_SIGNATURES), declared ^ set(capi.WIRE_SIGNATURES)
+    assert not declared & set(capi.SIGNATURES)
+    L = capi.load()
+    for name in declared:
+        assert getattr(L, name).argtypes == capi.WIRE_SIGNATURES[name][1]
+    out = subprocess.check_output(["nm", "-D", "--defined-only", capi.lib_path()], text=True)
+    assert declared <= set(re.findall(r" T (crender_\w+)", out))
+    for flag, value in (("CRENDER_WIRE_DOTS", capi.WIRE_DOTS), ("CRENDER_WIRE_FORCE_COLORS", capi.WIRE_FORCE_COLORS),
+                        ("CRENDER_WIRE_CLEAR", capi.WIRE_CLEAR)):
+        assert re.search(rf"\b{flag} = {value}u\b", header), flag
+
+
+def test_wire_sources_stay_out_of_the_profile_fingerprint():
+    from cython3dmodelrenderer_amd import _build
+    assert "wireframe.hip" in _build.WIRE_SOURCES and "wireframe.hip" not in _build.SOURCES
+    assert not any("crender_wire" in h for h in _build.HEADERS)
+
+
+def test_wire_argument_errors_without_a_gpu(capi):
+    L = capi.load()
+    E = capi.EINVAL
+    assert L.crender_wire_key_bytes(4, 5) == 80
+    assert L.crender_wire_key_bytes(0, 5) == 0 and L.crender_wire_key_bytes(4, -1) == 0
+    assert L.crender_wire_key_bytes((1 << 20) + 1, 4) == 0
+    line = (C.c_float * 3)(1, 2, 3)
+    fake = C.c_void_p(0x1000)          # never dereferenced: every call below fails its checks first
+
+    def draw(tri=fake, col=None, T=1, line=line, z=None, c=fake, n=None, key=None, H=4, W=4, flags=0, status=fake):
+        return L.crender_wire_draw(tri, col, T, line, z, c, n, key, H, W, flags, status, None)
+
+    assert draw(tri=None) == E
+    assert draw(c=None) == E
+    assert draw(status=None) == E
+    assert draw(T=-1) == E
+    assert draw(H=0) == E and draw(W=-3) == E and draw(W=(1 << 20) + 1) == E
+    assert draw(line=None) == E                                          # constant colour needs it
+    assert draw(flags=8) == E                                            # unknown flag
+    assert draw(flags=capi.WIRE_FORCE_COLORS, key=fake) == E             # no colours
+    assert draw(flags=capi.WIRE_FORCE_COLORS, col=fake) == E             # no key plane
+    assert draw(flags=capi.WIRE_FORCE_COLORS, col=fake, key=fake, T=1 << 30) == E
+    assert draw(flags=capi.WIRE_CLEAR) == E and draw(flags=capi.WIRE_CLEAR, z=fake) == E
+    assert b"crender_wire_draw" in L.crender_last_error()
+
+
+def test_device_path_refuses_a_foreign_line_drawer_and_missing_inputs():
+    from cython3dmodelrenderer_amd.pixel_buffer_filler import EdgeOnlyPixelBufferFiller, LineBresenham, LineDrawer
+
+    class Dashed(LineDrawer):
+        def draw_line(self, p1, p2, image, color):
+            image.set_pixel(*p1, color)
+
+    class Bresenham2(LineBresenham):
+        def draw_line(self, p1, p2, image, color):
+            super().draw_line(p1, p2, image, color)
+
+    tri = np.zeros((1, 3, 3), np.float32)
+    for drawer in (Dashed(), Bresenham2()):
+        f = EdgeOnlyPixelBufferFiller(drawer, (255, 255, 255), h=8, w=8)
+        with pytest.raises(TypeError):
+            f.render_arrays(tri)
+
+    class M:
+        _vertices_by_triangles = tri
+        _colors_by_triangles = None
+
+    with pytest.raises(TypeError):
+        EdgeOnlyPixelBufferFiller(Dashed(), (1, 2, 3), h=8, w=8).render_model(M())
+    with pytest.raises(ValueError):                                      # no frame size
+        EdgeOnlyPixelBufferFiller(LineBresenham(), (1, 2, 3)).render_arrays(tri)
+    with pytest.raises(ValueError):                                      # forced colours, none given
+        EdgeOnlyPixelBufferFiller(LineBresenham(), (1, 2, 3), force_triangle_colors=True, h=8, w=8).render_model(M())
+    # the host method takes any line drawer, as the reference's does
+    f = EdgeOnlyPixelBufferFiller(Dashed(), (1, 2, 3))
+    img = HostImage(8, 8)
+    f.compute_triangle_statistics(np.array([[1, 2, 0], [5, 5, 0], [3, 7, 0]], np.float32), None, None, img, None, None)
+    assert (img.a[2, 1] == (1, 2, 3)).all() and (img.a[5, 5] == (1, 2, 3)).all() and (img.a[7, 3] == (1, 2, 3)).all()
+    assert int((img.a != 0).any(-1).sum()) == 3
