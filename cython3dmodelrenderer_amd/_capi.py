@@ -85,6 +85,14 @@ WIRE_SIGNATURES = {
     "crender_wire_draw": (_i32, [_vp, _vp, _i64, _f32p, _vp, _vp, _vp, _vp, _i32, _i32, _u32, _vp, _vp]),
 }
 
+# the numpy filler's entry points (include/crender_py.h), bound from a table of their own
+PY_CLEAR = 1
+PY_SIGNATURES = {
+    "crender_py_scratch_bytes": (_sz, [_i32, _i32, _i64]),
+    "crender_py_draw": (_i32, [_vp, _vp, _vp, _i64, _f32p, _vp, _vp, _vp, _i32, _i32, _u32, _vp, _vp, _vp]),
+    "crender_py_guro": (_i32, [_vp, _vp, _f32p, _i32, _i32, _vp]),
+}
+
 _lib = None
 
 
@@ -108,7 +116,8 @@ def load():
             f"{path} is missing: build it with `python -m cython3dmodelrenderer_amd._build` "
             "(or __graft_entry__.build()).  There is no CPU fallback for the rasterizer.")
     L = C.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(WIRE_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(WIRE_SIGNATURES.items()) + \
+            list(PY_SIGNATURES.items()):
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

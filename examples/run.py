@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
 """The reference's run.py scene (reference: run.py:20-41) on the MI355X path.
 
-    python examples/run.py /path/to/objects/T-Rex.obj output.png [size] [--device-model]
+    python examples/run.py /path/to/objects/T-Rex.obj output.png [size] [--device-model] [--py]
 
 ``--device-model``: the transforms of the scene — two rotations with their vertex-normal
 recomputation (1.2 s of numpy loops on the host for T-Rex) and the fit — run on a
 ``DeviceModel`` kept in HBM (rotate / normals to 1e-5 of the host Model, the rest bit for bit).
+
+``--py``: the reference's ``py_renderer`` instead (run.py:11-18): the numpy path's ``py.Renderer`` with
+its filler, ``SimpleIterator`` and uint8 ``GuroIllumination``, drawn in one GPU call, then
+``write_to_file``.
 
 Model -> AdvancedPixelBufferFiller (HIP, GuroIllumination fused into the raster kernel's stores)
 -> flip + uint8 (HIP) -> PNG.
@@ -24,6 +28,17 @@ from cython3dmodelrenderer_amd.pixel_buffer_filler import AdvancedPixelBufferFil
 from cython3dmodelrenderer_amd.scenes import fit_model                            # noqa: E402
 
 
+def py_renderer(model, size, out):
+    """The reference's py_renderer (run.py:11-18)."""
+    from cython3dmodelrenderer_amd import py
+    from cython3dmodelrenderer_amd.triangle_iterator import SimpleIterator
+    filler = py.pixel_buffer_filler.AdvancedPixelBufferFiller(size, size, fov=45)
+    illumination = py.illumination.GuroIllumination([0, 0, 1])
+    renderer = py.Renderer(filler, illumination, SimpleIterator, *filler.get_size())
+    image = renderer.render(model)
+    image.write_to_file(out)
+
+
 def main():
     if len(sys.argv) < 3:
         raise SystemExit(__doc__)
@@ -32,6 +47,14 @@ def main():
     size = int(args[2]) if len(args) > 2 else 1024
     t0 = time.perf_counter()
     model = Model.read_model(obj, recalculate_normals="--device-model" not in sys.argv)
+    if "--py" in sys.argv:
+        model.rotate([-90, 180, 0])
+        model.rotate([10, -80, 0])
+        fit_model(model)
+        t1 = time.perf_counter()
+        py_renderer(model, size, out)
+        print(f"model {t1 - t0:.2f} s, py renderer {1e3 * (time.perf_counter() - t1):.1f} ms, wrote {out}")
+        return
     if model._colors_by_triangles is None:
         model.set_uniform_color()            # untextured models: white, as the py renderer does
     if "--device-model" in sys.argv:

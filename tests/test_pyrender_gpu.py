@@ -1,0 +1,376 @@
+"""The numpy path on the GPU (csrc/pyfill.hip): every fixture case bit for bit through py.Renderer and
+the C ABI, random near-tie soups and T-Rex at 4096^2 against tests/py_ref.py, culls, single-pixel
+triangles, custom iterators and fillers, the device Guro and the domain errors."""
+import ctypes as C
+import hashlib
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from cython3dmodelrenderer_amd import _capi, py, scenes
+from cython3dmodelrenderer_amd.py.data_structures import Buffer
+from cython3dmodelrenderer_amd.py.illumination import GuroIllumination, NoIllumination
+from cython3dmodelrenderer_amd.py.pixel_buffer_filler import AdvancedPixelBufferFiller, EdgeOnlyPixelBufferFiller
+from cython3dmodelrenderer_amd.triangle_iterator import DepthIterator, SimpleIterator, TriangleIterator
+
+import py_ref
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
+with open(os.path.join(GOLDEN, "py_golden.json")) as _fh:
+    DOC = json.load(_fh)
+SOUPS = np.load(os.path.join(GOLDEN, "py_soups.npz"))
+ITERS = {"simple": SimpleIterator, "depth": DepthIterator}
+
+
+def sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+class Soup:
+    def __init__(self, tri, col, nrm):
+        self._vertices_by_triangles, self._colors_by_triangles, self._normals_by_triangles = tri, col, nrm
+
+    def n_triangles(self):
+        return len(self._vertices_by_triangles)
+
+    def get_triangle(self, i):
+        return (self._vertices_by_triangles[i],
+                None if self._colors_by_triangles is None else self._colors_by_triangles[i],
+                self._normals_by_triangles[i])
+
+
+def renderer(h, w, it, fov, light=False):
+    filler = AdvancedPixelBufferFiller(h, w, fov=fov)
+    illum = GuroIllumination([0, 0, 1]) if light else NoIllumination()
+    return py.Renderer(filler, illum, it, h, w, use_tqdm=False)
+
+
+def assert_planes(r, want):
+    assert sha(r.z_buffer.get_image()) == want["z"]
+    assert sha(r.color_buffer.get_image()) == want["color"]
+    assert sha(r.n_buffer.get_image()) == want["normals"]
+
+
+SCENE_CASES = [(s, c) for s in DOC["scenes"] for c in DOC["scenes"][s]["cases"]]
+
+
+@pytest.mark.parametrize("scene,case", SCENE_CASES)
+def test_renderer_scenes_match_fixtures(scene, case):
+    sc = DOC["scenes"][scene]
+    tri, col, nrm = scenes.load_fixture(sc["fixture"])
+    it, colours = case.split("_")
+    want = sc["cases"][case]
+    for light in (False, True):
+        r = renderer(sc["h"], sc["w"], ITERS[it], DOC["fov"], light)
+        np.random.seed(DOC["seed"])
+        r.render(Soup(tri, col if colours == "own" else None, nrm), random_colors=colours == "random")
+        if light:
+            assert sha(r.color_buffer.get_image()) == want["guro_color"]
+        else:
+            assert_planes(r, want)
+
+
+def test_renderer_composites_until_reset():
+    r = renderer(1024, 1024, SimpleIterator, DOC["fov"])
+    t1, c1, n1 = scenes.load_fixture("trex_inputs.npz")
+    t2, _, n2 = scenes.load_fixture("cube_inputs.npz")
+    r.render(Soup(t1, c1, n1))
+    np.random.seed(DOC["seed"])
+    r.render(Soup(t2, None, n2))
+    assert_planes(r, DOC["composite"]["planes"])
+    r.reset_buffers()
+    r.render(Soup(t1, c1, n1))
+    assert_planes(r, DOC["scenes"]["trex1024"]["cases"]["simple_own"])
+
+
+@pytest.mark.parametrize("s", range(DOC["soups"]["n"]))
+@pytest.mark.parametrize("it", ["simple", "depth"])
+def test_soups_match_fixtures(s, it):
+    tri, col, nrm = SOUPS[f"s{s}_tri"], SOUPS[f"s{s}_col"], SOUPS[f"s{s}_nrm"]
+    h, w = DOC["soups"]["h"], DOC["soups"]["w"]
+    r = renderer(h, w, ITERS[it], DOC["soups"]["fov"])
+    r.render(Soup(tri, col, nrm))
+    for plane, buf in (("z", r.z_buffer), ("color", r.color_buffer), ("normals", r.n_buffer)):
+        assert np.array_equal(buf.get_image().view(np.uint8), SOUPS[f"s{s}_{it}_{plane}"].view(np.uint8)), plane
+
+
+def c_abi_draw(tri, col, nrm, z, c, n, fov, clear=False):
+    """crender_py_draw on device copies of the planes, which are written back."""
+    lib = _capi.load()
+    h, w = z.shape[:2]
+    filler = AdvancedPixelBufferFiller(h, w, fov=fov)
+    dev = torch.device("cuda:0")
+    d = [torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev) for a in (tri, col, nrm)]
+    planes = [torch.from_numpy(np.ascontiguousarray(p)).to(dev) for p in (z, c, n)]
+    scratch = torch.empty(lib.crender_py_scratch_bytes(h, w, len(tri)), dtype=torch.uint8, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _capi.check(lib.crender_py_draw(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), len(tri),
+                                    (C.c_float * 4)(*filler._proj.tolist()), planes[0].data_ptr(),
+                                    planes[1].data_ptr(), planes[2].data_ptr(), h, w,
+                                    _capi.PY_CLEAR if clear else 0, scratch.data_ptr(), status.data_ptr(),
+                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), "crender_py_draw")
+    torch.cuda.synchronize()
+    for p, dp in zip((z, c, n), planes):
+        p[...] = dp.cpu().numpy()
+    return int(status.item())
+
+
+def test_c_abi_matches_fixture_with_clear():
+    sc = DOC["scenes"]["trex1024"]
+    tri, col, nrm = scenes.load_fixture(sc["fixture"])
+    order = DepthIterator.draw_order(Soup(tri, col, nrm))
+    z = np.zeros((1024, 1024, 1), np.float32)             # garbage: CLEAR starts afresh
+    c = np.full((1024, 1024, 3), 7, np.uint8)
+    n = np.ones((1024, 1024, 3), np.float32)
+    assert c_abi_draw(tri[order], col[order], nrm[order], z, c, n, DOC["fov"], clear=True) == 0
+    want = sc["cases"]["depth_own"]
+    assert (sha(z), sha(c), sha(n)) == (want["z"], want["color"], want["normals"])
+
+
+def near_tie_soup(rng, T, h, w):
+    """Triangles in a few shared planes and duplicates, the normals facing the camera."""
+    base = rng.uniform(-0.4, 0.4, (T, 3, 2)).astype(np.float32)
+    z = rng.choice(np.float32([0.7, 0.9, 1.3]), (T, 1, 1)) + \
+        rng.integers(-2, 3, (T, 3, 1)).astype(np.float32) * np.float32(1e-7)
+    tri = np.concatenate([base * z, np.broadcast_to(z, (T, 3, 1))], axis=2).astype(np.float32)
+    dup = rng.integers(0, T, T // 4)
+    tri[rng.integers(0, T, T // 4)] = tri[dup]
+    col = rng.integers(0, 256, (T, 3, 3)).astype(np.float32)
+    nrm = rng.normal(0, 0.3, (T, 3, 3)).astype(np.float32)
+    nrm[..., 2] = -1
+    return tri, col, nrm
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_random_near_tie_soups_match_host_model(seed):
+    rng = np.random.default_rng(100 + seed)
+    h, w = (37, 53) if seed % 2 else (64, 64)
+    tri, col, nrm = near_tie_soup(rng, 300, h, w)
+    want = py_ref.new_planes(h, w)
+    got = py_ref.new_planes(h, w)
+    if seed >= 3:                                            # on top of an earlier draw
+        t0, c0, n0 = near_tie_soup(rng, 100, h, w)
+        for planes in (want, got):
+            py_ref.draw(t0, c0, n0, *planes, 60.0)
+    py_ref.draw(tri, col, nrm, *want, 60.0)
+    assert c_abi_draw(tri, col, nrm, *got, 60.0) == 0
+    for a, b in zip(got, want):
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+def test_single_inside_pixel_triangles():
+    h = w = 32
+    rng = np.random.default_rng(9)
+    sx = np.floor(rng.uniform(2, 30, (200, 1))) + np.float32([[-0.3, 0.4, 0.05]])
+    sy = np.floor(rng.uniform(2, 30, (200, 1))) + np.float32([[-0.2, -0.25, 0.45]])
+    z = rng.uniform(0.5, 2.0, (200, 3))
+    x, y = (sx / (w / 2) - 1) * z, (sy / (h / 2) - 1) * z              # fov 90, square
+    tri = np.stack([x, y, z], -1).astype(np.float32)
+    col = rng.integers(0, 256, (200, 3, 3)).astype(np.float32)
+    nrm = np.broadcast_to(np.float32([0, 0, -1]), (200, 3, 3)).copy()
+    want, got = py_ref.new_planes(h, w), py_ref.new_planes(h, w)
+    py_ref.draw(tri, col, nrm, *want, 90.0)
+    assert c_abi_draw(tri, col, nrm, *got, 90.0) == 0
+    assert (want[0] < 1e6).sum() > 20
+    for a, b in zip(got, want):
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+def test_culls():
+    """Back-facing and degenerate triangles draw nothing; an inf in the normals' x is not culled."""
+    h = w = 32
+    tri = np.float32([[[-0.5, -0.5, 1], [0.5, -0.5, 1], [0, 0.5, 1]]] * 3)
+    tri[1, 2, :2] = tri[1, 1, :2]                                    # degenerate in x / y
+    nrm = np.broadcast_to(np.float32([0, 0, 1]), (3, 3, 3)).copy()   # all back-facing
+    col = np.full((3, 3, 3), 200, np.float32)
+    r = renderer(h, w, SimpleIterator, 90.0)
+    r.pixel_buffer_filler.draw_sequence(tri, col, nrm, r.color_buffer, r.z_buffer, r.n_buffer)
+    assert (r.z_buffer.get_image() == np.float32(1e6)).all() and r.color_buffer.get_image().sum() == 0
+    nrm[0, 0, 2] = -3                                                # triangle 0 faces the camera
+    r.pixel_buffer_filler.draw_sequence(tri, col, nrm, r.color_buffer, r.z_buffer, r.n_buffer)
+    assert (r.color_buffer.get_image() == 200).all(axis=-1).sum() > 100
+
+
+class ReverseIterator(TriangleIterator):
+    def __init__(self, model):
+        self._items = [model.get_triangle(i) for i in reversed(range(model.n_triangles()))]
+
+    def __iter__(self):
+        return iter(self._items)
+
+    def __next__(self):
+        raise StopIteration
+
+
+def test_custom_iterator_is_drained_on_the_host():
+    tri, col, nrm = SOUPS["s1_tri"], SOUPS["s1_col"], SOUPS["s1_nrm"]
+    h, w = DOC["soups"]["h"], DOC["soups"]["w"]
+    r = renderer(h, w, ReverseIterator, DOC["soups"]["fov"])
+    r.render(Soup(tri, col, nrm))
+    want = py_ref.new_planes(h, w)
+    py_ref.draw(tri[::-1], col[::-1], nrm[::-1], *want, DOC["soups"]["fov"])
+    for a, b in zip((r.z_buffer.get_image(), r.color_buffer.get_image(), r.n_buffer.get_image()), want):
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+def test_custom_filler_takes_the_per_triangle_loop():
+    calls = []
+
+    class Counting:
+        def compute_triangle_statistics(self, triangle, colors, normals, cb, zb, nb):
+            calls.append(colors)
+
+    tri, col, nrm = SOUPS["s0_tri"], SOUPS["s0_col"], SOUPS["s0_nrm"]
+    r = py.Renderer(Counting(), NoIllumination(), SimpleIterator, 8, 8, use_tqdm=False)
+    np.random.seed(3)
+    r.render(Soup(tri, None, nrm))
+    np.random.seed(3)
+    assert len(calls) == len(tri) and all((c == np.random.randint(256, size=3)).all() for c in calls)
+    wire = EdgeOnlyPixelBufferFiller(None, [255, 255, 255], draw_edges=False)
+    r = py.Renderer(wire, NoIllumination(), SimpleIterator, 48, 48, use_tqdm=False)
+    px = np.random.default_rng(1).uniform(2, 40, (20, 3, 3)).astype(np.float32)
+    r.render(Soup(px, col[:20], nrm[:20]))
+    assert r.color_buffer.get_image().sum() > 0
+
+
+def test_device_guro_matches_host():
+    rng = np.random.default_rng(4)
+    c = rng.integers(0, 256, (40, 50, 3)).astype(np.uint8)
+    n = rng.normal(0, 1, (40, 50, 3)).astype(np.float32)
+    n[0, 0] = 0
+    n[1, 1] = [np.nan, 0, 1]
+    for light in ([0, 0, 1], [0.3, -0.2, 0.9]):
+        g = GuroIllumination(light)
+        hc, hn = Buffer(40, 50, dim=3, dtype="uint8"), Buffer(40, 50, dim=3)
+        hc[...], hn[...] = c, n
+        g.draw_illumination(hc, hn)
+        dc, dn = torch.from_numpy(c.copy()).cuda(), torch.from_numpy(n).cuda()
+        g.draw_illumination_device(dc, dn)
+        assert np.array_equal(dc.cpu().numpy(), hc[...])
+
+
+@pytest.mark.parametrize("what", ["nan_vertex", "inf_normal", "zero_z", "too_big"])
+def test_domain_errors_draw_nothing(what):
+    tri, col, nrm = [a.copy() for a in (SOUPS["s0_tri"], SOUPS["s0_col"], SOUPS["s0_nrm"])]
+    h = w = DOC["soups"]["h"]
+    r = renderer(h, w, SimpleIterator, 90.0)
+    r.render(Soup(SOUPS["s2_tri"], SOUPS["s2_col"], SOUPS["s2_nrm"]))
+    before = [b.get_image().copy() for b in (r.z_buffer, r.color_buffer, r.n_buffer)]
+    if what == "nan_vertex":
+        tri[5, 1, 0] = np.nan
+    elif what == "inf_normal":
+        nrm[3, 2, 1] = np.inf
+    elif what == "zero_z":
+        tri[7, 0, 2] = -0.0
+    if what == "too_big":
+        with pytest.raises(ValueError):
+            AdvancedPixelBufferFiller(1 << 16, 8).draw_sequence(tri, col, nrm, Buffer(1 << 16, 8, 3, "uint8"),
+                                                                Buffer(1 << 16, 8, 1), Buffer(1 << 16, 8, 3))
+        return
+    with pytest.raises(ValueError):
+        r.render(Soup(tri, col, nrm))
+    for b, want in zip((r.z_buffer, r.color_buffer, r.n_buffer), before):
+        assert np.array_equal(b.get_image(), want)
+
+
+def test_trex_4096_matches_host_model():
+    tri, col, nrm = scenes.load_fixture("trex_inputs.npz")
+    order = DepthIterator.draw_order(Soup(tri, col, nrm))
+    tri, col, nrm = tri[order], col[order], nrm[order]
+    got, want = py_ref.new_planes(4096, 4096), py_ref.new_planes(4096, 4096)
+    assert c_abi_draw(tri, col, nrm, *got, 45.0) == 0
+    py_ref.draw(tri, col, nrm, *want, 45.0)
+    assert (want[0] < 1e6).sum() > 1_000_000
+    for a, b in zip(got, want):
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+@pytest.mark.parametrize("what", ["nan_vertex", "inf_colour", "inf_normal", "zero_z"])
+def test_c_abi_domain_error_draws_nothing_even_with_clear(what):
+    """The device check alone (no host check in the way): status 1 and the planes untouched."""
+    tri, col, nrm = [a.copy() for a in (SOUPS["s0_tri"], SOUPS["s0_col"], SOUPS["s0_nrm"])]
+    h = w = DOC["soups"]["h"]
+    z, c, n = py_ref.new_planes(h, w)
+    assert c_abi_draw(SOUPS["s2_tri"], SOUPS["s2_col"], SOUPS["s2_nrm"], z, c, n, 90.0) == 0
+    before = [p.copy() for p in (z, c, n)]
+    {"nan_vertex": lambda: tri.__setitem__((5, 1, 0), np.nan),
+     "inf_colour": lambda: col.__setitem__((9, 0, 2), np.inf),
+     "inf_normal": lambda: nrm.__setitem__((3, 2, 1), -np.inf),
+     "zero_z": lambda: tri.__setitem__((7, 0, 2), -0.0)}[what]()
+    assert c_abi_draw(tri, col, nrm, z, c, n, 90.0, clear=True) == 1
+    for p, want in zip((z, c, n), before):
+        assert np.array_equal(p.view(np.uint8), want.view(np.uint8))
+
+
+def test_tiny_negative_normal_sum_is_culled_on_the_device():
+    tri = np.float32([[[-0.5, -0.5, 1], [0.5, -0.5, 1], [0, 0.5, 1]]] * 2)
+    col = np.full((2, 3, 3), 200, np.float32)
+    nrm = np.zeros((2, 3, 3), np.float32)
+    nrm[0, 0, 2] = -np.float32(2.0 ** -149)                # mean z -0: culled
+    nrm[1, :2, 2] = -np.float32(2.0 ** -149)               # mean z -2^-149: drawn
+    for k, drawn in ((0, False), (1, True)):
+        z, c, n = py_ref.new_planes(16, 16)
+        assert c_abi_draw(tri[k:k + 1], col[k:k + 1], nrm[k:k + 1], z, c, n, 90.0) == 0
+        assert ((z < 1e6).sum() > 20) == drawn
+
+
+def test_get_triangle_only_model_is_drained():
+    class Plain:                                            # the reference iterators' protocol only
+        def __init__(self, s):
+            self._s = Soup(SOUPS[f"s{s}_tri"], SOUPS[f"s{s}_col"], SOUPS[f"s{s}_nrm"])
+
+        def n_triangles(self):
+            return self._s.n_triangles()
+
+        def get_triangle(self, i):
+            return self._s.get_triangle(i)
+
+    h, w = DOC["soups"]["h"], DOC["soups"]["w"]
+    for it in ("simple", "depth"):
+        r = renderer(h, w, ITERS[it], DOC["soups"]["fov"])
+        r.render(Plain(3))
+        for plane, buf in (("z", r.z_buffer), ("color", r.color_buffer), ("normals", r.n_buffer)):
+            assert np.array_equal(buf.get_image().view(np.uint8), SOUPS[f"s3_{it}_{plane}"].view(np.uint8))
+
+
+def test_input_contract_raises_before_drawing():
+    tri, col, nrm = SOUPS["s0_tri"], SOUPS["s0_col"], SOUPS["s0_nrm"]
+    h = w = DOC["soups"]["h"]
+    r = renderer(h, w, SimpleIterator, 90.0)
+    f = r.pixel_buffer_filler
+    args = (r.color_buffer, r.z_buffer, r.n_buffer)
+    with pytest.raises(ValueError):
+        f.draw_sequence(tri.astype(np.float64), col, nrm, *args)
+    with pytest.raises(ValueError):
+        f.draw_sequence(tri, col, nrm.astype(np.float64), *args)
+    with pytest.raises(ValueError):
+        f.draw_sequence(tri, col.astype(np.float64) + 1e-9, nrm, *args)
+    assert (r.z_buffer.get_image() == np.float32(1e6)).all()
+    f.draw_sequence(tri, col.astype(np.float64), nrm, *args)     # float64 values float32 holds: the same draw
+    assert np.array_equal(r.color_buffer.get_image(), SOUPS["s0_simple_color"])
+
+
+@pytest.mark.parametrize("size", [512, 2048])
+def test_large_triangles_match_host_model(size):
+    """Triangles covering most of the frame (one workgroup's worth of box pixels and far more), with
+    small ones around them."""
+    rng = np.random.default_rng(size)
+    big = np.float32([[[-0.9, -0.9, 1.0], [0.9, -0.8, 1.2], [0.0, 0.95, 0.9]],
+                      [[-0.95, 0.9, 1.1], [0.9, 0.9, 0.95], [0.1, -0.9, 1.05]]])
+    small, scol, snrm = near_tie_soup(rng, 600, size, size)
+    centre = rng.uniform(-0.5, 0.5, (600, 1, 2)).astype(np.float32) * small[:, :1, 2:]
+    small[..., :2] = centre + (small[..., :2] - small[..., :2].mean(axis=1, keepdims=True)) * np.float32(0.04)
+    tri = np.concatenate([big, small])
+    col = np.concatenate([rng.integers(0, 256, (2, 3, 3)).astype(np.float32), scol])
+    nrm = np.concatenate([np.broadcast_to(np.float32([0.1, 0.2, -1]), (2, 3, 3)), snrm])
+    got, want = py_ref.new_planes(size, size), py_ref.new_planes(size, size)
+    assert c_abi_draw(tri, col, nrm, *got, 60.0) == 0
+    py_ref.draw(tri, col, nrm, *want, 60.0, chunk=1)
+    assert (want[0] < 1e6).mean() > 0.5
+    for a, b in zip(got, want):
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
