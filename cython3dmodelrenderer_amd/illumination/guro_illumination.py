@@ -4,13 +4,12 @@
     colour *= clip(n . l / (|n| + 1e-6), 0, 1)      per pixel, float32, in place
 
 ``draw_illumination`` is the numpy form on host arrays (same call sequence as the
-reference, so the same bits); ``draw_illumination_device`` runs the HIP kernel
-``crender_guro_illumination`` on the filler's device buffers; ``fuse_into`` hands the light
+reference, so the same bits); ``draw_illumination_device`` has the filler run the HIP kernel
+``crender_guro_illumination`` on its device buffers (``shade_guro`` of
+pixel_buffer_filler/_device_planes.py, which also keeps the host views right); ``fuse_into`` hands the light
 to the filler, whose cleared frames then shade each pixel as the raster kernel stores it
 (CRENDER_FUSED_GURO: no second pass over the colour and normal planes).
 """
-import ctypes as C
-
 import numpy as np
 
 from .illumination_drawer import IlluminationDrawer
@@ -28,15 +27,10 @@ class GuroIllumination(IlluminationDrawer):
         color_buffer *= np.clip(cos / (length + 1e-6), 0, 1)
 
     def draw_illumination_device(self, filler):
-        from .. import _capi
-        lib = _capi.load()
-        light = (C.c_float * 3)(*[float(v) for v in self.light_direction])
+        light = [float(v) for v in self.light_direction]      # (before the wait, not after it)
         filler._push_host_edits()
         filler.synchronize()      # the frame must be complete (bin lists may grow and redo it)
-        _capi.check(lib.crender_guro_illumination(
-            filler.color_buffer.data_ptr(), filler.normals_buffer.data_ptr(), light,
-            filler.h, filler.w, filler.y0, filler.y1, filler._stream()), "crender_guro_illumination")
-        filler._host_fresh = False
+        filler.shade_guro(light)
         return True
 
     def fuse_into(self, filler):

@@ -1,6 +1,6 @@
 """Thin tensor-level wrappers over the C ABI (include/crender_hip.h): one Python function
 per entry point, torch-ROCm tensors in, work enqueued on torch's current stream.
-The filler class and the tests are built on these."""
+The tests and the scripts use these; the fillers call the C ABI themselves (``_capi``, ``crender_torch``)."""
 from __future__ import annotations
 
 import ctypes as C

@@ -1,0 +1,157 @@
+"""What the fillers that keep their framebuffers in HBM share (``AdvancedPixelBufferFiller``,
+``EdgeOnlyPixelBufferFiller``): the three planes in the reference's initial state, and the HOST-VIEW
+PROTOCOL that makes them look like the reference's own numpy buffers (.pyx:246-253).  Getters hand out
+writable numpy views of PINNED host buffers, allocated once per plane, that stay valid and show every
+later render: in-place changes are carried to the device before the next compositing render, and every
+array handed out so far is refreshed at the end of a render.
+  * ``_host_exposed``: the caller may have written into the views.  The next compositing render carries
+    them to the device first (``_push_host_edits``); a frame that starts from cleared planes voids them
+    instead (the filler stores ``_host_exposed = False``).
+  * ``_host_fresh``: the views equal the planes.  Whatever writes the planes stores ``False``; a getter,
+    or a render that refreshes the views, copies the handed-out planes back (``_refresh_mirrors``).
+Only planes that have been handed out cross PCIe (one asynchronous copy each way per render); a filler
+nobody asked a buffer of copies nothing.
+
+A filler supplies ``device, h, w, y0, y1, _lib``, calls ``_allocate_planes`` when it has a GPU, and defines
+  ``_ready_planes()``  make the planes usable on the current stream (create them, order the stream after
+                       whatever renders into them elsewhere); no host synchronisation;
+  ``_wait_planes()``   wait until the planes hold the finished frame; True if a frame was rendered again
+                       meanwhile (the planes changed since the call began).
+What needs the GPU or the library is in leaf methods of its own; the protocol around them only copies
+tensors, so tests/test_host_views_cpu.py runs it on CPU tensors.
+"""
+import ctypes as C
+
+import torch
+
+from .. import _capi
+
+
+class DevicePlanes:
+    def __init__(self):
+        self.z_buffer = self.color_buffer = self.normals_buffer = self.winner_buffer = None
+        self._host = {}                # name -> numpy view handed out by a getter (of _host_pin[name])
+        self._host_pin = {}            # name -> pinned host tensor behind the view
+        self._host_fresh = False       # the views equal the device planes
+        self._host_exposed = False     # a view was handed out and may have been edited
+
+    # ------------------------------------------- leaves: the GPU and the library --
+    def _allocate_planes(self, track_winner=False):
+        """The planes in the state __cinit__ leaves (.pyx:65-67)."""
+        with torch.cuda.device(self.device):
+            self.z_buffer = torch.full((self.h, self.w), 1e6, dtype=torch.float32, device=self.device)
+            self.color_buffer = torch.zeros((self.h, self.w, 3), dtype=torch.float32, device=self.device)
+            self.normals_buffer = torch.zeros((self.h, self.w, 3), dtype=torch.float32, device=self.device)
+            self.winner_buffer = torch.full((self.h, self.w), -1, dtype=torch.int32, device=self.device) if track_winner else None
+
+    def _pinned_like(self, buf):
+        with torch.cuda.device(self.device):
+            return torch.empty(tuple(buf.shape), dtype=buf.dtype, pin_memory=True)
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _win_ptr(self):
+        return self.winner_buffer.data_ptr() if self.winner_buffer is not None else None
+
+    def _clear_planes(self):
+        with torch.cuda.device(self.device):
+            _capi.check(self._lib.crender_clear(self.z_buffer.data_ptr(), self.color_buffer.data_ptr(),
+                                                self.normals_buffer.data_ptr(), self._win_ptr(), self.h, self.w,
+                                                self.y0, self.y1, self._stream()), "crender_clear")
+
+    def _present_planes(self, flip_rows):
+        out = torch.empty((self.h, self.w, 3), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _capi.check(self._lib.crender_present_u8(self.color_buffer.data_ptr(), out.data_ptr(), self.h, self.w,
+                                                     1 if flip_rows else 0, self._stream()), "crender_present_u8")
+        return out
+
+    def _shade_planes(self, light):
+        _capi.check(self._lib.crender_guro_illumination(
+            self.color_buffer.data_ptr(), self.normals_buffer.data_ptr(), (C.c_float * 3)(*light),
+            self.h, self.w, self.y0, self.y1, self._stream()), "crender_guro_illumination")
+
+    # ----------------------------------------------------------------- protocol --
+    def _planes(self):
+        return {"z": self.z_buffer, "color": self.color_buffer, "normals": self.normals_buffer}
+
+    def _push_host_edits(self):
+        """Carry in-place edits of handed-out numpy views back to the device."""
+        self._ready_planes()
+        if not self._host_exposed:
+            return
+        planes = self._planes()
+        for name, pin in self._host_pin.items():
+            planes[name].copy_(pin, non_blocking=True)        # (pinned: one DMA, stream-ordered)
+        self._host_exposed = False
+
+    def _refresh_mirrors(self, only=None):
+        """Bring the handed-out arrays up to date with the device planes: one asynchronous copy per
+        plane into its pinned buffer, issued BEFORE the wait so that one wait covers both (a frame
+        that has to be redone — rare — is copied again)."""
+        names = [n for n in self._host_pin if only is None or n in only]
+        while True:
+            self._ready_planes()
+            planes = self._planes()
+            for n in names:
+                self._host_pin[n].copy_(planes[n], non_blocking=True)
+            if not self._wait_planes():
+                break
+        if only is None:
+            self._host_fresh = True
+            # The arrays the caller holds show the planes again — and are the caller's to write into from here on,
+            # getter call or not: the next compositing render carries them back first.  (While only a getter call
+            # raised this flag, an edit made after a render into arrays handed out before it never reached the device.)
+            if self._host:
+                self._host_exposed = True
+
+    def _mirror(self, name):
+        if not self._host_fresh:
+            self._refresh_mirrors()
+        if name not in self._host:
+            self._host_pin[name] = self._pinned_like(self._planes()[name])
+            self._host[name] = self._host_pin[name].numpy()
+            self._refresh_mirrors(only=(name,))
+        self._host_exposed = True
+        return self._host[name]
+
+    def get_normals_buffer(self):
+        return self._mirror("normals")
+
+    def get_color_buffer(self):
+        return self._mirror("color")
+
+    def get_z_buffer(self):
+        return self._mirror("z")
+
+    # --------------------------------------------------------------- extensions --
+    def get_z_tensor(self):
+        self._ready_planes()
+        return self.z_buffer
+
+    def get_color_tensor(self):
+        self._ready_planes()
+        return self.color_buffer
+
+    def get_normals_tensor(self):
+        self._ready_planes()
+        return self.normals_buffer
+
+    def clear(self):
+        """Back to the state __cinit__ leaves (.pyx:65-67): colour 0, z 1e6, normals 0."""
+        self._ready_planes()
+        self._clear_planes()
+        self._host_fresh = False
+        self._host_exposed = False
+
+    def present_u8(self, flip_rows=True):
+        """uint8 [H, W, 3] device tensor of the colour plane, rows flipped: what run.py:26 writes to disk."""
+        self.get_color_tensor()        # (what the filler does before it hands the plane out: it must be complete)
+        self._push_host_edits()
+        return self._present_planes(flip_rows)
+
+    def shade_guro(self, light):
+        """``GuroIllumination.draw_illumination`` over rows y0 … y1 of the planes; `light`: that class's vector, as floats."""
+        self._shade_planes(light)
+        self._host_fresh = False

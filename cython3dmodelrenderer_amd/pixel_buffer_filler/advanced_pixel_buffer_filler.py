@@ -20,11 +20,9 @@ Behaviour kept from the reference
     renders composite (``Renderer.reset_buffers`` is a no-op there, renderer.py:51-52);
   * getters hand out writable numpy arrays that stay valid, that callers may change in place
     (GuroIllumination does, guro_illumination.py:27) and that show every later render, like the
-    reference's views of its own buffers (.pyx:246-253): in-place changes are carried to the
-    device before the next render, and every array handed out so far is refreshed at the end of
-    each ``render_model``.  The arrays are views of PINNED host buffers allocated once per plane;
-    only planes that have actually been handed out cross PCIe (one asynchronous copy each way
-    per render), a filler nobody asked a buffer of copies nothing;
+    reference's views of its own buffers (.pyx:246-253).  That protocol, the planes themselves,
+    ``clear``, ``present_u8`` and the tensor getters are ``_device_planes.DevicePlanes``, shared
+    with the wireframe filler;
   * the three model arrays are read afresh on every ``render_model`` call, as the reference's
     per-call ``.copy()`` does (.pyx:94-96): an in-place edit of ``model._vertices_by_triangles``
     is honoured (``cache_inputs=True`` restores the upload cache keyed by array identity).
@@ -38,6 +36,7 @@ a vertex with z == 0 (out of contract; IEEE inf/NaN semantics apply instead).
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import os
 import weakref
 
@@ -45,16 +44,24 @@ import numpy as np
 import torch
 
 from .. import _capi, _torch_ext
+from ._device_planes import DevicePlanes
 
 
-def _check_host_f32(a, name):
-    """numpy view of a [T, 3, 3] float32 host array (any strides), with the reference's errors."""
+def _host_f32(a):
+    """numpy view of a float32 host array, with what the reference raises for None (``None.copy()``)
+    and for another dtype (.pyx:94-96 binds ``float[:, :, :]``)."""
     if a is None:
-        raise AttributeError("'NoneType' object has no attribute 'copy'")     # .pyx:94-96
+        raise AttributeError("'NoneType' object has no attribute 'copy'")
     arr = np.asarray(a)
     if arr.dtype != np.float32:
         kind = "double" if arr.dtype == np.float64 else str(arr.dtype)
         raise ValueError(f"Buffer dtype mismatch, expected 'float' but got '{kind}'")
+    return arr
+
+
+def _check_host_f32(a, name):
+    """numpy view of a [T, 3, 3] float32 host array (any strides), with the reference's errors."""
+    arr = _host_f32(a)
     if arr.ndim != 3 or arr.shape[1] != 3 or arr.shape[2] != 3:
         raise ValueError(f"{name} must have shape [T, 3, 3], got {tuple(arr.shape)}")
     return arr
@@ -62,19 +69,12 @@ def _check_host_f32(a, name):
 
 def _as_device_f32(a, name, device):
     """[T, 3, 3] float32 contiguous tensor on `device` from numpy / torch input."""
-    if a is None:
-        # what `None.copy()` raises in the reference (.pyx:94-96)
-        raise AttributeError("'NoneType' object has no attribute 'copy'")
     if isinstance(a, torch.Tensor):
         if a.dtype != torch.float32:
             raise ValueError(f"Buffer dtype mismatch, expected 'float' but got '{a.dtype}' ({name})")
         t = a.to(device=device).contiguous()
     else:
-        arr = np.asarray(a)
-        if arr.dtype != np.float32:
-            kind = "double" if arr.dtype == np.float64 else str(arr.dtype)
-            raise ValueError(f"Buffer dtype mismatch, expected 'float' but got '{kind}'")
-        t = torch.from_numpy(np.ascontiguousarray(arr)).to(device)
+        t = torch.from_numpy(np.ascontiguousarray(_host_f32(a))).to(device)
     if t.dim() != 3 or t.shape[1] != 3 or t.shape[2] != 3:
         raise ValueError(f"{name} must have shape [T, 3, 3], got {tuple(t.shape)}")
     return t
@@ -89,6 +89,10 @@ _current_device = getattr(torch._C, "_cuda_getDevice", torch.cuda.current_device
 
 
 _DIRECT_MAX_TRIANGLES = 1 << 16      # kDirectMaxTriangles of csrc/plan.h: beyond, count / scan / fill
+
+# what the filler reads off a model (.pyx:94-96), and the names its errors give them
+_model_arrays = operator.attrgetter("_vertices_by_triangles", "_colors_by_triangles", "_normals_by_triangles")
+_MODEL_ARRAYS = ("model._vertices_by_triangles", "model._colors_by_triangles", "model._normals_by_triangles")
 
 
 class _Stage:
@@ -259,7 +263,7 @@ class _FramePipeline:
         return n.value, ms.value
 
 
-class AdvancedPixelBufferFiller:
+class AdvancedPixelBufferFiller(DevicePlanes):
     def __init__(self, h, w, fov=90.0, z_near=0.1, z_far=1000.0, n_threads=1, *,
                  device=None, tile=0, row_strip=None, track_winner=False, cache_inputs=False,
                  bin_capacity=0, direct_bins=True, pipeline=False, pipeline_depth=None,
@@ -268,6 +272,7 @@ class AdvancedPixelBufferFiller:
         self._ext = _torch_ext.load()                 # raises if the torch extension is not built
         if not torch.cuda.is_available():
             raise _capi.CrenderError("AdvancedPixelBufferFiller needs a ROCm GPU (no CPU fallback)")
+        super().__init__()                            # the planes' names and the host-view state
         self.h, self.w = int(h), int(w)
         self.fov, self.z_near, self.z_far = float(fov), float(z_near), float(z_far)
         self.n_threads = n_threads                    # accepted for API parity, unused
@@ -285,13 +290,7 @@ class AdvancedPixelBufferFiller:
         self.proj_mat = np.array(P[:], dtype=np.float32).reshape(4, 4)
         self._P_t = torch.from_numpy(self.proj_mat.reshape(16).copy())      # host tensor for the extension
 
-        with torch.cuda.device(self.device):
-            # same initial state as __cinit__ (.pyx:65-67)
-            self.z_buffer = torch.full((self.h, self.w), 1e6, dtype=torch.float32, device=self.device)
-            self.color_buffer = torch.zeros((self.h, self.w, 3), dtype=torch.float32, device=self.device)
-            self.normals_buffer = torch.zeros((self.h, self.w, 3), dtype=torch.float32, device=self.device)
-            self.winner_buffer = (torch.full((self.h, self.w), -1, dtype=torch.int32, device=self.device)
-                                  if track_winner else None)
+        self._allocate_planes(track_winner)
         self._plan = C.c_void_p()
         self._plan_max_T = -1
         self._plan_capacity = 0
@@ -302,10 +301,6 @@ class AdvancedPixelBufferFiller:
         self._input_key = None
         self._last_flags = 0
         self._extra_flags = 0 if direct_bins else _capi.NO_DIRECT_BINS
-        self._host = {}                # name -> numpy mirror handed out by a getter (view of _host_pin[name])
-        self._host_pin = {}            # name -> pinned host tensor behind the mirror
-        self._host_fresh = False       # mirrors equal the device buffers
-        self._host_exposed = False     # a mirror was handed out and may have been edited
         self._stages = []              # numpy inputs' way up: up to two _Stage (pinned + device [3, T, 3, 3])
         self._inputs_stage = None      # the staging slot the resident inputs live in, if any
         self._model_ref = None         # weak reference to a generation-counting model behind the resident inputs,
@@ -358,9 +353,6 @@ class AdvancedPixelBufferFiller:
                 self._plan = C.c_void_p()
         except Exception:
             pass
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _ensure_plan(self, T, capacity=None):
         capacity = self._bin_request if capacity is None else capacity
@@ -428,19 +420,7 @@ class AdvancedPixelBufferFiller:
         if self._pipe is not None and self._pipe.pending:
             self._pipe.join(self)
 
-    def _push_host_edits(self):
-        """Carry in-place edits of handed-out numpy views back to the device."""
-        self._join_pipe()
-        if not self._host_exposed:
-            return
-        for name, buf in (("z", self.z_buffer), ("color", self.color_buffer),
-                          ("normals", self.normals_buffer)):
-            if name in self._host_pin:
-                buf.copy_(self._host_pin[name], non_blocking=True)    # (pinned: one DMA, stream-ordered)
-        self._host_exposed = False
-
-    def _win_ptr(self):
-        return self.winner_buffer.data_ptr() if self.winner_buffer is not None else None
+    _ready_planes = _join_pipe         # (DevicePlanes' hooks, without a call in between: _wait_planes below)
 
     def _launch(self, flags, inputs=None, private=False, generation=None, stage=None):
         self._join_pipe()
@@ -553,6 +533,8 @@ class AdvancedPixelBufferFiller:
         self._settle(block=True)
         return self._redone
 
+    _wait_planes = _check_bins
+
     def _poll(self, frame):
         """None while the frame's usage record has not landed, else (entries needed, capacity)."""
         need, cap = C.c_int64(), C.c_int64()
@@ -646,7 +628,7 @@ class AdvancedPixelBufferFiller:
         ``clear=True`` (extension) renders into freshly initialised buffers in the same pass.
         ``refresh_views=False`` (extension) leaves the numpy arrays handed out earlier stale until
         the next getter call — for callers that go on working on the device first (Renderer)."""
-        src = (model._vertices_by_triangles, model._colors_by_triangles, model._normals_by_triangles)
+        src = _model_arrays(model)
         # a model that rewrites its arrays in place (DeviceModel: HIP kernels through raw pointers,
         # invisible to torch's version counter) counts its changes itself
         generation = getattr(model, "generation", None)
@@ -654,8 +636,7 @@ class AdvancedPixelBufferFiller:
         private = not any(isinstance(a, torch.Tensor) for a in src)
         self._upload_stage = None
         if refresh or not self.cache_inputs or key != self._input_key:
-            inputs = self._upload(src, ("model._vertices_by_triangles", "model._colors_by_triangles",
-                                        "model._normals_by_triangles"), composite=not clear)
+            inputs = self._upload(src, _MODEL_ARRAYS, composite=not clear)
             self._input_key = key if self.cache_inputs else None
             self._input_refs = src         # keep ids alive while the key is cached
         else:
@@ -729,15 +710,6 @@ class AdvancedPixelBufferFiller:
     # north_star wording; the reference's method is render_model
     render = render_model
 
-    def get_normals_buffer(self):
-        return self._mirror("normals", self.normals_buffer)
-
-    def get_color_buffer(self):
-        return self._mirror("color", self.color_buffer)
-
-    def get_z_buffer(self):
-        return self._mirror("z", self.z_buffer)
-
     # ------------------------------------------------------------------ extensions --
     def render_arrays(self, tri, col, nrm, clear=False):
         """``render_model`` on explicit [T,3,3] float32 arrays (numpy or torch, any device).
@@ -802,9 +774,7 @@ class AdvancedPixelBufferFiller:
             # rewrite) — until round 6 an unsorted resident model kept rendering the old tensor here.
             self._join_pipe()
             was_sorted = self._order is not None
-            src = (model._vertices_by_triangles, model._colors_by_triangles, model._normals_by_triangles)
-            inputs = self._upload(src, ("model._vertices_by_triangles", "model._colors_by_triangles",
-                                        "model._normals_by_triangles"), composite=False)
+            inputs = self._upload(_model_arrays(model), _MODEL_ARRAYS, composite=False)
             if was_sorted:
                 self._inputs, self._order = self._tile_coherent(inputs, False, model.generation)
                 self._inputs_private = self._order is not None
@@ -864,16 +834,8 @@ class AdvancedPixelBufferFiller:
                                     None, self._inputs_private, self._fused_light, self._inputs_stage))
 
     def clear(self):
-        """Back to the state __cinit__ leaves (.pyx:65-67)."""
-        self._join_pipe()
-        with torch.cuda.device(self.device):
-            _capi.check(self._lib.crender_clear(self.z_buffer.data_ptr(), self.color_buffer.data_ptr(),
-                                                self.normals_buffer.data_ptr(), self._win_ptr(),
-                                                self.h, self.w, self.y0, self.y1, self._stream()),
-                        "crender_clear")
+        super().clear()
         self._pending.clear()          # (whatever those frames dropped is gone with the rest)
-        self._host_fresh = False
-        self._host_exposed = False
 
     def join(self):
         """Order the current stream after any pipelined frames still in flight (no host sync).
@@ -902,18 +864,9 @@ class AdvancedPixelBufferFiller:
                                                       C.byref(b), C.byref(r)), "crender_plan_timing_end")
         return n.value, b.value, r.value
 
-    def present_u8(self, flip_rows=True):
-        """uint8 [H, W, 3] device tensor of the colour plane, rows flipped — what the
-        reference's run.py:26 writes to disk (``image[::-1].astype('uint8')``)."""
-        self._check_bins()
-        self._push_host_edits()
-        out = torch.empty((self.h, self.w, 3), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _capi.check(self._lib.crender_present_u8(self.color_buffer.data_ptr(), out.data_ptr(),
-                                                     self.h, self.w, 1 if flip_rows else 0,
-                                                     self._stream()), "crender_present_u8")
-        return out
-
+    # First the bin lists are settled: a frame may have to be redone (present_u8 goes through get_color_tensor).
+    # That joins the swap chain too, so these do not go on to DevicePlanes' getters: two more calls after the
+    # wait were a microsecond of Renderer.render(on_device=True).
     def get_z_tensor(self):
         self._check_bins()
         return self.z_buffer
@@ -929,35 +882,3 @@ class AdvancedPixelBufferFiller:
     def get_winner_tensor(self):
         self._check_bins()
         return self.winner_buffer
-
-    def _refresh_mirrors(self, only=None):
-        """Bring the handed-out arrays up to date with the device buffers: one asynchronous copy per
-        plane into its pinned buffer, issued BEFORE the synchronising bin-list check so that one wait
-        covers both (a frame that has to be redone — rare — is copied again)."""
-        names = [n for n in self._host_pin if only is None or n in only]
-        while True:
-            self._join_pipe()
-            bufs = {"z": self.z_buffer, "color": self.color_buffer, "normals": self.normals_buffer}
-            for n in names:
-                self._host_pin[n].copy_(bufs[n], non_blocking=True)
-            if not self._check_bins():              # synchronises the stream; True = the frame was redone
-                break
-        if only is None:
-            self._host_fresh = True
-            # The arrays the caller holds show the buffers again — and are the caller's to write into from
-            # here on, getter call or not (they are the reference's buffers themselves, .pyx:246-253): the next
-            # compositing render carries them back first.  (Until round 5 only a getter call raised this flag:
-            # an edit made after a render_model, into arrays handed out before it, never reached the device.)
-            if self._host:
-                self._host_exposed = True
-
-    def _mirror(self, name, buf):
-        if not self._host_fresh:
-            self._refresh_mirrors()
-        if name not in self._host:
-            with torch.cuda.device(self.device):
-                self._host_pin[name] = torch.empty(tuple(buf.shape), dtype=buf.dtype, pin_memory=True)
-            self._host[name] = self._host_pin[name].numpy()
-            self._refresh_mirrors(only=(name,))
-        self._host_exposed = True
-        return self._host[name]

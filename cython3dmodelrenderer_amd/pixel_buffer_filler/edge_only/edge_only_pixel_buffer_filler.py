@@ -14,9 +14,10 @@ bit what ``compute_triangle_statistics`` leaves when called on each triangle in 
 ``LineBresenham``.  The filler then behaves like ``AdvancedPixelBufferFiller`` towards its callers
 (``Renderer``, the illuminations): the same three planes, initial state (colour 0, z 1e6, normals
 0), getters of writable numpy views whose in-place edits are carried back before the next
-compositing draw, device tensors, ``clear``, ``present_u8``.  The z and normal planes are never
-drawn into.  The device path needs ``h`` and ``w`` and the ``LineBresenham`` line (another
-``draw_line`` raises TypeError: there is no device form of it).
+compositing draw, device tensors, ``clear``, ``present_u8``: the code of both is
+``.._device_planes.DevicePlanes``.  The z and normal planes are never drawn into.  The device path
+needs ``h`` and ``w`` and the ``LineBresenham`` line (another ``draw_line`` raises TypeError: there is
+no device form of it).
 
 Domain: the GPU path is exact for vertex x / y with ``|c| < 2**30``.  Any other x / y (NaN, inf,
 huge) raises ValueError before anything is drawn — the buffers keep their contents — where the
@@ -30,6 +31,7 @@ import numpy as np
 import torch
 
 from ... import _capi
+from .._device_planes import DevicePlanes
 from .line_drawer import LineBresenham, LineDrawer
 
 _MAX_ORDERED_T = 1 << 30     # per-triangle colours: a uint32 key 3 i + e + 1 per pixel
@@ -55,9 +57,10 @@ def _as_device(a, name, device, cast):
     return t
 
 
-class EdgeOnlyPixelBufferFiller:
+class EdgeOnlyPixelBufferFiller(DevicePlanes):
     def __init__(self, line_drawer: LineDrawer, line_color, draw_edges=True, force_triangle_colors=False,
                  *, h=None, w=None, device=None):
+        super().__init__()             # the planes (None until _ensure_device) and the host-view state
         self.line_drawer = line_drawer
         self.line_color = line_color
         self.draw_edges = draw_edges
@@ -68,15 +71,10 @@ class EdgeOnlyPixelBufferFiller:
         self.device = torch.device(device if device is not None else "cuda:0")
         # device state, made at the first draw or getter call
         self._lib = None
-        self.z_buffer = self.color_buffer = self.normals_buffer = None
         self._key = None               # uint32 key plane of per-triangle colours (zero between draws)
         self._status = None            # device int32: the draw's domain flag
         self._status_host = None       # pinned copy of it
         self._fused_light = None
-        self._host = {}                # name -> numpy view handed out by a getter (of _host_pin[name])
-        self._host_pin = {}
-        self._host_fresh = False       # the views equal the device planes
-        self._host_exposed = False     # a view was handed out and may have been edited
 
     # ------------------------------------------------------------- reference API --
     def compute_triangle_statistics(self, triangle, colors, normals, color_buffer, z_buffer, n_buffer):
@@ -115,16 +113,17 @@ class EdgeOnlyPixelBufferFiller:
             raise _capi.CrenderError("EdgeOnlyPixelBufferFiller.render_model needs a ROCm GPU (no CPU fallback)")
         if lib.crender_wire_key_bytes(self.h, self.w) == 0:
             raise ValueError(f"bad frame size for the wireframe filler: h={self.h} w={self.w}")
+        self._allocate_planes()
         with torch.cuda.device(self.device):
-            self.z_buffer = torch.full((self.h, self.w), 1e6, dtype=torch.float32, device=self.device)
-            self.color_buffer = torch.zeros((self.h, self.w, 3), dtype=torch.float32, device=self.device)
-            self.normals_buffer = torch.zeros((self.h, self.w, 3), dtype=torch.float32, device=self.device)
             self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
             self._status_host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
         self._lib = lib
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    _ready_planes = _ensure_device     # (DevicePlanes' hooks)
+
+    def _wait_planes(self):
+        torch.cuda.current_stream(self.device).synchronize()
+        return False
 
     def render_model(self, model, refresh=False, clear=False, refresh_views=True):
         """Draw the wireframe of ``model`` (a ``Model``, a ``DeviceModel``, anything with
@@ -179,7 +178,8 @@ class EdgeOnlyPixelBufferFiller:
             self._host_exposed = False         # (edits of the views are void: the frame started afresh)
         self._host_fresh = False
         if clear and self._fused_light is not None:
-            self._guro(self._fused_light)
+            with torch.cuda.device(self.device):
+                self.shade_guro(self._fused_light)
         if self._host and refresh_views:
             self._refresh_mirrors()
 
@@ -189,90 +189,6 @@ class EdgeOnlyPixelBufferFiller:
         ``None`` switches it off."""
         self._fused_light = None if light_direction is None else tuple(float(v) for v in light_direction)
 
-    def _guro(self, light):
-        with torch.cuda.device(self.device):
-            _capi.check(self._lib.crender_guro_illumination(
-                self.color_buffer.data_ptr(), self.normals_buffer.data_ptr(), (C.c_float * 3)(*light),
-                self.h, self.w, 0, self.h, self._stream()), "crender_guro_illumination")
-
-    def clear(self):
-        """Back to the initial state: colour 0, z 1e6, normals 0."""
-        self._ensure_device()
-        with torch.cuda.device(self.device):
-            _capi.check(self._lib.crender_clear(self.z_buffer.data_ptr(), self.color_buffer.data_ptr(),
-                                                self.normals_buffer.data_ptr(), None, self.h, self.w, 0, self.h,
-                                                self._stream()), "crender_clear")
-        self._host_fresh = False
-        self._host_exposed = False
-
     def synchronize(self):
         if self.color_buffer is not None:
             torch.cuda.current_stream(self.device).synchronize()
-
-    def present_u8(self, flip_rows=True):
-        """uint8 [H, W, 3] device tensor of the colour plane, rows flipped (``crender_present_u8``)."""
-        self._ensure_device()
-        self._push_host_edits()
-        out = torch.empty((self.h, self.w, 3), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _capi.check(self._lib.crender_present_u8(self.color_buffer.data_ptr(), out.data_ptr(), self.h, self.w,
-                                                     1 if flip_rows else 0, self._stream()), "crender_present_u8")
-        return out
-
-    def get_z_tensor(self):
-        self._ensure_device()
-        return self.z_buffer
-
-    def get_color_tensor(self):
-        self._ensure_device()
-        return self.color_buffer
-
-    def get_normals_tensor(self):
-        self._ensure_device()
-        return self.normals_buffer
-
-    def get_normals_buffer(self):
-        return self._mirror("normals")
-
-    def get_color_buffer(self):
-        return self._mirror("color")
-
-    def get_z_buffer(self):
-        return self._mirror("z")
-
-    # ------------------------------------------------------------ host mirrors --
-    def _planes(self):
-        return {"z": self.z_buffer, "color": self.color_buffer, "normals": self.normals_buffer}
-
-    def _push_host_edits(self):
-        """Carry in-place edits of handed-out numpy views back to the device."""
-        if not self._host_exposed:
-            return
-        planes = self._planes()
-        for name, pin in self._host_pin.items():
-            planes[name].copy_(pin, non_blocking=True)        # (pinned: stream-ordered)
-        self._host_exposed = False
-
-    def _refresh_mirrors(self, only=None):
-        planes = self._planes()
-        for name in self._host_pin:
-            if only is None or name in only:
-                self._host_pin[name].copy_(planes[name], non_blocking=True)
-        torch.cuda.current_stream(self.device).synchronize()
-        if only is None:
-            self._host_fresh = True
-            # the views are the caller's to write into from here on: carried back before the next draw
-            self._host_exposed = bool(self._host)
-
-    def _mirror(self, name):
-        self._ensure_device()
-        if not self._host_fresh:
-            self._refresh_mirrors()
-        if name not in self._host:
-            buf = self._planes()[name]
-            with torch.cuda.device(self.device):
-                self._host_pin[name] = torch.empty(tuple(buf.shape), dtype=buf.dtype, pin_memory=True)
-            self._host[name] = self._host_pin[name].numpy()
-            self._refresh_mirrors(only=(name,))
-        self._host_exposed = True
-        return self._host[name]
