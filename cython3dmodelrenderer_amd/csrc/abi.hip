@@ -137,6 +137,45 @@ int tile_frame(crender_plan *plan, bool project, const float *d_tri, const float
     return CRENDER_OK;
 }
 
+// The optional HIP events of crender_plan_timing_* (3 per frame) and crender_pipeline_timing_* (2 per frame):
+// all created up front; a frame is timed while events are left.
+void drop_events(std::vector<hipEvent_t> &events, int &timed_frames)
+{
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    events.clear();
+    timed_frames = 0;
+}
+
+int make_events(std::vector<hipEvent_t> &events, int &timed_frames, int n)
+{
+    drop_events(events, timed_frames);
+    events.reserve((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        hipEvent_t e;
+        CR_HIP(hipEventCreate(&e));
+        events.push_back(e);
+    }
+    return CRENDER_OK;
+}
+
+// avg[k] = mean time in ms between events k and k + 1 of the timed frames' `per` events each; drops the events
+int average_events(std::vector<hipEvent_t> &events, int &timed_frames, int per, int *frames, double *avg)
+{
+    const int n = timed_frames;
+    for (int k = 0; k + 1 < per; ++k) {
+        double sum = 0.0;
+        for (int f = 0; f < n; ++f) {
+            float ms = 0.f;
+            CR_HIP(hipEventElapsedTime(&ms, events[(size_t)f * per + k], events[(size_t)f * per + k + 1]));
+            sum += ms;
+        }
+        avg[k] = n ? sum / n : 0.0;
+    }
+    if (frames) *frames = n;
+    drop_events(events, timed_frames);
+    return CRENDER_OK;
+}
+
 // Pinned host memory for the plans' usage records: one allocation of kUsageSlots slots, made at the first
 // plan and kept for the life of the process (portable: every device's kernels may write into it); a plan
 // takes a slot and gives it back.  Beyond kUsageSlots plans alive at once, a plan gets an allocation of
@@ -215,24 +254,25 @@ void usage_slot_give(uint32_t *host, int slot)
     P.free_slots.push_back(slot);
 }
 
-// What the header words of a frame mean (crender_plan_last_bin_usage, crender_plan_poll_bin_usage).
-void usage_figures(crender_plan *plan, int mode, uint32_t h0, uint32_t h1, uint32_t h4, int64_t *needed,
+// What a frame's header words kHdrEntriesLo, kHdrOverflow, kHdrEntriesHi (binning.h) mean to
+// crender_plan_last_bin_usage and crender_plan_poll_bin_usage.
+void usage_figures(crender_plan *plan, BinMode mode, uint32_t lo, uint32_t over, uint32_t hi, int64_t *needed,
                    int64_t *capacity)
 {
-    if (mode != 0) {
-        // direct bins / pair bins: per-tile figures.  h1 is sticky: the longest list that did not fit
-        // (0xFFFFFFFF = a triangle spans too many tiles).  On overflow this plan switches to
+    if (mode != kFrameScan) {
+        // direct bins / pair bins: per-tile figures.  The overflow word is sticky: the longest list that did
+        // not fit (0xFFFFFFFF = a triangle spans too many tiles).  On overflow this plan switches to
         // the count / scan / fill path for good; the caller renders the frame again.
-        const int64_t cap = mode == 1 ? plan->L.direct_cap : plan->L.pair_cap;
-        if (h1 > (uint32_t)cap) {                          // h1 stays set: the answer is repeatable
-            if (mode == 1) plan->direct_ok = false;
+        const int64_t cap = mode == kFrameDirect ? plan->L.direct_cap : plan->L.pair_cap;
+        if (over > (uint32_t)cap) {                        // the word stays set: the answer is repeatable
+            if (mode == kFrameDirect) plan->direct_ok = false;
             else plan->pairbins_ok = false;
         }
-        if (needed) *needed = h1 > (uint32_t)cap ? (int64_t)h1 : 0;
+        if (needed) *needed = over > (uint32_t)cap ? (int64_t)over : 0;
         if (capacity) *capacity = cap;
         return;
     }
-    if (needed) *needed = (int64_t)(((unsigned long long)h4 << 32) | h0);
+    if (needed) *needed = (int64_t)(((unsigned long long)hi << 32) | lo);
     if (capacity) *capacity = plan->L.capacity;
 }
 
@@ -317,16 +357,7 @@ void crender_plan_destroy(crender_plan *plan)
 int crender_plan_timing_begin(crender_plan *plan, int max_frames)
 {
     if (!plan || max_frames < 0) return fail(CRENDER_EINVAL, "crender_plan_timing_begin: bad argument");
-    for (hipEvent_t e : plan->events) (void)hipEventDestroy(e);
-    plan->events.clear();
-    plan->timed_frames = 0;
-    plan->events.reserve((size_t)max_frames * 3);
-    for (int i = 0; i < max_frames * 3; ++i) {
-        hipEvent_t e;
-        CR_HIP(hipEventCreate(&e));
-        plan->events.push_back(e);
-    }
-    return CRENDER_OK;
+    return make_events(plan->events, plan->timed_frames, max_frames * 3);
 }
 
 int crender_plan_timing_end(crender_plan *plan, void *stream, int *frames, double *bin_ms_avg,
@@ -334,21 +365,11 @@ int crender_plan_timing_end(crender_plan *plan, void *stream, int *frames, doubl
 {
     if (!plan) return fail(CRENDER_EINVAL, "null plan");
     CR_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    double bin = 0.0, ras = 0.0;
-    const int n = plan->timed_frames;
-    for (int f = 0; f < n; ++f) {
-        float a = 0.f, b = 0.f;
-        CR_HIP(hipEventElapsedTime(&a, plan->events[(size_t)f * 3], plan->events[(size_t)f * 3 + 1]));
-        CR_HIP(hipEventElapsedTime(&b, plan->events[(size_t)f * 3 + 1], plan->events[(size_t)f * 3 + 2]));
-        bin += a;
-        ras += b;
-    }
-    if (frames) *frames = n;
-    if (bin_ms_avg) *bin_ms_avg = n ? bin / n : 0.0;
-    if (raster_ms_avg) *raster_ms_avg = n ? ras / n : 0.0;
-    for (hipEvent_t e : plan->events) (void)hipEventDestroy(e);
-    plan->events.clear();
-    plan->timed_frames = 0;
+    double avg[2] = {0.0, 0.0};
+    const int rc = average_events(plan->events, plan->timed_frames, 3, frames, avg);
+    if (rc != CRENDER_OK) return rc;
+    if (bin_ms_avg) *bin_ms_avg = avg[0];
+    if (raster_ms_avg) *raster_ms_avg = avg[1];
     return CRENDER_OK;
 }
 
@@ -358,9 +379,9 @@ int crender_plan_last_bin_usage(crender_plan *plan, void *stream, int64_t *neede
     // (into the plan's own pinned memory: a pageable destination makes the runtime stage the copy)
     volatile uint32_t *h = plan->usage + kUsageWords * kUsageRing;       // (the record behind the ring)
     hipStream_t s = static_cast<hipStream_t>(stream);
-    CR_HIP(hipMemcpyAsync(const_cast<uint32_t *>(h), plan->hdr(), 5 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    CR_HIP(hipMemcpyAsync(const_cast<uint32_t *>(h), plan->hdr(), (kHdrEntriesHi + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     CR_HIP(hipStreamSynchronize(s));
-    usage_figures(plan, plan->last_frame_direct ? 1 : plan->last_frame_pairbins ? 2 : 0, h[0], h[1], h[4], needed, capacity);
+    usage_figures(plan, plan->last_frame_mode, h[kHdrEntriesLo], h[kHdrOverflow], h[kHdrEntriesHi], needed, capacity);
     return CRENDER_OK;
 }
 
@@ -372,16 +393,9 @@ int crender_plan_poll_bin_usage(crender_plan *plan, uint64_t ticket, int64_t *ne
     if (ticket == 0 || ticket > plan->ticket || plan->ticket - ticket >= (uint64_t)kUsageRing)
         return fail(CRENDER_EINVAL, "crender_plan_poll_bin_usage: no such frame (not launched yet, or more than "
                                     "8 frames ago: its record has been reused)");
-    const int slot = (int)(ticket % kUsageRing);
-    const volatile uint32_t *rec = plan->usage + kUsageWords * slot;
-    // the record is two aligned 16-byte stores of the launch, the frame's sequence word leading the first
-    // and trailing the second: taken only when BOTH are there (a record half landed reads as not landed)
-    const uint32_t want = (uint32_t)ticket ^ plan->usage_salt;
-    if (__atomic_load_n(const_cast<const uint32_t *>(rec), __ATOMIC_ACQUIRE) != want || rec[7] != want)
-        return CRENDER_EBUSY;                                                      // (not an error: no text)
-    const uint32_t h0 = rec[1], h1 = rec[2], h4 = rec[3];
-    if (rec[0] != want || rec[7] != want) return CRENDER_EBUSY;                    // (rewritten under the read: a frame 8 later)
-    usage_figures(plan, plan->usage_mode[slot], h0, h1, h4, needed, capacity);
+    uint32_t rec[kUsageWords];
+    if (!plan->usage_record(ticket, rec)) return CRENDER_EBUSY;                    // (not landed; not an error: no text)
+    usage_figures(plan, plan->usage_mode[ticket % kUsageRing], rec[1], rec[2], rec[3], needed, capacity);
     return CRENDER_OK;
 }
 
@@ -424,8 +438,9 @@ int crender_plan_debug_check(crender_plan *plan, void *stream, char *msg, size_t
             if (cnt[par ^ 1][i]) { if (first < 0) first = i; ++nz; }
         if (nz) say("%d counters of parity %d (the NEXT frame's) are not zero, first tile %d = %u", nz, par ^ 1, first, cnt[par ^ 1][first]);
         if (plan->awaiting[par ^ 1]) say("host flag awaiting[%d] still set after the raster launch", par ^ 1);
-        if (hdr[2 + (par ^ 1)]) say("registration counter of the next frame hdr[%d] = %u", 2 + (par ^ 1), hdr[2 + (par ^ 1)]);
-        if (hdr[5 + (par ^ 1)]) say("hint_bad of the next frame hdr[%d] = %u", 5 + (par ^ 1), hdr[5 + (par ^ 1)]);
+        const int ctr = kHdrHeavyCtr + (par ^ 1), bad_at = kHdrHintBad + (par ^ 1);
+        if (hdr[ctr]) say("registration counter of the next frame hdr[%d] = %u", ctr, hdr[ctr]);
+        if (hdr[bad_at]) say("hint_bad of the next frame hdr[%d] = %u", bad_at, hdr[bad_at]);
         int nf = 0, ff = -1;
         for (int i = 0; i < nt; ++i)
             if (hflag[i]) { if (ff < 0) ff = i; ++nf; }
@@ -440,10 +455,10 @@ int crender_plan_debug_check(crender_plan *plan, void *stream, char *msg, size_t
         // one starts the plan over (flags, slots and the order hint exist once, not per parity)
         if (plan->unrastered[par ^ 1])
             say("%s", "both parities hold a binned frame that was never rasterized: the binning pass did not start the plan over");
-        const bool split = plan->last_frame_direct && plan->frame_hmax > 0;
+        const bool split = plan->last_frame_mode == kFrameDirect && plan->frame_hmax > 0;
         const uint32_t at = plan->frame_heavy_at;
         if (split) {
-            const uint32_t reg = hdr[2 + par];
+            const uint32_t reg = hdr[kHdrHeavyCtr + par];
             const uint32_t hm = (uint32_t)plan->frame_hmax;
             const uint32_t used = reg < hm ? reg : hm;
             std::vector<int> slot_of(nt, -1);
@@ -555,12 +570,12 @@ int crender_set_default_raster_path(int path)
 
 int crender_plan_last_frame_direct(crender_plan *plan)
 {
-    return plan && (plan->last_frame_direct || plan->last_frame_pairbins) ? 1 : 0;
+    return plan && plan->last_frame_mode != kFrameScan ? 1 : 0;
 }
 
 int crender_plan_last_frame_binning(crender_plan *plan)
 {
-    return !plan ? 0 : plan->last_frame_direct ? 1 : plan->last_frame_pairbins ? 2 : 0;
+    return plan ? plan->last_frame_mode : 0;
 }
 
 int crender_raster(crender_plan *plan, const float *d_tri_proj, const float *d_col, const float *d_nrm,
@@ -592,15 +607,6 @@ int crender_render_model(crender_plan *plan, const float *d_tri, const float *d_
 {
     return tile_frame(plan, true, d_tri, d_col, d_nrm, T, P16, d_z, d_color, d_normal, d_winner, flags,
                       stream);
-}
-
-static int crender_render_model_on(crender_plan *plan, const float *d_tri, const float *d_col,
-                                   const float *d_nrm, int64_t T, const float *P16, float *d_z,
-                                   float *d_color, float *d_normal, int32_t *d_winner, unsigned flags,
-                                   hipStream_t s)
-{
-    return tile_frame(plan, P16 != nullptr, d_tri, d_col, d_nrm, T, P16, d_z, d_color, d_normal,
-                      d_winner, flags, s);
 }
 
 int crender_pipeline_create(crender_pipeline **out, crender_plan *const *plans, int depth)
@@ -715,8 +721,8 @@ int crender_pipeline_frame(crender_pipeline *p, const float *d_tri, const float 
     // whatever was binned ahead: that is void then)
     p->primed[k].ok = false;
     p->sel[k] = 0;
-    int rc = crender_render_model_on(p->plan[k], d_tri, d_col, d_nrm, T, P16, d_z, d_color, d_normal,
-                                     d_winner, flags, p->s[k]);
+    int rc = tile_frame(p->plan[k], P16 != nullptr, d_tri, d_col, d_nrm, T, P16, d_z, d_color, d_normal, d_winner,
+                        flags, p->s[k]);
     if (rc != CRENDER_OK) return rc;
     p->n++;
     return stamp.close();
@@ -725,35 +731,17 @@ int crender_pipeline_frame(crender_pipeline *p, const float *d_tri, const float 
 int crender_pipeline_timing_begin(crender_pipeline *p, int max_frames)
 {
     if (!p || max_frames < 0) return fail(CRENDER_EINVAL, "crender_pipeline_timing_begin: bad argument");
-    for (hipEvent_t e : p->events) (void)hipEventDestroy(e);
-    p->events.clear();
-    p->timed_frames = 0;
-    p->events.reserve((size_t)max_frames * 2);
-    for (int i = 0; i < max_frames * 2; ++i) {
-        hipEvent_t e;
-        CR_HIP(hipEventCreate(&e));
-        p->events.push_back(e);
-    }
-    return CRENDER_OK;
+    return make_events(p->events, p->timed_frames, max_frames * 2);
 }
 
 int crender_pipeline_timing_end(crender_pipeline *p, int *frames, double *launch_ms_avg)
 {
     if (!p) return fail(CRENDER_EINVAL, "null pipeline");
     for (int k = 0; k < p->depth; ++k) CR_HIP(hipStreamSynchronize(p->s[k]));
-    double sum = 0.0;
-    const int n = p->timed_frames;
-    for (int f = 0; f < n; ++f) {
-        float ms = 0.f;
-        CR_HIP(hipEventElapsedTime(&ms, p->events[(size_t)f * 2], p->events[(size_t)f * 2 + 1]));
-        sum += ms;
-    }
-    if (frames) *frames = n;
-    if (launch_ms_avg) *launch_ms_avg = n ? sum / n : 0.0;
-    for (hipEvent_t e : p->events) (void)hipEventDestroy(e);
-    p->events.clear();
-    p->timed_frames = 0;
-    return CRENDER_OK;
+    double avg = 0.0;
+    const int rc = average_events(p->events, p->timed_frames, 2, frames, &avg);
+    if (rc == CRENDER_OK && launch_ms_avg) *launch_ms_avg = avg;
+    return rc;
 }
 
 int crender_pipeline_set_lookahead(crender_pipeline *p, crender_plan *const *plans, int n)

@@ -13,6 +13,21 @@ namespace crender_detail {
 enum { kBinCountLds = 0, kBinCountGlobal = 1 };
 constexpr int kDirectMaxTilesPerTriangle = 4096;  // beyond this the scan path is used instead
 
+// ---- the plan's header --------------------------------------------------------------------------------
+// kHdrWords u32 at the start of a plan's workspace, zero from crender_plan_create on, that the kernels of both
+// passes and the host address by these names:
+//   kHdrEntriesLo, kHdrEntriesHi   scan path: the number of list entries the frame needs, low and high word
+//                                  (k_scan; beyond the plan's capacity: the lists were cut short)
+//   kHdrOverflow                   direct and pair bins: the longest list that did not fit its slab (atomicMax,
+//                                  sticky; 0xFFFFFFFF: a triangle spans more than kDirectMaxTilesPerTriangle
+//                                  tiles) — the plan then goes back to count / scan / fill for good
+//   kHdrHeavyCtr + parity          tiles the parity's binning pass registered as heavy (register_heavy); the
+//                                  raster launch of one parity zeroes the other's for the next frame
+//   kHdrHintBad + parity           the parity's binning pass found the dispatch-order hint stale
+//                                  (first_entry_of); zeroed like the counter
+// Every raster launch copies the first three into its usage record (crender_plan_poll_bin_usage).
+enum : int { kHdrEntriesLo = 0, kHdrOverflow = 1, kHdrHeavyCtr = 2, kHdrEntriesHi = 4, kHdrHintBad = 5, kHdrWords = 7 };
+
 #ifdef CRENDER_STAMPS
 // Diagnostic build only: phase timestamps per workgroup of the setup kernels, 8 per workgroup
 // (crender_debug_set_setup_stamps); same clock as k_raster's stamps.  One pointer per translation
@@ -46,7 +61,7 @@ constexpr int kEntryPieces = sizeof(BinEntry) / 16;
 // half), from kQuadAt entries on by four (one per 8x8 quadrant), instead of one: a workgroup's
 // time grows with the trips its sweep takes and on T-Rex 1024^2 the 105 tiles with >= 32 records
 // set the end of the raster launch, 4 us after the median tile (in-kernel timeline, profiles/r02).  The append that crosses kHeavyAt registers
-// the tile: it draws an index from the frame's counter (hdr[2 + parity]) and, if one of the
+// the tile: it draws an index from the frame's counter (kHdrHeavyCtr + parity) and, if one of the
 // launch's `hmax` helper triples is still free, raises the tile's flag and writes tile + 1 into
 // the triple's three slot words.  k_raster's helper workgroups take parts 1..3 (part 1 alone when
 // the list stays below kQuadAt); the tile's own workgroup takes part 0 when the flag is up.  Flag and slots are reset by their
@@ -133,7 +148,7 @@ CR_DEV void bin_direct_append(uint2 r_keep, const float4 *img, int ntx,
                 for (int k = 0; k < kPassC; ++k) {
                     if (on[k]) {
                         if (slot[k] < dcap) put_entry<NP>(entry_at(tile[k], slot[k]), img, lane);
-                        else atomicMax(&hdr[1], slot[k] + 1);
+                        else atomicMax(&hdr[kHdrOverflow], slot[k] + 1);
                         if (hv.ctr && slot[k] == hv.heavy_at - 1) register_heavy(hv, tile[k]);
                         if (slot[k] == 0) first_entry_of(hv, tile[k]);
                     }
@@ -188,7 +203,7 @@ CR_DEV void bin_direct_append(uint2 r_keep, const float4 *img, int ntx,
                 if (tw[u] >> 31) {
                     const uint32_t tile = tw[u] & 0xFFFFFu;
                     if (slot[u] < dcap) put_entry<NP>(entry_at(tile, slot[u]), img, (int)((tw[u] >> 20) & 63u));
-                    else atomicMax(&hdr[1], slot[u] + 1);
+                    else atomicMax(&hdr[kHdrOverflow], slot[u] + 1);
                     if (hv.ctr && slot[u] == hv.heavy_at - 1) register_heavy(hv, tile);
                     if (slot[u] == 0) first_entry_of(hv, tile);
                 }
@@ -281,7 +296,7 @@ CR_DEV void setup_wave_body(const float *__restrict__ tri_in, const float *__res
         if (r.x != kNoTiles) {
             const int ntl = (int)((r.x >> 16) - (r.x & 0xFFFF) + 1) * (int)((r.y >> 16) - (r.y & 0xFFFF) + 1);
             if (ntl > kDirectMaxTilesPerTriangle) {
-                atomicMax(&hdr[1], 0xFFFFFFFFu);  // sticky: this scene needs the scan path
+                atomicMax(&hdr[kHdrOverflow], 0xFFFFFFFFu);  // sticky: this scene needs the scan path
                 r.x = kNoTiles;
             }
         }
@@ -334,7 +349,7 @@ CR_DEV void setup_wave_body(const float *__restrict__ tri_in, const float *__res
             for (int k = 0; k < kPassB; ++k) {
                 if (c[k]) {
                     hist[(k0 + k) * kWave + lane] = base[k];
-                    if (base[k] + c[k] > dcap) atomicMax(&hdr[1], base[k] + c[k]);
+                    if (base[k] + c[k] > dcap) atomicMax(&hdr[kHdrOverflow], base[k] + c[k]);
                     if (hv.ctr && base[k] < hv.heavy_at && base[k] + c[k] >= hv.heavy_at) register_heavy(hv, t[k]);
                     if (base[k] == 0) first_entry_of(hv, t[k]);
                 }

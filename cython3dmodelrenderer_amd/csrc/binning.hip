@@ -56,6 +56,51 @@ __global__ __launch_bounds__(kThreads) void k_clear(float *__restrict__ zb, floa
     }
 }
 
+// ---- what the wavefront kernels below share ---------------------------------------------------
+// The tile bounding box of a wavefront's ranges: every lane starts from X0 = Y0 = INT_MAX, X1 = Y1 = -1, grows
+// that by its own ranges, and wave_box() takes the extremes over the lanes (X1 < 0 then: no lane had a range).
+CR_DEV void grow_box(uint2 r, int &X0, int &X1, int &Y0, int &Y1)
+{
+    if (r.x != kNoTiles) {
+        const int x0 = r.x & 0xFFFF, x1 = r.x >> 16, y0 = r.y & 0xFFFF, y1 = r.y >> 16;
+        X0 = x0 < X0 ? x0 : X0; X1 = x1 > X1 ? x1 : X1; Y0 = y0 < Y0 ? y0 : Y0; Y1 = y1 > Y1 ? y1 : Y1;
+    }
+}
+
+// Pass B of a wavefront that has counted its entries per tile of its bounding box in `hist` (pass A): one
+// returning atomic per touched tile reserves the run, `reserve(tile, n)` -> the run's first slot, which becomes
+// the tile's LDS cursor for pass C; `reserved(first, n)` sees every run (the overflow report).  All rounds of 64
+// tiles in flight together.
+template <typename Reserve, typename Reserved>
+CR_DEV void reserve_runs(uint32_t *hist, int lane, int X0, int Y0, int bw, int area, int ntx, Reserve reserve,
+                         Reserved reserved)
+{
+    constexpr int kRounds = kWaveHistTiles / kWave;
+    const float rbw = 1.0f / (float)bw;
+    uint32_t c[kRounds], t[kRounds], base[kRounds];
+    const int nr = (area + kWave - 1) / kWave;      // rounds that have tiles at all (uniform; mostly 1)
+#pragma unroll
+    for (int k = 0; k < kRounds; ++k) {
+        c[k] = 0u; t[k] = 0u;
+        if (k < nr) {
+            const int i = k * kWave + lane;
+            c[k] = i < area ? hist[i] : 0u;
+            const int dy = (int)(((float)i + 0.5f) * rbw);          // exact: i < 2^22
+            t[k] = (uint32_t)((Y0 + dy) * ntx + X0 + (i - dy * bw));
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kRounds; ++k)                            // all in flight together
+        base[k] = c[k] ? reserve(t[k], c[k]) : 0u;
+#pragma unroll
+    for (int k = 0; k < kRounds; ++k) {
+        if (c[k]) {
+            hist[k * kWave + lane] = base[k];
+            reserved(base[k], c[k]);
+        }
+    }
+}
+
 // dynamic LDS: [hist: ntiles u32 if kBinCountLds][verts: 256*9 f32][normals: 256*9 f32]
 template <int TS, bool PROJECT, int BIN>
 __global__ __launch_bounds__(kThreads) void k_setup(const float *__restrict__ tri_in,
@@ -163,7 +208,7 @@ __global__ __launch_bounds__(kWave) void k_count_wave(const float *__restrict__ 
     stage_in<kWave>(tri_in + b0 * 9, sv, n * 9);
 #pragma unroll
     for (int i = 0; i < kWaveHistTiles / kWave; ++i) hist[i * kWave + lane] = 0;   // (while the inputs are on their way)
-    float nz0 = 0.0f, nz1 = 0.0f, nz2 = 0.0f;      // .pyx:202 looks at the normals' z only
+    float nz0 = 0.0f, nz1 = 0.0f, nz2 = 0.0f;
     if (lane < n) {
         if (nz3) {          // the components apart (crender_plan_set_normal_z): 12 contiguous bytes per triangle
             const float *nn = nz3 + (b0 + lane) * 3;
@@ -221,7 +266,7 @@ __global__ __launch_bounds__(kWave) void k_count_wave(const float *__restrict__ 
 // written and read again) nor the scan nor a second pass over the triangles exist.  Entries are
 // (position, caller's index) pairs (the position itself without a triangle order).  10 M small triangles:
 // k_count_wave 0.152 + k_scan 0.015 + k_fill_wave 0.087 ms -> this kernel alone.  A list that outgrows its
-// slab is reported like an overflow of the direct bins (hdr[1], sticky) and the plan returns to the three passes.
+// slab is reported like an overflow of the direct bins (kHdrOverflow, sticky) and the plan returns to the three passes.
 // Groups of 64 triangles a wavefront takes through the chain together.  One: more groups lengthen the runs
 // of neighbouring positions in the lists (the raster launch gathers its records faster: 0.559 / 0.552 / 0.524 ms
 // with 1 / 2 / 4) but slow this pass down by more (0.176 / 0.195 / 0.279 ms; profiles/r05/ab_pair_bins_synth10m.txt).
@@ -246,7 +291,7 @@ __global__ __launch_bounds__(kWave) void k_bin_wave(const float *__restrict__ tr
     stage_in<kWave>(tri_in + b0 * 9, sv, n * 9);
 #pragma unroll
     for (int i = 0; i < kWaveHistTiles / kWave; ++i) hist[i * kWave + lane] = 0;   // (while the inputs are on their way)
-    float nz[kBinPer][3];                          // .pyx:202 looks at the normals' z only
+    float nz[kBinPer][3];
 #pragma unroll
     for (int p = 0; p < kBinPer; ++p) {
         const int k = p * kWave + lane;
@@ -283,10 +328,7 @@ __global__ __launch_bounds__(kWave) void k_bin_wave(const float *__restrict__ tr
             const TriXYZ t{a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8]};
             if (!backface(nz[p][0], nz[p][1], nz[p][2])) r[p] = tile_range<TS>(t, G);
         }
-        if (r[p].x != kNoTiles) {
-            const int x0 = r[p].x & 0xFFFF, x1 = r[p].x >> 16, y0 = r[p].y & 0xFFFF, y1 = r[p].y >> 16;
-            X0 = x0 < X0 ? x0 : X0; X1 = x1 > X1 ? x1 : X1; Y0 = y0 < Y0 ? y0 : Y0; Y1 = y1 > Y1 ? y1 : Y1;
-        }
+        grow_box(r[p], X0, X1, Y0, Y1);
     }
     wave_box(X0, X1, Y0, Y1);
     __syncthreads();
@@ -296,52 +338,30 @@ __global__ __launch_bounds__(kWave) void k_bin_wave(const float *__restrict__ tr
         if (slot < cap) pairs[(size_t)tile * cap + slot] = make_uint2((uint32_t)(b0 + owner), orig[owner]);
     };
     const int bw = X1 - X0 + 1, area = bw * (Y1 - Y0 + 1);
+    auto cell = [&](int tx, int ty) { return (ty - Y0) * bw + (tx - X0); };     // a tile's word of the histogram
     if (area > kWaveHistTiles) {
         // (large triangles: the wavefront's box exceeds the histogram) pair by pair
 #pragma unroll
         for (int p = 0; p < kBinPer; ++p)
             for_each_tile(r[p], (uint32_t)(p * kWave + lane), G.ntx, [&](int tile, uint32_t owner) {
                 const uint32_t slot = atomicAdd(&count[tile], 1u);
-                if (slot >= cap) atomicMax(&hdr[1], slot + 1u);
+                if (slot >= cap) atomicMax(&hdr[kHdrOverflow], slot + 1u);
                 put((uint32_t)tile, slot, (int)owner);
             });
         return;
     }
 #pragma unroll
     for (int p = 0; p < kBinPer; ++p)
-        for_each_tile_xy(r[p], [&](int tx, int ty, int) { atomicAdd(&hist[(ty - Y0) * bw + (tx - X0)], 1u); });
+        for_each_tile_xy(r[p], [&](int tx, int ty, int) { atomicAdd(&hist[cell(tx, ty)], 1u); });
     __syncthreads();
-    {
-        constexpr int kRounds = kWaveHistTiles / kWave;
-        const float rbw = 1.0f / (float)bw;
-        uint32_t c[kRounds], t[kRounds], base[kRounds];
-        const int nr = (area + kWave - 1) / kWave;      // rounds that have tiles at all (uniform; mostly 1)
-#pragma unroll
-        for (int k = 0; k < kRounds; ++k) {
-            c[k] = 0u; t[k] = 0u;
-            if (k < nr) {
-                const int i = k * kWave + lane;
-                c[k] = i < area ? hist[i] : 0u;
-                const int dy = (int)(((float)i + 0.5f) * rbw);          // exact: i < 2^22
-                t[k] = (uint32_t)((Y0 + dy) * G.ntx + X0 + (i - dy * bw));
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < kRounds; ++k)                            // all in flight together
-            base[k] = c[k] ? atomicAdd(&count[t[k]], c[k]) : 0u;
-#pragma unroll
-        for (int k = 0; k < kRounds; ++k) {
-            if (c[k]) {
-                hist[k * kWave + lane] = base[k];
-                if (base[k] + c[k] > cap) atomicMax(&hdr[1], base[k] + c[k]);
-            }
-        }
-    }
+    reserve_runs(hist, lane, X0, Y0, bw, area, G.ntx,
+                 [&](uint32_t tile, uint32_t n_) { return atomicAdd(&count[tile], n_); },
+                 [&](uint32_t first, uint32_t n_) { if (first + n_ > cap) atomicMax(&hdr[kHdrOverflow], first + n_); });
     __syncthreads();
 #pragma unroll
     for (int p = 0; p < kBinPer; ++p)
         for_each_tile_xy(r[p], [&](int tx, int ty, int owner) {
-            const uint32_t slot = atomicAdd(&hist[(ty - Y0) * bw + (tx - X0)], 1u);
+            const uint32_t slot = atomicAdd(&hist[cell(tx, ty)], 1u);
             put((uint32_t)(ty * G.ntx + tx), slot, p * kWave + owner);
         });
 }
@@ -382,16 +402,12 @@ __global__ __launch_bounds__(kWave) void k_fill_wave(const uint2 *__restrict__ t
     for (int i = 0; i < kWaveHistTiles / kWave; ++i) hist[i * kWave + lane] = 0;   // (while the ranges are on their way)
     int X0 = 0x7FFFFFFF, X1 = -1, Y0 = 0x7FFFFFFF, Y1 = -1;
 #pragma unroll
-    for (int p = 0; p < kFillPer; ++p) {
-        if (r[p].x != kNoTiles) {
-            const int x0 = r[p].x & 0xFFFF, x1 = r[p].x >> 16, y0 = r[p].y & 0xFFFF, y1 = r[p].y >> 16;
-            X0 = x0 < X0 ? x0 : X0; X1 = x1 > X1 ? x1 : X1; Y0 = y0 < Y0 ? y0 : Y0; Y1 = y1 > Y1 ? y1 : Y1;
-        }
-    }
+    for (int p = 0; p < kFillPer; ++p) grow_box(r[p], X0, X1, Y0, Y1);
     wave_box(X0, X1, Y0, Y1);
     if (X1 < 0) return;
     __syncthreads();        // histogram zeroed, the caller's indices in LDS
     const int bw = X1 - X0 + 1, area = bw * (Y1 - Y0 + 1);
+    auto cell = [&](int tx, int ty) { return (ty - Y0) * bw + (tx - X0); };     // a tile's word of the histogram
     if (area > kWaveHistTiles) {
 #pragma unroll
         for (int p = 0; p < kFillPer; ++p)
@@ -406,35 +422,16 @@ __global__ __launch_bounds__(kWave) void k_fill_wave(const uint2 *__restrict__ t
     }
 #pragma unroll
     for (int p = 0; p < kFillPer; ++p)
-        for_each_tile_xy(r[p], [&](int tx, int ty, int) { atomicAdd(&hist[(ty - Y0) * bw + (tx - X0)], 1u); });
+        for_each_tile_xy(r[p], [&](int tx, int ty, int) { atomicAdd(&hist[cell(tx, ty)], 1u); });
     __syncthreads();
-    {
-        constexpr int kRounds = kWaveHistTiles / kWave;
-        const float rbw = 1.0f / (float)bw;
-        uint32_t c[kRounds], t[kRounds], base[kRounds];
-        const int nr = (area + kWave - 1) / kWave;      // rounds that have tiles at all (uniform; mostly 1)
-#pragma unroll
-        for (int k = 0; k < kRounds; ++k) {
-            c[k] = 0u; t[k] = 0u;
-            if (k < nr) {
-                const int i = k * kWave + lane;
-                c[k] = i < area ? hist[i] : 0u;
-                const int dy = (int)(((float)i + 0.5f) * rbw);          // exact: i < 2^22
-                t[k] = (uint32_t)((Y0 + dy) * G.ntx + X0 + (i - dy * bw));
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < kRounds; ++k)                            // all in flight together
-            base[k] = c[k] ? offs[t[k]] + atomicAdd(&cursor[t[k]], c[k]) : 0u;
-#pragma unroll
-        for (int k = 0; k < kRounds; ++k)
-            if (c[k]) hist[k * kWave + lane] = base[k];
-    }
+    reserve_runs(hist, lane, X0, Y0, bw, area, G.ntx,
+                 [&](uint32_t tile, uint32_t n_) { return offs[tile] + atomicAdd(&cursor[tile], n_); },
+                 [](uint32_t, uint32_t) { });     // (a list that outgrows the capacity shows in k_scan's total)
     __syncthreads();
 #pragma unroll
     for (int p = 0; p < kFillPer; ++p)
         for_each_tile_xy(r[p], [&](int tx, int ty, int owner) {
-            const uint32_t pos = atomicAdd(&hist[(ty - Y0) * bw + (tx - X0)], 1u);
+            const uint32_t pos = atomicAdd(&hist[cell(tx, ty)], 1u);
             if (pos < capacity) {
                 if constexpr (PAIRS) pairs[pos] = make_uint2((uint32_t)(b0 + p * kWave + owner), orig[p * kWave + owner]);
                 else entries[pos] = (uint32_t)(b0 + p * kWave + owner);
@@ -443,7 +440,7 @@ __global__ __launch_bounds__(kWave) void k_fill_wave(const uint2 *__restrict__ t
 }
 
 // Exclusive scan of count[0..ntiles) into offs[0..ntiles]; count is zeroed (k_fill uses
-// it as the per-tile cursor); hdr[0] / hdr[4] = low / high word of the number of list entries
+// it as the per-tile cursor); kHdrEntriesLo / kHdrEntriesHi = low / high word of the number of list entries
 // this frame needs.  The running sum is kept in 64 bits and the offsets saturate at 2^32 - 1, so
 // a frame that needs more entries than 32 bits can index reports an unsatisfiable figure instead
 // of a wrapped one (k_raster clamps every range to the capacity: such tiles come out empty).
@@ -500,8 +497,8 @@ __global__ __launch_bounds__(1024) void k_scan(uint32_t *__restrict__ count,
     }
     if (tid == 0) {
         offs[ntiles] = sat(carry);
-        hdr[0] = (uint32_t)carry;
-        hdr[4] = (uint32_t)(carry >> 32);
+        hdr[kHdrEntriesLo] = (uint32_t)carry;
+        hdr[kHdrEntriesHi] = (uint32_t)(carry >> 32);
     }
 }
 
@@ -580,7 +577,6 @@ int run_bin_pass(crender_plan *plan, bool project, const float *d_tri, const flo
     const Layout &L = plan->L;
     const Geom G = L.g;
     const bool direct = L.direct_cap > 0 && plan->direct_ok && !(flags & CRENDER_NO_DIRECT_BINS);
-    plan->last_frame_direct = direct;
     plan->last_T = T;
     const int par = (int)(plan->frame_no++ & 1u);
     plan->parity = par;
@@ -605,7 +601,7 @@ int run_bin_pass(crender_plan *plan, bool project, const float *d_tri, const flo
         // round 5: the discarded frame's tiles kept their split flags, and the next frame on the plan
         // cleared only half of those it did not cover — test_lone_chain_through_changing_scenes.)
         CR_HIP(hipMemsetAsync(plan->ws + L.off_count, 0, L.off_order - L.off_count, s));
-        CR_HIP(hipMemsetAsync(plan->hdr() + 2, 0, 5 * sizeof(uint32_t), s));   // heavy counters, hint_bad
+        CR_HIP(hipMemsetAsync(plan->heavy_ctr(0), 0, (kHdrWords - kHdrHeavyCtr) * sizeof(uint32_t), s));   // ... and hint_bad
         plan->awaiting[0] = plan->awaiting[1] = false;
         plan->unrastered[0] = plan->unrastered[1] = false;
     }
@@ -631,19 +627,25 @@ int run_bin_pass(crender_plan *plan, bool project, const float *d_tri, const flo
     // large scenes: ONE binning pass into fixed-capacity slabs of (position, index) pairs (k_bin_wave)
     const bool pairbins = !direct && wave_scan && T > 0 && L.pair_cap > 0 && plan->pairbins_ok &&
                           !(flags & CRENDER_NO_DIRECT_BINS);
-    plan->last_frame_pairbins = pairbins;
+    plan->last_frame_mode = direct ? kFrameDirect : pairbins ? kFramePairs : kFrameScan;
     plan->last_frame_pairs = pairbins || (!direct && wave_scan && plan->orig_of != nullptr && T > 0);
+    // one of the one-wavefront-per-workgroup kernels, with or without the projection
+#define CR_WAVES(kernel, nwg, ...)                                                                             \
+    do {                                                                                                       \
+        if (project) hipLaunchKernelGGL((kernel<TS, true>), dim3(nwg), dim3(kWave), 0, s, __VA_ARGS__);        \
+        else hipLaunchKernelGGL((kernel<TS, false>), dim3(nwg), dim3(kWave), 0, s, __VA_ARGS__);               \
+    } while (0)
     if (T > 0 && direct) {
         // direct bins: one wavefront per 64 triangles
         HeavyReg hv;
         if (plan->frame_hmax > 0) {
-            hv.ctr = plan->hdr() + 2 + par; hv.flag = plan->hflag(); hv.slots = plan->hslots();
+            hv.ctr = plan->heavy_ctr(par); hv.flag = plan->hflag(); hv.slots = plan->hslots();
             hv.hmax = (uint32_t)plan->frame_hmax;
             hv.heavy_at = plan->frame_heavy_at;
         }
         if (L.ordered) {
             hv.grouped = plan->grouped(plan->hint_par);    // of the order this frame's raster pass reads
-            hv.hint_bad = plan->hdr() + 5 + par;
+            hv.hint_bad = plan->hint_bad(par);
         }
         const unsigned nwg = (unsigned)((T + kWave - 1) / kWave);
         if (defer && project && TS <= 32) {
@@ -652,32 +654,17 @@ int run_bin_pass(crender_plan *plan, bool project, const float *d_tri, const flo
             *deferred = true;
             return CRENDER_OK;
         }
-        if (project)
-            hipLaunchKernelGGL((k_setup_wave<TS, true>), dim3(nwg), dim3(kWave), 0, s, d_tri, d_nrm,
-                               plan->proj(), count, plan->direct(), (uint32_t)L.direct_cap, plan->hdr(),
-                               hv, T, P, G);
-        else
-            hipLaunchKernelGGL((k_setup_wave<TS, false>), dim3(nwg), dim3(kWave), 0, s, d_tri, d_nrm,
-                               plan->proj(), count, plan->direct(), (uint32_t)L.direct_cap, plan->hdr(),
-                               hv, T, P, G);
+        CR_WAVES(k_setup_wave, nwg, d_tri, d_nrm, plan->proj(), count, plan->direct(), (uint32_t)L.direct_cap,
+                 plan->hdr(), hv, T, P, G);
         CR_LAUNCH_CHECK("k_setup_wave");
     } else if (pairbins) {
         const unsigned nwg = (unsigned)((T + kWave * kBinPer - 1) / (kWave * kBinPer));
-        if (project)
-            hipLaunchKernelGGL((k_bin_wave<TS, true>), dim3(nwg), dim3(kWave), 0, s, d_tri, d_nrm, plan->normal_z, plan->orig_of,
-                               plan->proj(), count, plan->pairbins(), (uint32_t)L.pair_cap, plan->hdr(), T, P, G);
-        else
-            hipLaunchKernelGGL((k_bin_wave<TS, false>), dim3(nwg), dim3(kWave), 0, s, d_tri, d_nrm, plan->normal_z, plan->orig_of,
-                               plan->proj(), count, plan->pairbins(), (uint32_t)L.pair_cap, plan->hdr(), T, P, G);
+        CR_WAVES(k_bin_wave, nwg, d_tri, d_nrm, plan->normal_z, plan->orig_of, plan->proj(), count, plan->pairbins(),
+                 (uint32_t)L.pair_cap, plan->hdr(), T, P, G);
         CR_LAUNCH_CHECK("k_bin_wave");
     } else if (T > 0 && wave_scan) {
         const unsigned nwg = (unsigned)((T + kWave - 1) / kWave);
-        if (project)
-            hipLaunchKernelGGL((k_count_wave<TS, true>), dim3(nwg), dim3(kWave), 0, s, d_tri, d_nrm, plan->normal_z,
-                               plan->proj(), plan->trange(), count, T, P, G);
-        else
-            hipLaunchKernelGGL((k_count_wave<TS, false>), dim3(nwg), dim3(kWave), 0, s, d_tri, d_nrm, plan->normal_z,
-                               plan->proj(), plan->trange(), count, T, P, G);
+        CR_WAVES(k_count_wave, nwg, d_tri, d_nrm, plan->normal_z, plan->proj(), plan->trange(), count, T, P, G);
         CR_LAUNCH_CHECK("k_count_wave");
     } else if (T > 0) {
         int64_t nblk, chunk;
@@ -700,6 +687,7 @@ int run_bin_pass(crender_plan *plan, bool project, const float *d_tri, const flo
             else CR_SETUP(false, kBinCountGlobal);
         }
 #undef CR_SETUP
+#undef CR_WAVES
         CR_LAUNCH_CHECK("k_setup");
     }
     if (!direct && !pairbins) {

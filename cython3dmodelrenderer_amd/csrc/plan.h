@@ -24,7 +24,7 @@ struct Layout {
            off_trange, off_proj, off_entries, off_direct, off_pairbins, total;
 };
 constexpr int kUsageRing = 8;
-constexpr int kUsageWords = 8;         // words per usage record: {seq, hdr[0], hdr[1], hdr[4]} {large, small, path, seq}
+constexpr int kUsageWords = 8;         // words per usage record: {seq, kHdrEntriesLo, kHdrOverflow, kHdrEntriesHi} {large, small, path, seq}
 constexpr int kStatWords = 2 * 16;     // per parity: kStatSlots (large, small) pairs (raster.hip, TileLists::stats)
 int default_raster_path();             // crender_set_default_raster_path (-1: none)
 constexpr int kOrderMaxTiles = 8192;   // ordered dispatch: the builder keeps one byte per tile in the batch queue's LDS
@@ -42,6 +42,10 @@ constexpr int64_t kDirectBinBytes = 512ll << 20;   // per-tile capacity = this b
 // frame that does not fit reports so like the direct bins and the plan goes back to count / scan / fill.
 constexpr int64_t kPairBinBytes = 2048ll << 20;
 bool make_layout(int H, int W, int y0, int y1, int64_t max_T, int64_t cap, int tile, Layout &L);
+// How a frame was binned (the values crender_plan_last_frame_binning returns): count / scan / fill into scanned
+// lists; direct bins of 48-byte entries (small scenes); ONE pass into fixed-capacity per-tile slabs of
+// (position, index) pairs (k_bin_wave).
+enum BinMode : unsigned char { kFrameScan = 0, kFrameDirect = 1, kFramePairs = 2 };
 
 }  // namespace crender_detail
 
@@ -56,10 +60,9 @@ struct crender_plan {
     std::vector<hipEvent_t> events;
     int timed_frames = 0;
     bool direct_ok = true;        // cleared once a frame overflowed the direct bins
-    bool last_frame_direct = false;
+    BinMode last_frame_mode = kFrameScan;
     bool last_frame_pairs = false;    // its list entries are (position, caller's index) pairs (k_fill_wave<true>, k_bin_wave)
     bool pairbins_ok = true;          // cleared once a frame overflowed the pair bins
-    bool last_frame_pairbins = false; // binned in ONE pass into fixed-capacity per-tile slabs of pairs (k_bin_wave)
     int64_t last_T = -1;          // triangle count of the last bin pass (crender_draw must match)
     // The per-tile counters exist twice.  Frame f bins into parity f & 1 and its raster pass
     // zeroes the OTHER parity for frame f + 1, so no raster workgroup ever writes a counter that
@@ -88,7 +91,7 @@ struct crender_plan {
     // Bin-list usage of every frame without a host round trip (crender_plan_poll_bin_usage): each
     // raster launch copies the header words crender_plan_last_bin_usage reads into a record of its
     // own in PINNED host memory the plan owns — two 16-byte stores by one thread of the launch,
-    // {frame number, hdr[0], hdr[1], hdr[4]} {large tiles, small tiles, kernel, frame number} — so that the host
+    // {frame number, kHdrEntriesLo, kHdrOverflow, kHdrEntriesHi} {large tiles, small tiles, kernel, frame number} — so that the host
     // learns of an overflow (and of the frames' size class) by reading its own memory: no copy command, no event,
     // no synchronisation.  Ring of kUsageRing frames.
     uint32_t *usage = nullptr;            // [kUsageRing + 1][kUsageWords] (the last one: staging of the blocking query)
@@ -96,7 +99,20 @@ struct crender_plan {
     int usage_slot = -1;                  // its slot in the process-wide pool of pinned records (-1: an allocation of its own)
     uint32_t usage_salt = 0;              // XORed into the sequence word of this plan's records (slots are recycled)
     uint64_t ticket = 0;                  // raster launches so far: the last frame's number
-    unsigned char usage_mode[kUsageRing] = {};   // how the frame of each record was binned: 0 scan, 1 direct bins, 2 pair bins
+    BinMode usage_mode[kUsageRing] = {};  // how the frame of each record was binned
+    // Record of launch `t` (one of the last kUsageRing), whole or not at all.  The record is two aligned 16-byte
+    // stores of the launch, the frame's sequence word leading the first and trailing the second: taken only
+    // when BOTH are there, before and after the payload is read (a record half landed, or rewritten under the
+    // read by a frame kUsageRing later, reads as not landed).
+    bool usage_record(uint64_t t, uint32_t w[kUsageWords]) const
+    {
+        const volatile uint32_t *rec = usage + kUsageWords * (int)(t % kUsageRing);
+        const uint32_t seq = (uint32_t)t ^ usage_salt;
+        if (__atomic_load_n(const_cast<const uint32_t *>(rec), __ATOMIC_ACQUIRE) != seq || rec[7] != seq) return false;
+        for (int i = 1; i < kUsageWords - 1; ++i) w[i] = rec[i];
+        w[0] = w[kUsageWords - 1] = seq;
+        return rec[0] == seq && rec[7] == seq;
+    }
     // which raster kernel a 32-pixel plan's frames get (raster.hip, kPath*): forced by the caller (-1: not),
     // else suggested by the size classes its last reported frame counted; what the last launch was
     int forced_path = -1, auto_path = 0, last_path = 0;
@@ -110,7 +126,9 @@ struct crender_plan {
     float4 *direct() const { return reinterpret_cast<float4 *>(ws + L.off_direct); }
     bool timing() const { return !events.empty() && (size_t)(timed_frames + 1) * 3 <= events.size(); }
     hipEvent_t ev(int k) const { return events[(size_t)timed_frames * 3 + k]; }
-    uint32_t *hdr() const { return reinterpret_cast<uint32_t *>(ws + L.off_hdr); }
+    uint32_t *hdr() const { return reinterpret_cast<uint32_t *>(ws + L.off_hdr); }      // (binning.h, kHdr*)
+    uint32_t *heavy_ctr(int par) const { return hdr() + kHdrHeavyCtr + par; }
+    uint32_t *hint_bad(int par) const { return hdr() + kHdrHintBad + par; }
     uint32_t *offs() const { return reinterpret_cast<uint32_t *>(ws + L.off_offs); }
     uint2 *trange() const { return reinterpret_cast<uint2 *>(ws + L.off_trange); }
     float *proj() const { return reinterpret_cast<float *>(ws + L.off_proj); }

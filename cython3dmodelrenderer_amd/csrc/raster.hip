@@ -209,6 +209,41 @@ CR_DEV uint32_t packed_xy(uint32_t b, int X0, int Y0)
     return (uint32_t)(X0 + (int)(b & 0x3Fu)) | ((uint32_t)(Y0 + (int)((b >> 6) & 0x3Fu)) << 16);
 }
 
+// (xy, wh) in frame coordinates -> the corners of the pixel box [x0, x1) x [y0, y1)
+struct BoxCorners {
+    int x0, y0, x1, y1;
+};
+CR_DEV BoxCorners box_corners(uint32_t xy, uint32_t wh)
+{
+    const int x0 = (int)(xy & 0xFFFF), y0 = (int)(xy >> 16);
+    return BoxCorners{x0, y0, x0 + box_w(wh), y0 + box_h(wh)};
+}
+// A list entry's pixel box (ebx = xl | xr << 16, eby = yt | yb << 16) clipped to a workgroup's rectangle
+struct ClipBox {
+    int xl, xr, yt, yb;
+    CR_DEV bool any() const { return xl < xr && yt < yb; }
+    CR_DEV uint32_t xy() const { return (uint32_t)xl | ((uint32_t)yt << 16); }
+    CR_DEV uint32_t wh() const { return (uint32_t)(xr - xl) | ((uint32_t)(yb - yt) << 16); }
+};
+CR_DEV ClipBox clip_box(uint32_t ebx, uint32_t eby, int X0, int Y0, int X1, int Y1)
+{
+    int xl = (int)(ebx & 0xFFFF), xr = (int)(ebx >> 16);
+    int yt = (int)(eby & 0xFFFF), yb = (int)(eby >> 16);
+    if (xl < X0) xl = X0;
+    if (xr > X1) xr = X1;
+    if (yt < Y0) yt = Y0;
+    if (yb > Y1) yb = Y1;
+    return ClipBox{xl, xr, yt, yb};
+}
+
+// ... of a queue's packed word (WorkQueue::box)
+CR_DEV BoxCorners packed_corners(uint32_t b, int X0, int Y0)
+{
+    const uint32_t wh = packed_wh(b);
+    const uint32_t xy = packed_xy(b, X0, Y0);
+    return box_corners(xy, wh);
+}
+
 CR_DEV int blocks_of(uint32_t box_wh)
 {
     return ((box_w(box_wh) + 3) >> 2) * ((box_h(box_wh) + 3) >> 2);
@@ -304,13 +339,53 @@ CR_DEV void coarse_cull(WorkQueue &q, const uint32_t *wo, int total, int tid, in
 // the whole device — s_memtime has a base per XCD / clock domain) written to a buffer of their
 // own that no kernel reads.  16 words per workgroup of the raster grid: t_start, t_ready, t_swept,
 // t_end, list length, t_loads, t_queue, XCC id, tile, quadrant + 1.
+// The forms below expand to nothing in the product build, so no function body asks which build it is in:
+//   CR_STAMP(slot)                 the clock into a slot          CR_STAMP_IF(cond, slot)   the same under a condition
+//   CR_STAMP_LOADED(cond, slot)    ... once the wavefront's loads have landed
+//   CR_STAMP_WORD(cond, slot, v)   a value into a slot            CR_STAMP_TILE(tile)       slots 7, 8, 10 of a workgroup
+//   CR_STAMP_LIST(len, quad)       slots 4, 9: the list's length, which part of the tile
+// (scripts/stamps*.py read the slots by number)
 __device__ unsigned long long *g_stamps = nullptr;
 #define CR_STAMP(slot)                                                             \
     do {                                                                           \
         if (g_stamps && threadIdx.x == 0) g_stamps[stamp_base + (slot)] = wall_clock64(); \
     } while (0)
+#define CR_STAMP_IF(cond, slot) do { if (cond) CR_STAMP(slot); } while (0)
+#define CR_STAMP_LOADED(cond, slot)                                                \
+    do {                                                                           \
+        if (cond) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); CR_STAMP(slot); } \
+    } while (0)
+#define CR_STAMP_WORD(cond, slot, value)                                           \
+    do {                                                                           \
+        if (g_stamps && (cond) && threadIdx.x == 0) g_stamps[stamp_base + (slot)] = (value); \
+    } while (0)
+#define CR_STAMP_LIST(len, quad)                                                   \
+    do {                                                                           \
+        if (g_stamps && tid == 0) {            /* (the body's own tid) */          \
+            g_stamps[stamp_base + 4] = (len);                                      \
+            g_stamps[stamp_base + 9] = (unsigned long long)((quad) + 1);           \
+        }                                                                          \
+    } while (0)
+#define CR_STAMP_TILE(tile)                                                        \
+    do {                                                                           \
+        if (g_stamps && threadIdx.x == 0) {                                        \
+            g_stamps[stamp_base + 7] = __builtin_amdgcn_s_getreg((3 << 11) | 20);   /* XCC_ID */ \
+            g_stamps[stamp_base + 8] = (unsigned long long)(tile);                 \
+            g_stamps[stamp_base + 10] = __builtin_amdgcn_s_memtime();              \
+        }                                                                          \
+    } while (0)
+// a workgroup's slots in the buffer: frames of a swap chain stamp into a region of their slot, 8192 workgroups each
+#define CR_TILE_STAMP_BASE(c, stamp_slot) (c).stamp_base = ((size_t)(stamp_slot) * 8192 + blockIdx.x) * 16
+#define CR_TILE_STAMPS(c) [[maybe_unused]] const size_t stamp_base = (c).stamp_base
 #else
 #define CR_STAMP(slot) do { } while (0)
+#define CR_STAMP_IF(cond, slot) do { } while (0)
+#define CR_STAMP_LOADED(cond, slot) do { } while (0)
+#define CR_STAMP_WORD(cond, slot, value) do { } while (0)
+#define CR_STAMP_LIST(len, quad) do { } while (0)
+#define CR_STAMP_TILE(tile) do { } while (0)
+#define CR_TILE_STAMP_BASE(c, stamp_slot) do { } while (0)
+#define CR_TILE_STAMPS(c) do { } while (0)
 #endif
 
 // Background of a tile rectangle (fused clear): z = 1e6, colour = normal = 0, winner = -1.
@@ -412,7 +487,7 @@ struct TileLists {
     int vec_clear;              // planes 16-byte aligned and W % 4 == 0
     Light light;                // CRENDER_FUSED_GURO: illumination applied as pixels are stored
     // this frame's bin-usage record in the plan's pinned host memory (crender_plan_poll_bin_usage):
-    // {frame number, hdr[0], hdr[1], hdr[4]} {large tiles, small tiles, kernel, frame number}, two 16-byte stores
+    // {frame number, kHdrEntriesLo, kHdrOverflow, kHdrEntriesHi} {large tiles, small tiles, kernel, frame number}, two 16-byte stores
     // by the launch's LAST main workgroup (in raster order a corner tile, in an ordered launch a group of empty
     // tiles: nobody's critical path)
     const uint32_t *hdr;
@@ -583,7 +658,67 @@ CR_DEV void build_order(const uint32_t *__restrict__ count, int ntx, int nty,
 // instead of 333 k; raster 149 -> 133 us).  The resolve only interpolates: no LDS atomics, no
 // second set of divisions.  Same device functions, same keys, same tie rule as the sweeps above:
 // the planes are bit-identical.
-constexpr uint32_t kOwnFast = 1u << 4;     // flags word of a record: bits 0..3 bands, 4 window, 5..10 signs
+// A queued record's coordinates and the six edge differences (one operation each: worked out anew, not stored).
+template <typename Q>
+CR_DEV void setup_edges(TriSetup &st, const Q &q, int r)
+{
+    st.x0 = q.x0[r]; st.y0 = q.y0[r]; st.z0 = q.z0[r];
+    st.x1 = q.x1[r]; st.y1 = q.y1[r]; st.z1 = q.z1[r];
+    st.x2 = q.x2[r]; st.y2 = q.y2[r]; st.z2 = q.z2[r];
+    st.l01 = st.x1 - st.x2; st.l02 = st.y1 - st.y2;
+    st.l11 = st.x2 - st.x0; st.l12 = st.y2 - st.y0;
+    st.l21 = st.x0 - st.x1; st.l22 = st.y0 - st.y1;
+}
+// ... and the denominators and refined reciprocals its thread left in q.pre with the queue (r1 = 0: outside the
+// division window).  The caller sets rej*.
+CR_DEV TriSetup queued_setup(const WorkQueue &q, int r)
+{
+    TriSetup st;
+    setup_edges(st, q, r);
+    st.l03 = q.pre.l03[r]; st.l13 = q.pre.l13[r]; st.l23 = q.pre.l23[r];
+    st.r1 = q.pre.r1[r]; st.r2 = q.pre.r2[r]; st.r3 = q.pre.r3[r];
+    st.fast = st.r1 != 0.0f;
+    return st;
+}
+// The pixel owners' eight words per record: {l03, l13, l23, flags} {r1, r2, r3, -}.  The flags word: bits 0..3
+// which of the four wavefronts' bands of eight rows the triangle can touch at all, bit 4 the denominators lie
+// inside the division window, bits 5..10 the signs rej1..3 of the denominators, two bits each (1: +1, 2: -1, 0: 0).
+constexpr uint32_t kOwnFast = 1u << 4;
+constexpr int kOwnSigns = 5;
+CR_DEV uint32_t owner_signs(const TriSetup &st)
+{
+    auto two_bits = [](float rej) { return (uint32_t)(rej > 0.0f ? 1 : rej < 0.0f ? 2 : 0); };
+    return (st.fast ? kOwnFast : 0u) | two_bits(st.rej1) << kOwnSigns | two_bits(st.rej2) << (kOwnSigns + 2) |
+           two_bits(st.rej3) << (kOwnSigns + 4);
+}
+// ... with the band bits of a record that has a box (the block cull's corner test, raster_math.h (1), on
+// box ∩ band; the rectangle's rows are [Y0, Y1))
+CR_DEV uint32_t owner_bands(uint32_t flags, const TriSetup &st, uint32_t box_xy, uint32_t box_wh, int Y0, int Y1)
+{
+    const auto [bx0, by0, bx1, by1] = box_corners(box_xy, box_wh);
+#pragma unroll
+    for (int band = 0; band < 4; ++band) {
+        const int ya = Y0 + 8 * band, yb = (ya + 8 < Y1) ? ya + 8 : Y1;
+        if (by1 > ya && by0 < yb &&
+            !rect_surely_missed(st, bx0, bx1 - 1, by0 > ya ? by0 : ya, (by1 < yb ? by1 : yb) - 1))
+            flags |= 1u << band;
+    }
+    return flags;
+}
+// A record's setup as the owners sweep it: the queue's coordinates, the rest from its eight words.
+template <typename Q>
+CR_DEV TriSetup owner_setup(const Q &q, const float *pre, int r, const float4 &p0, uint32_t flags)
+{
+    const float4 p1 = *reinterpret_cast<const float4 *>(pre + 8 * r + 4);
+    TriSetup st;
+    setup_edges(st, q, r);
+    st.l03 = p0.x; st.l13 = p0.y; st.l23 = p0.z; st.fast = (flags & kOwnFast) != 0;
+    st.r1 = p1.x; st.r2 = p1.y; st.r3 = p1.z;
+    auto sign_of = [](uint32_t two_bits) { return two_bits == 1u ? 1.0f : two_bits == 2u ? -1.0f : 0.0f; };
+    st.rej1 = sign_of((flags >> kOwnSigns) & 3u); st.rej2 = sign_of((flags >> (kOwnSigns + 2)) & 3u);
+    st.rej3 = sign_of((flags >> (kOwnSigns + 4)) & 3u);
+    return st;
+}
 template <bool CLEAR, typename I, typename Q>
 CR_DEV void owner_tile(const Q &q, const float *pre, int nrec, const float *__restrict__ col, const float *__restrict__ nrm,
                        const uint32_t *__restrict__ pos_of, const Light &Lt,
@@ -611,24 +746,8 @@ CR_DEV void owner_tile(const Q &q, const float *pre, int nrec, const float *__re
         const uint32_t flags = __float_as_uint(p0.w);
         // the triangle cannot touch this wavefront's rows (no work, box or triangle elsewhere): uniform
         if (!(flags & my_band)) continue;
-        const uint32_t wh = packed_wh(q.box[r]);
-        const uint32_t xy = packed_xy(q.box[r], X0, Y0);
-        const int bx0 = (int)(xy & 0xFFFF), by0 = (int)(xy >> 16);
-        const int bx1 = bx0 + box_w(wh), by1 = by0 + box_h(wh);
-        TriSetup st;
-        {   // the record's setup: differences anew (one operation each), the rest as its thread left it
-            const float4 p1 = *reinterpret_cast<const float4 *>(pre + 8 * r + 4);
-            st.x0 = q.x0[r]; st.y0 = q.y0[r]; st.z0 = q.z0[r];
-            st.x1 = q.x1[r]; st.y1 = q.y1[r]; st.z1 = q.z1[r];
-            st.x2 = q.x2[r]; st.y2 = q.y2[r]; st.z2 = q.z2[r];
-            st.l01 = st.x1 - st.x2; st.l02 = st.y1 - st.y2;
-            st.l11 = st.x2 - st.x0; st.l12 = st.y2 - st.y0;
-            st.l21 = st.x0 - st.x1; st.l22 = st.y0 - st.y1;
-            st.l03 = p0.x; st.l13 = p0.y; st.l23 = p0.z; st.fast = (flags & kOwnFast) != 0;
-            st.r1 = p1.x; st.r2 = p1.y; st.r3 = p1.z;
-            auto sign_of = [](uint32_t two_bits) { return two_bits == 1u ? 1.0f : two_bits == 2u ? -1.0f : 0.0f; };
-            st.rej1 = sign_of((flags >> 5) & 3u); st.rej2 = sign_of((flags >> 7) & 3u); st.rej3 = sign_of((flags >> 9) & 3u);
-        }
+        const auto [bx0, by0, bx1, by1] = packed_corners(q.box[r], X0, Y0);
+        const TriSetup st = owner_setup(q, pre, r, p0, flags);
         const uint32_t low = 0xFFFFFFFEu - q.tri[r];
         const bool rows_ok = Y >= by0 && Y < by1;
         // numerators() with the row's share of each edge worked out once for the four x-neighbours
@@ -685,20 +804,10 @@ CR_DEV void owner_tile(const Q &q, const float *pre, int nrec, const float *__re
                 load9(elem(col, (I)((I)at * 9)), c);
                 load9(elem(nrm, (I)((I)at * 9)), n);
             }
-            const float b1 = w1[j], b2 = w2[j], b3 = w3[j];
-            zv[j] = interp(z0, z1, z2, b1, b2, b3);
-            float c0 = interp(c[0], c[3], c[6], b1, b2, b3);
-            float c1 = interp(c[1], c[4], c[7], b1, b2, b3);
-            float c2 = interp(c[2], c[5], c[8], b1, b2, b3);
-            const float n0 = interp(n[0], n[3], n[6], b1, b2, b3);
-            const float n1 = interp(n[1], n[4], n[7], b1, b2, b3);
-            const float n2 = interp(n[2], n[5], n[8], b1, b2, b3);
-            if (Lt.on) {
-                const float f = guro_factor(Lt, n0, n1, n2);
-                c0 *= f; c1 *= f; c2 *= f;
-            }
-            cv[3 * j] = c0; cv[3 * j + 1] = c1; cv[3 * j + 2] = c2;
-            nv[3 * j] = n0; nv[3 * j + 1] = n1; nv[3 * j + 2] = n2;
+            zv[j] = interp(z0, z1, z2, w1[j], w2[j], w3[j]);
+            const Shade sh = shade_fragment(c, n, w1[j], w2[j], w3[j], Lt);
+            cv[3 * j] = sh.c0; cv[3 * j + 1] = sh.c1; cv[3 * j + 2] = sh.c2;
+            nv[3 * j] = sh.n0; nv[3 * j + 1] = sh.n1; nv[3 * j + 2] = sh.n2;
             iv[j] = (int32_t)id;
         }
     }
@@ -737,11 +846,6 @@ struct Tile {
     size_t stamp_base;
 #endif
 };
-#ifdef CRENDER_STAMPS
-#define CR_TILE_STAMPS(c) [[maybe_unused]] const size_t stamp_base = (c).stamp_base
-#else
-#define CR_TILE_STAMPS(c) do { } while (0)
-#endif
 // (the names the bodies below were written with)
 #define CR_TILE_LOCALS(c)                                                                                        \
     [[maybe_unused]] const float *const proj = (c).proj, *const col = (c).col, *const nrm = (c).nrm;             \
@@ -848,7 +952,7 @@ CR_DEV bool pick_tile(const Tile<TS> &c, int b, int &b_out, int &tile, int &quad
             // reader takes the record only when both are this frame's
             uint4 *rec = reinterpret_cast<uint4 *>(L.usage);
             rec[1] = make_uint4(nl, ns, L.path, L.usage_seq);
-            rec[0] = make_uint4(L.usage_seq, L.hdr[0], L.hdr[1], L.hdr[4]);
+            rec[0] = make_uint4(L.usage_seq, L.hdr[kHdrEntriesLo], L.hdr[kHdrOverflow], L.hdr[kHdrEntriesHi]);
         }
         if (L.order && L.hint[0] && !*L.hint_bad) {
             const int ns = (int)L.hint[1], ng = (int)L.hint[2];
@@ -965,9 +1069,7 @@ CR_DEV void pixel_path16(const Tile<16> &c, uint32_t left, bool first, const Tri
     if (!first) __syncthreads();
     if (tid < (int)left) put_rec16(&recs[tid], cur_t, key_low, box_xy, box_wh);
     __syncthreads();
-#ifdef CRENDER_STAMPS
-    if (first) CR_STAMP(6);
-#endif
+    CR_STAMP_IF(first, 6);
     const int px = X0 + (tid & 15), py = Y0 + (tid >> 4);
     unsigned long long best = key[tid];
     for (uint32_t r = 0; r < left; ++r) {
@@ -1067,22 +1169,11 @@ CR_DEV void sweep_runs32(const Tile<32> &c, const uint32_t *wo_, int total_)
         const uint32_t pb = q.box[r];
         const uint32_t xy = packed_xy(pb, X0, Y0), wh = packed_wh(pb);
         const int bw = box_w(wh), bh = box_h(wh);
-        const TriXYZ t{q.x0[r], q.y0[r], q.z0[r], q.x1[r], q.y1[r], q.z1[r], q.x2[r], q.y2[r], q.z2[r]};
-        const uint32_t id = q.tri[r];
         // the item's samples share its twelve LDS reads, the nine edge constants and the refined
         // reciprocals (raster_math.h (2)): per sample that was 150 vector instructions, a pair costs 175
-        TriSetup st;
-        {
-            st.x0 = t.x0; st.y0 = t.y0; st.z0 = t.z0; st.x1 = t.x1; st.y1 = t.y1; st.z1 = t.z1;
-            st.x2 = t.x2; st.y2 = t.y2; st.z2 = t.z2;
-            st.l01 = t.x1 - t.x2; st.l02 = t.y1 - t.y2;
-            st.l11 = t.x2 - t.x0; st.l12 = t.y2 - t.y0;
-            st.l21 = t.x0 - t.x1; st.l22 = t.y0 - t.y1;
-            st.l03 = q.pre.l03[r]; st.l13 = q.pre.l13[r]; st.l23 = q.pre.l23[r];
-            st.r1 = q.pre.r1[r]; st.r2 = q.pre.r2[r]; st.r3 = q.pre.r3[r];
-            st.fast = st.r1 != 0.0f;
-            st.rej1 = st.rej2 = st.rej3 = 0.0f;
-        }
+        TriSetup st = queued_setup(q, r);
+        st.rej1 = st.rej2 = st.rej3 = 0.0f;
+        const uint32_t id = q.tri[r];
         const int x = (int)(xy & 0xFFFF) + px0, y = (int)(xy >> 16) + dy;
 #pragma unroll
         for (int j = 0; j < kItemPixels32; ++j) {
@@ -1121,32 +1212,10 @@ CR_DEV void owner_path32(const Tile<32> &c, int nrec)
         // (the constants of a record with a box are in q.pre since the queue was written; one without a box
         // gets no band bit below and is never looked at)
         const uint32_t bwh = packed_wh(q.box[tid]), bxy = packed_xy(q.box[tid], X0, Y0);
-        TriSetup st;
-        st.x0 = q.x0[tid]; st.y0 = q.y0[tid]; st.z0 = q.z0[tid];
-        st.x1 = q.x1[tid]; st.y1 = q.y1[tid]; st.z1 = q.z1[tid];
-        st.x2 = q.x2[tid]; st.y2 = q.y2[tid]; st.z2 = q.z2[tid];
-        st.l01 = st.x1 - st.x2; st.l02 = st.y1 - st.y2;
-        st.l11 = st.x2 - st.x0; st.l12 = st.y2 - st.y0;
-        st.l21 = st.x0 - st.x1; st.l22 = st.y0 - st.y1;
-        st.l03 = q.pre.l03[tid]; st.l13 = q.pre.l13[tid]; st.l23 = q.pre.l23[tid];
-        st.r1 = q.pre.r1[tid]; st.r2 = q.pre.r2[tid]; st.r3 = q.pre.r3[tid];
-        st.fast = st.r1 != 0.0f;
+        TriSetup st = queued_setup(q, tid);
         st.rej1 = rej_sign(st.l03); st.rej2 = rej_sign(st.l13); st.rej3 = rej_sign(st.l23);
-        uint32_t flags = st.fast ? kOwnFast : 0u;
-        flags |= (uint32_t)(st.rej1 > 0.0f ? 1 : st.rej1 < 0.0f ? 2 : 0) << 5;
-        flags |= (uint32_t)(st.rej2 > 0.0f ? 1 : st.rej2 < 0.0f ? 2 : 0) << 7;
-        flags |= (uint32_t)(st.rej3 > 0.0f ? 1 : st.rej3 < 0.0f ? 2 : 0) << 9;
-        if (bwh != 0) {
-            const int bx0 = (int)(bxy & 0xFFFF), by0 = (int)(bxy >> 16);
-            const int bx1 = bx0 + box_w(bwh), by1 = by0 + box_h(bwh);
-#pragma unroll
-            for (int band = 0; band < 4; ++band) {
-                const int ya = Y0 + 8 * band, yb = (ya + 8 < Y1) ? ya + 8 : Y1;
-                if (by1 > ya && by0 < yb &&
-                    !rect_surely_missed(st, bx0, bx1 - 1, by0 > ya ? by0 : ya, (by1 < yb ? by1 : yb) - 1))
-                    flags |= 1u << band;
-            }
-        }
+        uint32_t flags = owner_signs(st);
+        if (bwh != 0) flags = owner_bands(flags, st, bxy, bwh, Y0, Y1);
         float4 *o = reinterpret_cast<float4 *>(pre + 8 * tid);
         o[0] = make_float4(st.l03, st.l13, st.l23, __uint_as_float(flags));
         o[1] = make_float4(st.r1, st.r2, st.r3, 0.0f);
@@ -1192,16 +1261,8 @@ CR_DEV int owners_queue(const Tile<32> &c, uint32_t base, bool first)
     if (ok) ok = load_record(L, proj, G, base + tid, id, t, ebx, eby);
     uint32_t box_xy = 0, box_wh = 0;
     if (ok) {
-        int xl = (int)(ebx & 0xFFFF), xr = (int)(ebx >> 16);
-        int yt = (int)(eby & 0xFFFF), yb = (int)(eby >> 16);
-        if (xl < X0) xl = X0;
-        if (xr > X1) xr = X1;
-        if (yt < Y0) yt = Y0;
-        if (yb > Y1) yb = Y1;
-        if (xl < xr && yt < yb) {
-            box_xy = (uint32_t)xl | ((uint32_t)yt << 16);
-            box_wh = (uint32_t)(xr - xl) | ((uint32_t)(yb - yt) << 16);
-        }
+        const ClipBox cl = clip_box(ebx, eby, X0, Y0, X1, Y1);
+        if (cl.any()) { box_xy = cl.xy(); box_wh = cl.wh(); }
     }
     if (first && __builtin_amdgcn_readfirstlane(wave) == 0)    // the tile's size class (TileLists::stats), reported at the tile's end
         tile_class = tile_class_of(wave_incl_sum((uint32_t)blocks_of(box_wh)), end - beg);
@@ -1213,21 +1274,7 @@ CR_DEV int owners_queue(const Tile<32> &c, uint32_t base, bool first)
     oq.box[tid] = pack_box(box_xy, box_wh, X0, Y0);
     uint32_t flags = 0;
     const TriSetup st = make_setup(t, true);
-    if (box_wh != 0) {
-        flags = st.fast ? kOwnFast : 0u;
-        flags |= (uint32_t)(st.rej1 > 0.0f ? 1 : st.rej1 < 0.0f ? 2 : 0) << 5;
-        flags |= (uint32_t)(st.rej2 > 0.0f ? 1 : st.rej2 < 0.0f ? 2 : 0) << 7;
-        flags |= (uint32_t)(st.rej3 > 0.0f ? 1 : st.rej3 < 0.0f ? 2 : 0) << 9;
-        const int bx0 = (int)(box_xy & 0xFFFF), by0 = (int)(box_xy >> 16);
-        const int bx1 = bx0 + box_w(box_wh), by1 = by0 + box_h(box_wh);
-#pragma unroll
-        for (int band = 0; band < 4; ++band) {
-            const int ya = Y0 + 8 * band, yb = (ya + 8 < Y1) ? ya + 8 : Y1;
-            if (by1 > ya && by0 < yb &&
-                !rect_surely_missed(st, bx0, bx1 - 1, by0 > ya ? by0 : ya, (by1 < yb ? by1 : yb) - 1))
-                flags |= 1u << band;
-        }
-    }
+    if (box_wh != 0) flags = owner_bands(owner_signs(st), st, box_xy, box_wh, Y0, Y1);
     float4 *o = reinterpret_cast<float4 *>(pre + 8 * tid);
     o[0] = make_float4(st.l03, st.l13, st.l23, __uint_as_float(flags));
     o[1] = make_float4(st.fast ? st.r1 : 0.0f, st.r2, st.r3, 0.0f);
@@ -1272,25 +1319,9 @@ CR_DEV void owners_batches(const Tile<32> &c)
                 const float4 p0 = *reinterpret_cast<const float4 *>(pre + 8 * r);
                 const uint32_t flags = __float_as_uint(p0.w);
                 if (!(flags & my_band)) continue;           // (uniform over the wavefront)
-                const uint32_t pb = oq.box[r];
-                const uint32_t wh = packed_wh(pb), xy = packed_xy(pb, X0, Y0);
-                const int bx0 = (int)(xy & 0xFFFF), by0 = (int)(xy >> 16);
-                const int bx1 = bx0 + box_w(wh), by1 = by0 + box_h(wh);
+                const auto [bx0, by0, bx1, by1] = packed_corners(oq.box[r], X0, Y0);
                 if (X0 + XS * j >= bx1 || X0 + XS * j + XS <= bx0) continue;     // the box misses block j (uniform)
-                TriSetup st;
-                {
-                    const float4 p1 = *reinterpret_cast<const float4 *>(pre + 8 * r + 4);
-                    st.x0 = oq.x0[r]; st.y0 = oq.y0[r]; st.z0 = oq.z0[r];
-                    st.x1 = oq.x1[r]; st.y1 = oq.y1[r]; st.z1 = oq.z1[r];
-                    st.x2 = oq.x2[r]; st.y2 = oq.y2[r]; st.z2 = oq.z2[r];
-                    st.l01 = st.x1 - st.x2; st.l02 = st.y1 - st.y2;
-                    st.l11 = st.x2 - st.x0; st.l12 = st.y2 - st.y0;
-                    st.l21 = st.x0 - st.x1; st.l22 = st.y0 - st.y1;
-                    st.l03 = p0.x; st.l13 = p0.y; st.l23 = p0.z; st.fast = (flags & kOwnFast) != 0;
-                    st.r1 = p1.x; st.r2 = p1.y; st.r3 = p1.z;
-                    auto sign_of = [](uint32_t two_bits) { return two_bits == 1u ? 1.0f : two_bits == 2u ? -1.0f : 0.0f; };
-                    st.rej1 = sign_of((flags >> 5) & 3u); st.rej2 = sign_of((flags >> 7) & 3u); st.rej3 = sign_of((flags >> 9) & 3u);
-                }
+                const TriSetup st = owner_setup(oq, pre, r, p0, flags);
                 // numerators() (mu.pyx:34 before the division), the operations in the reference's order
                 const float n1 = st.l01 * (fy - st.y2) - st.l02 * (fx - st.x2);
                 const float n2 = st.l11 * (fy - st.y0) - st.l12 * (fx - st.x0);
@@ -1322,31 +1353,16 @@ CR_DEV void owners_batches(const Tile<32> &c)
                 load9(elem(col, (I)((I)at * 9)), cc);
                 load9(elem(nrm, (I)((I)at * 9)), nn);
                 const float zv = interp(oq.z0[slot], oq.z1[slot], oq.z2[slot], w1, w2, w3);
-                float c0 = interp(cc[0], cc[3], cc[6], w1, w2, w3);
-                float c1 = interp(cc[1], cc[4], cc[7], w1, w2, w3);
-                float c2 = interp(cc[2], cc[5], cc[8], w1, w2, w3);
-                const float n0 = interp(nn[0], nn[3], nn[6], w1, w2, w3);
-                const float n1 = interp(nn[1], nn[4], nn[7], w1, w2, w3);
-                const float n2 = interp(nn[2], nn[5], nn[8], w1, w2, w3);
-                if (L.light.on) {
-                    const float f = guro_factor(L.light, n0, n1, n2);
-                    c0 *= f; c1 *= f; c2 *= f;
-                }
+                const Shade sh = shade_fragment(cc, nn, w1, w2, w3, L.light);
                 *elem(zb, pix) = zv;
                 float *cp = elem(cb, (I)(pix * 3)), *np_ = elem(nb, (I)(pix * 3));
-                cp[0] = c0; cp[1] = c1; cp[2] = c2;
-                np_[0] = n0; np_[1] = n1; np_[2] = n2;
-                if (win) *reinterpret_cast<int32_t *>(elem(reinterpret_cast<float *>(win), pix)) = (int32_t)tid_w;
+                cp[0] = sh.c0; cp[1] = sh.c1; cp[2] = sh.c2;
+                np_[0] = sh.n0; np_[1] = sh.n1; np_[2] = sh.n2;
+                store_winner(win, pix, (int32_t)tid_w);
             }
         }
         // ---- background: a pixel no batch won (fused clear) --------------------------------------------
-        if (CLEAR && mine_in && (uint32_t)best == KEY_LOW_PRIOR) {
-            *elem(zb, pix) = 1e6f;
-            float *cp = elem(cb, (I)(pix * 3)), *np_ = elem(nb, (I)(pix * 3));
-            cp[0] = 0.0f; cp[1] = 0.0f; cp[2] = 0.0f;
-            np_[0] = 0.0f; np_[1] = 0.0f; np_[2] = 0.0f;
-            if (win) *reinterpret_cast<int32_t *>(elem(reinterpret_cast<float *>(win), pix)) = -1;
-        }
+        if (CLEAR && mine_in && (uint32_t)best == KEY_LOW_PRIOR) store_background(pix, zb, cb, nb, win);
     }
     if (tid == 0) count_tile_class(L, tile_class);
     CR_STAMP(3);
@@ -1547,13 +1563,7 @@ CR_DEV void resolve_tile(const Tile<TS> &c, bool slotted)
         const I pix = (I)((I)y * (I)G.W + (I)x);
         const uint32_t low = (uint32_t)key[key_slot<TS>(dx, dy)];
         if (low == KEY_LOW_PRIOR) {
-            if (CLEAR) {
-                *elem(zb, pix) = 1e6f;
-                float *cp = elem(cb, (I)(pix * 3)), *np_ = elem(nb, (I)(pix * 3));
-                cp[0] = 0.0f; cp[1] = 0.0f; cp[2] = 0.0f;
-                np_[0] = 0.0f; np_[1] = 0.0f; np_[2] = 0.0f;
-                if (win) *reinterpret_cast<int32_t *>(elem(reinterpret_cast<float *>(win), pix)) = -1;
-            }
+            if (CLEAR) store_background(pix, zb, cb, nb, win);
             continue;
         }
         uint32_t id = 0xFFFFFFFEu - low;
@@ -1563,12 +1573,12 @@ CR_DEV void resolve_tile(const Tile<TS> &c, bool slotted)
                 // the winner's record is still in LDS (it came with the last batch)
                 shade16_store(load_rec16(&recs[low & 0xFFu]), col, nrm, L.pos_of ? L.pos_of[id] : id, x, y, pix,
                               zb, cb, nb, L.light);
-                if (win) *reinterpret_cast<int32_t *>(elem(reinterpret_cast<float *>(win), pix)) = (int32_t)id;
+                store_winner(win, pix, (int32_t)id);
                 continue;
             }
         }
         shade_and_store(proj, col, nrm, position_of(id), x, y, pix, zb, cb, nb, L.light);
-        if (win) *reinterpret_cast<int32_t *>(elem(reinterpret_cast<float *>(win), pix)) = (int32_t)id;
+        store_winner(win, pix, (int32_t)id);
     }
     };
     if (L.addr32) resolve(uint32_t{}); else resolve(size_t{});
@@ -1585,10 +1595,7 @@ CR_DEV void raster_body(const float *__restrict__ proj, const float *__restrict_
                         unsigned long long *key, unsigned char *qraw)
 {
     Tile<TS> c{proj, col, nrm, L, zb, cb, nb, win, G, key, qraw, 0, 0, 0, 0, TS, -1, 0u, 0u};
-#ifdef CRENDER_STAMPS
-    // frames of a swap chain stamp into a region of their slot, 8192 workgroups each
-    c.stamp_base = ((size_t)stamp_slot * 8192 + blockIdx.x) * 16;
-#endif
+    CR_TILE_STAMP_BASE(c, stamp_slot);
     CR_TILE_STAMPS(c);
     [[maybe_unused]] WorkQueue &q = *reinterpret_cast<WorkQueue *>(qraw);                 // (TS != 16 only)
     [[maybe_unused]] Rec16 *recs = reinterpret_cast<Rec16 *>(qraw);                       // (TS == 16 only)
@@ -1610,13 +1617,7 @@ CR_DEV void raster_body(const float *__restrict__ proj, const float *__restrict_
     int Y1 = (Y0 + TS < G.y1) ? (Y0 + TS) : G.y1;
 
     CR_STAMP(0);
-#ifdef CRENDER_STAMPS
-    if (g_stamps && threadIdx.x == 0) {
-        g_stamps[stamp_base + 7] = __builtin_amdgcn_s_getreg((3 << 11) | 20);   // XCC_ID
-        g_stamps[stamp_base + 8] = (unsigned long long)tile;
-        g_stamps[stamp_base + 10] = __builtin_amdgcn_s_memtime();
-    }
-#endif
+    CR_STAMP_TILE(tile);
     // the tile's triangle list: a run of the scanned index array, or (direct bins, offs == null)
     // a fixed-capacity slab of entries whose fill count k_setup_wave left in count[tile]
     uint32_t beg, end;
@@ -1671,12 +1672,7 @@ CR_DEV void raster_body(const float *__restrict__ proj, const float *__restrict_
     } else if constexpr (PATH == kPathOwners) {
         c.X0 = X0; c.Y0 = Y0; c.X1 = X1; c.Y1 = Y1; c.rw = rw; c.quad = quad; c.beg = beg; c.end = end;
         CR_STAMP(1);
-#ifdef CRENDER_STAMPS
-        if (g_stamps && tid == 0) {
-            g_stamps[stamp_base + 4] = end - beg;
-            g_stamps[stamp_base + 9] = (unsigned long long)(quad + 1);
-        }
-#endif
+        CR_STAMP_LIST(end - beg, quad);
         if (end - beg <= (uint32_t)kThreads) {
             const int tile_class = owners_queue(c, beg, true);
             CR_STAMP(6);
@@ -1710,41 +1706,29 @@ CR_DEV void raster_body(const float *__restrict__ proj, const float *__restrict_
     // (32-pixel tiles: the keys once it is known that the tile is not the pixel owners', see below)
     if constexpr (TS != 32) init_keys<TS, CLEAR>(c);
     CR_STAMP(1);
-#ifdef CRENDER_STAMPS
-    if (g_stamps && tid == 0) {
-        g_stamps[stamp_base + 4] = end - beg;
-        g_stamps[stamp_base + 9] = (unsigned long long)(quad + 1);
-    }
-#endif
+    CR_STAMP_LIST(end - beg, quad);
 
     [[maybe_unused]] int tile_class = -1;        // (wavefront 0 learns it with the first batch, reports it last)
     for (uint32_t base = beg; base < end; base += kBatch) {
         // ---- queue this batch: one record per thread, slot = thread index --------------
         uint32_t box_xy = 0, box_wh = 0;
         if (cur_ok) {
-            int xl = (int)(cur_bx & 0xFFFF), xr = (int)(cur_bx >> 16);
-            int yt = (int)(cur_by & 0xFFFF), yb = (int)(cur_by >> 16);
-            if (xl < X0) xl = X0;
-            if (xr > X1) xr = X1;
-            if (yt < Y0) yt = Y0;
-            if (yb > Y1) yb = Y1;
-            if (xl < xr && yt < yb) {
-                box_xy = (uint32_t)xl | ((uint32_t)yt << 16);
-                box_wh = (uint32_t)(xr - xl) | ((uint32_t)(yb - yt) << 16);
+            const ClipBox cl = clip_box(cur_bx, cur_by, X0, Y0, X1, Y1);
+            if (cl.any()) {
+                box_xy = cl.xy();
+                box_wh = cl.wh();
                 // A large triangle's pixel box covers about twice its area: a good part of the
                 // entries of a frame of large triangles (bunny 4096^2: 8 per tile) name tiles the
                 // triangle never touches.  Exact test on (box ∩ tile); not worth its ~80
                 // instructions for a small box.
-                if (TS >= 32 && (xr - xl) * (yb - yt) >= 256 &&
-                    rect_surely_missed(make_setup(cur_t, false), xl, xr - 1, yt, yb - 1))
+                if (TS >= 32 && (cl.xr - cl.xl) * (cl.yb - cl.yt) >= 256 &&
+                    rect_surely_missed(make_setup(cur_t, false), cl.xl, cl.xr - 1, cl.yt, cl.yb - 1))
                     box_wh = 0;
             }
         }
         const uint32_t key_low = slotted ? ((0xFFFFu - (cur_id & 0xFFFFu)) << 16) | ((((base - beg) / kBatch) & 0xFFu) << 8) | (uint32_t)tid
                                          : 0xFFFFFFFEu - cur_id;
-#ifdef CRENDER_STAMPS
-        if (base == beg) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); CR_STAMP(5); }
-#endif
+        CR_STAMP_LOADED(base == beg, 5);
         if constexpr (TS == 16) {
             // a short last batch goes pixel-parallel
             const uint32_t left = end - base;
@@ -1807,9 +1791,7 @@ CR_DEV void raster_body(const float *__restrict__ proj, const float *__restrict_
             }
         }
         __syncthreads();  // queue complete
-#ifdef CRENDER_STAMPS
-        if (base == beg) CR_STAMP(6);
-#endif
+        CR_STAMP_IF(base == beg, 6);
 
         // ---- sweep: the batch's work items, flattened and split evenly -------------------------
         {
@@ -1822,9 +1804,7 @@ CR_DEV void raster_body(const float *__restrict__ proj, const float *__restrict_
             const uint32_t blk_excl = incl - my_blocks;
             bool small_by_pixel = false;    // 32-pixel tiles: small records go per pixel too
             if constexpr (either) small_by_pixel = total < 16 * nrec;
-#ifdef CRENDER_STAMPS
-            if (base == beg) CR_STAMP(13);
-#endif
+            CR_STAMP_IF(base == beg, 13);
             // next batch: issue its loads now, they complete under the sweeps
             const uint32_t nxt = base + kBatch + tid;
             cur_ok = tid < kBatch && nxt < end;
@@ -1849,9 +1829,7 @@ CR_DEV void raster_body(const float *__restrict__ proj, const float *__restrict_
                     init_keys<TS, CLEAR>(c);
                     __syncthreads();
                 }
-#ifdef CRENDER_STAMPS
-                if (base == beg) CR_STAMP(14);         // key plane initialised (composite frames)
-#endif
+                CR_STAMP_IF(base == beg, 14);          // key plane initialised (composite frames)
             }
             if constexpr (per_pixel) {
                 sweep_items(c, scan16, wo, total, nrec);
@@ -1862,21 +1840,15 @@ CR_DEV void raster_body(const float *__restrict__ proj, const float *__restrict_
 #pragma unroll
                     for (int w = 0; w < kThreads / 64; ++w) wop[w + 1] = wop[w] + q.wave_px[w];
                     const int items = (int)wop[kThreads / 64];
-#ifdef CRENDER_STAMPS
-                    if (g_stamps && base == beg && tid == 0) g_stamps[stamp_base + 12] = (unsigned long long)items;
-#endif
+                    CR_STAMP_WORD(base == beg, 12, (unsigned long long)items);
                     sweep_runs32(c, wop, items);
-#ifdef CRENDER_STAMPS
-                    if (base == beg) CR_STAMP(15);     // thread 0's run of the first batch walked
-#endif
+                    CR_STAMP_IF(base == beg, 15);      // thread 0's run of the first batch walked
                 }
             } else if constexpr (TS == 64) {
                 if (total < 16 * nrec) walk64_small(c, wo, total);
                 else walk64_dense(c, wo, total);
             } else {
-#ifdef CRENDER_STAMPS
-                if (g_stamps && base == beg && tid == 0) g_stamps[stamp_base + 12] = (1ull << 32) | (unsigned long long)total;
-#endif
+                CR_STAMP_WORD(base == beg, 12, (1ull << 32) | (unsigned long long)total);
                 sweep_blocks_culled<TS>(c, wo, total, blk_excl);
             }
         }
@@ -1887,9 +1859,7 @@ CR_DEV void raster_body(const float *__restrict__ proj, const float *__restrict_
     resolve_tile<TS, CLEAR>(c, slotted);
     if constexpr (TS == 32) if (tid == 0) count_tile_class(L, tile_class);
     CR_STAMP(3);
-#ifdef CRENDER_STAMPS
-    if (g_stamps && threadIdx.x == 0) g_stamps[stamp_base + 11] = __builtin_amdgcn_s_memtime();
-#endif
+    CR_STAMP_WORD(true, 11, __builtin_amdgcn_s_memtime());
     }   // work
     // hand-off words of a heavy tile go back to zero once every wavefront has read them
     if (quad >= 0) {
@@ -2063,11 +2033,9 @@ bool raster_path_hint(crender_plan *plan)
     for (uint64_t back = 0; back + 1 < (uint64_t)kUsageRing && back < plan->ticket; ++back) {
         const uint64_t t = plan->ticket - back;
         if (t <= plan->hint_ticket) break;
-        const volatile uint32_t *rec = plan->usage + kUsageWords * (int)(t % kUsageRing);
-        const uint32_t seq = (uint32_t)t ^ plan->usage_salt;
-        if (__atomic_load_n(const_cast<const uint32_t *>(rec), __ATOMIC_ACQUIRE) != seq || rec[7] != seq) continue;
+        uint32_t rec[kUsageWords];
+        if (!plan->usage_record(t, rec)) continue;
         const uint32_t nl = rec[4], ns = rec[5];
-        if (rec[0] != seq || rec[7] != seq) continue;       // (rewritten under the read)
         plan->hint_ticket = t;
         if (nl + ns == 0) return false;
         plan->auto_path = nl >= 3u * ns ? kPathOwners : kPathGeneral;
@@ -2090,8 +2058,7 @@ int run_raster_pass(crender_plan *plan, const float *proj, const float *d_col, c
 {
     const Layout &L = plan->L;
     const Geom G = L.g;
-    const bool direct = plan->last_frame_direct;          // direct bins of 48-byte entries (small scenes)
-    const bool pairbins = plan->last_frame_pairbins;      // fixed-capacity slabs of (position, index) pairs (k_bin_wave)
+    const bool direct = plan->last_frame_mode == kFrameDirect, pairbins = plan->last_frame_mode == kFramePairs;
     const int par = plan->parity;
     TileLists tl;
     tl.offs = direct || pairbins ? nullptr : plan->offs();
@@ -2107,8 +2074,8 @@ int run_raster_pass(crender_plan *plan, const float *proj, const float *d_col, c
     const bool split = direct && plan->frame_hmax > 0;    // (lone frames: the plan's thresholds; frames in flight: long lists only)
     tl.heavy_flag = split ? plan->hflag() : nullptr;
     tl.heavy_slots = split ? plan->hslots() : nullptr;
-    tl.heavy_ctr_next = plan->hdr() + 2 + (par ^ 1);
-    tl.heavy_ctr = plan->hdr() + 2 + par;
+    tl.heavy_ctr_next = plan->heavy_ctr(par ^ 1);
+    tl.heavy_ctr = plan->heavy_ctr(par);
     tl.nhelp = split ? 3 * plan->frame_hmax : 0;
     tl.quad_at = plan->frame_quad_at;
     // ordered launches: read the order the previous launch left, leave one for the next
@@ -2119,8 +2086,8 @@ int run_raster_pass(crender_plan *plan, const float *proj, const float *d_col, c
     tl.order_next = ordered ? plan->order(hp ^ 1) : nullptr;
     tl.hint_next = plan->hint(hp ^ 1);
     tl.grouped_next = ordered ? plan->grouped(hp ^ 1) : nullptr;
-    tl.hint_bad = plan->hdr() + 5 + par;
-    tl.hint_bad_next = plan->hdr() + 5 + (par ^ 1);
+    tl.hint_bad = plan->hint_bad(par);
+    tl.hint_bad_next = plan->hint_bad(par ^ 1);
     tl.addr32 = (uint64_t)G.H * (uint64_t)G.W * 12ull < (1ull << 32) &&
                 (uint64_t)(plan->last_T > 0 ? plan->last_T : 1) * 36ull < (1ull << 32);
     if (ordered) plan->hint_par = hp ^ 1;
@@ -2141,7 +2108,7 @@ int run_raster_pass(crender_plan *plan, const float *proj, const float *d_col, c
     // this launch's usage record (crender_plan_poll_bin_usage)
     plan->ticket++;
     const int uslot = (int)(plan->ticket % kUsageRing);
-    plan->usage_mode[uslot] = direct ? 1 : pairbins ? 2 : 0;
+    plan->usage_mode[uslot] = plan->last_frame_mode;
     tl.hdr = plan->hdr();
     tl.usage = plan->usage_dev + kUsageWords * uslot;
     tl.usage_seq = (uint32_t)plan->ticket ^ plan->usage_salt;

@@ -340,14 +340,13 @@ CR_DEV const float *elem(const float *base, I idx)
     else return base + idx;
 }
 
-// z, colour and normal of a fragment from its barycentrics and the triangle's attributes
-// (.pyx:219, 226-242), with the optional fused illumination.
-template <typename I>
-CR_DEV void store_fragment(float z, const float c[9], const float n[9], float b1, float b2, float b3,
-                           const Light &L, I pix, float *__restrict__ zb, float *__restrict__ cb,
-                           float *__restrict__ nb)
+// Colour and normal of a fragment from its barycentrics and the triangle's attributes
+// (.pyx:226-242), with the optional fused illumination.
+struct Shade {
+    float c0, c1, c2, n0, n1, n2;
+};
+CR_DEV Shade shade_fragment(const float c[9], const float n[9], float b1, float b2, float b3, const Light &L)
 {
-    *elem(zb, pix) = z;
     float c0 = interp(c[0], c[3], c[6], b1, b2, b3);
     float c1 = interp(c[1], c[4], c[7], b1, b2, b3);
     float c2 = interp(c[2], c[5], c[8], b1, b2, b3);
@@ -358,9 +357,39 @@ CR_DEV void store_fragment(float z, const float c[9], const float n[9], float b1
         const float f = guro_factor(L, n0, n1, n2);
         c0 *= f; c1 *= f; c2 *= f;
     }
+    return Shade{c0, c1, c2, n0, n1, n2};
+}
+
+// z, colour and normal of a fragment stored (.pyx:219, 226-242).
+template <typename I>
+CR_DEV void store_fragment(float z, const float c[9], const float n[9], float b1, float b2, float b3,
+                           const Light &L, I pix, float *__restrict__ zb, float *__restrict__ cb,
+                           float *__restrict__ nb)
+{
+    *elem(zb, pix) = z;
+    const Shade s = shade_fragment(c, n, b1, b2, b3, L);
     float *cp = elem(cb, (I)(pix * 3)), *np_ = elem(nb, (I)(pix * 3));
-    cp[0] = c0; cp[1] = c1; cp[2] = c2;
-    np_[0] = n0; np_[1] = n1; np_[2] = n2;
+    cp[0] = s.c0; cp[1] = s.c1; cp[2] = s.c2;
+    np_[0] = s.n0; np_[1] = s.n1; np_[2] = s.n2;
+}
+
+// The winner plane's word of a pixel, if the caller wants that plane.
+template <typename I>
+CR_DEV void store_winner(int32_t *__restrict__ win, I pix, int32_t id)
+{
+    if (win) *reinterpret_cast<int32_t *>(elem(reinterpret_cast<float *>(win), pix)) = id;
+}
+
+// A pixel no fragment won, fused clear: __cinit__'s buffer state (.pyx:65-67).
+template <typename I>
+CR_DEV void store_background(I pix, float *__restrict__ zb, float *__restrict__ cb, float *__restrict__ nb,
+                             int32_t *__restrict__ win)
+{
+    *elem(zb, pix) = 1e6f;
+    float *cp = elem(cb, (I)(pix * 3)), *np_ = elem(nb, (I)(pix * 3));
+    cp[0] = 0.0f; cp[1] = 0.0f; cp[2] = 0.0f;
+    np_[0] = 0.0f; np_[1] = 0.0f; np_[2] = 0.0f;
+    store_winner(win, pix, -1);
 }
 
 // Recompute the winning fragment of pixel (X, Y) and store z, colour, normal
