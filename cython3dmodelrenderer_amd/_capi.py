@@ -93,6 +93,13 @@ PY_SIGNATURES = {
     "crender_py_guro": (_i32, [_vp, _vp, _f32p, _i32, _i32, _vp]),
 }
 
+# the deferred texture pass (include/crender_tex.h), bound from a table of its own
+TEX_PERSPECTIVE, TEX_BILINEAR = 1, 2
+TEX_SIGNATURES = {
+    "crender_tex_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _i32, _vp, _f32p, _vp,
+                                 _i32, _i32, _i32, _i32, _u32, _vp]),
+}
+
 _lib = None
 
 
@@ -117,7 +124,7 @@ def load():
             "(or __graft_entry__.build()).  There is no CPU fallback for the rasterizer.")
     L = C.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(WIRE_SIGNATURES.items()) + \
-            list(PY_SIGNATURES.items()):
+            list(PY_SIGNATURES.items()) + list(TEX_SIGNATURES.items()):
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

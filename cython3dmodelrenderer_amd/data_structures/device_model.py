@@ -76,6 +76,7 @@ class DeviceModel:
         self._triangles_vertices = self._dev_index(m._triangles_vertices, len(m._vertices))
         self._normals = self._dev(m._normals, np.float32)
         self._triangles_normals = self._dev_index(m._triangles_normals, len(m._normals))
+        self._uv_by_triangles = self._texture = None
         if m._texture is not None:
             self._sample_texture(m)
         elif m._colors_by_triangles is not None:
@@ -104,6 +105,10 @@ class DeviceModel:
         idx = self._dev_index(m._triangles_texture_coords, uv.shape[0])
         self._colors_by_triangles = torch.empty((idx.shape[0], 3, 3), dtype=torch.float32, device=self.device)
         self._gather(self._colors, idx, self._colors_by_triangles)
+        # what the per-pixel texture pass reads (AdvancedPixelBufferFiller.bind_texture): the image, and
+        # u, v per corner — an index_select once per upload, not per frame
+        self._texture = tex
+        self._uv_by_triangles = uv[:, :2].index_select(0, idx.reshape(-1).long()).reshape(idx.shape[0], 3, 2).contiguous()
 
     def _gather(self, attr, index, out):
         self.generation += 1
@@ -225,6 +230,14 @@ class DeviceModel:
 
     def n_vertices(self):
         return int(self._vertices.shape[0])
+
+    def get_texture_coords_by_triangles(self):
+        """Device float32 [T, 3, 2] (u, v per corner), or None for a model without a texture."""
+        return self._uv_by_triangles
+
+    def get_texture(self):
+        """Device uint8 [h, w, 3] (BGR), or None."""
+        return self._texture
 
     def set_uniform_color(self, bgr=(255.0, 255.0, 255.0)):
         T = self.n_triangles()

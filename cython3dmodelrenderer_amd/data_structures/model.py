@@ -280,6 +280,17 @@ class Model:
     def get_max_span(self):
         return self._max_span
 
+    def get_texture_coords_by_triangles(self):
+        """float32 [T, 3, 2]: u and v of every triangle's corners (a ``vt`` record's third number is
+        dropped), for the per-pixel texture pass; None for a model without texture coordinates."""
+        if self._texture_coords is None or self._triangles_texture_coords is None:
+            return None
+        return np.ascontiguousarray(self._texture_coords[:, :2][self._triangles_texture_coords], dtype=np.float32)
+
+    def get_texture(self):
+        """The texture image, uint8 [h, w, 3] in BGR order (None without one)."""
+        return self._texture
+
     def set_uniform_color(self, bgr=(255.0, 255.0, 255.0)):
         """Give an untextured model one colour (the reference leaves
         ``_colors_by_triangles`` None for such models and its filler then raises;

@@ -326,6 +326,7 @@ class AdvancedPixelBufferFiller(DevicePlanes):
         self._order = None             # (orig_of, pos_of) int32 device tensors of the resident inputs
         self._plan_order = None        # what the single-stream plan currently holds
         self._fused_light = None       # (l0, l1, l2): illumination fused into cleared frames
+        self._texture = None           # (uv [T, 3, 2] float32, image [th, tw, 3] uint8) device tensors: bind_texture
         self._plan_light = None        # what the single-stream plan currently holds
         self._pipeline = bool(pipeline)  # render_frame(): overlap consecutive frames (see _FramePipeline)
         if not pipeline_depth:
@@ -735,6 +736,67 @@ class AdvancedPixelBufferFiller(DevicePlanes):
         render)."""
         self._join_pipe()
         self._fused_light = None if light_direction is None else tuple(float(v) for v in light_direction)
+
+    def bind_texture(self, uv_by_triangles, texture):
+        """Keep a texture resident for ``texture_pass``: `uv_by_triangles` float32 [T, 3, 2] (u, v per corner,
+        in the caller's triangle order: ``Model.get_texture_coords_by_triangles()``) and `texture` uint8
+        [th, tw, 3] (``Model.get_texture()``), numpy arrays or device tensors.  ``bind_texture(None, None)``
+        drops them."""
+        if uv_by_triangles is None and texture is None:
+            self._texture = None
+            return
+        if uv_by_triangles is None or texture is None:
+            raise ValueError("bind_texture needs both the texture coordinates and the texture (or None, None)")
+        uv = uv_by_triangles if isinstance(uv_by_triangles, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(uv_by_triangles))
+        tex = texture if isinstance(texture, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(texture))
+        if uv.dtype != torch.float32 or uv.dim() != 3 or uv.shape[1] != 3 or uv.shape[2] != 2:
+            raise ValueError(f"uv_by_triangles must be float32 [T, 3, 2], got {uv.dtype} {tuple(uv.shape)}")
+        if tex.dtype != torch.uint8 or tex.dim() != 3 or tex.shape[2] < 3 or tex.shape[0] < 1 or tex.shape[1] < 1:
+            raise ValueError(f"texture must be uint8 [th, tw, 3], got {tex.dtype} {tuple(tex.shape)}")
+        self._texture = (uv.to(self.device).contiguous(), tex[:, :, :3].to(self.device).contiguous())
+
+    def texture_pass(self, perspective=False, filter="nearest", light_direction=None):
+        """Per-pixel texture mapping of the LAST frame's colour plane (``crender_tex_shade``,
+        include/crender_tex.h): every pixel a triangle won gets the bound texture's texel at its
+        interpolated (u, v) — affine like the reference's attributes, or perspective-correct; the nearest
+        texel or four of them — instead of the blend of three vertex colours.  Rows of the filler's
+        ``row_strip``, on torch's current stream.  With `light_direction` (the illumination object's own
+        flipped, normalised vector, as ``set_fused_illumination`` takes it) the pass also shades every
+        pixel of the rows: the same bits as the separate illumination pass afterwards, without its
+        traffic.
+
+        The frame is settled first (one stream synchronisation, as every getter does): a frame whose bin
+        lists overflowed is rendered again, and the pass must land on the frame that stays."""
+        if filter not in ("nearest", "bilinear"):
+            raise ValueError(f"filter must be 'nearest' or 'bilinear', got {filter!r}")
+        if self._pipeline:
+            raise ValueError("texture_pass is not available on a swap chain (pipeline=True): per-slot passes are not implemented")
+        if self.winner_buffer is None:
+            raise ValueError("texture_pass needs the winner plane: construct the filler with track_winner=True")
+        if self._texture is None:
+            raise ValueError("texture_pass: no texture is bound (bind_texture)")
+        if self._inputs is None:
+            raise ValueError("texture_pass: no frame has been rendered")
+        if not (self._last_flags & _capi.FUSED_CLEAR):
+            raise ValueError("texture_pass: the last frame did not start from cleared buffers (clear=True): the winner "
+                             "plane of a composite mixes the triangle indices of several models")
+        uv, tex = self._texture
+        tri = self._inputs[0]
+        T = tri.shape[0]
+        if uv.shape[0] != T:
+            raise ValueError(f"texture_pass: {uv.shape[0]} triangles of texture coordinates are bound, the last frame drew {T}")
+        light = None if light_direction is None else (C.c_float * 3)(*[float(v) for v in light_direction])
+        self._push_host_edits()
+        self._check_bins()             # nothing pending from here on: no later redo can undo the pass
+        flags = (_capi.TEX_PERSPECTIVE if perspective else 0) | (_capi.TEX_BILINEAR if filter == "bilinear" else 0)
+        pos_of = None if self._order is None else self._order[1].data_ptr()
+        with torch.cuda.device(self.device):
+            _capi.check(self._lib.crender_tex_shade(
+                self.winner_buffer.data_ptr(), tri.data_ptr() if T else None, T, pos_of, self._P,
+                uv.data_ptr() if T else None, tex.data_ptr(), int(tex.shape[0]), int(tex.shape[1]),
+                None if light is None else self.normals_buffer.data_ptr(), light, self.color_buffer.data_ptr(),
+                self.h, self.w, self.y0, self.y1, flags, self._stream()), "crender_tex_shade")
+        self._host_fresh = False       # views handed out earlier show the textured colours at the next getter call
 
     def render_frame(self, pipelined=None):
         """One benchmark frame: clear + project + rasterize the resident model

@@ -1,6 +1,8 @@
 """Caller of the hot path — mirror of the reference's ``crender.cy.Renderer``
 (reference: crender/cy/renderer.py:9-52): optional model fit, ``render_model``,
 illumination, return the colour buffer."""
+import weakref
+
 import numpy as np
 
 
@@ -19,7 +21,7 @@ def _device_form_is_the_same_shading(illumination):
 
 class Renderer:
     def __init__(self, pixel_buffer_filler, illumination, triangle_iterator_type=None,
-                 image_height=512, image_width=512, use_tqdm=True, on_device=None):
+                 image_height=512, image_width=512, use_tqdm=True, on_device=None, texture_pass=None):
         self.pixel_buffer_filler = pixel_buffer_filler
         self.illumination = illumination
         self.triangle_iterator_type = triangle_iterator_type   # stored, unused (as in Version C)
@@ -36,6 +38,32 @@ class Renderer:
         # on_device="fused": one model per frame — the frame starts from cleared buffers and the
         #   raster kernel shades each pixel as it stores it (no illumination pass at all).
         self.on_device = on_device
+        # texture_pass=None (default): the reference's colours — three vertex colours blended across each triangle.
+        # A dict of ``perspective`` / ``filter`` (AdvancedPixelBufferFiller.texture_pass's arguments; {} = affine,
+        # nearest): every frame starts from cleared buffers (one model per frame, as "fused") and the model's
+        # texture is mapped per pixel before the illumination; with on_device="fused" the texture pass carries
+        # the light and the raster kernel does not shade.
+        self.texture_pass = None if texture_pass is None else dict(texture_pass)
+        self._textured = None          # weak reference to the model whose texture the filler holds
+
+    def _draw(self, model, light=None, **kw):
+        """``render_model``; with a texture pass, a cleared frame and the pass on top of it."""
+        filler = self.pixel_buffer_filler
+        if self.texture_pass is None:
+            return filler.render_model(model, **kw)
+        if self._textured is None or self._textured() is not model:      # once per model, not per frame
+            getters = [getattr(model, n, None) for n in ("get_texture_coords_by_triangles", "get_texture")]
+            uv, tex = [g() if g is not None else None for g in getters]
+            if uv is None or tex is None:
+                raise ValueError("Renderer(texture_pass=...) needs a textured model: this one has no texture "
+                                 "coordinates or no texture image")
+            filler.bind_texture(uv, tex)
+            self._textured = weakref.ref(model)
+        # (the views handed out so far are refreshed by the next getter call, after the pass; and the raster
+        # kernel never shades here: the colours it stores are replaced by the texture's)
+        filler.set_fused_illumination(None)
+        filler.render_model(model, clear=True, refresh_views=False)
+        filler.texture_pass(light_direction=light, **self.texture_pass)
 
     def render(self, model, normalize_model=False, random_colors=True):
         if normalize_model:
@@ -46,6 +74,10 @@ class Renderer:
             model.shift(-model.get_mean_vertex() + [centre[0], centre[1], -span])
         filler = self.pixel_buffer_filler
         if self.on_device == "fused" and getattr(self.illumination, "fuse_into", None):
+            if self.texture_pass is not None:
+                # the texture pass carries the light
+                self._draw(model, light=self.illumination.light_direction)
+                return filler.get_color_tensor()
             self.illumination.fuse_into(filler)
             filler.render_model(model, clear=True)
             return filler.get_color_tensor()
@@ -56,11 +88,11 @@ class Renderer:
             device_form = None
         if self.on_device is not False and device_form is not None and hasattr(filler, "get_color_tensor"):
             # (the views handed out so far are refreshed by the getter below, after the shading)
-            filler.render_model(model, refresh_views=False)
+            self._draw(model, refresh_views=False)
             if device_form(filler):
                 return filler.get_color_tensor() if self.on_device is True else filler.get_color_buffer()
         else:
-            filler.render_model(model)
+            self._draw(model)
         self.illumination.draw_illumination(filler.get_color_buffer(), filler.get_normals_buffer())
         return filler.get_color_buffer()
 

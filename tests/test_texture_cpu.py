@@ -1,0 +1,250 @@
+"""The texture pass without a GPU: the host model the GPU tests compare with (tests/tex_ref.py) pinned on
+the oracle's planes, ``oracle.bar`` and ``Model``'s texel rule; the perspective statement against its
+float64 evaluation and against geometry; the C ABI's exports and argument checks."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import tex_ref
+from util import assert_bit_equal, random_soup
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+# Largest |u32 - u64| and |v32 - v64| over the covered pixels of T-Rex at 1024^2, perspective mode, where u64 /
+# v64 are the statements of include/crender_tex.h evaluated in float64 from the same float32 inputs (projection
+# included): measured 2.173e-06 (u) and 2.492e-06 (v) on 252 539 pixels.  Four times the larger, for other scenes' rounding.
+PERSPECTIVE_UV_BOUND = 4 * 2.492e-06
+
+
+@pytest.fixture(scope="module")
+def capi():
+    from cython3dmodelrenderer_amd import _build, _capi
+    _build.build()           # hipcc cross-compiles for gfx950 without a GPU
+    return _capi
+
+
+@pytest.fixture(scope="module")
+def trex():
+    from cython3dmodelrenderer_amd import scenes
+    tri, col, nrm = scenes.load_fixture("trex_inputs.npz")
+    with np.load(os.path.join(GOLDEN, "trex_uv.npz")) as z:
+        uv = np.ascontiguousarray(z["uv"][z["faces_uv"]], dtype=np.float32)
+    return tri, col, nrm, uv
+
+
+def _oracle_frame(oracle, tri, col, nrm, size):
+    f = oracle.OracleFiller(size, size, fov=45.0)
+    f.render_arrays(tri, col, nrm)
+    return f
+
+
+def _interpolated_colours(f, tri, col):
+    """The colour plane from the winner plane alone: tex_ref's barycentrics applied to the vertex colours."""
+    H, W = f.winner.shape
+    ys, xs, t = tex_ref.covered(f.winner, tri.shape[0])
+    proj = tex_ref.project(tri, f.proj_mat, W, H)
+    b = tex_ref.barycentrics(proj[t], xs, ys)
+    out = np.zeros((H, W, 3), np.float32)
+    for k in range(3):
+        out[ys, xs, k] = tex_ref.interp(col[t, 0, k], col[t, 1, k], col[t, 2, k], *b)
+    z = np.full((H, W), 1e6, np.float32)
+    z[ys, xs] = tex_ref.interp(proj[t, 0, 2], proj[t, 1, 2], proj[t, 2, 2], *b)
+    return out, z, len(ys)
+
+
+@pytest.mark.parametrize("size", [256, 1024])
+def test_interpolation_reproduces_the_oracle_planes_on_trex(oracle, trex, size):
+    tri, col, nrm, _ = trex
+    f = _oracle_frame(oracle, tri, col, nrm, size)
+    got, z, n = _interpolated_colours(f, tri, col)
+    assert n == {256: 15801, 1024: 252539}[size]
+    assert_bit_equal(got, f.color_buffer, f"trex{size} colour")
+    assert_bit_equal(z, f.z_buffer, f"trex{size} z")
+
+
+def test_interpolation_reproduces_the_oracle_planes_on_a_random_soup(oracle):
+    rng = np.random.default_rng(11)
+    tri, col, nrm = random_soup(rng, 3000, 192)
+    f = _oracle_frame(oracle, tri, col, nrm, 192)
+    got, z, n = _interpolated_colours(f, tri, col)
+    assert n > 5000
+    assert_bit_equal(got, f.color_buffer, "soup colour")
+    assert_bit_equal(z, f.z_buffer, "soup z")
+
+
+def test_barycentrics_equal_the_oracle_on_sampled_pixels(oracle, trex):
+    tri, col, nrm, _ = trex
+    f = _oracle_frame(oracle, tri, col, nrm, 256)
+    ys, xs, t = tex_ref.covered(f.winner, tri.shape[0])
+    proj = tex_ref.project(tri, f.proj_mat, 256, 256)
+    b = np.stack(tex_ref.barycentrics(proj[t], xs, ys), axis=1)
+    pick = np.random.default_rng(5).choice(len(ys), 400, replace=False)
+    for i in pick:
+        want = oracle.bar(proj[t[i]], int(xs[i]), int(ys[i]))
+        assert_bit_equal(b[i], want, f"pixel {xs[i]}, {ys[i]}")
+
+
+def test_nearest_rule_equals_the_models_colours():
+    from cython3dmodelrenderer_amd.data_structures.model import Model
+    rng = np.random.default_rng(3)
+    for th, tw in ((709, 709), (1, 1), (3, 1000)):
+        tex = rng.integers(0, 256, (th, tw, 3), dtype=np.uint8)
+        uv = np.concatenate([
+            rng.uniform(0, 1, (500, 2)), rng.uniform(-3, 4, (300, 2)), rng.uniform(-1e12, 1e12, (100, 2)),
+            [[np.nan, 0.5], [0.5, np.nan], [np.inf, 0.2], [0.2, -np.inf], [-np.inf, np.inf], [1.0, 0.0], [0.0, 1.0],
+             [3e9, -3e9], [-0.0, 1.0000001]]]).astype(np.float32)
+        faces = np.arange(3, dtype=np.int32).reshape(1, 3)
+        with np.errstate(all="ignore"):
+            m = Model(np.zeros((3, 3), np.float32), faces, uv, faces, tex)
+            got = tex_ref.nearest(uv[:, 0], uv[:, 1], tex)
+        assert_bit_equal(got, m._colors, f"texture {th} x {tw}")
+        assert np.array_equal(m.get_texture_coords_by_triangles(), uv[faces])
+        assert m.get_texture() is m._texture
+
+
+def test_perspective_statement_stays_within_its_bound_of_float64(oracle, trex):
+    tri, col, nrm, uv = trex
+    f = _oracle_frame(oracle, tri, col, nrm, 1024)
+    _, _, _, u32, v32 = tex_ref.pixel_uv(f.winner, tri, f.proj_mat, uv, perspective=True)
+    _, _, _, u64, v64 = tex_ref.pixel_uv(f.winner, tri, f.proj_mat, uv, perspective=True, dtype=np.float64)
+    du, dv = float(np.abs(u32 - u64).max()), float(np.abs(v32 - v64).max())
+    print(f"perspective uv: max |u32 - u64| = {du:.3e}, max |v32 - v64| = {dv:.3e} over {len(u32)} pixels")
+    assert u32.dtype == np.float32 and u64.dtype == np.float64
+    assert du <= PERSPECTIVE_UV_BOUND and dv <= PERSPECTIVE_UV_BOUND, (du, dv)
+
+
+def _receding_quad():
+    """A parallelogram receding in depth (z from 0.9 to 3.2) as two triangles, uv = its own plane coordinates."""
+    p00 = np.array([-0.30, -0.28, 0.9])
+    e1 = np.array([0.62, 0.02, 0.15])           # u direction
+    e2 = np.array([0.35, 0.95, 2.15])           # v direction: away from the camera
+    p10, p01, p11 = p00 + e1, p00 + e2, p00 + e1 + e2
+    tri = np.array([[p00, p10, p11], [p00, p11, p01]], np.float32)
+    uv = np.array([[[0, 0], [1, 0], [1, 1]], [[0, 0], [1, 1], [0, 1]]], np.float32)
+    nrm = np.zeros_like(tri)
+    nrm[..., 2] = -1.0
+    return tri, uv, nrm
+
+
+def test_perspective_mode_lands_on_the_texel_of_the_ray_plane_intersection(oracle):
+    H = W = 256
+    tri, uv, nrm = _receding_quad()
+    f = oracle.OracleFiller(H, W, fov=45.0)
+    f.render_arrays(tri, np.full_like(tri, 255.0), nrm)
+    # an 8 x 8-texel checkerboard (channel 0); channels 1 and 2 name the texel, so that a neighbour of the same
+    # colour does not pass for it
+    r, c = np.mgrid[0:8, 0:8]
+    tex = np.stack([((r + c) % 2) * 255, r * 16, c * 16], axis=-1).astype(np.uint8)
+    base = np.zeros((H, W, 3), np.float32)
+    persp = tex_ref.texture_pass(base, f.winner, tri, f.proj_mat, uv, tex, perspective=True)
+    affine = tex_ref.texture_pass(base, f.winner, tri, f.proj_mat, uv, tex, perspective=False)
+    ys, xs, _ = tex_ref.covered(f.winner, 2)
+    assert len(ys) > 3000
+    # float64 geometry: the points (x, y, z) that project to pixel (X, Y) satisfy, per axis,
+    #   x P[0][j] + y P[1][j] + z P[2][j] + P[3][j] = (X / xs - 1) z       (crender_project, .pyx:116-130)
+    # and on the plane p00 + s e1 + r e2 that is two linear equations in (s, r) = (u, v)
+    P = f.proj_mat.astype(np.float64)
+    assert P[0, 1] == 0.0            # (the in-place projection then forms column 1 from the original x)
+    tri64 = tri.astype(np.float64)   # the corners as the kernel gets them
+    p00, e1, e2 = tri64[0, 0], tri64[0, 1] - tri64[0, 0], tri64[1, 2] - tri64[0, 0]
+    A = np.zeros((len(ys), 2, 2))
+    rhs = np.zeros((len(ys), 2))
+    for j, (pixel, half) in enumerate(((xs, W / 2.0), (ys, H / 2.0))):
+        k = pixel / half - 1.0
+        lin = lambda p: p[0] * P[0, j] + p[1] * P[1, j] + p[2] * P[2, j] - k * p[2]      # noqa: E731
+        A[:, j, 0], A[:, j, 1] = lin(e1), lin(e2)
+        rhs[:, j] = -(lin(p00) + P[3, j])
+    sr = np.linalg.solve(A, rhs[:, :, None])[:, :, 0]
+    u, v = sr[:, 0], sr[:, 1]
+    dist = np.minimum(np.abs(u * 8 - np.round(u * 8)), np.abs(v * 8 - np.round(v * 8))) / 8
+    clear_of_edges = dist > PERSPECTIVE_UV_BOUND
+    left_out = 1.0 - clear_of_edges.mean()
+    print(f"quad: {len(ys)} covered pixels, {left_out:.4%} within the bound of a texel edge")
+    assert left_out <= 0.05
+    row = np.clip(np.floor((1 - v) * 8).astype(int), 0, 7)
+    colm = np.clip(np.floor(u * 8).astype(int), 0, 7)
+    want = tex[row, colm].astype(np.float32)
+    got = persp[ys, xs]
+    bad = (got != want).any(axis=1) & clear_of_edges
+    assert not bad.any(), (int(bad.sum()), xs[bad][:5], ys[bad][:5])
+    # affine interpolation bends the texture on this quad: without that the test shows nothing
+    differs = (affine[ys, xs] != got).any(axis=1)
+    print(f"quad: affine differs from perspective on {differs.mean():.1%} of the covered pixels")
+    assert differs.mean() > 0.25
+
+
+def test_bilinear_statement_on_hand_computed_texels():
+    tex = np.array([[[0, 10, 20], [100, 110, 120]], [[200, 210, 220], [40, 50, 60]]], np.uint8)
+    # the centre of the texture: fx = fy = 0.5, equal weights of all four texels
+    got = tex_ref.bilinear(np.float32([0.5]), np.float32([0.5]), tex)
+    assert_bit_equal(got, np.float32([[85.0, 95.0, 105.0]]), "centre")
+    # the centre of texel (row 0, column 1): u = 0.75, v = 0.75 -> exactly that texel
+    got = tex_ref.bilinear(np.float32([0.75]), np.float32([0.75]), tex)
+    assert_bit_equal(got, np.float32([[100.0, 110.0, 120.0]]), "texel centre")
+    # far outside: the edge texel, clamped on both sides
+    got = tex_ref.bilinear(np.float32([-7.0]), np.float32([-9.0]), tex)
+    assert_bit_equal(got, np.float32([[200.0, 210.0, 220.0]]), "clamped")
+    with np.errstate(all="ignore"):
+        assert np.isnan(tex_ref.bilinear(np.float32([np.nan, np.inf]), np.float32([0.5, 0.5]), tex)).all()
+
+
+def test_tex_header_symbols_are_exported_and_bound(capi):
+    header = open(os.path.join(ROOT, "include", "crender_tex.h")).read()
+    declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
+    assert declared == set(capi.TEX_SIGNATURES) == {"crender_tex_shade"}, declared ^ set(capi.TEX_SIGNATURES)
+    assert not declared & (set(capi.SIGNATURES) | set(capi.WIRE_SIGNATURES) | set(capi.PY_SIGNATURES))
+    L = capi.load()
+    for name in declared:
+        assert getattr(L, name).argtypes == capi.TEX_SIGNATURES[name][1]
+    out = subprocess.check_output(["nm", "-D", "--defined-only", capi.lib_path()], text=True)
+    assert declared <= set(re.findall(r" T (crender_\w+)", out))
+    for flag, value in (("CRENDER_TEX_PERSPECTIVE", capi.TEX_PERSPECTIVE), ("CRENDER_TEX_BILINEAR", capi.TEX_BILINEAR)):
+        assert re.search(rf"\b{flag} = {value}u\b", header), flag
+
+
+def test_tex_sources_stay_out_of_the_profile_fingerprint():
+    from cython3dmodelrenderer_amd import _build
+    assert "texture.hip" in _build.TEX_SOURCES and "texture.hip" not in _build.SOURCES
+    assert not any("crender_tex" in h for h in _build.HEADERS)
+    assert _build.source_sha16() == "f3a47bfc1afb1a02"         # the sources the committed profiles were measured on
+
+
+def test_tex_argument_errors_without_a_gpu(capi):
+    L = capi.load()
+    E = capi.EINVAL
+    P = (C.c_float * 16)(*([0.0] * 16))
+    light = (C.c_float * 3)(0, 0, -1)
+    fake = C.c_void_p(0x1000)          # never dereferenced: every call below fails its checks first
+
+    def shade(win=fake, tri=fake, T=1, pos=None, P=P, uv=fake, tex=fake, th=4, tw=4, nrm=None, light=None, col=fake,
+              H=8, W=8, y0=0, y1=8, flags=0):
+        return L.crender_tex_shade(win, tri, T, pos, P, uv, tex, th, tw, nrm, light, col, H, W, y0, y1, flags, None)
+
+    assert shade(win=None) == E and shade(tri=None) == E and shade(P=None) == E and shade(uv=None) == E
+    assert shade(tex=None) == E and shade(col=None) == E
+    assert shade(T=-1) == E
+    assert shade(th=0) == E and shade(tw=0) == E and shade(th=-2) == E
+    assert shade(H=0) == E and shade(W=-1) == E
+    assert shade(y0=-1) == E and shade(y1=9) == E and shade(y0=4, y1=4) == E and shade(y0=5, y1=3) == E
+    assert shade(light=light) == E                                       # a light without normals
+    assert shade(nrm=fake) == E                                          # normals without a light
+    assert shade(flags=4) == E and shade(flags=0x80000001) == E          # unknown flag bits
+    assert b"crender_tex_shade" in L.crender_last_error()
+    # an empty scene without a light is no work at all: nothing is launched
+    assert shade(T=0, tri=None, uv=None) == capi.OK
+
+
+def test_filler_methods_exist_and_model_without_texture_has_none():
+    from cython3dmodelrenderer_amd.data_structures.model import Model
+    from cython3dmodelrenderer_amd.pixel_buffer_filler import AdvancedPixelBufferFiller
+    from cython3dmodelrenderer_amd.renderer import Renderer
+    assert callable(AdvancedPixelBufferFiller.bind_texture) and callable(AdvancedPixelBufferFiller.texture_pass)
+    m = Model(np.zeros((3, 3), np.float32), np.arange(3).reshape(1, 3))
+    assert m.get_texture_coords_by_triangles() is None and m.get_texture() is None
+    assert Renderer(None, None).texture_pass is None
+    assert Renderer(None, None, texture_pass={"filter": "bilinear"}).texture_pass == {"filter": "bilinear"}
