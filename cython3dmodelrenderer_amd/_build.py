@@ -29,6 +29,10 @@ PY_HEADERS = [os.path.join("..", "..", "include", "crender_py.h")]
 # source_sha16() likewise.
 TEX_SOURCES = ["texture.hip"]
 TEX_HEADERS = [os.path.join("..", "..", "include", "crender_tex.h")]
+# texmip.hip  the mip chain and the trilinear texture pass (include/crender_mip.h); kept out of
+# source_sha16() likewise.
+MIP_SOURCES = ["texmip.hip"]
+MIP_HEADERS = [os.path.join("..", "..", "include", "crender_mip.h")]
 
 # Float parity with the reference depends on these (DESIGN.md "Numerics"):
 #   -ffp-contract=off                           no FMA contraction (hipcc defaults to fast)
@@ -75,7 +79,8 @@ def needs_build() -> bool:
         return True
     built = os.path.getmtime(LIB_PATH)
     deps = [os.path.join(SRC_DIR, s) for s in SOURCES + HEADERS + WIRE_SOURCES + WIRE_HEADERS +
-                                                PY_SOURCES + PY_HEADERS + TEX_SOURCES + TEX_HEADERS] + \
+                                                PY_SOURCES + PY_HEADERS + TEX_SOURCES + TEX_HEADERS +
+                                                MIP_SOURCES + MIP_HEADERS] + \
         [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > built for d in deps)
 
@@ -86,7 +91,7 @@ def compile_library(out: str, extra_flags=(), sources=None, src_dir: str = SRC_D
     defines of diagnostic builds (-DCRENDER_STAMPS, ...)."""
     import tempfile
     from concurrent.futures import ThreadPoolExecutor
-    sources = list(sources or SOURCES + WIRE_SOURCES + PY_SOURCES + TEX_SOURCES)
+    sources = list(sources or SOURCES + WIRE_SOURCES + PY_SOURCES + TEX_SOURCES + MIP_SOURCES)
     err = subprocess.DEVNULL if quiet else None
     with tempfile.TemporaryDirectory(prefix="crender_build_") as tmp:
         objs = [os.path.join(tmp, os.path.splitext(s)[0] + ".o") for s in sources]

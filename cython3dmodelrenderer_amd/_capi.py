@@ -100,6 +100,17 @@ TEX_SIGNATURES = {
                                  _i32, _i32, _i32, _i32, _u32, _vp]),
 }
 
+# the mip chain and the trilinear texture pass (include/crender_mip.h), bound from a table of their own
+MIP_PERSPECTIVE = 1
+MIP_MAX_LEVELS = 16
+_u64p = C.POINTER(C.c_uint64)
+MIP_SIGNATURES = {
+    "crender_mip_layout": (_i32, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _u64p, _u64p]),
+    "crender_mip_build": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "crender_mip_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _i32, _vp, _f32p, _vp,
+                                 _i32, _i32, _i32, _i32, _u32, _vp]),
+}
+
 _lib = None
 
 
@@ -124,7 +135,7 @@ def load():
             "(or __graft_entry__.build()).  There is no CPU fallback for the rasterizer.")
     L = C.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(WIRE_SIGNATURES.items()) + \
-            list(PY_SIGNATURES.items()) + list(TEX_SIGNATURES.items()):
+            list(PY_SIGNATURES.items()) + list(TEX_SIGNATURES.items()) + list(MIP_SIGNATURES.items()):
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -327,6 +327,7 @@ class AdvancedPixelBufferFiller(DevicePlanes):
         self._plan_order = None        # what the single-stream plan currently holds
         self._fused_light = None       # (l0, l1, l2): illumination fused into cleared frames
         self._texture = None           # (uv [T, 3, 2] float32, image [th, tw, 3] uint8) device tensors: bind_texture
+        self._mip = None               # (chain, [(h_k, w_k)], [byte offsets]) of that image: bind_texture(mipmaps=True)
         self._plan_light = None        # what the single-stream plan currently holds
         self._pipeline = bool(pipeline)  # render_frame(): overlap consecutive frames (see _FramePipeline)
         if not pipeline_depth:
@@ -737,13 +738,14 @@ class AdvancedPixelBufferFiller(DevicePlanes):
         self._join_pipe()
         self._fused_light = None if light_direction is None else tuple(float(v) for v in light_direction)
 
-    def bind_texture(self, uv_by_triangles, texture):
+    def bind_texture(self, uv_by_triangles, texture, mipmaps=False):
         """Keep a texture resident for ``texture_pass``: `uv_by_triangles` float32 [T, 3, 2] (u, v per corner,
         in the caller's triangle order: ``Model.get_texture_coords_by_triangles()``) and `texture` uint8
-        [th, tw, 3] (``Model.get_texture()``), numpy arrays or device tensors.  ``bind_texture(None, None)``
-        drops them."""
+        [th, tw, 3] (``Model.get_texture()``), numpy arrays or device tensors.  With `mipmaps` the texture's
+        mip chain is built on the device as well (``crender_mip_build``, on torch's current stream), which
+        ``texture_pass(filter="trilinear")`` needs.  ``bind_texture(None, None)`` drops both."""
         if uv_by_triangles is None and texture is None:
-            self._texture = None
+            self._texture = self._mip = None
             return
         if uv_by_triangles is None or texture is None:
             raise ValueError("bind_texture needs both the texture coordinates and the texture (or None, None)")
@@ -753,13 +755,47 @@ class AdvancedPixelBufferFiller(DevicePlanes):
             raise ValueError(f"uv_by_triangles must be float32 [T, 3, 2], got {uv.dtype} {tuple(uv.shape)}")
         if tex.dtype != torch.uint8 or tex.dim() != 3 or tex.shape[2] < 3 or tex.shape[0] < 1 or tex.shape[1] < 1:
             raise ValueError(f"texture must be uint8 [th, tw, 3], got {tex.dtype} {tuple(tex.shape)}")
-        self._texture = (uv.to(self.device).contiguous(), tex[:, :, :3].to(self.device).contiguous())
+        bound = (uv.to(self.device).contiguous(), tex[:, :, :3].to(self.device).contiguous())
+        self._mip = self._build_mip_chain(bound[1]) if mipmaps else None
+        self._texture = bound
+
+    def _build_mip_chain(self, tex):
+        """(chain uint8 [total bytes], [(h_k, w_k)], [byte offset of level k]) of a device texture."""
+        th, tw = int(tex.shape[0]), int(tex.shape[1])
+        n = _capi.MIP_MAX_LEVELS
+        levels, total = C.c_int32(0), C.c_uint64(0)
+        hs, ws, offs = (C.c_int32 * n)(), (C.c_int32 * n)(), (C.c_uint64 * n)()
+        _capi.check(self._lib.crender_mip_layout(th, tw, C.byref(levels), hs, ws, offs, C.byref(total)),
+                    "crender_mip_layout")
+        chain = torch.empty(total.value, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _capi.check(self._lib.crender_mip_build(tex.data_ptr(), th, tw, chain.data_ptr(), self._stream()),
+                        "crender_mip_build")
+        L = levels.value
+        return chain, [(hs[k], ws[k]) for k in range(L)], [offs[k] for k in range(L)]
+
+    def mip_levels(self):
+        """[(h_k, w_k)] of the bound texture's mip chain, or None without one."""
+        return None if self._mip is None else list(self._mip[1])
+
+    def get_mip_level(self, k):
+        """Level `k` of the mip chain: a uint8 [h_k, w_k, 3] device tensor that views the chain."""
+        if self._mip is None:
+            raise ValueError("no mip chain is bound: bind_texture(..., mipmaps=True)")
+        chain, levels, offsets = self._mip
+        if not 0 <= k < len(levels):
+            raise IndexError(f"the chain has levels 0 .. {len(levels) - 1}, got {k}")
+        h, w = levels[k]
+        return chain[offsets[k]:offsets[k] + 3 * h * w].view(h, w, 3)
 
     def texture_pass(self, perspective=False, filter="nearest", light_direction=None):
         """Per-pixel texture mapping of the LAST frame's colour plane (``crender_tex_shade``,
         include/crender_tex.h): every pixel a triangle won gets the bound texture's texel at its
         interpolated (u, v) — affine like the reference's attributes, or perspective-correct; the nearest
-        texel or four of them — instead of the blend of three vertex colours.  Rows of the filler's
+        texel or four of them — instead of the blend of three vertex colours.  ``filter="trilinear"``
+        (``crender_mip_shade``, include/crender_mip.h) picks a mip level per pixel from the screen-space
+        derivatives of (u, v) and blends the bilinear samples of two levels; it needs the chain of
+        ``bind_texture(..., mipmaps=True)``.  Rows of the filler's
         ``row_strip``, on torch's current stream.  With `light_direction` (the illumination object's own
         flipped, normalised vector, as ``set_fused_illumination`` takes it) the pass also shades every
         pixel of the rows: the same bits as the separate illumination pass afterwards, without its
@@ -767,14 +803,16 @@ class AdvancedPixelBufferFiller(DevicePlanes):
 
         The frame is settled first (one stream synchronisation, as every getter does): a frame whose bin
         lists overflowed is rendered again, and the pass must land on the frame that stays."""
-        if filter not in ("nearest", "bilinear"):
-            raise ValueError(f"filter must be 'nearest' or 'bilinear', got {filter!r}")
+        if filter not in ("nearest", "bilinear", "trilinear"):
+            raise ValueError(f"filter must be 'nearest', 'bilinear' or 'trilinear', got {filter!r}")
         if self._pipeline:
             raise ValueError("texture_pass is not available on a swap chain (pipeline=True): per-slot passes are not implemented")
         if self.winner_buffer is None:
             raise ValueError("texture_pass needs the winner plane: construct the filler with track_winner=True")
         if self._texture is None:
             raise ValueError("texture_pass: no texture is bound (bind_texture)")
+        if filter == "trilinear" and self._mip is None:
+            raise ValueError("filter 'trilinear' needs a mip chain: bind_texture(..., mipmaps=True)")
         if self._inputs is None:
             raise ValueError("texture_pass: no frame has been rendered")
         if not (self._last_flags & _capi.FUSED_CLEAR):
@@ -788,14 +826,19 @@ class AdvancedPixelBufferFiller(DevicePlanes):
         light = None if light_direction is None else (C.c_float * 3)(*[float(v) for v in light_direction])
         self._push_host_edits()
         self._check_bins()             # nothing pending from here on: no later redo can undo the pass
-        flags = (_capi.TEX_PERSPECTIVE if perspective else 0) | (_capi.TEX_BILINEAR if filter == "bilinear" else 0)
         pos_of = None if self._order is None else self._order[1].data_ptr()
+        if filter == "trilinear":
+            shade, name, image = self._lib.crender_mip_shade, "crender_mip_shade", self._mip[0]
+            flags = _capi.MIP_PERSPECTIVE if perspective else 0
+        else:
+            shade, name, image = self._lib.crender_tex_shade, "crender_tex_shade", tex
+            flags = (_capi.TEX_PERSPECTIVE if perspective else 0) | (_capi.TEX_BILINEAR if filter == "bilinear" else 0)
         with torch.cuda.device(self.device):
-            _capi.check(self._lib.crender_tex_shade(
+            _capi.check(shade(
                 self.winner_buffer.data_ptr(), tri.data_ptr() if T else None, T, pos_of, self._P,
-                uv.data_ptr() if T else None, tex.data_ptr(), int(tex.shape[0]), int(tex.shape[1]),
+                uv.data_ptr() if T else None, image.data_ptr(), int(tex.shape[0]), int(tex.shape[1]),
                 None if light is None else self.normals_buffer.data_ptr(), light, self.color_buffer.data_ptr(),
-                self.h, self.w, self.y0, self.y1, flags, self._stream()), "crender_tex_shade")
+                self.h, self.w, self.y0, self.y1, flags, self._stream()), name)
         self._host_fresh = False       # views handed out earlier show the textured colours at the next getter call
 
     def render_frame(self, pipelined=None):

@@ -40,9 +40,9 @@ class Renderer:
         self.on_device = on_device
         # texture_pass=None (default): the reference's colours — three vertex colours blended across each triangle.
         # A dict of ``perspective`` / ``filter`` (AdvancedPixelBufferFiller.texture_pass's arguments; {} = affine,
-        # nearest): every frame starts from cleared buffers (one model per frame, as "fused") and the model's
-        # texture is mapped per pixel before the illumination; with on_device="fused" the texture pass carries
-        # the light and the raster kernel does not shade.
+        # nearest; the filter "trilinear" binds the texture with its mip chain): every frame starts from cleared
+        # buffers (one model per frame, as "fused") and the model's texture is mapped per pixel before the
+        # illumination; with on_device="fused" the texture pass carries the light and the raster kernel does not shade.
         self.texture_pass = None if texture_pass is None else dict(texture_pass)
         self._textured = None          # weak reference to the model whose texture the filler holds
 
@@ -57,7 +57,10 @@ class Renderer:
             if uv is None or tex is None:
                 raise ValueError("Renderer(texture_pass=...) needs a textured model: this one has no texture "
                                  "coordinates or no texture image")
-            filler.bind_texture(uv, tex)
+            if self.texture_pass.get("filter") == "trilinear":
+                filler.bind_texture(uv, tex, mipmaps=True)
+            else:
+                filler.bind_texture(uv, tex)
             self._textured = weakref.ref(model)
         # (the views handed out so far are refreshed by the next getter call, after the pass; and the raster
         # kernel never shades here: the colours it stores are replaced by the texture's)

@@ -1,7 +1,9 @@
-"""Device time of the texture pass (csrc/texture.hip): crender_tex_shade between two HIP events, mean of 50
-passes over the same frame, for T-Rex at 1024^2 and 4096^2 under a random 709 x 709 texture, in the four modes,
-with and without the fused light; and, next to them, the existing illumination pass alone
-(crender_guro_illumination) on the same frames — the figure the fused light has to beat is pass + illumination.
+"""Device time of the texture pass (csrc/texture.hip, csrc/texmip.hip): crender_tex_shade and crender_mip_shade
+between two HIP events, mean of 50 passes over the same frame, for T-Rex at 256^2 (where most pixels are
+minified), 1024^2 and 4096^2 under a random 709 x 709 texture, in the four modes of the first and the two of the
+second (trilinear rows carry the bilinear time of the same frame and run as `bilinear_us`), with and without the
+fused light; next to them, the existing illumination pass alone (crender_guro_illumination) on the same frames —
+the figure the fused light has to beat is pass + illumination — and crender_mip_build of the texture.
 
 Prints one JSON line per scene and mode.  Run without arguments it measures each scene in a child process of its
 own under ``timeout`` and stops at the first one that fails:
@@ -19,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 REPS, WARMUP = 50, 5
-SCENES = {"trex1024": 1024, "trex4096": 4096}
+SCENES = {"trex256": 256, "trex1024": 1024, "trex4096": 4096}
 CHILD_SECONDS = 240
 
 
@@ -48,10 +50,11 @@ def measure(name):
         uv = np.ascontiguousarray(z["uv"][z["faces_uv"]], dtype=np.float32)
     tex = np.random.default_rng(1).integers(0, 256, (709, 709, 3), dtype=np.uint8)
     f = AdvancedPixelBufferFiller(size, size, fov=45.0, track_winner=True)
-    f.bind_texture(uv, tex)
+    f.bind_texture(uv, tex, mipmaps=True)
     f.render_arrays(tri, col, nrm, clear=True)
     f.texture_pass()                                   # settles the frame; the direct calls below repeat the pass
     d_uv, d_tex = f._texture
+    d_chain = f._mip[0]
     assert f._order is None                            # (below 2^18 triangles the inputs stay in the caller's order)
     covered = int((f.get_winner_tensor() >= 0).sum())
     npix = size * size
@@ -60,12 +63,13 @@ def measure(name):
     light = (C.c_float * 3)(-0.28, 0.19, -0.94)
     rows = []
 
-    def row(mode, us, nbytes):
+    def row(mode, us, nbytes, **more):
         r = {"scene": name, "T": int(tri.shape[0]), "covered": round(covered / npix, 3), "mode": mode,
              "device_us": round(us, 2), "bytes_per_pixel": round(nbytes / npix, 2),
-             "GB_per_s": round(nbytes / us / 1e3, 1)}
+             "GB_per_s": round(nbytes / us / 1e3, 1), **more}
         rows.append(r)
         print(json.dumps(r), flush=True)
+        return r
 
     for with_light in (False, True):
         for persp in (False, True):
@@ -85,12 +89,27 @@ def measure(name):
                     nbytes += 12 * npix + 24 * (npix - covered)
                 mode = ("perspective" if persp else "affine") + ("_bilinear" if bilinear else "_nearest") + \
                     ("_light" if with_light else "")
-                row(mode, _timed(stream, launch), nbytes)
+                bilinear_us = row(mode, _timed(stream, launch), nbytes)["device_us"]
+
+            def launch_mip():
+                _capi.check(lib.crender_mip_shade(
+                    f.winner_buffer.data_ptr(), f._inputs[0].data_ptr(), tri.shape[0], None, f._P, d_uv.data_ptr(),
+                    d_chain.data_ptr(), 709, 709, f.normals_buffer.data_ptr() if with_light else None,
+                    light if with_light else None, f.color_buffer.data_ptr(), size, size, 0, size,
+                    _capi.MIP_PERSPECTIVE if persp else 0, st), "crender_mip_shade")
+            mode = ("perspective" if persp else "affine") + "_trilinear" + ("_light" if with_light else "")
+            row(mode, _timed(stream, launch_mip), nbytes, bilinear_us=bilinear_us)
 
     def guro():
         _capi.check(lib.crender_guro_illumination(f.color_buffer.data_ptr(), f.normals_buffer.data_ptr(), light, size,
                                                   size, 0, size, st), "crender_guro_illumination")
     row("illumination_pass_alone", _timed(stream, guro), 36 * npix)
+
+    def build():
+        _capi.check(lib.crender_mip_build(d_tex.data_ptr(), 709, 709, d_chain.data_ptr(), st), "crender_mip_build")
+    us = _timed(stream, build)
+    print(json.dumps({"scene": name, "mode": "mip_build_709x709", "levels": len(f.mip_levels()),
+                      "chain_bytes": int(d_chain.numel()), "device_us": round(us, 2)}), flush=True)
     return rows
 
 
