@@ -111,6 +111,14 @@ MIP_SIGNATURES = {
                                  _i32, _i32, _i32, _i32, _u32, _vp]),
 }
 
+# the anisotropic texture pass (include/crender_aniso.h), bound from a table of its own: crender_mip_shade's
+# arguments with max_aniso in front of the stream
+ANISO_MAX = 16
+ANISO_SIGNATURES = {
+    "crender_aniso_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _i32, _vp, _f32p, _vp,
+                                   _i32, _i32, _i32, _i32, _u32, _i32, _vp]),
+}
+
 _lib = None
 
 
@@ -135,7 +143,8 @@ def load():
             "(or __graft_entry__.build()).  There is no CPU fallback for the rasterizer.")
     L = C.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(WIRE_SIGNATURES.items()) + \
-            list(PY_SIGNATURES.items()) + list(TEX_SIGNATURES.items()) + list(MIP_SIGNATURES.items()):
+            list(PY_SIGNATURES.items()) + list(TEX_SIGNATURES.items()) + list(MIP_SIGNATURES.items()) + \
+            list(ANISO_SIGNATURES.items()):
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

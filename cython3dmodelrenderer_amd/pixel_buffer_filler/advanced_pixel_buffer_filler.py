@@ -788,15 +788,18 @@ class AdvancedPixelBufferFiller(DevicePlanes):
         h, w = levels[k]
         return chain[offsets[k]:offsets[k] + 3 * h * w].view(h, w, 3)
 
-    def texture_pass(self, perspective=False, filter="nearest", light_direction=None):
+    def texture_pass(self, perspective=False, filter="nearest", light_direction=None, anisotropy=1):
         """Per-pixel texture mapping of the LAST frame's colour plane (``crender_tex_shade``,
         include/crender_tex.h): every pixel a triangle won gets the bound texture's texel at its
         interpolated (u, v) — affine like the reference's attributes, or perspective-correct; the nearest
         texel or four of them — instead of the blend of three vertex colours.  ``filter="trilinear"``
         (``crender_mip_shade``, include/crender_mip.h) picks a mip level per pixel from the screen-space
         derivatives of (u, v) and blends the bilinear samples of two levels; it needs the chain of
-        ``bind_texture(..., mipmaps=True)``.  Rows of the filler's
-        ``row_strip``, on torch's current stream.  With `light_direction` (the illumination object's own
+        ``bind_texture(..., mipmaps=True)``.  With `anisotropy` A from 2 to 16 on top of it
+        (``crender_aniso_shade``, include/crender_aniso.h) the level comes from the shorter of a pixel's two
+        texel-space steps, never more than A times shorter than the longer, and up to A trilinear samples
+        span the longer one: a surface seen at a grazing angle keeps its detail across the short axis.  Rows of
+        the filler's ``row_strip``, on torch's current stream.  With `light_direction` (the illumination object's own
         flipped, normalised vector, as ``set_fused_illumination`` takes it) the pass also shades every
         pixel of the rows: the same bits as the separate illumination pass afterwards, without its
         traffic.
@@ -805,6 +808,10 @@ class AdvancedPixelBufferFiller(DevicePlanes):
         lists overflowed is rendered again, and the pass must land on the frame that stays."""
         if filter not in ("nearest", "bilinear", "trilinear"):
             raise ValueError(f"filter must be 'nearest', 'bilinear' or 'trilinear', got {filter!r}")
+        if isinstance(anisotropy, bool) or not isinstance(anisotropy, int) or not 1 <= anisotropy <= _capi.ANISO_MAX:
+            raise ValueError(f"anisotropy must be an int from 1 to {_capi.ANISO_MAX}, got {anisotropy!r}")
+        if anisotropy > 1 and filter != "trilinear":
+            raise ValueError(f"anisotropy={anisotropy} needs filter=\"trilinear\" (and its mip chain), got {filter!r}")
         if self._pipeline:
             raise ValueError("texture_pass is not available on a swap chain (pipeline=True): per-slot passes are not implemented")
         if self.winner_buffer is None:
@@ -827,9 +834,12 @@ class AdvancedPixelBufferFiller(DevicePlanes):
         self._push_host_edits()
         self._check_bins()             # nothing pending from here on: no later redo can undo the pass
         pos_of = None if self._order is None else self._order[1].data_ptr()
+        more = ()
         if filter == "trilinear":
             shade, name, image = self._lib.crender_mip_shade, "crender_mip_shade", self._mip[0]
             flags = _capi.MIP_PERSPECTIVE if perspective else 0
+            if anisotropy > 1:
+                shade, name, more = self._lib.crender_aniso_shade, "crender_aniso_shade", (anisotropy,)
         else:
             shade, name, image = self._lib.crender_tex_shade, "crender_tex_shade", tex
             flags = (_capi.TEX_PERSPECTIVE if perspective else 0) | (_capi.TEX_BILINEAR if filter == "bilinear" else 0)
@@ -838,7 +848,7 @@ class AdvancedPixelBufferFiller(DevicePlanes):
                 self.winner_buffer.data_ptr(), tri.data_ptr() if T else None, T, pos_of, self._P,
                 uv.data_ptr() if T else None, image.data_ptr(), int(tex.shape[0]), int(tex.shape[1]),
                 None if light is None else self.normals_buffer.data_ptr(), light, self.color_buffer.data_ptr(),
-                self.h, self.w, self.y0, self.y1, flags, self._stream()), name)
+                self.h, self.w, self.y0, self.y1, flags, *more, self._stream()), name)
         self._host_fresh = False       # views handed out earlier show the textured colours at the next getter call
 
     def render_frame(self, pipelined=None):

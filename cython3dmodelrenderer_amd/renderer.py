@@ -39,8 +39,9 @@ class Renderer:
         #   raster kernel shades each pixel as it stores it (no illumination pass at all).
         self.on_device = on_device
         # texture_pass=None (default): the reference's colours — three vertex colours blended across each triangle.
-        # A dict of ``perspective`` / ``filter`` (AdvancedPixelBufferFiller.texture_pass's arguments; {} = affine,
-        # nearest; the filter "trilinear" binds the texture with its mip chain): every frame starts from cleared
+        # A dict of ``perspective`` / ``filter`` / ``anisotropy`` (AdvancedPixelBufferFiller.texture_pass's arguments;
+        # {} = affine, nearest; the filter "trilinear", which ``anisotropy`` above 1 needs, binds the texture with
+        # its mip chain): every frame starts from cleared
         # buffers (one model per frame, as "fused") and the model's texture is mapped per pixel before the
         # illumination; with on_device="fused" the texture pass carries the light and the raster kernel does not shade.
         self.texture_pass = None if texture_pass is None else dict(texture_pass)

@@ -43,8 +43,9 @@
  *   Fused light, Other planes
  *                word for word as in tex.h.
  *
- * Not covered: anisotropic filtering (a surface seen at a grazing angle takes the level of its longer
- * axis, and blurs along the shorter), nearest-within-level filters.
+ * Not covered here: anisotropic filtering (a surface seen at a grazing angle takes the level of its longer
+ * axis, and blurs along the shorter) is include/crender_aniso.h's crender_aniso_shade, on this chain;
+ * nearest-within-level filters.
  */
 #ifndef CRENDER_MIP_H
 #define CRENDER_MIP_H
