@@ -37,6 +37,10 @@ MIP_HEADERS = [os.path.join("..", "..", "include", "crender_mip.h"), "mip_sample
 # mip_sample.h is what it shares with texmip.hip: the chain's layout, the bilinear sample, uv at a pixel.
 ANISO_SOURCES = ["texaniso.hip"]
 ANISO_HEADERS = [os.path.join("..", "..", "include", "crender_aniso.h"), "mip_sample.h"]
+# resolve.hip  the supersampling resolve with the fused light and uint8 presentation (include/crender_ssaa.h);
+# kept out of source_sha16() likewise.
+SSAA_SOURCES = ["resolve.hip"]
+SSAA_HEADERS = [os.path.join("..", "..", "include", "crender_ssaa.h")]
 
 # Float parity with the reference depends on these (DESIGN.md "Numerics"):
 #   -ffp-contract=off                           no FMA contraction (hipcc defaults to fast)
@@ -84,7 +88,8 @@ def needs_build() -> bool:
     built = os.path.getmtime(LIB_PATH)
     deps = [os.path.join(SRC_DIR, s) for s in SOURCES + HEADERS + WIRE_SOURCES + WIRE_HEADERS +
                                                 PY_SOURCES + PY_HEADERS + TEX_SOURCES + TEX_HEADERS +
-                                                MIP_SOURCES + MIP_HEADERS + ANISO_SOURCES + ANISO_HEADERS] + \
+                                                MIP_SOURCES + MIP_HEADERS + ANISO_SOURCES + ANISO_HEADERS +
+                                                SSAA_SOURCES + SSAA_HEADERS] + \
         [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > built for d in deps)
 
@@ -95,7 +100,8 @@ def compile_library(out: str, extra_flags=(), sources=None, src_dir: str = SRC_D
     defines of diagnostic builds (-DCRENDER_STAMPS, ...)."""
     import tempfile
     from concurrent.futures import ThreadPoolExecutor
-    sources = list(sources or SOURCES + WIRE_SOURCES + PY_SOURCES + TEX_SOURCES + MIP_SOURCES + ANISO_SOURCES)
+    sources = list(sources or SOURCES + WIRE_SOURCES + PY_SOURCES + TEX_SOURCES + MIP_SOURCES + ANISO_SOURCES +
+                   SSAA_SOURCES)
     err = subprocess.DEVNULL if quiet else None
     with tempfile.TemporaryDirectory(prefix="crender_build_") as tmp:
         objs = [os.path.join(tmp, os.path.splitext(s)[0] + ".o") for s in sources]

@@ -119,6 +119,13 @@ ANISO_SIGNATURES = {
                                    _i32, _i32, _i32, _i32, _u32, _i32, _vp]),
 }
 
+# the supersampling resolve (include/crender_ssaa.h), bound from a table of its own
+SSAA_U8, SSAA_FLIP = 1, 2
+SSAA_MAX = 8
+SSAA_SIGNATURES = {
+    "crender_ssaa_resolve": (_i32, [_vp, _vp, _f32p, _i32, _i32, _i32, _i32, _i32, _vp, _u32, _vp]),
+}
+
 _lib = None
 
 
@@ -144,7 +151,7 @@ def load():
     L = C.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(WIRE_SIGNATURES.items()) + \
             list(PY_SIGNATURES.items()) + list(TEX_SIGNATURES.items()) + list(MIP_SIGNATURES.items()) + \
-            list(ANISO_SIGNATURES.items()):
+            list(ANISO_SIGNATURES.items()) + list(SSAA_SIGNATURES.items()):
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

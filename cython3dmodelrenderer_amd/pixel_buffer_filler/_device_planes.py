@@ -72,6 +72,14 @@ class DevicePlanes:
             self.color_buffer.data_ptr(), self.normals_buffer.data_ptr(), (C.c_float * 3)(*light),
             self.h, self.w, self.y0, self.y1, self._stream()), "crender_guro_illumination")
 
+    def _resolve_planes(self, out, factor, light, flags, Y0, Y1):
+        """crender_ssaa_resolve (include/crender_ssaa.h) of the colour plane into output rows Y0 .. Y1 of `out`."""
+        with torch.cuda.device(self.device):
+            _capi.check(self._lib.crender_ssaa_resolve(
+                self.color_buffer.data_ptr(), None if light is None else self.normals_buffer.data_ptr(),
+                None if light is None else (C.c_float * 3)(*light), self.h, self.w, factor, Y0, Y1,
+                out.data_ptr(), flags, self._stream()), "crender_ssaa_resolve")
+
     # ----------------------------------------------------------------- protocol --
     def _planes(self):
         return {"z": self.z_buffer, "color": self.color_buffer, "normals": self.normals_buffer}
@@ -150,6 +158,41 @@ class DevicePlanes:
         self.get_color_tensor()        # (what the filler does before it hands the plane out: it must be complete)
         self._push_host_edits()
         return self._present_planes(flip_rows)
+
+    def resolve(self, factor, light_direction=None, dtype="float32", flip_rows=False):
+        """Supersampled anti-aliasing: a NEW device tensor [h / factor, w / factor, 3] whose pixels are the means
+        of the factor x factor blocks of the colour plane (``crender_ssaa_resolve``, include/crender_ssaa.h: the
+        samples of a block summed in row-major order, one float32 division).  With `light_direction` (the
+        illumination object's own flipped, normalised vector, as ``texture_pass`` and ``set_fused_illumination``
+        take it) every sample is shaded as it is read — the bits of ``shade_guro`` followed by the plain
+        resolve, without that pass over the supersampled planes.  `dtype` "uint8" stores
+        ``present_u8``'s cast of the mean and `flip_rows` stores the rows bottom up:
+        ``resolve(s, dtype="uint8", flip_rows=True)`` is the image run.py:26 writes to disk.
+
+        Edits made in the numpy views handed out so far are carried to the device first, and the frame is
+        settled after the launch (one stream synchronisation per call, as every getter and ``texture_pass``
+        pay): a frame whose bin lists overflowed is rendered again, and resolved again into the same tensor.
+        A filler with a ``row_strip`` resolves its rows (both ends multiples of `factor`) and leaves the other
+        rows of the result zero.  The planes are only read: the views stay as fresh or as stale as they were."""
+        if isinstance(factor, bool) or not isinstance(factor, int) or not 1 <= factor <= _capi.SSAA_MAX:
+            raise ValueError(f"factor must be an int from 1 to {_capi.SSAA_MAX}, got {factor!r}")
+        if dtype not in ("float32", "uint8"):
+            raise ValueError(f"dtype must be 'float32' or 'uint8', got {dtype!r}")
+        self._push_host_edits()        # (first of all: a filler may create its planes here)
+        if self.h % factor or self.w % factor:
+            raise ValueError(f"the frame {self.h} x {self.w} is not a multiple of factor={factor} in both directions")
+        if self.y0 % factor or self.y1 % factor:
+            raise ValueError(f"the row strip ({self.y0}, {self.y1}) must start and end on multiples of factor={factor}")
+        light = None if light_direction is None else [float(v) for v in light_direction]
+        flags = (_capi.SSAA_U8 if dtype == "uint8" else 0) | (_capi.SSAA_FLIP if flip_rows else 0)
+        new = torch.empty if (self.y0, self.y1) == (0, self.h) else torch.zeros
+        out = new((self.h // factor, self.w // factor, 3), dtype=getattr(torch, dtype), device=self.color_buffer.device)
+        while True:
+            self._resolve_planes(out, factor, light, flags, self.y0 // factor, self.y1 // factor)
+            if not self._wait_planes():
+                break
+            self._ready_planes()       # (a frame was rendered again: the same planes, settled now)
+        return out
 
     def shade_guro(self, light):
         """``GuroIllumination.draw_illumination`` over rows y0 … y1 of the planes; `light`: that class's vector, as floats."""

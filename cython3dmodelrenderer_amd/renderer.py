@@ -21,7 +21,8 @@ def _device_form_is_the_same_shading(illumination):
 
 class Renderer:
     def __init__(self, pixel_buffer_filler, illumination, triangle_iterator_type=None,
-                 image_height=512, image_width=512, use_tqdm=True, on_device=None, texture_pass=None):
+                 image_height=512, image_width=512, use_tqdm=True, on_device=None, texture_pass=None,
+                 supersample=None):
         self.pixel_buffer_filler = pixel_buffer_filler
         self.illumination = illumination
         self.triangle_iterator_type = triangle_iterator_type   # stored, unused (as in Version C)
@@ -46,6 +47,22 @@ class Renderer:
         # illumination; with on_device="fused" the texture pass carries the light and the raster kernel does not shade.
         self.texture_pass = None if texture_pass is None else dict(texture_pass)
         self._textured = None          # weak reference to the model whose texture the filler holds
+        # supersample=None (default): the filler's frame is the image.  An int s from 1 to 8: the filler IS the
+        # supersampled frame — the caller constructs it at s*H x s*W, and image_height / image_width stay ITS size,
+        # so that normalize_model fits the model to the frame actually drawn — and ``render`` returns the mean of
+        # every s x s block of it, [H, W, 3] float32, resolved on the device (``filler.resolve``):
+        #   "fused"  the raster kernel (or the texture pass) shades as ever, then the resolve; the tensor;
+        #   True, or None with an illumination whose device form is its shading and has a ``light_direction``:
+        #            the resolve shades each sample as it reads it, there is no illumination pass over the
+        #            supersampled planes and the filler's colour plane stays UNSHADED; the tensor for True,
+        #            for None a fresh numpy array (a copy: not a live view of a filler plane, edits go nowhere);
+        #   False, or an illumination without such a device form: the reference's flow on the host views at
+        #            full size, then the resolve (which the edits made there reach); a fresh numpy array.
+        # ``filler.resolve(s, light_direction=..., dtype="uint8", flip_rows=True)`` gives the PNG's bytes.
+        if supersample is not None and not hasattr(pixel_buffer_filler, "resolve"):
+            raise ValueError("Renderer(supersample=...) needs a filler that keeps its planes on the device "
+                             "(AdvancedPixelBufferFiller, EdgeOnlyPixelBufferFiller): this one has no resolve()")
+        self.supersample = supersample
 
     def _draw(self, model, light=None, **kw):
         """``render_model``; with a texture pass, a cleared frame and the pass on top of it."""
@@ -77,6 +94,8 @@ class Renderer:
             model.scale(span / model.get_max_span())
             model.shift(-model.get_mean_vertex() + [centre[0], centre[1], -span])
         filler = self.pixel_buffer_filler
+        if self.supersample is not None:
+            return self._render_supersampled(model)
         if self.on_device == "fused" and getattr(self.illumination, "fuse_into", None):
             if self.texture_pass is not None:
                 # the texture pass carries the light
@@ -99,6 +118,29 @@ class Renderer:
             self._draw(model)
         self.illumination.draw_illumination(filler.get_color_buffer(), filler.get_normals_buffer())
         return filler.get_color_buffer()
+
+    def _render_supersampled(self, model):
+        """``render`` after the model fit, with ``supersample=s``: the same draws, the resolve at the end."""
+        filler, s = self.pixel_buffer_filler, self.supersample
+        if self.on_device == "fused" and getattr(self.illumination, "fuse_into", None):
+            if self.texture_pass is not None:
+                self._draw(model, light=self.illumination.light_direction)
+            else:
+                self.illumination.fuse_into(filler)
+                filler.render_model(model, clear=True)
+            return filler.resolve(s)
+        light = getattr(self.illumination, "light_direction", None)
+        device_form = getattr(self.illumination, "draw_illumination_device", None)
+        if self.on_device is None and not _device_form_is_the_same_shading(self.illumination):
+            device_form = None
+        if self.on_device is not False and device_form is not None and light is not None:
+            # the resolve carries the light: the supersampled colour plane is read once and stays unshaded
+            self._draw(model, refresh_views=False)
+            image = filler.resolve(s, light_direction=light)
+            return image if self.on_device is True else image.cpu().numpy()
+        self._draw(model)
+        self.illumination.draw_illumination(filler.get_color_buffer(), filler.get_normals_buffer())
+        return filler.resolve(s).cpu().numpy()
 
     def reset_buffers(self):
         pass   # a no-op in the reference too (renderer.py:51-52): renders composite
