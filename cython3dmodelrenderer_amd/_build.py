@@ -41,6 +41,10 @@ ANISO_HEADERS = [os.path.join("..", "..", "include", "crender_aniso.h"), "mip_sa
 # kept out of source_sha16() likewise.
 SSAA_SOURCES = ["resolve.hip"]
 SSAA_HEADERS = [os.path.join("..", "..", "include", "crender_ssaa.h")]
+# shadow.hip  the deferred shadow-mapping pass over the winner plane (include/crender_shadow.h); kept out of
+# source_sha16() likewise.
+SHADOW_SOURCES = ["shadow.hip"]
+SHADOW_HEADERS = [os.path.join("..", "..", "include", "crender_shadow.h")]
 
 # Float parity with the reference depends on these (DESIGN.md "Numerics"):
 #   -ffp-contract=off                           no FMA contraction (hipcc defaults to fast)
@@ -89,7 +93,7 @@ def needs_build() -> bool:
     deps = [os.path.join(SRC_DIR, s) for s in SOURCES + HEADERS + WIRE_SOURCES + WIRE_HEADERS +
                                                 PY_SOURCES + PY_HEADERS + TEX_SOURCES + TEX_HEADERS +
                                                 MIP_SOURCES + MIP_HEADERS + ANISO_SOURCES + ANISO_HEADERS +
-                                                SSAA_SOURCES + SSAA_HEADERS] + \
+                                                SSAA_SOURCES + SSAA_HEADERS + SHADOW_SOURCES + SHADOW_HEADERS] + \
         [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > built for d in deps)
 
@@ -101,7 +105,7 @@ def compile_library(out: str, extra_flags=(), sources=None, src_dir: str = SRC_D
     import tempfile
     from concurrent.futures import ThreadPoolExecutor
     sources = list(sources or SOURCES + WIRE_SOURCES + PY_SOURCES + TEX_SOURCES + MIP_SOURCES + ANISO_SOURCES +
-                   SSAA_SOURCES)
+                   SSAA_SOURCES + SHADOW_SOURCES)
     err = subprocess.DEVNULL if quiet else None
     with tempfile.TemporaryDirectory(prefix="crender_build_") as tmp:
         objs = [os.path.join(tmp, os.path.splitext(s)[0] + ".o") for s in sources]

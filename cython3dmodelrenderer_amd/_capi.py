@@ -126,6 +126,13 @@ SSAA_SIGNATURES = {
     "crender_ssaa_resolve": (_i32, [_vp, _vp, _f32p, _i32, _i32, _i32, _i32, _i32, _vp, _u32, _vp]),
 }
 
+# the deferred shadow pass (include/crender_shadow.h), bound from a table of its own
+SHADOW_PCF = (1, 3, 5)
+SHADOW_SIGNATURES = {
+    "crender_shadow_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _f32p, _vp, _vp, _i32, _i32, C.c_float, C.c_float,
+                                    _i32, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
+}
+
 _lib = None
 
 
@@ -151,7 +158,7 @@ def load():
     L = C.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(WIRE_SIGNATURES.items()) + \
             list(PY_SIGNATURES.items()) + list(TEX_SIGNATURES.items()) + list(MIP_SIGNATURES.items()) + \
-            list(ANISO_SIGNATURES.items()) + list(SSAA_SIGNATURES.items()):
+            list(ANISO_SIGNATURES.items()) + list(SSAA_SIGNATURES.items()) + list(SHADOW_SIGNATURES.items()):
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

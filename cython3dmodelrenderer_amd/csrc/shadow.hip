@@ -1,0 +1,170 @@
+// shadow.hip — shadow mapping as a deferred pass over the winner plane
+// (include/crender_shadow.h states the arithmetic; this file keeps its operation order).
+//
+// The shape of k_tex_shade (texture.hip): a pixel per work item, an 8 x 8 block of pixels per wavefront
+// (a workgroup is four of them side by side: 32 x 8), a grid-stride loop over row blocks.  The "texture"
+// is the z plane of a second frame, the light's, and what is blended across the triangle is its three
+// light-frame corners (36 B per winner, gathered like the uv).  A wavefront whose 64 winners are all
+// background leaves after its one load.
+//
+// The K x K taps are plain gathers with constant trip counts (the kernel is instantiated on K and on
+// whether the light's winner plane is given): neighbouring pixels land on neighbouring texels, so the
+// 64 lanes of a tap touch a few cache lines of the map.  Measured figures: README, "Shadow mapping".
+#include <math.h>
+
+#include "common.h"
+#include "../../include/crender_shadow.h"
+
+using namespace crender_detail;
+
+namespace {
+
+constexpr int kShadowBlock = 8;      // pixels along each side of a wavefront's block
+
+// The host's truncating float -> int32 conversion (cvttss2si): INT_MIN for a NaN and out of range.
+// (Restated from model_ops.hip, whose text is fingerprinted.)
+CR_DEV int host_f32_to_i32(float f)
+{
+    return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : (int)0x80000000;
+}
+
+// What the kernel needs of the light's frame.
+struct ShadowMap {
+    ProjConst P;                     // the light's projection, as make_proj(PL16, Wl, Hl)
+    const float *z;                  // [Hl][Wl]
+    const int32_t *winner;           // [Hl][Wl], read only by the WINNER instances
+    int h, w;
+    float bias, ambient;
+};
+
+template <int K, bool WINNER>
+__global__ __launch_bounds__(kThreads) void k_shadow_shade(const int32_t *__restrict__ win, const float *__restrict__ tri,
+                                                            int64_t T, const uint32_t *__restrict__ pos_of, ProjConst P,
+                                                            const float *__restrict__ ltri, ShadowMap M,
+                                                            float *__restrict__ cb, int W, int y0, int y1, int row_blocks)
+{
+    constexpr int R = (K - 1) / 2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = ((int)blockIdx.x * (kThreads / 64) + wave) * kShadowBlock + (lane & (kShadowBlock - 1));
+    for (int rb = blockIdx.y; rb < row_blocks; rb += gridDim.y) {
+        const int y = y0 + rb * kShadowBlock + (lane >> 3);
+        const bool inside = x < W && y < y1;
+        const size_t pix = (size_t)y * (size_t)W + (size_t)x;
+        int64_t orig = -1;           // the winner in the caller's order (ltri, the light's winners), and where it sits in d_tri
+        if (inside) orig = win[pix];
+        bool covered = orig >= 0 && orig < T;
+        int64_t t = orig;
+        if (covered && pos_of) {
+            t = pos_of[orig];
+            covered = t < T;
+        }
+        if (!wave_any(covered)) continue;           // a scalar branch: the whole wavefront leaves
+        if (!covered) continue;
+        float a[3], b[3], c[3];
+        const float *v = tri + t * 9;
+        a[0] = v[0]; a[1] = v[1]; a[2] = v[2];
+        b[0] = v[3]; b[1] = v[4]; b[2] = v[5];
+        c[0] = v[6]; c[1] = v[7]; c[2] = v[8];
+        const float za = a[2], zb = b[2], zc = c[2];
+        project_vertex(P, a);
+        project_vertex(P, b);
+        project_vertex(P, c);
+        const TriXYZ X{a[0], a[1], a[2], b[0], b[1], b[2], c[0], c[1], c[2]};
+        float b1, b2, b3;
+        barycentric(X, x, y, b1, b2, b3);
+        const float q1 = b1 / za, q2 = b2 / zb, q3 = b3 / zc;
+        const float s = (q1 + q2) + q3;
+        const float *l = ltri + orig * 9;
+        float p[3];
+        p[0] = ((l[0] * q1 + l[3] * q2) + l[6] * q3) / s;
+        p[1] = ((l[1] * q1 + l[4] * q2) + l[7] * q3) / s;
+        p[2] = ((l[2] * q1 + l[5] * q2) + l[8] * q3) / s;
+        if (!(p[2] > 0.0f)) continue;               // behind the light, or NaN: every tap is lit
+        project_vertex(M.P, p);
+        // The tap sums stay in int32: the conversion's largest value is 2^31 - 128, so only a centre near INT_MIN
+        // could overflow, and a centre three texels or more before the map has every tap outside it wherever it is.
+        const int cx = max(host_f32_to_i32(floorf(p[0] + 0.5f)), -(R + 1));
+        const int cy = max(host_f32_to_i32(floorf(p[1] + 0.5f)), -(R + 1));
+        const float depth = p[2] - M.bias;
+        // Every tap loads — a tap outside the map from the first texel of a row inside it — so that the K * K loads
+        // are independent of the tests and issue back to back (measured against a branch per tap: README).
+        int n = 0;
+#pragma unroll
+        for (int j = -R; j <= R; ++j) {
+            const int row = cy + j;
+            const bool row_in = (unsigned)row < (unsigned)M.h;
+            const size_t row_at = row_in ? (size_t)row * (size_t)M.w : 0;
+#pragma unroll
+            for (int i = -R; i <= R; ++i) {
+                const int colm = cx + i;
+                const bool in = row_in && (unsigned)colm < (unsigned)M.w;
+                const size_t at = row_at + (in ? (size_t)colm : 0);
+                bool lit = !in || !(depth > M.z[at]);
+                if (WINNER) lit = lit || (int64_t)M.winner[at] == orig;
+                n += lit ? 1 : 0;
+            }
+        }
+        if (n == K * K) continue;                   // lit: the pixel keeps its bits
+        const float frac = (float)n / (float)(K * K);
+        const float om = 1.0f - M.ambient;
+        const float m = om * frac;
+        const float f = M.ambient + m;
+        float *cp = cb + pix * 3;
+        cp[0] = cp[0] * f;
+        cp[1] = cp[1] * f;
+        cp[2] = cp[2] * f;
+    }
+}
+
+template <int K>
+void launch_shadow(dim3 grid, hipStream_t st, const int32_t *win, const float *tri, int64_t T, const uint32_t *pos_of,
+                   const ProjConst &P, const float *ltri, const ShadowMap &M, float *cb, int W, int y0, int y1,
+                   int row_blocks)
+{
+    if (M.winner)
+        hipLaunchKernelGGL((k_shadow_shade<K, true>), grid, dim3(kThreads), 0, st, win, tri, T, pos_of, P, ltri, M, cb,
+                           W, y0, y1, row_blocks);
+    else
+        hipLaunchKernelGGL((k_shadow_shade<K, false>), grid, dim3(kThreads), 0, st, win, tri, T, pos_of, P, ltri, M, cb,
+                           W, y0, y1, row_blocks);
+}
+
+}  // namespace
+
+extern "C" {
+
+int crender_shadow_shade(const int32_t *d_winner, const float *d_tri, int64_t T, const uint32_t *d_pos_of,
+                         const float *P16, const float *d_ltri, const float *PL16, const float *d_lz,
+                         const int32_t *d_lwinner, int Hl, int Wl, float bias, float ambient, int pcf, float *d_color,
+                         int H, int W, int y0, int y1, unsigned flags, void *stream)
+{
+    if (!d_winner || !P16 || !PL16 || !d_lz || !d_color)
+        return fail(CRENDER_EINVAL, "crender_shadow_shade: d_winner, P16, PL16, d_lz or d_color is NULL");
+    if (T < 0) return fail(CRENDER_EINVAL, "crender_shadow_shade: T is negative");
+    if (T > 0 && (!d_tri || !d_ltri)) return fail(CRENDER_EINVAL, "crender_shadow_shade: d_tri or d_ltri is NULL with T > 0");
+    if (H < 1 || W < 1) return fail(CRENDER_EINVAL, "crender_shadow_shade: H or W is below 1");
+    if (Hl < 1 || Wl < 1) return fail(CRENDER_EINVAL, "crender_shadow_shade: Hl or Wl is below 1");
+    if (y0 < 0 || y1 > H || y0 >= y1) return fail(CRENDER_EINVAL, "crender_shadow_shade: rows outside the frame");
+    if (pcf != 1 && pcf != 3 && pcf != 5) return fail(CRENDER_EINVAL, "crender_shadow_shade: pcf is not 1, 3 or 5");
+    if (!(ambient >= 0.0f && ambient <= 1.0f))
+        return fail(CRENDER_EINVAL, "crender_shadow_shade: ambient outside [0, 1] or NaN");
+    if (!isfinite(bias)) return fail(CRENDER_EINVAL, "crender_shadow_shade: bias is not finite");
+    if (flags) return fail(CRENDER_EINVAL, "crender_shadow_shade: unknown flag bits");
+    if (T == 0) return CRENDER_OK;
+    const ProjConst P = make_proj(P16, W, H);
+    const ShadowMap M{make_proj(PL16, Wl, Hl), d_lz, d_lwinner, Hl, Wl, bias, ambient};
+    const int row_blocks = (y1 - y0 + kShadowBlock - 1) / kShadowBlock;
+    const int across = kShadowBlock * (kThreads / 64);
+    const dim3 grid((unsigned)((W + across - 1) / across), (unsigned)(row_blocks < 65535 ? row_blocks : 65535));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (pcf == 1)
+        launch_shadow<1>(grid, st, d_winner, d_tri, T, d_pos_of, P, d_ltri, M, d_color, W, y0, y1, row_blocks);
+    else if (pcf == 3)
+        launch_shadow<3>(grid, st, d_winner, d_tri, T, d_pos_of, P, d_ltri, M, d_color, W, y0, y1, row_blocks);
+    else
+        launch_shadow<5>(grid, st, d_winner, d_tri, T, d_pos_of, P, d_ltri, M, d_color, W, y0, y1, row_blocks);
+    CR_LAUNCH_CHECK("k_shadow_shade");
+    return CRENDER_OK;
+}
+
+}  // extern "C"

@@ -328,6 +328,7 @@ class AdvancedPixelBufferFiller(DevicePlanes):
         self._fused_light = None       # (l0, l1, l2): illumination fused into cleared frames
         self._texture = None           # (uv [T, 3, 2] float32, image [th, tw, 3] uint8) device tensors: bind_texture
         self._mip = None               # (chain, [(h_k, w_k)], [byte offsets]) of that image: bind_texture(mipmaps=True)
+        self._shadow = None            # (the light's filler, its vertices [T, 3, 3] float32 on the device): bind_shadow_map
         self._plan_light = None        # what the single-stream plan currently holds
         self._pipeline = bool(pipeline)  # render_frame(): overlap consecutive frames (see _FramePipeline)
         if not pipeline_depth:
@@ -850,6 +851,73 @@ class AdvancedPixelBufferFiller(DevicePlanes):
                 None if light is None else self.normals_buffer.data_ptr(), light, self.color_buffer.data_ptr(),
                 self.h, self.w, self.y0, self.y1, flags, *more, self._stream()), name)
         self._host_fresh = False       # views handed out earlier show the textured colours at the next getter call
+
+    def bind_shadow_map(self, light_filler, light_vertices):
+        """Name the shadow map of ``shadow_pass``: `light_filler`, another ``AdvancedPixelBufferFiller`` on the same
+        device (not a swap chain) into which the SAME triangles are rendered from the light, and `light_vertices`
+        float32 [T, 3, 3], numpy or a device tensor, in the caller's triangle order: the vertex array that filler
+        was given to draw (``shadow.light_arrays``).  The binding holds the filler object; its planes are read when
+        the pass runs.  ``bind_shadow_map(None, None)`` drops the binding."""
+        if light_filler is None and light_vertices is None:
+            self._shadow = None
+            return
+        if light_filler is None or light_vertices is None:
+            raise ValueError("bind_shadow_map needs both the light's filler and its vertices (or None, None)")
+        if not isinstance(light_filler, AdvancedPixelBufferFiller):
+            raise ValueError(f"bind_shadow_map: the light's filler must be an AdvancedPixelBufferFiller, "
+                             f"got {type(light_filler).__name__}")
+        if light_filler._pipeline:
+            raise ValueError("bind_shadow_map: the light's filler is a swap chain (pipeline=True): its planes rotate")
+        if light_filler.device != self.device:
+            raise ValueError(f"bind_shadow_map: the light's filler is on {light_filler.device}, this one on {self.device}")
+        self._shadow = (light_filler, _as_device_f32(light_vertices, "light_vertices", self.device))
+
+    def shadow_pass(self, bias=1e-3, pcf=1, ambient=0.25, use_winner=True):
+        """Shadow mapping of the LAST frame's colour plane (``crender_shadow_shade``, include/crender_shadow.h)
+        against the last frame of the filler bound with ``bind_shadow_map``: the surface point every covered pixel
+        shows is carried into the light's frame (perspective-correct) and projected into the light's z plane; the
+        pixel is shadowed where that plane holds something nearer by more than `bias` (in the light's projected z).
+        `pcf` K = 1, 3 or 5 averages the K x K texels around it; a fully shadowed pixel keeps `ambient` of its
+        colour, a fully lit one is not written at all.  With `use_winner` and a light filler that tracks its winner
+        plane, a texel the pixel's own triangle won is lit whatever the depths say, which removes the self-shadowing
+        of a surface on itself without a bias.  Rows of the filler's ``row_strip``, on torch's current stream.
+
+        Both frames are settled first (one stream synchronisation each, as every getter does): a frame whose bin
+        lists overflowed is rendered again, the pass must land on the camera frame that stays and see the light's
+        final z."""
+        if self._pipeline:
+            raise ValueError("shadow_pass is not available on a swap chain (pipeline=True): per-slot passes are not implemented")
+        if self.winner_buffer is None:
+            raise ValueError("shadow_pass needs the winner plane: construct the filler with track_winner=True")
+        if self._shadow is None:
+            raise ValueError("shadow_pass: no shadow map is bound (bind_shadow_map)")
+        light, ltri = self._shadow
+        for who, f in (("the camera's filler", self), ("the light's filler", light)):
+            if f._inputs is None:
+                raise ValueError(f"shadow_pass: no frame has been rendered by {who}")
+            if not (f._last_flags & _capi.FUSED_CLEAR):
+                raise ValueError(f"shadow_pass: the last frame of {who} did not start from cleared buffers (clear=True): "
+                                 "the planes of a composite mix several models")
+        tri = self._inputs[0]
+        T = tri.shape[0]
+        if not ltri.shape[0] == light._inputs[0].shape[0] == T:
+            raise ValueError(f"shadow_pass: {ltri.shape[0]} triangles of light-frame vertices are bound, the light's last "
+                             f"frame drew {light._inputs[0].shape[0]}, the camera's {T}")
+        if isinstance(pcf, bool) or pcf not in _capi.SHADOW_PCF:
+            raise ValueError(f"pcf must be 1, 3 or 5, got {pcf!r}")
+        self._push_host_edits()
+        light._push_host_edits()
+        light._check_bins()            # the map the pass reads is the light's final z
+        self._check_bins()             # nothing pending from here on: no later redo can undo the pass
+        pos_of = None if self._order is None else self._order[1].data_ptr()
+        lwinner = light.winner_buffer if use_winner else None
+        with torch.cuda.device(self.device):
+            _capi.check(self._lib.crender_shadow_shade(
+                self.winner_buffer.data_ptr(), tri.data_ptr() if T else None, T, pos_of, self._P,
+                ltri.data_ptr() if T else None, light._P, light.z_buffer.data_ptr(),
+                None if lwinner is None else lwinner.data_ptr(), light.h, light.w, float(bias), float(ambient), int(pcf),
+                self.color_buffer.data_ptr(), self.h, self.w, self.y0, self.y1, 0, self._stream()), "crender_shadow_shade")
+        self._host_fresh = False       # views handed out earlier show the shadowed colours at the next getter call
 
     def render_frame(self, pipelined=None):
         """One benchmark frame: clear + project + rasterize the resident model

@@ -22,7 +22,7 @@ def _device_form_is_the_same_shading(illumination):
 class Renderer:
     def __init__(self, pixel_buffer_filler, illumination, triangle_iterator_type=None,
                  image_height=512, image_width=512, use_tqdm=True, on_device=None, texture_pass=None,
-                 supersample=None):
+                 shadow=None, supersample=None):
         self.pixel_buffer_filler = pixel_buffer_filler
         self.illumination = illumination
         self.triangle_iterator_type = triangle_iterator_type   # stored, unused (as in Version C)
@@ -63,12 +63,33 @@ class Renderer:
             raise ValueError("Renderer(supersample=...) needs a filler that keeps its planes on the device "
                              "(AdvancedPixelBufferFiller, EdgeOnlyPixelBufferFiller): this one has no resolve()")
         self.supersample = supersample
+        # shadow=None (default): no light is occluded.  A dict of ``filler`` (a second AdvancedPixelBufferFiller, the
+        # light's: its frame is the shadow map), ``R`` and ``t`` (the light's frame, ``shadow.look_at``) and, optionally,
+        # ``bias`` / ``pcf`` / ``ambient`` / ``use_winner`` (AdvancedPixelBufferFiller.shadow_pass's arguments): every
+        # frame starts from cleared buffers (one model per frame, as "fused"), the model is drawn a second time from the
+        # light, and the shadow pass runs on the camera's frame after any texture pass and before the illumination and
+        # the resolve (with on_device="fused" the raster kernel or the texture pass has shaded already: the factors of
+        # light and shadow commute up to rounding, the pass multiplies what it finds).
+        self.shadow = None
+        if shadow is not None:
+            if not hasattr(pixel_buffer_filler, "shadow_pass"):
+                raise ValueError("Renderer(shadow=...) needs a filler with a shadow pass (AdvancedPixelBufferFiller): "
+                                 "this one has no shadow_pass()")
+            missing = [k for k in ("filler", "R", "t") if k not in shadow]
+            if missing:
+                raise ValueError(f"Renderer(shadow=...) needs the keys 'filler', 'R' and 't': {missing} missing")
+            self.shadow = dict(shadow)
 
     def _draw(self, model, light=None, **kw):
-        """``render_model``; with a texture pass, a cleared frame and the pass on top of it."""
+        """``render_model``; with a texture pass or a shadow map, a cleared frame and the passes on top of it."""
         filler = self.pixel_buffer_filler
         if self.texture_pass is None:
-            return filler.render_model(model, **kw)
+            if self.shadow is None:
+                return filler.render_model(model, **kw)
+            if not kw.get("clear"):        # (the "fused" caller asks for the cleared frame itself: its raster kernel shades)
+                filler.set_fused_illumination(None)
+            filler.render_model(model, clear=True, refresh_views=False)
+            return self._cast_shadows(model)
         if self._textured is None or self._textured() is not model:      # once per model, not per frame
             getters = [getattr(model, n, None) for n in ("get_texture_coords_by_triangles", "get_texture")]
             uv, tex = [g() if g is not None else None for g in getters]
@@ -85,6 +106,20 @@ class Renderer:
         filler.set_fused_illumination(None)
         filler.render_model(model, clear=True, refresh_views=False)
         filler.texture_pass(light_direction=light, **self.texture_pass)
+        if self.shadow is not None:
+            self._cast_shadows(model)
+
+    def _cast_shadows(self, model):
+        """The model again, from the light, into the light's filler; then the shadow pass over the camera's frame."""
+        from . import shadow
+        from .pixel_buffer_filler.advanced_pixel_buffer_filler import _model_arrays
+        opts = dict(self.shadow)
+        light_filler, R, t = opts.pop("filler"), opts.pop("R"), opts.pop("t")
+        tri, col, nrm = _model_arrays(model)
+        ltri, lnrm = shadow.light_arrays(tri, nrm, R, t)
+        light_filler.render_arrays(ltri, col, lnrm, clear=True)
+        self.pixel_buffer_filler.bind_shadow_map(light_filler, ltri)
+        self.pixel_buffer_filler.shadow_pass(**opts)
 
     def render(self, model, normalize_model=False, random_colors=True):
         if normalize_model:
@@ -102,7 +137,7 @@ class Renderer:
                 self._draw(model, light=self.illumination.light_direction)
                 return filler.get_color_tensor()
             self.illumination.fuse_into(filler)
-            filler.render_model(model, clear=True)
+            self._draw(model, clear=True)
             return filler.get_color_tensor()
         device_form = getattr(self.illumination, "draw_illumination_device", None)
         if self.on_device is None and not _device_form_is_the_same_shading(self.illumination):
@@ -127,7 +162,7 @@ class Renderer:
                 self._draw(model, light=self.illumination.light_direction)
             else:
                 self.illumination.fuse_into(filler)
-                filler.render_model(model, clear=True)
+                self._draw(model, clear=True)
             return filler.resolve(s)
         light = getattr(self.illumination, "light_direction", None)
         device_form = getattr(self.illumination, "draw_illumination_device", None)
