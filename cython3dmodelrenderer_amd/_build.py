@@ -45,6 +45,10 @@ SSAA_HEADERS = [os.path.join("..", "..", "include", "crender_ssaa.h")]
 # source_sha16() likewise.
 SHADOW_SOURCES = ["shadow.hip"]
 SHADOW_HEADERS = [os.path.join("..", "..", "include", "crender_shadow.h")]
+# chain.hip  the swap chain's shared slot: one slot on the caller's stream (include/crender_chain.h; host code
+# only, over the pipeline handle of plan.h); kept out of source_sha16() likewise: it launches nothing.
+CHAIN_SOURCES = ["chain.hip"]
+CHAIN_HEADERS = [os.path.join("..", "..", "include", "crender_chain.h")]
 
 # Float parity with the reference depends on these (DESIGN.md "Numerics"):
 #   -ffp-contract=off                           no FMA contraction (hipcc defaults to fast)
@@ -93,7 +97,8 @@ def needs_build() -> bool:
     deps = [os.path.join(SRC_DIR, s) for s in SOURCES + HEADERS + WIRE_SOURCES + WIRE_HEADERS +
                                                 PY_SOURCES + PY_HEADERS + TEX_SOURCES + TEX_HEADERS +
                                                 MIP_SOURCES + MIP_HEADERS + ANISO_SOURCES + ANISO_HEADERS +
-                                                SSAA_SOURCES + SSAA_HEADERS + SHADOW_SOURCES + SHADOW_HEADERS] + \
+                                                SSAA_SOURCES + SSAA_HEADERS + SHADOW_SOURCES + SHADOW_HEADERS +
+                                                CHAIN_SOURCES + CHAIN_HEADERS] + \
         [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > built for d in deps)
 
@@ -105,7 +110,7 @@ def compile_library(out: str, extra_flags=(), sources=None, src_dir: str = SRC_D
     import tempfile
     from concurrent.futures import ThreadPoolExecutor
     sources = list(sources or SOURCES + WIRE_SOURCES + PY_SOURCES + TEX_SOURCES + MIP_SOURCES + ANISO_SOURCES +
-                   SSAA_SOURCES + SHADOW_SOURCES)
+                   SSAA_SOURCES + SHADOW_SOURCES + CHAIN_SOURCES)
     err = subprocess.DEVNULL if quiet else None
     with tempfile.TemporaryDirectory(prefix="crender_build_") as tmp:
         objs = [os.path.join(tmp, os.path.splitext(s)[0] + ".o") for s in sources]

@@ -133,6 +133,14 @@ SHADOW_SIGNATURES = {
                                     _i32, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
 }
 
+# the swap chain's shared slot (include/crender_chain.h), bound from a table of its own
+CHAIN_SIGNATURES = {
+    "crender_pipeline_share_stream": (_i32, [_vp, _i32, _vp]),
+    "crender_pipeline_unshare": (_i32, [_vp]),
+    "crender_pipeline_shared_slot": (_i32, [_vp]),
+    "crender_pipeline_owned_streams": (_i32, [_vp]),
+}
+
 _lib = None
 
 
@@ -158,7 +166,8 @@ def load():
     L = C.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(WIRE_SIGNATURES.items()) + \
             list(PY_SIGNATURES.items()) + list(TEX_SIGNATURES.items()) + list(MIP_SIGNATURES.items()) + \
-            list(ANISO_SIGNATURES.items()) + list(SSAA_SIGNATURES.items()) + list(SHADOW_SIGNATURES.items()):
+            list(ANISO_SIGNATURES.items()) + list(SSAA_SIGNATURES.items()) + list(SHADOW_SIGNATURES.items()) + \
+            list(CHAIN_SIGNATURES.items()):
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -132,15 +132,26 @@ class _FramePipeline:
     """Swap chain for ``render_frame`` (``crender_pipeline_*``): frame i renders on the library's
     stream i % depth with plan i % depth into framebuffer set i % depth, so up to `depth` frames
     overlap on the GPU with no event between them (T-Rex 1024^2 on MI355X: 30 / 16 / 12.2 us per
-    frame at depth 1 / 2 / 3, 11.0 at depth 4 with GPU_MAX_HW_QUEUES=8).  Every frame still does all of its work
+    frame at depth 1 / 2 / 3, 11.0 at depth 4 with GPU_MAX_HW_QUEUES=8; today's kernels, K = 200: 8.5 us at depth 3,
+    7.4 at depth 4, profiles/chain/).  Every frame still does all of its work
     (clear + project + bin + rasterize) into a complete framebuffer; the filler's
     ``z_buffer / color_buffer / normals_buffer`` always name the most recently submitted frame's
-    set.  ``join`` orders the caller's stream after all submitted frames."""
+    set.  ``join`` orders the caller's stream after all submitted frames.
 
-    def __init__(self, filler, T, depth=2):
+    ``share`` (``crender_pipeline_share_stream``, include/crender_chain.h): the last slot runs on the CALLER's
+    stream — torch's current stream at the first frame after a join — instead of a stream of the chain's own,
+    so that a chain of 4 is three streams and the caller's: one each of the HIP runtime's default of four
+    hardware queues.  The caller's stream is idle during a burst of frames; what the caller enqueues there
+    later runs behind that slot's frames, which is the order ``join`` asks for anyway.  The same frames, bit
+    for bit."""
+
+    def __init__(self, filler, T, depth=2, share=False):
         self.lib = filler._lib
         self.device = filler.device
         self.depth = int(depth)
+        self.share = bool(share) and self.depth > 1    # (a chain of 1 has no other slot to overlap with)
+        self._shared = None        # the torch stream the last slot runs on: kept alive while it does
+        self._shared_raw = None    # its handle
         self.plans, self.workspaces = [], []
         # look-ahead (crender_pipeline_set_lookahead): a second plan per slot, so that the launch that
         # rasterizes a frame also bins the slot's next one — scenes that fit the direct bins
@@ -183,11 +194,42 @@ class _FramePipeline:
         self._submit = filler._ext.pipeline_submit       # (handle, device index): torch's current stream
         self._handle_int = self.handle.value
         self._index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        if self.share:
+            self._share_current()
+
+    def _share_current(self):
+        """The last slot runs on torch's current stream from here on (no frame is in flight)."""
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            _capi.check(self.lib.crender_pipeline_share_stream(self.handle, self.depth - 1, stream.cuda_stream),
+                        "crender_pipeline_share_stream")
+        self._shared, self._shared_raw = stream, stream.cuda_stream     # (the stream shared before may go now)
+
+    def shared_slot(self):
+        """The slot that runs on the caller's stream, or -1."""
+        return int(self.lib.crender_pipeline_shared_slot(self.handle))
+
+    def owned_streams(self):
+        """How many streams of its own the chain holds (depth, less the shared slot)."""
+        return int(self.lib.crender_pipeline_owned_streams(self.handle))
 
     def close(self):
         if self.handle:
-            self.lib.crender_pipeline_destroy(self.handle)
+            # the library's destroy synchronises and destroys every stream of the chain: the borrowed one
+            # is exchanged for a stream of the chain's own first, ordered behind it
+            try:
+                guard = torch.cuda.device(self.device)
+                guard.__enter__()
+            except Exception:          # (interpreter shutdown: torch may be gone; the handle is freed regardless)
+                guard = None
+            try:
+                self.lib.crender_pipeline_unshare(self.handle)
+                self.lib.crender_pipeline_destroy(self.handle)
+            finally:
+                if guard is not None:
+                    guard.__exit__(None, None, None)
             self.handle = C.c_void_p()
+            self._shared = self._shared_raw = None
         for plan in self.plans:
             self.lib.crender_plan_destroy(plan)
         self.plans = []
@@ -219,6 +261,8 @@ class _FramePipeline:
                 filler._ext.pipeline_bind(self.handle.value, k, tri, col, nrm, filler._P_t, z, c, n, w,
                                           _capi.FUSED_CLEAR | overlapped | guro | want[1])
             self._args = want
+        if self.share and not self.pending and _current_raw_stream(self._index) != self._shared_raw:
+            self._share_current()          # (first frame after a join: the caller has changed streams)
         if _current_device() == self._index:
             self._submit(self._handle_int, self._index)
         else:                              # the library launches on the calling thread's device
@@ -267,7 +311,7 @@ class AdvancedPixelBufferFiller(DevicePlanes):
     def __init__(self, h, w, fov=90.0, z_near=0.1, z_far=1000.0, n_threads=1, *,
                  device=None, tile=0, row_strip=None, track_winner=False, cache_inputs=False,
                  bin_capacity=0, direct_bins=True, pipeline=False, pipeline_depth=None,
-                 presort=None, lookahead=None, raster_path=None):
+                 presort=None, lookahead=None, raster_path=None, share_caller_stream=None):
         self._lib = _capi.load()                      # raises if the HIP library is missing
         self._ext = _torch_ext.load()                 # raises if the torch extension is not built
         if not torch.cuda.is_available():
@@ -331,17 +375,26 @@ class AdvancedPixelBufferFiller(DevicePlanes):
         self._shadow = None            # (the light's filler, its vertices [T, 3, 3] float32 on the device): bind_shadow_map
         self._plan_light = None        # what the single-stream plan currently holds
         self._pipeline = bool(pipeline)  # render_frame(): overlap consecutive frames (see _FramePipeline)
+        # share_caller_stream: the chain's last slot runs on the caller's stream (_FramePipeline).  None = the
+        # rule below, True / False = always / never.  An explicit pipeline_depth shares only when asked.
+        share = False if share_caller_stream is None else bool(share_caller_stream)
         if not pipeline_depth:
-            # measured on MI355X (scripts/ab_depth.sh): three frames in flight, or four for small
-            # frames when the HIP runtime may use more than its default of 4 hardware queues
-            # (GPU_MAX_HW_QUEUES >= 6, read by the runtime when it starts) — with 4 queues a
-            # fourth stream shares a queue with another one and the frames serialise
+            # measured on MI355X (scripts/ab_chain.sh): four frames in flight for frames up to 1024 x 1024, three
+            # for larger ones.  Four streams of the chain's own and the caller's are five, and the HIP runtime
+            # maps them onto 4 hardware queues unless GPU_MAX_HW_QUEUES, read when the runtime starts, says
+            # more: two streams on one queue serialise their frames.  So with fewer than 6 queues (or none
+            # stated) the fourth slot runs on the caller's stream instead: three streams and the caller's,
+            # a queue each.  Without the shared slot such a process gets three frames in flight, as before.
             try:
                 queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
             except ValueError:
                 queues = 4
-            pipeline_depth = 4 if (self.h * self.w <= 1024 * 1024 and queues >= 6) else 3
+            small = self.h * self.w <= 1024 * 1024
+            if share_caller_stream is None:
+                share = small and queues < 6
+            pipeline_depth = 4 if small and (queues >= 6 or share) else 3
         self._pipeline_depth = max(1, min(8, int(pipeline_depth)))   # (1: frames one after another on ONE stream of the chain)
+        self._share_caller_stream = share
         self._pipe = None
         self._checking = False
 
@@ -923,9 +976,11 @@ class AdvancedPixelBufferFiller(DevicePlanes):
         """One benchmark frame: clear + project + rasterize the resident model
         (SURVEY.md section 8d 'one frame').  Inputs must have been set by a previous
         render_model / render_arrays call.  With ``pipeline=True`` (constructor) the filler is
-        a swap chain of ``pipeline_depth`` (3 or 4 by default): consecutive frames render into
-        rotating framebuffer sets on as many streams and overlap on the GPU; the buffer
-        attributes and getters always refer to the most recently submitted frame.
+        a swap chain of ``pipeline_depth`` (4 by default for frames up to 1024 x 1024, else 3): consecutive
+        frames render into rotating framebuffer sets on as many streams and overlap on the GPU; the buffer
+        attributes and getters always refer to the most recently submitted frame.  With
+        ``share_caller_stream`` (the default where the runtime has fewer than 6 hardware queues) the last of
+        those streams is torch's current stream: that slot's frames are ordinary work on it.
 
         What "resident" means: device tensors handed in by the caller are read in place, every frame,
         as they are then.  A model of 2^18 triangles or more (or ``presort=True``) is rendered from a
@@ -981,7 +1036,7 @@ class AdvancedPixelBufferFiller(DevicePlanes):
                 if pipe is not None:
                     torch.cuda.synchronize(self.device)
                     pipe.close()
-                pipe = self._pipe = _FramePipeline(self, T, self._pipeline_depth)
+                pipe = self._pipe = _FramePipeline(self, T, self._pipeline_depth, self._share_caller_stream)
         pipe.frame(self)
         self._host_fresh = False
 
