@@ -1,0 +1,268 @@
+"""Every instance of every deferred pass over the hand-built scenes of tests/pass_edges.py, through the C entry points
+(crender_tex_shade, crender_mip_shade, crender_aniso_shade, crender_shadow_shade) on planes the test allocates itself:
+the rasterizer is not involved, so the kernels meet winners that do not contain their pixel, triangles of no area and
+of 10^13 px^2, corners at z = 2^-43, 2^40 or NaN, and take both sides of every window decision of the shared-reciprocal
+shortcut (tests/test_pass_edges_cpu.py counts them).  Bit for bit against the host models; where a model's colour is
+a NaN the kernel's must be one."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import aniso_ref
+import mip_ref
+import pass_edges as E
+import shadow_ref
+import tex_ref
+from util import assert_bit_equal
+
+pytestmark = pytest.mark.gpu
+
+AMBIENT = 0.25
+ROWS = (5, 77)                       # a strip whose ends are no multiples of 8
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _same(got, want, what):
+    nan = np.isnan(want)
+    assert np.array_equal(np.isnan(got), nan), f"{what}: {int((np.isnan(got) != nan).sum())} pixels differ in NaN-ness"
+    zero = np.float32(0)
+    assert_bit_equal(np.where(nan, zero, got), np.where(nan, zero, want), what)
+
+
+class _Device:
+    """A scene's arrays on the device, and the host copies they must still equal afterwards."""
+
+    def __init__(self, s):
+        self.s = s
+        self.kept = {k: getattr(s, k) for k in ("winner", "tri", "uv", "ltri", "normals", "lz", "lwinner")}
+        for k, v in self.kept.items():
+            setattr(self, k, _dev(v))
+        if hasattr(s, "pos_of"):
+            self.moved, self.pos_of = _dev(s.moved), _dev(s.pos_of.view(np.int32))
+
+    def untouched(self, what):
+        for k, v in self.kept.items():
+            assert_bit_equal(getattr(self, k).cpu().numpy(), v, f"{what}: the pass wrote to {k}")
+
+
+class _Texture:
+    def __init__(self, lib, name, tex):
+        import torch
+        from cython3dmodelrenderer_amd import _capi
+        self.name, self.tex = name, tex
+        self.th, self.tw = tex.shape[:2]
+        self.chain = mip_ref.build_chain(tex)
+        self.d_tex = _dev(tex)
+        self.d_chain = torch.empty(mip_ref.layout(self.th, self.tw)[2], dtype=torch.uint8, device="cuda")
+        _capi.check(lib.crender_mip_build(self.d_tex.data_ptr(), self.th, self.tw, self.d_chain.data_ptr(), _stream()),
+                    "crender_mip_build")
+
+
+def _stream():
+    import torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+SHAPES = {"1x1": (1, 1), "3x1000": (3, 1000), "64x97": (64, 97), "1x65535": (1, 65535), "40000x2": (40000, 2)}
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import torch                     # (before the library: the two then share one HIP runtime, torch's)
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    from cython3dmodelrenderer_amd import _capi
+    return _capi.load()
+
+
+@pytest.fixture(scope="module")
+def textures(lib):
+    rng = np.random.default_rng(20243)
+    return {name: _Texture(lib, name, rng.integers(0, 256, (th, tw, 3), dtype=np.uint8)) for name, (th, tw) in SHAPES.items()}
+
+
+@pytest.fixture(scope="module")
+def edge(oracle):
+    return _Device(E.scene())
+
+
+@pytest.fixture(scope="module")
+def mini(oracle):
+    return _Device(E.mini_scene())
+
+
+@pytest.fixture(scope="module")
+def tall(oracle):
+    return _Device(E.tall_scene())
+
+
+def _light3(oracle):
+    return (C.c_float * 3)(*[float(v) for v in oracle.guro_light(E.LIGHT)])
+
+
+def _texture_family(lib, oracle, D, kind, tx, persp, light, y0=0, y1=None, pos_of=False, bilinear=False, A=1):
+    """(got, want): one call of a texture entry on a fresh copy of the scene's colour plane, and the host model's answer."""
+    from cython3dmodelrenderer_amd import _capi
+    s = D.s
+    y1 = s.H if y1 is None else y1
+    color = _dev(s.color)
+    head = (D.winner.data_ptr(), (D.moved if pos_of else D.tri).data_ptr(), s.T, D.pos_of.data_ptr() if pos_of else None,
+            _capi.f32_16(E.P), D.uv.data_ptr())
+    tail = (D.normals.data_ptr() if light else None, _light3(oracle) if light else None, color.data_ptr(), s.H, s.W, y0, y1)
+    winner = s.winner_without_gone if pos_of else s.winner
+    lit = dict(normals=s.normals, light_direction=E.LIGHT) if light else {}
+    if kind == "tex":
+        flags = (_capi.TEX_PERSPECTIVE if persp else 0) | (_capi.TEX_BILINEAR if bilinear else 0)
+        _capi.check(lib.crender_tex_shade(*head, tx.d_tex.data_ptr(), tx.th, tx.tw, *tail, flags, _stream()), "crender_tex_shade")
+        want = tex_ref.texture_pass(s.color, winner, s.tri, E.P, s.uv, tx.tex, persp, bilinear, y0=y0, y1=y1, **lit)
+    elif kind == "mip":
+        _capi.check(lib.crender_mip_shade(*head, tx.d_chain.data_ptr(), tx.th, tx.tw, *tail, _capi.MIP_PERSPECTIVE if persp else 0,
+                                          _stream()), "crender_mip_shade")
+        want = mip_ref.texture_pass(s.color, winner, s.tri, E.P, s.uv, None, persp, y0=y0, y1=y1, chain=tx.chain, **lit)
+    else:
+        _capi.check(lib.crender_aniso_shade(*head, tx.d_chain.data_ptr(), tx.th, tx.tw, *tail, _capi.MIP_PERSPECTIVE if persp else 0,
+                                            A, _stream()), "crender_aniso_shade")
+        want = aniso_ref.texture_pass(s.color, winner, s.tri, E.P, s.uv, None, persp, A, y0=y0, y1=y1, chain=tx.chain, **lit)
+    return color.cpu().numpy(), want
+
+
+def _every_variant(lib, oracle, D, textures, kind, what, **kw):
+    """The whole frame under every texture, then a strip of rows and d_pos_of under the 64 x 97 one."""
+    changed = 0
+    for tx in textures.values():
+        got, want = _texture_family(lib, oracle, D, kind, tx, **kw)
+        _same(got, want, f"{what}, texture {tx.name}")
+        changed += int((want.view(np.uint32) != D.s.color.view(np.uint32)).any(2).sum())
+    assert changed > 5 * 5000
+    tx = textures["64x97"]
+    y0, y1 = ROWS
+    got, want = _texture_family(lib, oracle, D, kind, tx, y0=y0, y1=y1, **kw)
+    assert_bit_equal(got[:y0], D.s.color[:y0], f"{what}: rows above the strip")
+    assert_bit_equal(got[y1:], D.s.color[y1:], f"{what}: rows below the strip")
+    _same(got, want, f"{what}, rows {y0} .. {y1}")
+    got, want = _texture_family(lib, oracle, D, kind, tx, pos_of=True, **kw)
+    _same(got, want, f"{what}, d_pos_of")
+    gone = D.s.winner == D.s.gone
+    if not kw["light"]:
+        assert_bit_equal(got[gone], D.s.color[gone], f"{what}: a triangle d_pos_of sends beyond T is background")
+    D.untouched(what)
+
+
+# ---- crender_mip_build -----------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", list(SHAPES))
+def test_mip_build_matches_the_model(textures, name):
+    tx = textures[name]
+    assert len(tx.chain) == {"1x1": 1, "3x1000": 10, "64x97": 7, "1x65535": 16, "40000x2": 16}[name]
+    assert_bit_equal(tx.d_chain.cpu().numpy(), mip_ref.pack_chain(tx.chain), f"the chain of a {name} texture")
+    assert_bit_equal(tx.d_tex.cpu().numpy(), tx.tex, "the texture is only read")
+
+
+# ---- the edge scene ----------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("light", [False, True])
+@pytest.mark.parametrize("bilinear", [False, True])
+@pytest.mark.parametrize("persp", [False, True])
+def test_tex_shade_every_instance(lib, oracle, edge, textures, persp, bilinear, light):
+    _every_variant(lib, oracle, edge, textures, "tex", f"tex persp={persp} bilinear={bilinear} light={light}",
+                   persp=persp, bilinear=bilinear, light=light)
+
+
+@pytest.mark.parametrize("light", [False, True])
+@pytest.mark.parametrize("persp", [False, True])
+def test_mip_shade_every_instance(lib, oracle, edge, textures, persp, light):
+    _every_variant(lib, oracle, edge, textures, "mip", f"mip persp={persp} light={light}", persp=persp, light=light)
+
+
+@pytest.mark.parametrize("light", [False, True])
+@pytest.mark.parametrize("A", [1, 2, 3, 4, 16])
+@pytest.mark.parametrize("persp", [False, True])
+def test_aniso_shade_every_instance(lib, oracle, edge, textures, persp, A, light):
+    _every_variant(lib, oracle, edge, textures, "aniso", f"aniso persp={persp} A={A} light={light}", persp=persp, A=A, light=light)
+    if A == 1:
+        for tx in textures.values():
+            a, _ = _texture_family(lib, oracle, edge, "aniso", tx, persp=persp, light=light, A=1)
+            m, _ = _texture_family(lib, oracle, edge, "mip", tx, persp=persp, light=light)
+            _same(a, m, f"max_aniso = 1 against crender_mip_shade, persp={persp} light={light}, texture {tx.name}")
+
+
+def _shadow(lib, D, K, use_winner, y0=0, y1=None, pos_of=False, ambient=AMBIENT):
+    from cython3dmodelrenderer_amd import _capi
+    s = D.s
+    y1 = s.H if y1 is None else y1
+    color = _dev(s.color)
+    Hl, Wl = s.lz.shape
+    _capi.check(lib.crender_shadow_shade(
+        D.winner.data_ptr(), (D.moved if pos_of else D.tri).data_ptr(), s.T, D.pos_of.data_ptr() if pos_of else None,
+        _capi.f32_16(E.P), D.ltri.data_ptr(), _capi.f32_16(E.P), D.lz.data_ptr(), D.lwinner.data_ptr() if use_winner else None,
+        Hl, Wl, E.BIAS, ambient, K, color.data_ptr(), s.H, s.W, y0, y1, 0, _stream()), "crender_shadow_shade")
+    want = shadow_ref.shadow_pass(s.color, s.winner_without_gone if pos_of else s.winner, s.tri, E.P, s.ltri, E.P, s.lz,
+                                  s.lwinner if use_winner else None, bias=E.BIAS, ambient=ambient, pcf=K, y0=y0, y1=y1)
+    return color.cpu().numpy(), want
+
+
+@pytest.mark.parametrize("use_winner", [False, True])
+@pytest.mark.parametrize("K", [1, 3, 5])
+def test_shadow_shade_every_instance(lib, oracle, edge, K, use_winner):
+    what = f"shadow K={K} use_winner={use_winner}"
+    s = edge.s
+    got, want = _shadow(lib, edge, K, use_winner)
+    assert not np.isnan(want).any()                  # every NaN is lit: none reaches the colours
+    _same(got, want, what)
+    assert (want.view(np.uint32) != s.color.view(np.uint32)).any(2).sum() > 500
+    y0, y1 = ROWS
+    got, want = _shadow(lib, edge, K, use_winner, y0=y0, y1=y1)
+    assert_bit_equal(got[:y0], s.color[:y0], f"{what}: rows above the strip")
+    assert_bit_equal(got[y1:], s.color[y1:], f"{what}: rows below the strip")
+    _same(got, want, f"{what}, rows {y0} .. {y1}")
+    got, want = _shadow(lib, edge, K, use_winner, pos_of=True)
+    _same(got, want, f"{what}, d_pos_of")
+    gone = s.winner == s.gone
+    assert_bit_equal(got[gone], s.color[gone], f"{what}: a triangle d_pos_of sends beyond T is background")
+    for ambient in (0.0, 1.0):
+        got, want = _shadow(lib, edge, K, use_winner, ambient=ambient)
+        _same(got, want, f"{what}, ambient {ambient}")
+    edge.untouched(what)
+
+
+# ---- the small frame: denominators under the window that are not zero ------------------------------------------------------
+
+@pytest.mark.parametrize("kind,kw", [("tex", dict(persp=True, bilinear=True, light=False)), ("tex", dict(persp=False, bilinear=False, light=True)),
+                                     ("mip", dict(persp=True, light=False)), ("mip", dict(persp=False, light=True)),
+                                     ("aniso", dict(persp=True, A=16, light=True)), ("aniso", dict(persp=False, A=4, light=False))])
+def test_the_small_frame(lib, oracle, mini, textures, kind, kw):
+    for name in ("64x97", "3x1000"):
+        got, want = _texture_family(lib, oracle, mini, kind, textures[name], **kw)
+        _same(got, want, f"28 x 20, {kind} {kw}, texture {name}")
+    mini.untouched(f"28 x 20, {kind}")
+
+
+def test_the_small_frame_shadowed(lib, oracle, mini):
+    for K, use_winner in ((1, True), (3, False), (5, True)):
+        got, want = _shadow(lib, mini, K, use_winner)
+        _same(got, want, f"28 x 20, shadow K={K} use_winner={use_winner}")
+
+
+# ---- the tall frame: the row-block loop's second trip --------------------------------------------------------------------
+
+@pytest.mark.parametrize("kind", ["tex", "mip", "aniso", "shadow"])
+def test_more_row_blocks_than_the_grid_is_tall(lib, oracle, tall, textures, kind):
+    """H = 524 296, W = 3, rows 3 .. H: 65 537 blocks of 8 rows against a grid of 65 535, so the last sixteen rows are
+    the loop's second trip.  No plan can be that tall: only the entry reaches it.  The texture families run with the
+    light, which touches every pixel of the rows."""
+    s = tall.s
+    y0 = E.TALL_Y0
+    if kind == "shadow":
+        got, want = _shadow(lib, tall, 3, True, y0=y0)
+    else:
+        kw = dict(tex=dict(persp=True, bilinear=True), mip=dict(persp=True), aniso=dict(persp=True, A=4))[kind]
+        got, want = _texture_family(lib, oracle, tall, kind, textures["64x97"], light=True, y0=y0, **kw)
+    assert_bit_equal(got[:y0], s.color[:y0], f"tall frame, {kind}: rows above y0")
+    last = slice(E.TALL_H - 16, E.TALL_H)
+    assert (want[last].view(np.uint32) != s.color[last].view(np.uint32)).any(), "the second trip's rows change"
+    _same(got[last], want[last], f"tall frame, {kind}: the second trip's rows")
+    _same(got, want, f"tall frame, {kind}")
