@@ -45,6 +45,10 @@ SSAA_HEADERS = [os.path.join("..", "..", "include", "crender_ssaa.h")]
 # source_sha16() likewise.
 SHADOW_SOURCES = ["shadow.hip"]
 SHADOW_HEADERS = [os.path.join("..", "..", "include", "crender_shadow.h")]
+# winner_pass.h  what the four deferred passes over the winner plane share (texture.hip, texmip.hip, texaniso.hip,
+# shadow.hip): the pixel frame, the corner gather, the store with the fused light, the texel fetches and the launch
+# geometry; a group of its own, so that each pass's header list stays its own; kept out of source_sha16() likewise.
+PASS_HEADERS = ["winner_pass.h"]
 # chain.hip  the swap chain's shared slot: one slot on the caller's stream (include/crender_chain.h; host code
 # only, over the pipeline handle of plan.h); kept out of source_sha16() likewise: it launches nothing.
 CHAIN_SOURCES = ["chain.hip"]
@@ -98,7 +102,7 @@ def needs_build() -> bool:
                                                 PY_SOURCES + PY_HEADERS + TEX_SOURCES + TEX_HEADERS +
                                                 MIP_SOURCES + MIP_HEADERS + ANISO_SOURCES + ANISO_HEADERS +
                                                 SSAA_SOURCES + SSAA_HEADERS + SHADOW_SOURCES + SHADOW_HEADERS +
-                                                CHAIN_SOURCES + CHAIN_HEADERS] + \
+                                                CHAIN_SOURCES + CHAIN_HEADERS + PASS_HEADERS] + \
         [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > built for d in deps)
 

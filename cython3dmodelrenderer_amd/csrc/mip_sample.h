@@ -1,12 +1,12 @@
 // mip_sample.h — what the two texture passes over a mip chain share (texmip.hip: trilinear; texaniso.hip:
-// anisotropic): the chain's layout, one bilinear sample of a level, and (u, v) of an integer pixel through
-// raster_math.h's TriSetup.  Each translation unit gets its own copy (anonymous namespace); include after
-// common.h and crender_mip.h.
+// anisotropic): the chain's layout, the level of a footprint, and (u, v) of a pixel and of its two neighbours through
+// raster_math.h's TriSetup.  The block constant, host_f32_to_i32, texel and bilinear are not here: every pass over
+// the winner plane needs them, so they are winner_pass.h's.  Each translation unit gets its own copy (anonymous
+// namespace); include after common.h, crender_mip.h and winner_pass.h.
 #pragma once
 
 namespace {
 
-constexpr int kTexBlock = 8;         // pixels along each side of a wavefront's block
 constexpr int kMaxLevels = CRENDER_MIP_MAX_LEVELS;
 
 // Where each level starts in the chain, by value in the kernel's arguments; a level's height and width are
@@ -35,32 +35,31 @@ bool chain_layout(int th, int tw, int &L, int h[kMaxLevels], int w[kMaxLevels], 
     return true;
 }
 
-// The host's truncating float -> int32 conversion (cvttss2si): INT_MIN for a NaN and out of range.
-// (Restated from model_ops.hip, whose text is fingerprinted, as texture.hip restates it.)
-CR_DEV int host_f32_to_i32(float f)
+// The chain of a th x tw texture for a kernel's arguments; false for a texture crender_mip_layout refuses.
+inline bool mip_chain(int th, int tw, MipChain &M)
 {
-    return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : (int)0x80000000;
+    int h[kMaxLevels], w[kMaxLevels];
+    unsigned long long total;
+    M.th = th;
+    M.tw = tw;
+    return chain_layout(th, tw, M.L, h, w, M.off, total);
 }
 
-CR_DEV const unsigned char *texel(const unsigned char *__restrict__ tex, int row, int colm, int tw)
+// The lower level l0 and the weight f of the one above it for a footprint of rho texels, of a chain of L levels.
+CR_DEV void mip_level(float rho, int L, int &l0, float &f)
 {
-    return tex + ((size_t)row * (size_t)tw + (size_t)colm) * 3;
-}
-
-// The Bilinear statement of crender_tex.h on one level (texture.hip's operation order).
-CR_DEV void bilinear(const unsigned char *__restrict__ tex, int th, int tw, float tu, float tv, float c[3])
-{
-    const float fx = tu * (float)tw - 0.5f, fy = (1.0f - tv) * (float)th - 0.5f;
-    const float x0 = floorf(fx), yf0 = floorf(fy);
-    const float ax = fx - x0, ay = fy - yf0;
-    const int cl = clipi(host_f32_to_i32(x0), 0, tw - 1), cr = clipi(host_f32_to_i32(x0 + 1.0f), 0, tw - 1);
-    const int rt = clipi(host_f32_to_i32(yf0), 0, th - 1), rbm = clipi(host_f32_to_i32(yf0 + 1.0f), 0, th - 1);
-    const unsigned char *t00 = texel(tex, rt, cl, tw), *t01 = texel(tex, rt, cr, tw);
-    const unsigned char *t10 = texel(tex, rbm, cl, tw), *t11 = texel(tex, rbm, cr, tw);
-    const float wx = 1.0f - ax, wy = 1.0f - ay;
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-        c[j] = ((float)t00[j] * wx + (float)t01[j] * ax) * wy + ((float)t10[j] * wx + (float)t11[j] * ax) * ay;
+    l0 = 0;
+    f = 0.0f;
+    if (rho > 1.0f) {
+        if (!(rho < (float)(1u << (L - 1)))) {
+            l0 = L - 1;
+        } else {
+            // 1 < rho < 2^15: a normal number whose exponent field is the level, and whose
+            // significand, scaled back by the exact power of two, is 1 + f
+            l0 = (int)(__float_as_uint(rho) >> 23) - 127;
+            f = rho * __uint_as_float((uint32_t)(127 - l0) << 23) - 1.0f;
+        }
+    }
 }
 
 struct CornerUV {
@@ -102,6 +101,34 @@ CR_DEV void uv_at(const TriSetup &S, const CornerUV &k, int X, int Y, float &tu,
         tu = interp(k.u0, k.u1, k.u2, b1, b2, b3);
         tv = interp(k.v0, k.v1, k.v2, b1, b2, b3);
     }
+}
+
+// (u, v) of a covered pixel and of its right and lower neighbours: the winner projected once, one TriSetup for the three.
+struct PixelUV {
+    float tu, tv, ux, vx, uy, vy;
+};
+
+template <bool PERSPECTIVE>
+CR_DEV PixelUV pixel_uv(const ProjConst &P, const float *__restrict__ tri, const float *__restrict__ uv,
+                        const WinnerPixel &p)
+{
+    float a[3], b[3], c[3];
+    gather_corners(tri, p.t, a, b, c);
+    const float *w = uv + p.orig * 6;
+    CornerUV K{w[0], w[1], w[2], w[3], w[4], w[5], a[2], b[2], c[2], 0.0f, 0.0f, 0.0f, false};
+    if (PERSPECTIVE && in_div_window(K.za) && in_div_window(K.zb) && in_div_window(K.zc)) {
+        K.ra = refined_rcp(K.za); K.rb = refined_rcp(K.zb); K.rc = refined_rcp(K.zc);
+        K.z_fast = true;
+    }
+    project_vertex(P, a);
+    project_vertex(P, b);
+    project_vertex(P, c);
+    const TriSetup S = make_setup(TriXYZ{a[0], a[1], a[2], b[0], b[1], b[2], c[0], c[1], c[2]}, true);
+    PixelUV r;
+    uv_at<PERSPECTIVE>(S, K, p.x, p.y, r.tu, r.tv);
+    uv_at<PERSPECTIVE>(S, K, p.x + 1, p.y, r.ux, r.vx);
+    uv_at<PERSPECTIVE>(S, K, p.x, p.y + 1, r.uy, r.vy);
+    return r;
 }
 
 }  // namespace

@@ -17,16 +17,9 @@
 
 using namespace crender_detail;
 
+#include "winner_pass.h"     // WinnerPixel, gather_corners, host_f32_to_i32, pass_grid
+
 namespace {
-
-constexpr int kShadowBlock = 8;      // pixels along each side of a wavefront's block
-
-// The host's truncating float -> int32 conversion (cvttss2si): INT_MIN for a NaN and out of range.
-// (Restated from model_ops.hip, whose text is fingerprinted.)
-CR_DEV int host_f32_to_i32(float f)
-{
-    return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : (int)0x80000000;
-}
 
 // What the kernel needs of the light's frame.
 struct ShadowMap {
@@ -44,34 +37,20 @@ __global__ __launch_bounds__(kThreads) void k_shadow_shade(const int32_t *__rest
                                                             float *__restrict__ cb, int W, int y0, int y1, int row_blocks)
 {
     constexpr int R = (K - 1) / 2;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int x = ((int)blockIdx.x * (kThreads / 64) + wave) * kShadowBlock + (lane & (kShadowBlock - 1));
     for (int rb = blockIdx.y; rb < row_blocks; rb += gridDim.y) {
-        const int y = y0 + rb * kShadowBlock + (lane >> 3);
-        const bool inside = x < W && y < y1;
-        const size_t pix = (size_t)y * (size_t)W + (size_t)x;
-        int64_t orig = -1;           // the winner in the caller's order (ltri, the light's winners), and where it sits in d_tri
-        if (inside) orig = win[pix];
-        bool covered = orig >= 0 && orig < T;
-        int64_t t = orig;
-        if (covered && pos_of) {
-            t = pos_of[orig];
-            covered = t < T;
-        }
-        if (!wave_any(covered)) continue;           // a scalar branch: the whole wavefront leaves
-        if (!covered) continue;
+        const WinnerPixel px = winner_pixel(win, T, pos_of, W, y0, y1, rb);
+        if (!wave_any(px.covered)) continue;        // a scalar branch: the whole wavefront leaves
+        if (!px.covered) continue;
+        const int64_t orig = px.orig;               // the winner in the caller's order: ltri, the light's winners
         float a[3], b[3], c[3];
-        const float *v = tri + t * 9;
-        a[0] = v[0]; a[1] = v[1]; a[2] = v[2];
-        b[0] = v[3]; b[1] = v[4]; b[2] = v[5];
-        c[0] = v[6]; c[1] = v[7]; c[2] = v[8];
+        gather_corners(tri, px.t, a, b, c);
         const float za = a[2], zb = b[2], zc = c[2];
         project_vertex(P, a);
         project_vertex(P, b);
         project_vertex(P, c);
         const TriXYZ X{a[0], a[1], a[2], b[0], b[1], b[2], c[0], c[1], c[2]};
         float b1, b2, b3;
-        barycentric(X, x, y, b1, b2, b3);
+        barycentric(X, px.x, px.y, b1, b2, b3);
         const float q1 = b1 / za, q2 = b2 / zb, q3 = b3 / zc;
         const float s = (q1 + q2) + q3;
         const float *l = ltri + orig * 9;
@@ -109,24 +88,11 @@ __global__ __launch_bounds__(kThreads) void k_shadow_shade(const int32_t *__rest
         const float om = 1.0f - M.ambient;
         const float m = om * frac;
         const float f = M.ambient + m;
-        float *cp = cb + pix * 3;
+        float *cp = cb + px.pix * 3;
         cp[0] = cp[0] * f;
         cp[1] = cp[1] * f;
         cp[2] = cp[2] * f;
     }
-}
-
-template <int K>
-void launch_shadow(dim3 grid, hipStream_t st, const int32_t *win, const float *tri, int64_t T, const uint32_t *pos_of,
-                   const ProjConst &P, const float *ltri, const ShadowMap &M, float *cb, int W, int y0, int y1,
-                   int row_blocks)
-{
-    if (M.winner)
-        hipLaunchKernelGGL((k_shadow_shade<K, true>), grid, dim3(kThreads), 0, st, win, tri, T, pos_of, P, ltri, M, cb,
-                           W, y0, y1, row_blocks);
-    else
-        hipLaunchKernelGGL((k_shadow_shade<K, false>), grid, dim3(kThreads), 0, st, win, tri, T, pos_of, P, ltri, M, cb,
-                           W, y0, y1, row_blocks);
 }
 
 }  // namespace
@@ -151,18 +117,16 @@ int crender_shadow_shade(const int32_t *d_winner, const float *d_tri, int64_t T,
     if (!isfinite(bias)) return fail(CRENDER_EINVAL, "crender_shadow_shade: bias is not finite");
     if (flags) return fail(CRENDER_EINVAL, "crender_shadow_shade: unknown flag bits");
     if (T == 0) return CRENDER_OK;
-    const ProjConst P = make_proj(P16, W, H);
     const ShadowMap M{make_proj(PL16, Wl, Hl), d_lz, d_lwinner, Hl, Wl, bias, ambient};
-    const int row_blocks = (y1 - y0 + kShadowBlock - 1) / kShadowBlock;
-    const int across = kShadowBlock * (kThreads / 64);
-    const dim3 grid((unsigned)((W + across - 1) / across), (unsigned)(row_blocks < 65535 ? row_blocks : 65535));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (pcf == 1)
-        launch_shadow<1>(grid, st, d_winner, d_tri, T, d_pos_of, P, d_ltri, M, d_color, W, y0, y1, row_blocks);
-    else if (pcf == 3)
-        launch_shadow<3>(grid, st, d_winner, d_tri, T, d_pos_of, P, d_ltri, M, d_color, W, y0, y1, row_blocks);
-    else
-        launch_shadow<5>(grid, st, d_winner, d_tri, T, d_pos_of, P, d_ltri, M, d_color, W, y0, y1, row_blocks);
+    // [pcf / 2][the light's winner plane given]
+    static constexpr decltype(&k_shadow_shade<1, false>) kernels[3][2] = {
+        {k_shadow_shade<1, false>, k_shadow_shade<1, true>},
+        {k_shadow_shade<3, false>, k_shadow_shade<3, true>},
+        {k_shadow_shade<5, false>, k_shadow_shade<5, true>}};
+    const PassGrid G = pass_grid(W, y0, y1);
+    hipLaunchKernelGGL(kernels[pcf / 2][d_lwinner != nullptr], G.grid, dim3(kThreads), 0,
+                       static_cast<hipStream_t>(stream), d_winner, d_tri, T, d_pos_of, make_proj(P16, W, H), d_ltri, M,
+                       d_color, W, y0, y1, G.row_blocks);
     CR_LAUNCH_CHECK("k_shadow_shade");
     return CRENDER_OK;
 }

@@ -22,7 +22,8 @@
 
 using namespace crender_detail;
 
-#include "mip_sample.h"      // chain_layout, MipChain, bilinear, CornerUV, uv_at
+#include "winner_pass.h"     // WinnerPixel, bilinear, store_shaded, pass_grid
+#include "mip_sample.h"      // MipChain, mip_chain, mip_level, pixel_uv
 
 namespace {
 
@@ -35,44 +36,15 @@ __global__ __launch_bounds__(kThreads) void k_aniso_shade(const int32_t *__restr
                                                            float *__restrict__ cb, int W, int y0, int y1, int row_blocks,
                                                            int A)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int x = ((int)blockIdx.x * (kThreads / 64) + wave) * kTexBlock + (lane & (kTexBlock - 1));
     for (int rb = blockIdx.y; rb < row_blocks; rb += gridDim.y) {
-        const int y = y0 + rb * kTexBlock + (lane >> 3);
-        const bool inside = x < W && y < y1;
-        const size_t pix = (size_t)y * (size_t)W + (size_t)x;
-        int64_t orig = -1;           // the winner in the caller's order (uv), and where it sits in d_tri
-        if (inside) orig = win[pix];
-        bool covered = orig >= 0 && orig < T;
-        int64_t t = orig;
-        if (covered && pos_of) {
-            t = pos_of[orig];
-            covered = t < T;
-        }
-        if (!LIGHT && !wave_any(covered)) continue;
+        const WinnerPixel px = winner_pixel(win, T, pos_of, W, y0, y1, rb);
+        if (!LIGHT && !wave_any(px.covered)) continue;
         float col[3] = {0.0f, 0.0f, 0.0f};
-        if (covered) {
-            float a[3], b[3], c[3];
-            const float *v = tri + t * 9;
-            a[0] = v[0]; a[1] = v[1]; a[2] = v[2];
-            b[0] = v[3]; b[1] = v[4]; b[2] = v[5];
-            c[0] = v[6]; c[1] = v[7]; c[2] = v[8];
-            const float *w = uv + orig * 6;
-            CornerUV K{w[0], w[1], w[2], w[3], w[4], w[5], a[2], b[2], c[2], 0.0f, 0.0f, 0.0f, false};
-            if (PERSPECTIVE && in_div_window(K.za) && in_div_window(K.zb) && in_div_window(K.zc)) {
-                K.ra = refined_rcp(K.za); K.rb = refined_rcp(K.zb); K.rc = refined_rcp(K.zc);
-                K.z_fast = true;
-            }
-            project_vertex(P, a);
-            project_vertex(P, b);
-            project_vertex(P, c);
-            const TriSetup S = make_setup(TriXYZ{a[0], a[1], a[2], b[0], b[1], b[2], c[0], c[1], c[2]}, true);
-            float tu, tv, ux, vx, uy, vy;
-            uv_at<PERSPECTIVE>(S, K, x, y, tu, tv);
-            uv_at<PERSPECTIVE>(S, K, x + 1, y, ux, vx);
-            uv_at<PERSPECTIVE>(S, K, x, y + 1, uy, vy);
+        if (px.covered) {
+            const PixelUV at = pixel_uv<PERSPECTIVE>(P, tri, uv, px);
+            const float tu = at.tu, tv = at.tv;
             const float ftw = (float)M.tw, fth = (float)M.th;
-            const float dux = ux - tu, dvx = vx - tv, duy = uy - tu, dvy = vy - tv;
+            const float dux = at.ux - tu, dvx = at.vx - tv, duy = at.uy - tu, dvy = at.vy - tv;
             const float dudx = dux * ftw, dvdx = dvx * fth;
             const float dudy = duy * ftw, dvdy = dvy * fth;
             const float rx = dudx * dudx + dvdx * dvdx;
@@ -94,17 +66,9 @@ __global__ __launch_bounds__(kThreads) void k_aniso_shade(const int32_t *__restr
                     N = (nf < fa) ? (int)nf : A;
                 }
             }
-            int l0 = 0;
-            float f = 0.0f;
-            if (rho > 1.0f) {
-                if (!(rho < (float)(1u << (M.L - 1)))) {
-                    l0 = M.L - 1;
-                } else {
-                    // 1 < rho < 2^15: the exponent field is the level, the scaled significand is 1 + f (texmip.hip)
-                    l0 = (int)(__float_as_uint(rho) >> 23) - 127;
-                    f = rho * __uint_as_float((uint32_t)(127 - l0) << 23) - 1.0f;
-                }
-            }
+            int l0;
+            float f;
+            mip_level(rho, M.L, l0, f);
             const int hl = max(1, M.th >> l0), wl = max(1, M.tw >> l0);
             const unsigned char *lower = chain + (l0 ? M.off[l0] : 0ull);       // (level 0 needs no look at the table)
             const bool two = f != 0.0f;      // (only between two levels: l0 + 1 <= L - 1)
@@ -135,32 +99,8 @@ __global__ __launch_bounds__(kThreads) void k_aniso_shade(const int32_t *__restr
                 for (int j = 0; j < 3; ++j) col[j] = col[j] / fn;
             }
         }
-        if (LIGHT) {
-            if (!inside) continue;
-            float *cp = cb + pix * 3;
-            const float *np_ = nb + pix * 3;
-            if (!covered) { col[0] = cp[0]; col[1] = cp[1]; col[2] = cp[2]; }
-            const float s = guro_factor(L, np_[0], np_[1], np_[2]);
-            cp[0] = col[0] * s; cp[1] = col[1] * s; cp[2] = col[2] * s;
-        } else if (covered) {
-            float *cp = cb + pix * 3;
-            cp[0] = col[0]; cp[1] = col[1]; cp[2] = col[2];
-        }
+        store_shaded<LIGHT>(px, col, nb, L, cb);
     }
-}
-
-template <bool PERSPECTIVE>
-void launch_aniso(bool light, dim3 grid, hipStream_t st, const int32_t *win, const float *tri, int64_t T,
-                  const uint32_t *pos_of, const ProjConst &P, const float *uv, const unsigned char *chain,
-                  const MipChain &M, const float *nb, const Light &L, float *cb, int W, int y0, int y1, int row_blocks,
-                  int A)
-{
-    if (light)
-        hipLaunchKernelGGL((k_aniso_shade<PERSPECTIVE, true>), grid, dim3(kThreads), 0, st, win, tri, T, pos_of, P, uv,
-                           chain, M, nb, L, cb, W, y0, y1, row_blocks, A);
-    else
-        hipLaunchKernelGGL((k_aniso_shade<PERSPECTIVE, false>), grid, dim3(kThreads), 0, st, win, tri, T, pos_of, P, uv,
-                           chain, M, nb, L, cb, W, y0, y1, row_blocks, A);
 }
 
 }  // namespace
@@ -173,29 +113,20 @@ int crender_aniso_shade(const int32_t *d_winner, const float *d_tri, int64_t T, 
                         unsigned flags, int max_aniso, void *stream)
 {
     MipChain M;
-    int h[kMaxLevels], w[kMaxLevels];
-    unsigned long long total;
-    if (!d_winner || !P16 || !d_chain || !d_color || T < 0 || (T > 0 && (!d_tri || !d_uv)) ||
-        !chain_layout(th, tw, M.L, h, w, M.off, total) || H < 1 || W < 1 || y0 < 0 || y1 > H || y0 >= y1 ||
-        (light3 && !d_normal) || (d_normal && !light3) || (flags & ~(unsigned)CRENDER_MIP_PERSPECTIVE) ||
+    if (!frame_args_ok(d_winner, P16, d_color, T, d_tri, H, W, y0, y1) || !d_chain || (T > 0 && !d_uv) ||
+        !mip_chain(th, tw, M) || !light_args_ok(light3, d_normal) || (flags & ~(unsigned)CRENDER_MIP_PERSPECTIVE) ||
         max_aniso < 1 || max_aniso > CRENDER_ANISO_MAX)
         return fail(CRENDER_EINVAL, "crender_aniso_shade: bad argument");
-    M.th = th;
-    M.tw = tw;
     const bool light = light3 != nullptr;
     if (T == 0 && !light) return CRENDER_OK;
-    const ProjConst P = make_proj(P16, W, H);
-    const Light L = light ? Light{light3[0], light3[1], light3[2], 1} : Light{0.0f, 0.0f, 0.0f, 0};
-    const int row_blocks = (y1 - y0 + kTexBlock - 1) / kTexBlock;
-    const int across = kTexBlock * (kThreads / 64);
-    const dim3 grid((unsigned)((W + across - 1) / across), (unsigned)(row_blocks < 65535 ? row_blocks : 65535));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (flags & CRENDER_MIP_PERSPECTIVE)
-        launch_aniso<true>(light, grid, st, d_winner, d_tri, T, d_pos_of, P, d_uv, d_chain, M, d_normal, L, d_color, W,
-                           y0, y1, row_blocks, max_aniso);
-    else
-        launch_aniso<false>(light, grid, st, d_winner, d_tri, T, d_pos_of, P, d_uv, d_chain, M, d_normal, L, d_color, W,
-                            y0, y1, row_blocks, max_aniso);
+    const bool persp = flags & CRENDER_MIP_PERSPECTIVE;
+    // [perspective][light]
+    static constexpr decltype(&k_aniso_shade<false, false>) kernels[2][2] = {
+        {k_aniso_shade<false, false>, k_aniso_shade<false, true>}, {k_aniso_shade<true, false>, k_aniso_shade<true, true>}};
+    const PassGrid G = pass_grid(W, y0, y1);
+    hipLaunchKernelGGL(kernels[persp][light], G.grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), d_winner,
+                       d_tri, T, d_pos_of, make_proj(P16, W, H), d_uv, d_chain, M, d_normal, pass_light(light3),
+                       d_color, W, y0, y1, G.row_blocks, max_aniso);
     CR_LAUNCH_CHECK("k_aniso_shade");
     return CRENDER_OK;
 }
