@@ -133,6 +133,14 @@ SHADOW_SIGNATURES = {
                                     _i32, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
 }
 
+# the deferred Phong pass (include/crender_phong.h), bound from a table of its own
+PHONG_MAX_LIGHTS = 4
+PHONG_MAX_SHININESS = 1 << 12
+PHONG_SIGNATURES = {
+    "crender_phong_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _f32p, _i32, _u32, C.c_float, _i32, _f32p, C.c_float,
+                                   _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
+}
+
 # the swap chain's shared slot (include/crender_chain.h), bound from a table of its own
 CHAIN_SIGNATURES = {
     "crender_pipeline_share_stream": (_i32, [_vp, _i32, _vp]),
@@ -167,7 +175,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(WIRE_SIGNATURES.items()) + \
             list(PY_SIGNATURES.items()) + list(TEX_SIGNATURES.items()) + list(MIP_SIGNATURES.items()) + \
             list(ANISO_SIGNATURES.items()) + list(SSAA_SIGNATURES.items()) + list(SHADOW_SIGNATURES.items()) + \
-            list(CHAIN_SIGNATURES.items()):
+            list(PHONG_SIGNATURES.items()) + list(CHAIN_SIGNATURES.items()):
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

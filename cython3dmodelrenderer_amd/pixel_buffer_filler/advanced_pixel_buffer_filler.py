@@ -972,6 +972,46 @@ class AdvancedPixelBufferFiller(DevicePlanes):
                 self.color_buffer.data_ptr(), self.h, self.w, self.y0, self.y1, 0, self._stream()), "crender_shadow_shade")
         self._host_fresh = False       # views handed out earlier show the shadowed colours at the next getter call
 
+    def phong_pass(self, lights, ambient=0.1, shininess=32, specular_color=(255, 255, 255), clamp=255.0):
+        """Per-pixel Blinn-Phong lighting of the LAST frame's colour plane (``crender_phong_shade``,
+        include/crender_phong.h): every covered pixel's colour c becomes ``min(c * F + Ws * specular_color, clamp)``
+        with ``F = ambient + sum kd_j * d_j`` and ``Ws = sum ks_j * sp_j ** shininess`` over the lights, d_j the
+        Guro factor of the pixel's stored normal under the unit vector towards light j, sp_j that of the half vector
+        between it and the direction to the camera, both taken at the surface point the pixel shows (the
+        perspective-correct blend of the winner's corners).  `lights` is a list of 1 to 4 dicts, each with exactly one
+        of ``position`` (a point in the camera's frame, where ``shadow.look_at(position=...)`` places a light) or
+        ``direction`` (the way the light travels, ``GuroIllumination``'s convention: flipped and normalised by that
+        class's own statements), and ``diffuse`` (kd) and ``specular`` (ks).  `shininess` is a power of two from 1 to
+        4096.  The background is not written.  Rows of the filler's ``row_strip``, on torch's current stream.
+
+        The frame is settled first (one stream synchronisation, as every getter does): a frame whose bin lists
+        overflowed is rendered again, and the pass must land on the frame that stays."""
+        from ..illumination.phong_illumination import light_rows, shininess_log2
+        if self._pipeline:
+            raise ValueError("phong_pass is not available on a swap chain (pipeline=True): per-slot passes are not implemented")
+        if self.winner_buffer is None:
+            raise ValueError("phong_pass needs the winner plane: construct the filler with track_winner=True")
+        rows, mask = light_rows(lights)
+        k = shininess_log2(shininess)
+        if self._inputs is None:
+            raise ValueError("phong_pass: no frame has been rendered")
+        if not (self._last_flags & _capi.FUSED_CLEAR):
+            raise ValueError("phong_pass: the last frame did not start from cleared buffers (clear=True): the winner "
+                             "plane of a composite mixes the triangle indices of several models")
+        tri = self._inputs[0]
+        T = tri.shape[0]
+        lights5 = (C.c_float * (5 * len(rows)))(*[v for row in rows for v in row])
+        spec = (C.c_float * 3)(*[float(v) for v in specular_color])
+        self._push_host_edits()
+        self._check_bins()             # nothing pending from here on: no later redo can undo the pass
+        pos_of = None if self._order is None else self._order[1].data_ptr()
+        with torch.cuda.device(self.device):
+            _capi.check(self._lib.crender_phong_shade(
+                self.winner_buffer.data_ptr(), tri.data_ptr() if T else None, T, pos_of, self._P,
+                self.normals_buffer.data_ptr(), lights5, len(rows), mask, float(ambient), k, spec, float(clamp),
+                self.color_buffer.data_ptr(), self.h, self.w, self.y0, self.y1, 0, self._stream()), "crender_phong_shade")
+        self._host_fresh = False       # views handed out earlier show the lit colours at the next getter call
+
     def render_frame(self, pipelined=None):
         """One benchmark frame: clear + project + rasterize the resident model
         (SURVEY.md section 8d 'one frame').  Inputs must have been set by a previous

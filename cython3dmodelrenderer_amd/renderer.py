@@ -79,8 +79,24 @@ class Renderer:
             if missing:
                 raise ValueError(f"Renderer(shadow=...) needs the keys 'filler', 'R' and 't': {missing} missing")
             self.shadow = dict(shadow)
+        # A PhongIllumination is a deferred pass of the filler over its winner plane (``phong_pass``): every frame
+        # starts from cleared buffers (one model per frame, as "fused"); the draw, then the texture pass (unlit) if
+        # asked for, then the Phong pass, then the shadow pass — AFTER the light here, since the specular term is
+        # additive and a factor applied before it would leave highlights inside shadows: the shadow's ``ambient`` is
+        # the floor of everything — then the plain resolve.  None returns the numpy colour view (with supersample a
+        # fresh numpy copy), True the tensor.
+        from .illumination.phong_illumination import PhongIllumination
+        self._phong = isinstance(illumination, PhongIllumination)
+        if self._phong:
+            if on_device is False or on_device == "fused":
+                raise ValueError(f"Renderer(on_device={on_device!r}) with a PhongIllumination: the model needs the winner "
+                                 "plane and the triangles, so it has no host form on two planes and is not fused into "
+                                 "the raster kernel; use on_device=None or True")
+            if not hasattr(pixel_buffer_filler, "phong_pass"):
+                raise ValueError("Renderer with a PhongIllumination needs a filler with a Phong pass "
+                                 f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no phong_pass()")
 
-    def _draw(self, model, light=None, **kw):
+    def _draw(self, model, light=None, shadows=True, **kw):
         """``render_model``; with a texture pass or a shadow map, a cleared frame and the passes on top of it."""
         filler = self.pixel_buffer_filler
         if self.texture_pass is None:
@@ -106,7 +122,7 @@ class Renderer:
         filler.set_fused_illumination(None)
         filler.render_model(model, clear=True, refresh_views=False)
         filler.texture_pass(light_direction=light, **self.texture_pass)
-        if self.shadow is not None:
+        if self.shadow is not None and shadows:
             self._cast_shadows(model)
 
     def _cast_shadows(self, model):
@@ -129,6 +145,8 @@ class Renderer:
             model.scale(span / model.get_max_span())
             model.shift(-model.get_mean_vertex() + [centre[0], centre[1], -span])
         filler = self.pixel_buffer_filler
+        if self._phong:
+            return self._render_phong(model)
         if self.supersample is not None:
             return self._render_supersampled(model)
         if self.on_device == "fused" and getattr(self.illumination, "fuse_into", None):
@@ -153,6 +171,22 @@ class Renderer:
             self._draw(model)
         self.illumination.draw_illumination(filler.get_color_buffer(), filler.get_normals_buffer())
         return filler.get_color_buffer()
+
+    def _render_phong(self, model):
+        """``render`` after the model fit, with a ``PhongIllumination``: the passes in the constructor's order."""
+        filler = self.pixel_buffer_filler
+        if self.texture_pass is not None:
+            self._draw(model, shadows=False)               # the texture, unlit
+        else:
+            filler.set_fused_illumination(None)
+            filler.render_model(model, clear=True, refresh_views=False)
+        self.illumination.draw_illumination_device(filler)
+        if self.shadow is not None:
+            self._cast_shadows(model)
+        if self.supersample is not None:
+            image = filler.resolve(self.supersample)
+            return image if self.on_device is True else image.cpu().numpy()
+        return filler.get_color_tensor() if self.on_device is True else filler.get_color_buffer()
 
     def _render_supersampled(self, model):
         """``render`` after the model fit, with ``supersample=s``: the same draws, the resolve at the end."""
