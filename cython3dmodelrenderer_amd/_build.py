@@ -49,6 +49,10 @@ SHADOW_HEADERS = [os.path.join("..", "..", "include", "crender_shadow.h")]
 # source_sha16() likewise.
 PHONG_SOURCES = ["phong.hip"]
 PHONG_HEADERS = [os.path.join("..", "..", "include", "crender_phong.h")]
+# ao.hip  the deferred ambient-occlusion pass over the z, winner and normal planes (include/crender_ao.h); kept out of
+# source_sha16() likewise.
+AO_SOURCES = ["ao.hip"]
+AO_HEADERS = [os.path.join("..", "..", "include", "crender_ao.h")]
 # winner_pass.h  what the deferred passes over the winner plane share (texture.hip, texmip.hip, texaniso.hip,
 # shadow.hip, phong.hip): the pixel frame, the corner gather, the store with the fused light, the texel fetches and the launch
 # geometry; a group of its own, so that each pass's header list stays its own; kept out of source_sha16() likewise.
@@ -106,7 +110,8 @@ def needs_build() -> bool:
                                                 PY_SOURCES + PY_HEADERS + TEX_SOURCES + TEX_HEADERS +
                                                 MIP_SOURCES + MIP_HEADERS + ANISO_SOURCES + ANISO_HEADERS +
                                                 SSAA_SOURCES + SSAA_HEADERS + SHADOW_SOURCES + SHADOW_HEADERS +
-                                                PHONG_SOURCES + PHONG_HEADERS + CHAIN_SOURCES + CHAIN_HEADERS + PASS_HEADERS] + \
+                                                PHONG_SOURCES + PHONG_HEADERS + AO_SOURCES + AO_HEADERS + CHAIN_SOURCES + CHAIN_HEADERS +
+                                                PASS_HEADERS] + \
         [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > built for d in deps)
 
@@ -118,7 +123,7 @@ def compile_library(out: str, extra_flags=(), sources=None, src_dir: str = SRC_D
     import tempfile
     from concurrent.futures import ThreadPoolExecutor
     sources = list(sources or SOURCES + WIRE_SOURCES + PY_SOURCES + TEX_SOURCES + MIP_SOURCES + ANISO_SOURCES +
-                   SSAA_SOURCES + SHADOW_SOURCES + PHONG_SOURCES + CHAIN_SOURCES)
+                   SSAA_SOURCES + SHADOW_SOURCES + PHONG_SOURCES + AO_SOURCES + CHAIN_SOURCES)
     err = subprocess.DEVNULL if quiet else None
     with tempfile.TemporaryDirectory(prefix="crender_build_") as tmp:
         objs = [os.path.join(tmp, os.path.splitext(s)[0] + ".o") for s in sources]

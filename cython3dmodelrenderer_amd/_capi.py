@@ -141,6 +141,15 @@ PHONG_SIGNATURES = {
                                    _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
 }
 
+# the deferred ambient-occlusion pass (include/crender_ao.h), bound from a table of its own
+AO_ROTATE, AO_FACE_NORMALS = 1, 2
+AO_MAX_TAPS = 64
+AO_MAX_RADIUS_PX = 32
+AO_SIGNATURES = {
+    "crender_ao_shade": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _i32, C.c_float, C.c_float, C.c_float,
+                                C.c_float, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
+}
+
 # the swap chain's shared slot (include/crender_chain.h), bound from a table of its own
 CHAIN_SIGNATURES = {
     "crender_pipeline_share_stream": (_i32, [_vp, _i32, _vp]),
@@ -175,7 +184,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(WIRE_SIGNATURES.items()) + \
             list(PY_SIGNATURES.items()) + list(TEX_SIGNATURES.items()) + list(MIP_SIGNATURES.items()) + \
             list(ANISO_SIGNATURES.items()) + list(SSAA_SIGNATURES.items()) + list(SHADOW_SIGNATURES.items()) + \
-            list(PHONG_SIGNATURES.items()) + list(CHAIN_SIGNATURES.items()):
+            list(PHONG_SIGNATURES.items()) + list(AO_SIGNATURES.items()) + list(CHAIN_SIGNATURES.items()):
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -1012,6 +1012,65 @@ class AdvancedPixelBufferFiller(DevicePlanes):
                 self.color_buffer.data_ptr(), self.h, self.w, self.y0, self.y1, 0, self._stream()), "crender_phong_shade")
         self._host_fresh = False       # views handed out earlier show the lit colours at the next getter call
 
+    def ao_pass(self, radius=0.03, radius_px=8, taps=16, min_cos=0.1, strength=2.0, floor=0.0, rotate=True, normals="plane"):
+        """Screen-space ambient occlusion of the LAST frame's colour plane (``crender_ao_shade``,
+        include/crender_ao.h): every covered pixel's colour is scaled by ``max(1 - strength * mean(o_i), floor)``,
+        where tap i looks at the covered pixel at its offset, takes the point that pixel shows (from the z plane) and
+        gives ``o_i = cos * (1 - (distance / radius) ** 2)`` if the point lies within `radius` (in the camera frame's
+        units) and the cosine between the pixel's normal and the way to it exceeds `min_cos`, else 0.  `taps` is a
+        count — the table ``ambient_occlusion.taps(radius_px, taps)`` — or an explicit list of (dx, dy) pairs, 1 to 64
+        of them within `radius_px` (1 to 32) in both coordinates.  With `rotate` a pixel turns the table by a quarter
+        turn picked by its parity, so that neighbours look in other directions.  `normals` is ``"plane"`` (the normal
+        plane the raster stored: interpolated vertex normals) or ``"face"`` (the winner's own geometric normal, turned
+        to the eye).  A pixel that nothing occludes is not written.  Rows of the filler's ``row_strip``, on torch's
+        current stream; the strip does not see across its edge.
+
+        The frame is settled first (one stream synchronisation, as every getter does): a frame whose bin lists
+        overflowed is rendered again, and the pass must land on the frame that stays."""
+        from .. import ambient_occlusion
+        if self._pipeline:
+            raise ValueError("ao_pass is not available on a swap chain (pipeline=True): per-slot passes are not implemented")
+        if self.winner_buffer is None:
+            raise ValueError("ao_pass needs the winner plane: construct the filler with track_winner=True")
+        if normals not in ("plane", "face"):
+            raise ValueError(f"normals must be 'plane' or 'face', got {normals!r}")
+        if isinstance(radius_px, bool) or not isinstance(radius_px, int) or not 1 <= radius_px <= _capi.AO_MAX_RADIUS_PX:
+            raise ValueError(f"radius_px must be an int from 1 to {_capi.AO_MAX_RADIUS_PX}, got {radius_px!r}")
+        if isinstance(taps, int) and not isinstance(taps, bool):
+            if not 1 <= taps <= _capi.AO_MAX_TAPS:
+                raise ValueError(f"taps must be a count from 1 to {_capi.AO_MAX_TAPS} or a list of (dx, dy) pairs, got {taps!r}")
+            table = ambient_occlusion.taps(radius_px, taps)
+        else:
+            try:
+                table = [(operator.index(dx), operator.index(dy)) for dx, dy in taps]
+            except (TypeError, ValueError):
+                raise ValueError(f"taps must be a count from 1 to {_capi.AO_MAX_TAPS} or a list of (dx, dy) pairs, "
+                                 f"got {taps!r}") from None
+            if not 1 <= len(table) <= _capi.AO_MAX_TAPS:
+                raise ValueError(f"taps must hold 1 to {_capi.AO_MAX_TAPS} pairs, got {len(table)}")
+            for dx, dy in table:
+                if max(abs(dx), abs(dy)) > radius_px or (dx, dy) == (0, 0):
+                    raise ValueError(f"the tap ({dx}, {dy}) is (0, 0) or reaches beyond radius_px={radius_px}")
+        if self._inputs is None:
+            raise ValueError("ao_pass: no frame has been rendered")
+        if not (self._last_flags & _capi.FUSED_CLEAR):
+            raise ValueError("ao_pass: the last frame did not start from cleared buffers (clear=True): the winner "
+                             "plane of a composite mixes the triangle indices of several models")
+        tri = self._inputs[0]
+        T = tri.shape[0]
+        taps2 = (C.c_int8 * (2 * len(table)))(*[v for pair in table for v in pair])
+        flags = (_capi.AO_ROTATE if rotate else 0) | (_capi.AO_FACE_NORMALS if normals == "face" else 0)
+        self._push_host_edits()
+        self._check_bins()             # nothing pending from here on: no later redo can undo the pass
+        pos_of = None if self._order is None else self._order[1].data_ptr()
+        with torch.cuda.device(self.device):
+            _capi.check(self._lib.crender_ao_shade(
+                self.winner_buffer.data_ptr(), self.z_buffer.data_ptr(), tri.data_ptr() if T else None, T, pos_of, self._P,
+                self.normals_buffer.data_ptr(), taps2, len(table), radius_px, float(radius), float(min_cos),
+                float(strength), float(floor), self.color_buffer.data_ptr(), self.h, self.w, self.y0, self.y1, flags,
+                self._stream()), "crender_ao_shade")
+        self._host_fresh = False       # views handed out earlier show the occluded colours at the next getter call
+
     def render_frame(self, pipelined=None):
         """One benchmark frame: clear + project + rasterize the resident model
         (SURVEY.md section 8d 'one frame').  Inputs must have been set by a previous

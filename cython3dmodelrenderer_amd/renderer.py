@@ -22,7 +22,7 @@ def _device_form_is_the_same_shading(illumination):
 class Renderer:
     def __init__(self, pixel_buffer_filler, illumination, triangle_iterator_type=None,
                  image_height=512, image_width=512, use_tqdm=True, on_device=None, texture_pass=None,
-                 shadow=None, supersample=None):
+                 shadow=None, ambient_occlusion=None, supersample=None):
         self.pixel_buffer_filler = pixel_buffer_filler
         self.illumination = illumination
         self.triangle_iterator_type = triangle_iterator_type   # stored, unused (as in Version C)
@@ -79,6 +79,18 @@ class Renderer:
             if missing:
                 raise ValueError(f"Renderer(shadow=...) needs the keys 'filler', 'R' and 't': {missing} missing")
             self.shadow = dict(shadow)
+        # ambient_occlusion=None (default): creases are lit like open surfaces.  A dict of AdvancedPixelBufferFiller.ao_pass's
+        # arguments ({} = its defaults): every frame starts from cleared buffers (one model per frame, as "fused") and the
+        # pass runs on the camera's frame after any texture pass and BEFORE the Phong pass, the shadow pass, the
+        # illumination and the resolve: it scales the surface colour, so Phong's additive highlight is not dimmed.  With
+        # on_device="fused" it multiplies what the raster kernel or the texture pass stored; with ``supersample=s`` it
+        # runs on the supersampled frame, and ``radius_px`` counts that frame's pixels.
+        self.ambient_occlusion = None
+        if ambient_occlusion is not None:
+            if not hasattr(pixel_buffer_filler, "ao_pass"):
+                raise ValueError("Renderer(ambient_occlusion=...) needs a filler with an ambient-occlusion pass "
+                                 f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no ao_pass()")
+            self.ambient_occlusion = dict(ambient_occlusion)
         # A PhongIllumination is a deferred pass of the filler over its winner plane (``phong_pass``): every frame
         # starts from cleared buffers (one model per frame, as "fused"); the draw, then the texture pass (unlit) if
         # asked for, then the Phong pass, then the shadow pass — AFTER the light here, since the specular term is
@@ -97,15 +109,20 @@ class Renderer:
                                  f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no phong_pass()")
 
     def _draw(self, model, light=None, shadows=True, **kw):
-        """``render_model``; with a texture pass or a shadow map, a cleared frame and the passes on top of it."""
+        """``render_model``; with a texture pass, ambient occlusion or a shadow map, a cleared frame and the passes on
+        top of it."""
         filler = self.pixel_buffer_filler
         if self.texture_pass is None:
-            if self.shadow is None:
+            if self.shadow is None and self.ambient_occlusion is None:
                 return filler.render_model(model, **kw)
             if not kw.get("clear"):        # (the "fused" caller asks for the cleared frame itself: its raster kernel shades)
                 filler.set_fused_illumination(None)
             filler.render_model(model, clear=True, refresh_views=False)
-            return self._cast_shadows(model)
+            if self.ambient_occlusion is not None:
+                filler.ao_pass(**self.ambient_occlusion)
+            if self.shadow is not None:
+                self._cast_shadows(model)
+            return None
         if self._textured is None or self._textured() is not model:      # once per model, not per frame
             getters = [getattr(model, n, None) for n in ("get_texture_coords_by_triangles", "get_texture")]
             uv, tex = [g() if g is not None else None for g in getters]
@@ -122,6 +139,8 @@ class Renderer:
         filler.set_fused_illumination(None)
         filler.render_model(model, clear=True, refresh_views=False)
         filler.texture_pass(light_direction=light, **self.texture_pass)
+        if self.ambient_occlusion is not None:
+            filler.ao_pass(**self.ambient_occlusion)
         if self.shadow is not None and shadows:
             self._cast_shadows(model)
 
@@ -180,6 +199,8 @@ class Renderer:
         else:
             filler.set_fused_illumination(None)
             filler.render_model(model, clear=True, refresh_views=False)
+            if self.ambient_occlusion is not None:
+                filler.ao_pass(**self.ambient_occlusion)
         self.illumination.draw_illumination_device(filler)
         if self.shadow is not None:
             self._cast_shadows(model)
