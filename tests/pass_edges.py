@@ -1,4 +1,4 @@
-"""Hand-built edge scenes for the deferred passes (texture, mip, aniso, shadow), shared by tests/test_pass_edges_cpu.py
+"""Hand-built edge scenes for the deferred passes (texture, mip, aniso, shadow, Phong, occlusion), shared by tests/test_pass_edges_cpu.py
 and tests/test_pass_edges_gpu.py.  Pure numpy on top of the host models (tests/tex_ref.py and its companions): a small
 frame whose winner plane is PAINTED, block by block, not rasterized, so that the passes meet operands no rasterizer
 hands them — pixels far outside their winner, triangles of no area or of 10^13 px^2, corners at z = 2^-43 or NaN —
@@ -13,11 +13,16 @@ n == 0) the full `/` is used."):
     z_fast  the three corners' unprojected z are inside the window                                 (per triangle)
     b       the three barycentrics are inside the window                                           (per point)
     s       s, nu and nv of the Perspective statement are inside the window                        (per point)
-`classify` restates them in numpy float32 from the host model's own operands; no kernel code is imported."""
+`classify` restates them in numpy float32 from the host model's own operands; no kernel code is imported.
+
+The Phong and the occlusion pass take no such shortcut; what they add to the scenes (`_lit`, at the end: a z plane,
+tap tables, light sets) is drawn after everything else, so that the arrays of the four older passes stay what they were."""
 import functools
 
 import numpy as np
 
+import ao_ref
+import phong_ref
 import shadow_ref
 import tex_ref
 
@@ -290,7 +295,7 @@ def shadow_points(s, winner, bias=BIAS):
 
 @functools.lru_cache(maxsize=None)
 def scene():
-    return _build()
+    return _lit(_build(), 20244)
 
 
 def classify(s, winner=None, dtype=np.float32):
@@ -360,7 +365,7 @@ def mini_scene():
     s.normals = nrm
     s.lz = rng.uniform(0.3, 1.0, (HL, WL)).astype(np.float32)
     s.lwinner = rng.integers(-1, T, (HL, WL)).astype(np.int32)
-    return s
+    return _lit(s, 20245)
 
 
 # ---- the tall frame: more 8-row blocks than a grid is tall ----------------------------------------------------------
@@ -398,4 +403,70 @@ def tall_scene():
     # the light looks along the camera's axis at a small map: the tall frame's columns fall into its middle
     s.lz = rng.uniform(0.3, 1.0, (HL, WL)).astype(np.float32)
     s.lwinner = rng.integers(-1, T, (HL, WL)).astype(np.int32)
+    s.lights = light_sets(s, None)
+    return s
+
+
+# ---- what the Phong and the occlusion pass need: drawn after everything above, from generators of their own ----------
+
+# tests/test_ao_gpu.py's table of 16 taps within 8 px, and the corners and edge midpoints of the largest halo
+TABLE = [(1, 0), (-2, 2), (0, -3), (2, 3), (-4, -1), (4, -3), (-1, 5), (-3, -5), (5, 2), (-6, 2), (3, -6), (2, 6), (-6, -4),
+         (7, -2), (-4, 6), (-1, -8)]
+HALO_TABLE = [(32, 32), (-32, 32), (32, -32), (-32, -32), (32, 0), (-32, 0), (0, 32), (0, -32)]
+POINT = (0.1, -0.1, 1.5)             # inside the depth range of the "ordinary" triangles (0.5 .. 3)
+LIGHT_SETS = ("point", "direction", "four")
+
+
+def phong_points(s, winner=None, y0=0, y1=None):
+    """(ys, xs, t, pt [N, 3], inside [N]) of the covered pixels: the surface point of crender_phong.h, restated from
+    the host model's own barycentrics, and whether the pixel lies inside its winner (false for a NaN)."""
+    winner = s.winner if winner is None else winner
+    ys, xs, t, b, z = phong_ref.surface_point(winner, s.tri, P, y0, y1)
+    with np.errstate(all="ignore"):
+        q = [b[k] / z[:, k] for k in range(3)]
+        sm = (q[0] + q[1]) + q[2]
+        c = s.tri[t]
+        pt = np.stack([((c[:, 0, a] * q[0] + c[:, 1, a] * q[1]) + c[:, 2, a] * q[2]) / sm for a in range(3)], 1)
+        b = np.stack(b)
+        inside = ((b >= 0) & (b <= 1)).all(0)
+    return ys, xs, t, pt, inside
+
+
+def light_sets(s, corner):
+    """The three light sets of the Phong pass: one point, one direction (both run the instance without the loop
+    frame) and four: a point, a direction, a point exactly on `corner` — a corner of a triangle that a pixel shows so
+    near that corner that the length of the vector to the light is 0 and its unit vector n / 0 or 0 / 0 — and the origin, where L = V at
+    every pixel, with kd = ks = 0.  (`corner` None: a corner of the first triangle.)"""
+    corner = s.tri[0, 0] if corner is None else corner
+    return {"point": [dict(position=POINT, diffuse=0.9, specular=0.5)],
+            "direction": [dict(direction=LIGHT, diffuse=0.9, specular=0.5)],
+            "four": [dict(position=POINT, diffuse=0.6, specular=0.5), dict(direction=LIGHT, diffuse=0.3, specular=0.25),
+                     dict(position=tuple(float(v) for v in corner), diffuse=0.5, specular=0.125),
+                     dict(position=(0.0, 0.0, 0.0), diffuse=0.0, specular=0.0)]}
+
+
+def _lit(s, seed):
+    """The z plane of the occlusion pass — view depths around 1 with a relief of +-3 pixel widths, stored as
+    z = P[2, 2] + P[3, 2] / zv, about 8 % of it NaN, infinite, P[2, 2] itself (zv is a division by zero) or 1e6 —
+    its radius of 6 pixel widths (and of 64 for the halo of 32 px, whose corners lie 50 widths away) and the light
+    sets of the Phong pass."""
+    rng = np.random.default_rng(seed)
+    d = np.float32
+    c = ao_ref.constants(P, s.W, s.H, 1.0, 1)
+    s.px = float(min(abs(c[2]), abs(c[3])))                   # (pixels are oblong where the frame is)
+    zv = (1.0 + s.px * rng.uniform(-3, 3, (s.H, s.W))).astype(d)
+    z = (d(P[2, 2]) + d(P[3, 2]) / zv).astype(d)
+    odd = rng.uniform(size=z.shape) < 0.08
+    z[odd] = rng.choice(d([np.nan, np.inf, -np.inf, P[2, 2], 1e6]), int(odd.sum()))
+    s.z = z
+    s.ao_radius, s.halo_radius = 6 * s.px, 64 * s.px
+    # the first pixel, in row order, whose point is so near a corner of its winner that the length of the vector to it
+    # is 0 (the corners of "z_low" at 1e-38: the squares underflow); none on a scene without such a triangle
+    ys, xs, t, pt, _ = phong_points(s)
+    with np.errstate(all="ignore"):
+        lv = s.tri[t] - pt[:, None, :]
+        ll = np.sqrt((lv[..., 0] * lv[..., 0] + lv[..., 1] * lv[..., 1]) + lv[..., 2] * lv[..., 2])
+    at, corner = np.nonzero(ll == 0)
+    s.on_corner = (int(t[at[0]]), int(corner[0])) if len(at) else None
+    s.lights = light_sets(s, s.tri[s.on_corner] if len(at) else None)
     return s

@@ -3,9 +3,15 @@ deferred passes.  A pure function of the seed — `plan(seed)` returns the fille
 dict that says everything the runner does and whether a pass in it is legal — so that tests/test_pass_edges_cpu.py can
 dry-run the default seeds without a GPU and hold the generator to its coverage floors.
 
+Two families of sessions.  The default one, "passes", draws texture and shadow passes; "lit" draws the Phong and
+the occlusion pass among them as well, from generators, ops, weights and instances of its own, and chains up to four
+passes on one frame.  The default family is the same function of the seed it was before the second one existed:
+tests/test_pass_sessions_cpu.py pins a digest of every default plan.
+
 The generator keeps the little state that decides legality, as the filler documents it: a pass needs a last frame that
 started from cleared buffers (``clear()`` afterwards empties the planes but leaves the pass legal: it finds background
-only); a texture pass needs uv of the last frame's triangle count bound, and a mip chain for "trilinear"."""
+only); a texture pass needs uv of the last frame's triangle count bound, and a mip chain for "trilinear"; a Phong or
+an occlusion pass needs the frame alone, and its own arguments well formed."""
 import numpy as np
 
 SEEDS = 12
@@ -22,10 +28,33 @@ WEIGHTS = (4, 2, 1, 1, 3, 1, 13, 7, 5, 2, 2, 2)
 # frame, on every seed of a soak as well.
 CAMERA_OVERFLOWS = (4, 9)
 
+FAMILIES = ("passes", "lit")
+# The "lit" family: a pass of each kind as an op of its own, "chain" (two to four passes on one frame) for "two passes".
+LIT_OPS = ("cleared frame", "render_frame", "composite", "clear", "bind", "unbind", "texture_pass", "shadow_pass",
+           "phong_pass", "ao_pass", "chain", "edit then pass", "resolve", "getters")
+# (tuned on the dry run of the default seeds, as WEIGHTS is)
+LIT_WEIGHTS = (4, 3, 1, 3, 2, 2, 11, 4, 1, 4, 8, 2, 2, 3)
+# In the "lit" family the session 4 (modulo SEEDS) opens with a Phong pass on its overflowed frame, the session 9 — a
+# presorted filler, and there a row strip as well — with an occlusion pass in the face mode.
+LIT_KINDS = (0.5, 0.03, 0.3, 0.17)                     # texture, shadow, phong, ao: what a pass of any kind is
+LIT_SEED = 28000
+LIT_OPENING = {4: "phong_pass", 9: "ao_pass"}
+# The lights a Phong mode draws from: points inside the soups' depth range (0.5 .. 3), behind the camera and beyond the
+# soups, directions, and a light that adds nothing.
+LIGHT_POOL = (dict(position=(0.1, -0.1, 1.5), diffuse=0.8, specular=0.5),
+              dict(position=(-0.4, 0.3, 0.9), diffuse=0.5, specular=0.25),
+              dict(position=(-0.8, -0.5, -0.2), diffuse=0.9, specular=0.5),
+              dict(position=(1.5, -2.0, 6.0), diffuse=0.6, specular=0.125),
+              dict(direction=(0.3, -0.2, 1.0), diffuse=0.3, specular=0.25),
+              dict(direction=(-1.0, 0.5, 0.25), diffuse=0.2, specular=0.125),
+              dict(position=(0.5, 0.5, 1.0), diffuse=0.0, specular=0.0))
+AO_RADIUS = {1: 0.03, 4: 0.05, 8: 0.1, 32: 0.4}       # the world radius grows with the halo, so that far taps are taken
+AO_TAP_COUNTS = {1: (1, 8), 4: (4, 16, 64), 8: (1, 16, 64), 32: (16, 64)}
 
-def options(seed):
+
+def options(seed, family="passes"):
     """The filler's construction options and the frame's size."""
-    rng = np.random.default_rng(17000 + seed)
+    rng = np.random.default_rng((17000 if family == "passes" else 27000) + seed)
     H = int(rng.choice([96, 128, 97, 111])) if seed % 3 else int(rng.choice([97, 111, 127]))
     W = int(rng.choice([160, 128, 131, 159])) if seed % 3 else int(rng.choice([131, 159, 105]))
     kw = {"tile": int(rng.choice([16, 32]))}
@@ -34,6 +63,9 @@ def options(seed):
     if seed % 5 == 2:
         a = 4 * int(rng.integers(0, H // 8))
         kw["row_strip"] = (a, min(H, a + 4 * int(rng.integers(4, H // 4))))
+    if family == "lit" and seed % SEEDS == 9:                          # a row strip, presorted and overflowing at once
+        a = 4 * int(rng.integers(1, H // 8))
+        kw["row_strip"] = (a, min(H, a + 4 * int(rng.integers(6, H // 4))))
     if seed % SEEDS in CAMERA_OVERFLOWS:
         kw.update(tile=32, bin_capacity=40, direct_bins=False)        # frames overflow; a pass settles and redraws them
     light = {"tile": int(rng.choice([0, 16, 32]))}
@@ -44,9 +76,11 @@ def options(seed):
     return dict(H=H, W=W, kw=kw, light_kw=light, Hl=int(rng.choice([64, 77])), Wl=int(rng.choice([64, 90])))
 
 
-def _texture_mode(rng, mip):
-    """A random mode of texture_pass; `legal` is False for "trilinear" without a chain."""
-    filt = str(rng.choice(["nearest", "bilinear", "trilinear", "trilinear", "aniso", "aniso"]))
+def _texture_mode(rng, mip, flat=False):
+    """A random mode of texture_pass; `legal` is False for "trilinear" without a chain.  `flat` (the "lit" family, which
+    has fewer texture passes to spend): every kernel instance as likely as any other."""
+    filt = str(rng.choice(["nearest", "bilinear", "trilinear", "aniso"] if flat else
+                          ["nearest", "bilinear", "trilinear", "trilinear", "aniso", "aniso"]))
     if filt in ("trilinear", "aniso") and not mip and rng.uniform() < 0.85:
         filt = str(rng.choice(["nearest", "bilinear"]))
     mode = dict(kind="texture", filter="trilinear" if filt == "aniso" else filt, perspective=bool(rng.integers(0, 2)),
@@ -61,8 +95,55 @@ def _shadow_mode(rng):
                 wrong=bool(rng.uniform() < 0.12))
 
 
+def _phong_mode(rng):
+    """A random mode of phong_pass; about one in eight is malformed: five lights, a shininess that is no power of two,
+    or a light with both a position and a direction."""
+    n = int(rng.choice([1, 1, 2, 3, 4]))
+    lights = [dict(LIGHT_POOL[int(i)]) for i in rng.choice(len(LIGHT_POOL), n, replace=False)]
+    mode = dict(kind="phong", lights=lights, shininess=int(rng.choice([1, 8, 256, 4096])),
+                ambient=float(rng.choice([0.0, 0.1, 0.4])), clamp=float(rng.choice([255.0, np.inf, 100.0])),
+                specular_color=tuple(float(v) for v in rng.choice([255.0, 200.0, 17.5, 3.0], 3)), malformed=None)
+    if rng.uniform() < 0.125:
+        mode["malformed"] = str(rng.choice(["five lights", "shininess 3", "position and direction"]))
+        if mode["malformed"] == "five lights":
+            mode["lights"] = [dict(LIGHT_POOL[i]) for i in range(5)]
+        elif mode["malformed"] == "shininess 3":
+            mode["shininess"] = 3
+        else:
+            mode["lights"][-1] = dict(mode["lights"][-1], position=(0.0, 0.0, 1.0), direction=(0.0, 0.0, 1.0))
+    return mode
+
+
+def _ao_mode(rng):
+    """A random mode of ao_pass; about one in eight is malformed: radius_px = 33, a (0, 0) tap, or normals="vertex"."""
+    R = int(rng.choice([1, 4, 8, 32], p=[0.3, 0.15, 0.2, 0.35]))
+    if rng.uniform() < 0.3:                                             # an explicit table: a corner of the halo and others
+        n = int(rng.integers(2, 13))
+        pairs = {(R, -R)} | {(int(a), int(b)) for a, b in rng.integers(-R, R + 1, (n, 2))}
+        taps = sorted(pairs - {(0, 0)})
+    else:
+        taps = int(rng.choice(AO_TAP_COUNTS[R]))
+    mode = dict(kind="ao", radius_px=R, taps=taps, radius=AO_RADIUS[R], normals=str(rng.choice(["plane", "face"])),
+                rotate=bool(rng.integers(0, 2)), strength=float(rng.choice([1.0, 3.0, 50.0])),
+                floor=float(rng.choice([0.0, 0.25, 1.0])), malformed=None)
+    if rng.uniform() < 0.125:
+        mode["malformed"] = str(rng.choice(["radius_px 33", "a (0, 0) tap", "vertex normals"]))
+        if mode["malformed"] == "radius_px 33":
+            mode["radius_px"] = 33
+        elif mode["malformed"] == "a (0, 0) tap":
+            mode["taps"] = [(1, 0), (0, 0)]
+        else:
+            mode["normals"] = "vertex"
+    return mode
+
+
 def instance(mode):
     """The kernel instance a legal pass runs."""
+    if mode["kind"] == "phong":
+        return ("phong", len(mode["lights"]) == 1, mode["shininess"] > 1)
+    if mode["kind"] == "ao":
+        R = mode["radius_px"]
+        return ("ao", mode["normals"] == "face", mode["rotate"], 1 if R == 1 else 8 if R <= 8 else 32)
     if mode["kind"] == "shadow":
         return ("shadow", mode["pcf"], mode["use_winner"])
     if mode["filter"] == "trilinear":
@@ -73,24 +154,36 @@ def instance(mode):
 INSTANCES = [("tex", p, b, l) for p in (False, True) for b in (False, True) for l in (False, True)] + \
             [(k, p, l) for k in ("mip", "aniso") for p in (False, True) for l in (False, True)] + \
             [("shadow", K, w) for K in (1, 3, 5) for w in (False, True)]
+LIT_INSTANCES = INSTANCES + [("phong", one, squared) for one in (False, True) for squared in (False, True)] + \
+                [("ao", face, rotate, R) for face in (False, True) for rotate in (False, True) for R in (1, 8, 32)]
 
 
-def plan(seed, steps=STEPS):
+def plan(seed, steps=STEPS, family="passes"):
     """(options, [step]) of a session.  Each step: op, its parameters, and for every pass in it `legal`."""
-    opt = options(seed)
-    rng = np.random.default_rng(18000 + seed)
+    lit = family == "lit"
+    assert family in FAMILIES
+    opt = options(seed, family)
+    rng = np.random.default_rng((LIT_SEED if lit else 18000) + seed)
+    ops, weights = (LIT_OPS, LIT_WEIGHTS) if lit else (OPS, WEIGHTS)
     soup = None            # the soup of the last render
     cleared = False        # that render started from cleared buffers
     bound = None           # (soup whose uv are bound, mipmaps)
     out = []
 
-    def a_pass():
-        if rng.uniform() < 0.62:
-            mode, ok = _texture_mode(rng, bound is not None and bound[1])
-            legal = ok and soup is not None and cleared and bound is not None and count(bound[0]) == count(soup)
+    def a_pass(kind=None):
+        if lit:
+            kind = kind or str(rng.choice(["texture", "shadow", "phong", "ao"], p=LIT_KINDS))
         else:
+            kind = "texture" if rng.uniform() < 0.62 else "shadow"
+        if kind == "texture":
+            mode, ok = _texture_mode(rng, bound is not None and bound[1], flat=lit)
+            legal = ok and soup is not None and cleared and bound is not None and count(bound[0]) == count(soup)
+        elif kind == "shadow":
             mode = _shadow_mode(rng)
             legal = soup is not None and cleared and not mode["wrong"]
+        else:                          # the frame alone: the empty soup is legal and writes nothing
+            mode = _phong_mode(rng) if kind == "phong" else _ao_mode(rng)
+            legal = soup is not None and cleared and mode["malformed"] is None
         return dict(mode, legal=bool(legal))
 
     def bind_now(right):
@@ -107,13 +200,13 @@ def plan(seed, steps=STEPS):
     # filler (the light's).  The rest of the session is drawn as everywhere.
     opening = []
     if opt["kw"].get("bin_capacity"):
-        opening += ["bind", "texture_pass"]
+        opening += [LIT_OPENING[seed % SEEDS]] if lit else ["bind", "texture_pass"]
     if opt["light_kw"].get("bin_capacity"):
         opening += ["shadow_pass"]
     opening = ["cleared frame"] + opening if opening else []
 
     for k in range(steps):
-        op = str(rng.choice(OPS, p=np.array(WEIGHTS) / sum(WEIGHTS)))
+        op = str(rng.choice(ops, p=np.array(weights) / sum(weights)))
         if k == 0:
             op = "cleared frame"
         if k < len(opening):
@@ -127,11 +220,16 @@ def plan(seed, steps=STEPS):
                 bound = (soup, True)
             elif op == "texture_pass":
                 step["mode"] = dict(_texture_mode(rng, True)[0], legal=True)
+            elif op in ("phong_pass", "ao_pass"):
+                mode = None
+                while mode is None or mode["malformed"]:               # (a well-formed one)
+                    mode = _phong_mode(rng) if op == "phong_pass" else dict(_ao_mode(rng), normals="face")
+                step["mode"] = dict(mode, legal=True)
             else:
                 step["mode"] = dict(_shadow_mode(rng), own=False, wrong=False, legal=True)
             out.append(step)
             continue
-        if op in ("texture_pass", "two passes", "edit then pass") and soup is not None and cleared and \
+        if op in ("texture_pass", "two passes", "edit then pass", "chain") and soup is not None and cleared and \
                 (bound is None or count(bound[0]) != count(soup)) and rng.uniform() < 0.8:
             op = "bind"                                                 # (most sessions bind before they texture)
         step = dict(op=op)
@@ -156,10 +254,20 @@ def plan(seed, steps=STEPS):
             if (p["kind"] == "texture") != (op == "texture_pass"):
                 p = a_pass() if rng.uniform() < 0.5 else p
             step.update(op="texture_pass" if p["kind"] == "texture" else "shadow_pass", mode=p)
+        elif op in ("phong_pass", "ao_pass"):
+            step["mode"] = a_pass(op[:-5])
         elif op == "two passes":
             step["modes"] = [a_pass(), a_pass()]
+        elif op == "chain":
+            if rng.uniform() < 0.6:                                     # a texture first, a shadow last, lights between
+                kinds = ["texture"] + [str(k) for k in rng.choice(["phong", "ao"], int(rng.integers(1, 3)))] + ["shadow"]
+            else:
+                kinds = [None] * int(rng.integers(2, 5))
+            step["modes"] = [a_pass(kind) for kind in kinds]
         elif op == "edit then pass":
             step.update(rows=[float(v) for v in rng.uniform(0, 1, 2)], value=float(rng.uniform(1, 200)), mode=a_pass())
+            if lit:                    # under an occlusion pass: covered pixels of the rows pushed towards the eye as well
+                step["z_edit"] = bool(rng.integers(0, 2)) and step["mode"]["kind"] == "ao"
         elif op == "resolve":
             step.update(factor=int(rng.integers(1, 5)), light=bool(rng.integers(0, 2)))
         out.append(step)
@@ -175,9 +283,9 @@ def passes(steps):
     for s in steps:
         if s["op"] == "composite":
             yield s["then"]
-        elif s["op"] in ("texture_pass", "shadow_pass", "edit then pass"):
+        elif s["op"] in ("texture_pass", "shadow_pass", "phong_pass", "ao_pass", "edit then pass"):
             yield s["mode"]
-        elif s["op"] == "two passes":
+        elif s["op"] in ("two passes", "chain"):
             yield from s["modes"]
 
 
@@ -189,7 +297,7 @@ def first_to_settle(steps):
     live = False
     for s in steps:
         op = s["op"]
-        modes = [s["mode"]] if op in ("texture_pass", "shadow_pass") else s.get("modes", [])
+        modes = [s["mode"]] if op in ("texture_pass", "shadow_pass", "phong_pass", "ao_pass") else s.get("modes", [])
         if op == "cleared frame":
             live = count(s["soup"]) > 0
         elif op == "clear":
@@ -215,3 +323,19 @@ def light_meets_a_pass(steps):
             if mode["kind"] == "shadow" and mode["legal"] and not mode["own"] and count(soup) > 0:
                 return True
     return False
+
+
+def lit_between(steps):
+    """The chains of a session that hold a legal Phong or occlusion pass after a legal texture pass and before a legal
+    shadow pass of the same chain, or before a resolve as the next step."""
+    n = 0
+    for k, s in enumerate(steps):
+        if s["op"] != "chain":
+            continue
+        kinds = [m["kind"] if m["legal"] else None for m in s["modes"]]
+        resolve_next = k + 1 < len(steps) and steps[k + 1]["op"] == "resolve"
+        for i, kind in enumerate(kinds):
+            if kind in ("phong", "ao") and "texture" in kinds[:i] and ("shadow" in kinds[i + 1:] or resolve_next):
+                n += 1
+                break
+    return n

@@ -1,5 +1,5 @@
 """Conditions on the hand-built scenes of tests/pass_edges.py, checked on the host model alone: the scenes take every
-window decision of the passes both ways, often enough and within one wavefront, before tests/test_pass_edges_gpu.py
+window decision of the passes, and every select of the Phong and occlusion passes, both ways, often enough and within one wavefront, before tests/test_pass_edges_gpu.py
 holds the kernels to them; and the float32 model of the scene is still the float64 form of its own statements where
 the operands are ordinary."""
 import inspect
@@ -10,8 +10,10 @@ import numpy as np
 import pytest
 
 import aniso_ref
+import ao_ref
 import mip_ref
 import pass_edges as E
+import phong_ref
 import shadow_ref
 import tex_ref
 from test_texture_cpu import PERSPECTIVE_UV_BOUND
@@ -232,3 +234,204 @@ def test_the_passes_share_one_header_that_the_build_watches_and_the_fingerprint_
         assert len(found) == 1, (name, found)
     for n in units:
         assert '#include "winner_pass.h"' in text[n], n
+
+
+# ---- the Phong pass ---------------------------------------------------------------------------------------------------
+
+PHONG_AMBIENT = 0.25
+
+
+def _phong_floors(s, kind, floor, rows=None, unlit_floor=None, odd_floor=None):
+    """The conditions on one scene under one light set.  `rows`: the rows anything is counted on."""
+    lights = s.lights[kind]
+    ys, xs, t, pt, inside = E.phong_points(s)
+    keep = np.ones(len(t), bool) if rows is None else np.isin(ys, rows)
+    counts = {}
+    out = phong_ref.phong_pass(s.color, s.winner, s.tri, E.P, s.normals, lights, ambient=PHONG_AMBIENT, counts=counts)
+    assert np.isfinite(out).all()                                                 # no NaN or inf reaches the colours
+    changed = (out.view(np.uint32) != s.color.view(np.uint32)).any(2)
+    assert changed[ys, xs].all() and changed.sum() == len(t) == counts["covered"]
+    # per light: both sides of `lit`, often enough and inside one 8 x 8 block
+    n = [s.normals[ys, xs, a] for a in range(3)]
+    L5, mask = phong_ref.lights5(lights)
+    with np.errstate(all="ignore"):
+        V = [-pt[:, a] for a in range(3)]
+        vl = phong_ref.length(V)
+        Vu = [v / vl for v in V]
+        F_dir = np.full(len(t), np.float32(PHONG_AMBIENT))
+        blk = (ys // E.BLOCK) * 100000 + xs // E.BLOCK
+        for j in range(len(lights)):
+            d, _ = phong_ref.light_terms([pt[:, a] for a in range(3)], Vu, n, L5[j, :3], bool(mask >> j & 1), 5)
+            lit = (d > 0) & keep
+            unlit = ~(d > 0) & keep
+            print(f"{kind}, light {j}: {int(lit.sum())} lit, {int(unlit.sum())} unlit")
+            assert lit.sum() >= floor and unlit.sum() >= (floor if unlit_floor is None or not mask >> j & 1 else unlit_floor)
+            assert any(lit[blk == b].any() and unlit[blk == b].any() for b in np.unique(blk[keep]))
+            if mask >> j & 1:
+                F_dir = F_dir + L5[j, 3] * d
+    # a surface point that is not finite: no point light and no highlight reaches the pixel — its colour times the
+    # ambient term, and the diffuse term of the DIRECTIONS, which need no point (under the clamp)
+    odd = ~np.isfinite(pt).all(1)
+    print(f"{kind}: {int((odd & keep).sum())} points that are not finite, {int((~odd & ~inside & keep).sum())} finite ones outside their winner")
+    assert (odd & keep).sum() >= (floor if odd_floor is None else odd_floor)
+    same = out[ys[odd], xs[odd]].view(np.uint32) == np.minimum(s.color[ys[odd], xs[odd]] * F_dir[odd, None], np.float32(255)).view(np.uint32)
+    assert same.all()
+    if not mask:
+        assert (F_dir == np.float32(PHONG_AMBIENT)).all()
+    return int((~odd & ~inside & keep).sum())
+
+
+@pytest.mark.parametrize("kind", E.LIGHT_SETS)
+def test_phong_on_the_edge_scene_takes_every_select_both_ways(scene, kind):
+    """Lit and unlit under every light, surface points that are NaN or infinite ("zero", "z_inf", most of "z_bad"),
+    finite ones far outside their winner, channels at the clamp."""
+    s = scene
+    outside = _phong_floors(s, kind, WAVE)
+    assert outside >= 1000
+    counts = {}
+    phong_ref.phong_pass(s.color, s.winner, s.tri, E.P, s.normals, s.lights[kind], ambient=PHONG_AMBIENT, clamp=100.0, counts=counts)
+    assert counts["clamped"] >= 16
+    ys, xs, t, pt, _ = E.phong_points(s)
+    odd = ~np.isfinite(pt).all(1)
+    assert set(s.classes["zero"] + s.classes["z_inf"]) <= set(t[odd].tolist())
+    assert odd[np.isin(t, s.classes["zero"] + s.classes["z_inf"])].all()
+    assert odd[np.isin(t, s.classes["z_bad"])].sum() > (~odd)[np.isin(t, s.classes["z_bad"])].sum()
+
+
+def test_the_light_sets_hold_what_they_are_for(scene):
+    s = scene
+    assert [len(s.lights[k]) for k in E.LIGHT_SETS] == [1, 1, 4]
+    assert "position" in s.lights["point"][0] and s.lights["direction"][0]["direction"] == E.LIGHT
+    z = s.tri[s.classes["ordinary"]][:, :, 2]
+    assert z.min() < s.lights["point"][0]["position"][2] < z.max()               # inside the ordinary triangles' depths
+    four = s.lights["four"]
+    assert ["position" in l for l in four] == [True, False, True, True]
+    assert four[3]["position"] == (0.0, 0.0, 0.0) and four[3]["diffuse"] == four[3]["specular"] == 0.0
+    assert len({l["diffuse"] for l in four}) == 4                                 # (a light's own kd: none stands for another)
+    # the third light is a corner of a triangle on the frame, and at some of its pixels the vector to it has no length
+    t, c = s.on_corner
+    on = np.float32(four[2]["position"]).view(np.uint32) == s.tri[t, c].view(np.uint32)
+    assert on.all() and (s.winner == t).any()
+    ys, xs, tt, pt, _ = E.phong_points(s)
+    with np.errstate(all="ignore"):
+        lv = [np.float32(four[2]["position"])[a] - pt[:, a] for a in range(3)]
+        ll = phong_ref.length(lv)
+    print(f"{int((ll == 0).sum())} pixels at no distance from the third light")
+    assert (ll == 0).sum() >= 1
+    # the origin: L = V at every pixel with a finite point
+    with np.errstate(all="ignore"):
+        V = [-pt[:, a] for a in range(3)]
+        L = [np.float32(0) - pt[:, a] for a in range(3)]
+    assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(V, L))        # (as values: 0 - 0 is +0)
+
+
+@pytest.mark.parametrize("kind", E.LIGHT_SETS)
+def test_phong_on_the_small_and_on_the_tall_frame(oracle, kind):
+    """The same floors at 16.  The tall frame holds ordinary triangles only (its arrays stay as they are), so no point
+    on it fails to be finite; and LIGHT leaves 13 of its rows' 129 covered pixels unlit, normals and direction both
+    being given: the floor of the directions' unlit side is 8 there, one block's rows of one column."""
+    _phong_floors(E.mini_scene(), kind, 16)
+    t = E.tall_scene()
+    _phong_floors(t, kind, 16, rows=t.rows, unlit_floor=8, odd_floor=0)
+
+
+# ---- the occlusion pass -------------------------------------------------------------------------------------------------
+
+def _ao(s, table=E.TABLE, radius_px=8, radius=None, pos_of=False, **kw):
+    counts = {}
+    out = ao_ref.ao_pass(s.color, s.z, s.winner, s.moved if pos_of else s.tri, E.P, s.normals, table,
+                         radius=s.ao_radius if radius is None else radius, radius_px=radius_px,
+                         pos_of=s.pos_of if pos_of else None, T=s.T, counts=counts, **kw)
+    assert not np.isnan(out).any()
+    return out, counts
+
+
+def test_the_z_plane_and_the_tap_table(scene):
+    import test_ao_gpu
+    s = scene
+    assert E.TABLE == test_ao_gpu.TABLE and len(E.TABLE) == 16
+    assert abs(s.px - 0.01) < 1e-6 and abs(E.mini_scene().px - 1 / 28) < 1e-6
+    c = ao_ref.constants(E.P, E.W, E.H, 1.0, 1)
+    assert abs(float(c[2]) - 0.01) < 1e-6 and abs(float(c[3]) - 0.0119) < 1e-4
+    P16 = E.P.reshape(16)                                                        # crender_ao_shade's shape check
+    assert all(P16[i] == 0 for i in (1, 2, 4, 6, 8, 9, 12, 13)) and all(np.isfinite(P16[i]) and P16[i] != 0 for i in (0, 5, 14))
+    for m in (s, E.mini_scene()):
+        z = m.z
+        assert z.shape == (m.H, m.W) and z.dtype == np.float32
+        for v in (np.inf, -np.inf, np.float32(E.P[2, 2]), np.float32(1e6)):
+            assert (z == v).sum() >= 3, v
+        assert np.isnan(z).sum() >= 3
+        with np.errstate(all="ignore"):
+            zv = np.float32(E.P[3, 2]) / (z - np.float32(E.P[2, 2]))
+        usual = np.isfinite(zv) & (np.abs(zv - 1) <= 3.001 * m.px)
+        assert 0.04 < 1 - usual.mean() < 0.12 and (zv[usual].max() - zv[usual].min()) > 5.5 * m.px
+    assert abs(s.ao_radius - 6 * s.px) < 1e-9
+
+
+@pytest.mark.parametrize("rotate", [False, True])
+@pytest.mark.parametrize("face", [False, True])
+def test_ao_on_the_edge_scene_takes_every_select_both_ways(scene, face, rotate):
+    s = scene
+    got = {}
+    for pos_of in (False, True):
+        out, c = _ao(s, face=face, rotate=rotate, pos_of=pos_of)
+        print(f"face={face} rotate={rotate} pos_of={pos_of}: {c['occluded']} occluded of {c['covered']}, {c['taps_taken']} taps taken")
+        assert c["occluded"] >= WAVE and c["covered"] - c["occluded"] >= WAVE and c["taps_taken"] > 0
+        got[pos_of] = out
+    if face:                     # the triangle d_pos_of drops is not written, and still occludes
+        assert (got[True] != got[False]).any()
+        gone = s.winner == s.gone
+        assert (got[True][gone] == s.color[gone]).all() and (got[False][gone] != s.color[gone]).any()
+    else:
+        assert (got[True] == got[False]).all()
+    out, c = _ao(s, table=E.HALO_TABLE, radius_px=32, radius=s.halo_radius, face=face, rotate=rotate)
+    assert c["taps_taken"] >= 100
+    # a strip: rows 5 .. 77 with pixels just outside that WOULD occlude
+    whole, _ = _ao(s, face=face, rotate=rotate)
+    strip, _ = _ao(s, face=face, rotate=rotate, y0=5, y1=77)
+    assert (strip[5:77] != whole[5:77]).any() and (strip[:5] == s.color[:5]).all() and (strip[77:] == s.color[77:]).all()
+
+
+def test_ao_face_normals_meet_overflow_nothing_and_nan_and_a_flip_test_at_zero(scene):
+    """The face mode's cross product overflows to inf ("huge", "z_high"), vanishes ("zero") and is NaN ("z_bad",
+    "z_inf") on triangles the frame shows; and `s > 0` is told from `s >= 0`: at a z of +-inf the view depth is
+    -+0, the pixel's point the origin and s exactly 0, and under a radius that takes every tap the other rule gives
+    other colours."""
+    s = scene
+    ys, xs, t = tex_ref.covered(s.winner, s.T)
+    c = s.tri[t]
+    with np.errstate(all="ignore"):
+        g = np.cross(c[:, 1] - c[:, 0], c[:, 2] - c[:, 0])
+    assert np.isinf(g).any(1).sum() >= WAVE and np.isnan(g).any(1).sum() >= WAVE and (g == 0).all(1).sum() >= WAVE
+    at_zero = np.isinf(s.z[ys, xs]) & np.isfinite(g).all(1) & (g != 0).any(1)
+    assert at_zero.sum() >= WAVE
+    real = ao_ref.face_normals
+
+    def other(tri_t, Pp):
+        A, B, C = tri_t[:, 0], tri_t[:, 1], tri_t[:, 2]
+        e1 = [B[:, k] - A[:, k] for k in range(3)]
+        e2 = [C[:, k] - A[:, k] for k in range(3)]
+        n = [e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]]
+        sgn = (n[0] * Pp[0] + n[1] * Pp[1]) + n[2] * Pp[2]
+        return [np.where(sgn >= 0, -v, v) for v in n]
+    want, _ = _ao(s, face=True, radius=1e30)
+    try:
+        ao_ref.face_normals = other
+        flipped, _ = _ao(s, face=True, radius=1e30)
+    finally:
+        ao_ref.face_normals = real
+    differ = (want != flipped).any(2)
+    print(f"{int(differ.sum())} pixels tell s > 0 from s >= 0")
+    assert differ.sum() >= 16 and np.isinf(s.z[differ]).all()
+
+
+def test_ao_on_the_small_frame(oracle):
+    m = E.mini_scene()
+    for R, table, radius in ((8, E.TABLE, m.ao_radius), (32, E.HALO_TABLE + E.TABLE, m.halo_radius)):
+        for face in (False, True):
+            counts = {}
+            out = ao_ref.ao_pass(m.color, m.z, m.winner, m.tri, E.P, m.normals, table, radius=radius, radius_px=R, face=face,
+                                 counts=counts)
+            assert not np.isnan(out).any()
+            assert counts["occluded"] >= 16 and counts["covered"] - counts["occluded"] >= 16 and counts["taps_taken"] > 0
+    assert m.H < 32 and m.W < 32                                                 # inside one tile, smaller than the halo

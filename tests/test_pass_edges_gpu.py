@@ -1,5 +1,6 @@
 """Every instance of every deferred pass over the hand-built scenes of tests/pass_edges.py, through the C entry points
-(crender_tex_shade, crender_mip_shade, crender_aniso_shade, crender_shadow_shade) on planes the test allocates itself:
+(crender_tex_shade, crender_mip_shade, crender_aniso_shade, crender_shadow_shade, crender_phong_shade,
+crender_ao_shade) on planes the test allocates itself:
 the rasterizer is not involved, so the kernels meet winners that do not contain their pixel, triangles of no area and
 of 10^13 px^2, corners at z = 2^-43, 2^40 or NaN, and take both sides of every window decision of the shared-reciprocal
 shortcut (tests/test_pass_edges_cpu.py counts them).  Bit for bit against the host models; where a model's colour is
@@ -10,8 +11,10 @@ import numpy as np
 import pytest
 
 import aniso_ref
+import ao_ref
 import mip_ref
 import pass_edges as E
+import phong_ref
 import shadow_ref
 import tex_ref
 from util import assert_bit_equal
@@ -39,7 +42,7 @@ class _Device:
 
     def __init__(self, s):
         self.s = s
-        self.kept = {k: getattr(s, k) for k in ("winner", "tri", "uv", "ltri", "normals", "lz", "lwinner")}
+        self.kept = {k: getattr(s, k) for k in ("winner", "tri", "uv", "ltri", "normals", "lz", "lwinner", "z") if hasattr(s, k)}
         for k, v in self.kept.items():
             setattr(self, k, _dev(v))
         if hasattr(s, "pos_of"):
@@ -229,13 +232,136 @@ def test_shadow_shade_every_instance(lib, oracle, edge, K, use_winner):
     edge.untouched(what)
 
 
+def _phong(lib, D, lights, shininess=32, y0=0, y1=None, pos_of=False, ambient=AMBIENT, clamp=255.0, spec=(255.0, 200.0, 17.5)):
+    """(got, want): one call of crender_phong_shade on a fresh copy of the scene's colour plane, and the host model's."""
+    from cython3dmodelrenderer_amd import _capi
+    s = D.s
+    y1 = s.H if y1 is None else y1
+    color = _dev(s.color)
+    L5, mask = phong_ref.lights5(lights)
+    _capi.check(lib.crender_phong_shade(
+        D.winner.data_ptr(), (D.moved if pos_of else D.tri).data_ptr(), s.T, D.pos_of.data_ptr() if pos_of else None,
+        _capi.f32_16(E.P), D.normals.data_ptr(), (C.c_float * L5.size)(*L5.reshape(-1).tolist()), len(lights), mask, ambient,
+        int(shininess).bit_length() - 1, (C.c_float * 3)(*spec), clamp, color.data_ptr(), s.H, s.W, y0, y1, 0, _stream()),
+        "crender_phong_shade")
+    want = phong_ref.phong_pass(s.color, s.winner_without_gone if pos_of else s.winner, s.tri, E.P, s.normals, lights,
+                                ambient=ambient, shininess=shininess, specular_color=spec, clamp=clamp, y0=y0, y1=y1)
+    return color.cpu().numpy(), want
+
+
+@pytest.mark.parametrize("shininess", [1, 32, 4096])
+@pytest.mark.parametrize("kind", E.LIGHT_SETS)
+def test_phong_shade_every_instance(lib, oracle, edge, kind, shininess):
+    """One light runs the instance without the loop frame, four the loop; 0, 5 and 12 squarings.  The pixels outside
+    their winner, the triangles of no area and the corners at z = 0, NaN and +-inf all end as finite colours
+    (tests/test_pass_edges_cpu.py), so every comparison is of bits."""
+    what = f"phong {kind} shininess={shininess}"
+    s = edge.s
+    lights = s.lights[kind]
+    got, want = _phong(lib, edge, lights, shininess)
+    assert np.isfinite(want).all()
+    _same(got, want, what)
+    covered = (s.winner >= 0) & (s.winner < s.T)
+    assert (want.view(np.uint32) != s.color.view(np.uint32)).any(2)[covered].all()
+    assert_bit_equal(got[~covered], s.color[~covered], f"{what}: the background and the pixels of bad winners")
+    y0, y1 = ROWS
+    got, want = _phong(lib, edge, lights, shininess, y0=y0, y1=y1)
+    assert_bit_equal(got[:y0], s.color[:y0], f"{what}: rows above the strip")
+    assert_bit_equal(got[y1:], s.color[y1:], f"{what}: rows below the strip")
+    _same(got, want, f"{what}, rows {y0} .. {y1}")
+    got, want = _phong(lib, edge, lights, shininess, pos_of=True)
+    _same(got, want, f"{what}, d_pos_of")
+    gone = s.winner == s.gone
+    assert_bit_equal(got[gone], s.color[gone], f"{what}: a triangle d_pos_of sends beyond T is background")
+    for kw in (dict(ambient=0.0), dict(clamp=float("inf")), dict(clamp=100.0)):
+        got, want = _phong(lib, edge, lights, shininess, **kw)
+        _same(got, want, f"{what}, {kw}")
+    assert (want == np.float32(100)).any(2).sum() >= 16
+    edge.untouched(what)
+
+
+def _ao(lib, D, table, face, rotate, radius_px, radius, y0=0, y1=None, pos_of=False, want_pos_of=None, strength=2.0, floor=0.0):
+    """(got, want): one call of crender_ao_shade on a fresh copy of the scene's colour plane, and the host model's.
+    `pos_of` hands the kernel d_pos_of and the moved triangles; `want_pos_of` (by default the same) the model."""
+    from cython3dmodelrenderer_amd import _capi
+    s = D.s
+    y1 = s.H if y1 is None else y1
+    color = _dev(s.color)
+    taps2 = (C.c_int8 * (2 * len(table)))(*[v for p in table for v in p])
+    flags = (_capi.AO_ROTATE if rotate else 0) | (_capi.AO_FACE_NORMALS if face else 0)
+    _capi.check(lib.crender_ao_shade(
+        D.winner.data_ptr(), D.z.data_ptr(), (D.moved if pos_of else D.tri).data_ptr(), s.T,
+        D.pos_of.data_ptr() if pos_of else None, _capi.f32_16(E.P), D.normals.data_ptr(), taps2, len(table), radius_px, radius,
+        0.1, strength, floor, color.data_ptr(), s.H, s.W, y0, y1, flags, _stream()), "crender_ao_shade")
+    model_pos_of = pos_of if want_pos_of is None else want_pos_of
+    counts = {}
+    want = ao_ref.ao_pass(s.color, s.z, s.winner, s.moved if model_pos_of else s.tri, E.P, s.normals, table, radius=radius,
+                          radius_px=radius_px, min_cos=0.1, strength=strength, floor=floor, rotate=rotate, face=face,
+                          pos_of=s.pos_of if model_pos_of else None, T=s.T, y0=y0, y1=y1, counts=counts)
+    assert not np.isnan(want).any() and counts["occluded"] > 0
+    return color.cpu().numpy(), want
+
+
+def _ao_table(s, radius_px):
+    """(table, radius): every neighbour at 1 px, tests/test_ao_gpu.py's 16 taps at 8, and at 32 the corners and the
+    edges of the halo as well, under a radius that reaches them."""
+    from cython3dmodelrenderer_amd import ambient_occlusion
+    return {1: (ambient_occlusion.taps(1, 8), s.ao_radius), 8: (E.TABLE, s.ao_radius),
+            32: (E.HALO_TABLE + E.TABLE, s.halo_radius)}[radius_px]
+
+
+@pytest.mark.parametrize("radius_px", [1, 8, 32])
+@pytest.mark.parametrize("rotate", [False, True])
+@pytest.mark.parametrize("face", [False, True])
+def test_ao_shade_on_the_edge_scene(lib, oracle, edge, face, rotate, radius_px):
+    """Face normals of triangles whose cross product is inf, 0 or NaN, a z plane with NaN, +-inf and the division by
+    zero, bad winners in the halo; a strip of rows 5 .. 77 on a frame of less than three tiles of 32 with up to 32 px
+    of halo on every side."""
+    what = f"ao face={face} rotate={rotate} radius_px={radius_px}"
+    s = edge.s
+    table, radius = _ao_table(s, radius_px)
+    got, want = _ao(lib, edge, table, face, rotate, radius_px, radius)
+    _same(got, want, what)
+    y0, y1 = ROWS
+    got, want = _ao(lib, edge, table, face, rotate, radius_px, radius, y0=y0, y1=y1)
+    assert_bit_equal(got[:y0], s.color[:y0], f"{what}: rows above the strip")
+    assert_bit_equal(got[y1:], s.color[y1:], f"{what}: rows below the strip")
+    _same(got, want, f"{what}, rows {y0} .. {y1}")             # (the model does not look across the strip's edge)
+    if face:
+        got, want = _ao(lib, edge, table, face, rotate, radius_px, radius, pos_of=True)
+        _same(got, want, f"{what}, d_pos_of")
+        gone = s.winner == s.gone
+        assert_bit_equal(got[gone], s.color[gone], f"{what}: a triangle d_pos_of sends beyond T is not written")
+        # `s > 0`, not `s >= 0`: under a radius that takes every tap (tests/test_pass_edges_cpu.py counts the pixels)
+        got, want = _ao(lib, edge, table, face, rotate, radius_px, 1e30)
+        _same(got, want, f"{what}, radius 1e30")
+    else:
+        got, want = _ao(lib, edge, table, face, rotate, radius_px, radius, pos_of=True, want_pos_of=False)
+        _same(got, want, f"{what}: the plane mode does not look at d_pos_of")
+    got, want = _ao(lib, edge, table, face, rotate, radius_px, radius, strength=50.0, floor=0.25)
+    _same(got, want, f"{what}, strength 50 over a floor")
+    edge.untouched(what)
+
+
 # ---- the small frame: denominators under the window that are not zero ------------------------------------------------------
 
 @pytest.mark.parametrize("kind,kw", [("tex", dict(persp=True, bilinear=True, light=False)), ("tex", dict(persp=False, bilinear=False, light=True)),
                                      ("mip", dict(persp=True, light=False)), ("mip", dict(persp=False, light=True)),
-                                     ("aniso", dict(persp=True, A=16, light=True)), ("aniso", dict(persp=False, A=4, light=False))])
+                                     ("aniso", dict(persp=True, A=16, light=True)), ("aniso", dict(persp=False, A=4, light=False)),
+                                     ("phong", dict(lights="point", shininess=1)), ("phong", dict(lights="direction", shininess=4096)),
+                                     ("phong", dict(lights="four", shininess=32)), ("ao", dict(radius_px=8)), ("ao", dict(radius_px=32))])
 def test_the_small_frame(lib, oracle, mini, textures, kind, kw):
-    for name in ("64x97", "3x1000"):
+    if kind == "phong":
+        got, want = _phong(lib, mini, mini.s.lights[kw["lights"]], kw["shininess"])
+        assert np.isfinite(want).all()
+        _same(got, want, f"28 x 20, phong {kw}")
+    elif kind == "ao":               # the whole frame lies inside one tile and is smaller than the halo of 32
+        table, radius = _ao_table(mini.s, kw["radius_px"])
+        for face in (False, True):
+            for rotate in (False, True):
+                got, want = _ao(lib, mini, table, face, rotate, kw["radius_px"], radius)
+                _same(got, want, f"28 x 20, ao face={face} rotate={rotate} {kw}")
+    for name in ("64x97", "3x1000") if kind in ("tex", "mip", "aniso") else ():
         got, want = _texture_family(lib, oracle, mini, kind, textures[name], **kw)
         _same(got, want, f"28 x 20, {kind} {kw}, texture {name}")
     mini.untouched(f"28 x 20, {kind}")
@@ -249,15 +375,17 @@ def test_the_small_frame_shadowed(lib, oracle, mini):
 
 # ---- the tall frame: the row-block loop's second trip --------------------------------------------------------------------
 
-@pytest.mark.parametrize("kind", ["tex", "mip", "aniso", "shadow"])
+@pytest.mark.parametrize("kind", ["tex", "mip", "aniso", "shadow", "phong"])
 def test_more_row_blocks_than_the_grid_is_tall(lib, oracle, tall, textures, kind):
     """H = 524 296, W = 3, rows 3 .. H: 65 537 blocks of 8 rows against a grid of 65 535, so the last sixteen rows are
     the loop's second trip.  No plan can be that tall: only the entry reaches it.  The texture families run with the
-    light, which touches every pixel of the rows."""
+    light, which touches every pixel of the rows; the Phong pass with four lights."""
     s = tall.s
     y0 = E.TALL_Y0
     if kind == "shadow":
         got, want = _shadow(lib, tall, 3, True, y0=y0)
+    elif kind == "phong":
+        got, want = _phong(lib, tall, s.lights["four"], y0=y0)
     else:
         kw = dict(tex=dict(persp=True, bilinear=True), mip=dict(persp=True), aniso=dict(persp=True, A=4))[kind]
         got, want = _texture_family(lib, oracle, tall, kind, textures["64x97"], light=True, y0=y0, **kw)

@@ -4,15 +4,19 @@ pass must raise and change nothing), clear(), textures bound, rebound at another
 every mode, shadow passes against a second filler that renders the light's view first (or against the camera itself),
 two passes on one frame, edits of a colour view carried into a pass, resolves and getters — against an oracle frame and
 the host models of the passes (tests/tex_ref.py, mip_ref.py, aniso_ref.py, shadow_ref.py, ssaa_ref.py) applied to it
-in the same order.  Every comparison is bit for bit."""
+in the same order.  The sessions of the "lit" family draw Phong and occlusion passes among them (tests/phong_ref.py,
+ao_ref.py), chain up to four passes on one frame and edit the z view under an occlusion pass.  Every comparison is bit
+for bit."""
 import os
 
 import numpy as np
 import pytest
 
 import aniso_ref
+import ao_ref
 import mip_ref
 import pass_sessions as S
+import phong_ref
 import shadow_ref
 import ssaa_ref
 import tex_ref
@@ -61,12 +65,15 @@ def pool(oracle):
     return _Pool()
 
 
-@pytest.mark.parametrize("seed", range(S.SEEDS * _SOAK))
-def test_fuzz_a_filler_through_its_passes(oracle, pool, seed):
+_SESSIONS = [(family, seed) for family in S.FAMILIES for seed in range(S.SEEDS * _SOAK)]
+
+
+@pytest.mark.parametrize("family,seed", _SESSIONS, ids=[str(k) if fam == "passes" else f"{fam}-{k}" for fam, k in _SESSIONS])
+def test_fuzz_a_filler_through_its_passes(oracle, pool, family, seed):
     import torch
-    from cython3dmodelrenderer_amd import shadow
+    from cython3dmodelrenderer_amd import ambient_occlusion, shadow
     from cython3dmodelrenderer_amd.pixel_buffer_filler import AdvancedPixelBufferFiller
-    opt, steps = S.plan(seed)
+    opt, steps = S.plan(seed, family=family)
     H, W, Hl, Wl = opt["H"], opt["W"], opt["Hl"], opt["Wl"]
     f = AdvancedPixelBufferFiller(H, W, fov=45, track_winner=True, **opt["kw"])
     g = AdvancedPixelBufferFiller(Hl, Wl, fov=45, track_winner=True, **opt["light_kw"])
@@ -87,7 +94,7 @@ def test_fuzz_a_filler_through_its_passes(oracle, pool, seed):
     story = []
 
     def what(k, more=""):
-        return f"pass session {seed} ({H}x{W}, {opt['kw']}; light {Hl}x{Wl}, {opt['light_kw']}), step {k} {more}: {story}"
+        return f"pass session {family} {seed} ({H}x{W}, {opt['kw']}; light {Hl}x{Wl}, {opt['light_kw']}), step {k} {more}: {story}"
 
     def ref_clear():                    # (a strip filler clears, and renders, its own rows only)
         ref.z_buffer[y0:y1] = np.float32(1e6); ref.color_buffer[y0:y1] = 0; ref.normals_buffer[y0:y1] = 0
@@ -122,6 +129,16 @@ def test_fuzz_a_filler_through_its_passes(oracle, pool, seed):
             else:
                 out = tex_ref.texture_pass(ref.color_buffer, ref.winner, tri, ref.proj_mat, uv, tex, mode["perspective"],
                                            mode["filter"] == "bilinear", y0=y0, y1=y1, **lit)
+        elif mode["kind"] == "phong":
+            out = phong_ref.phong_pass(ref.color_buffer, ref.winner, tri, ref.proj_mat, ref.normals_buffer, mode["lights"],
+                                       ambient=mode["ambient"], shininess=mode["shininess"],
+                                       specular_color=mode["specular_color"], clamp=mode["clamp"], y0=y0, y1=y1)
+        elif mode["kind"] == "ao":
+            taps = mode["taps"]
+            table = ambient_occlusion.taps(mode["radius_px"], taps) if isinstance(taps, int) else list(taps)
+            out = ao_ref.ao_pass(ref.color_buffer, ref.z_buffer, ref.winner, tri, ref.proj_mat, ref.normals_buffer, table,
+                                 radius=mode["radius"], radius_px=mode["radius_px"], strength=mode["strength"],
+                                 floor=mode["floor"], rotate=mode["rotate"], face=mode["normals"] == "face", y0=y0, y1=y1)
         else:
             if mode["own"]:
                 ltri, PL, lz, lw = tri, ref.proj_mat, ref.z_buffer, ref.winner
@@ -137,6 +154,12 @@ def test_fuzz_a_filler_through_its_passes(oracle, pool, seed):
         if mode["kind"] == "texture":
             f.texture_pass(perspective=mode["perspective"], filter=mode["filter"], anisotropy=mode["anisotropy"],
                            light_direction=light3 if mode["light"] else None)
+        elif mode["kind"] == "phong":
+            f.phong_pass(mode["lights"], ambient=mode["ambient"], shininess=mode["shininess"],
+                         specular_color=mode["specular_color"], clamp=mode["clamp"])
+        elif mode["kind"] == "ao":
+            f.ao_pass(radius=mode["radius"], radius_px=mode["radius_px"], taps=mode["taps"], strength=mode["strength"],
+                      floor=mode["floor"], rotate=mode["rotate"], normals=mode["normals"])
         else:
             f.shadow_pass(bias=mode["bias"], pcf=mode["pcf"], ambient=mode["ambient"], use_winner=mode["use_winner"])
 
@@ -221,12 +244,12 @@ def test_fuzz_a_filler_through_its_passes(oracle, pool, seed):
         elif op == "unbind":
             f.bind_texture(None, None)
             state["bound"] = None
-        elif op in ("texture_pass", "shadow_pass"):
+        elif op in ("texture_pass", "shadow_pass", "phong_pass", "ao_pass"):
             a_pass(k, step["mode"])
             continue
-        elif op == "two passes":
+        elif op in ("two passes", "chain"):
             for n, mode in enumerate(step["modes"]):
-                a_pass(k, mode, f"pass {n + 1} of two")
+                a_pass(k, mode, f"pass {n + 1} of {len(step['modes'])}")
             continue
         elif op == "edit then pass":
             view = f.get_color_buffer()
@@ -238,9 +261,17 @@ def test_fuzz_a_filler_through_its_passes(oracle, pool, seed):
             mode = step["mode"]
             if mode["kind"] == "shadow":
                 light_frame(mode)
+            zview = pushed = None
+            if step.get("z_edit"):     # covered pixels of the rows, 2e-3 nearer the eye: they occlude what surrounds them
+                zview = f.get_z_buffer()
+                assert_bit_equal(zview[y0:y1], ref.z_buffer[y0:y1], what(k, "z before the edit"))
+                pushed = np.where(ref.winner[a:b] >= 0, ref.z_buffer[a:b] - np.float32(2e-3), ref.z_buffer[a:b])
             if mode["legal"]:
                 view[a:b] = np.float32(step["value"])
                 ref.color_buffer[a:b] = np.float32(step["value"])
+                if zview is not None:
+                    zview[a:b] = pushed
+                    ref.z_buffer[a:b] = pushed
                 device_pass(mode)
                 host_pass(mode)
                 check(k, f"rows {a} .. {b} edited, then a pass")
@@ -249,10 +280,15 @@ def test_fuzz_a_filler_through_its_passes(oracle, pool, seed):
             else:
                 keep = view[a:b].copy()
                 view[a:b] = np.float32(step["value"])
+                if zview is not None:
+                    zkeep = zview[a:b].copy()
+                    zview[a:b] = pushed
                 with pytest.raises(ValueError):
                     device_pass(mode)
                 check(k, "a refused pass after an edit: nothing is carried, nothing changes")
                 view[a:b] = keep                       # (the caller takes the edit back)
+                if zview is not None:
+                    zview[a:b] = zkeep
             continue
         elif op == "resolve":
             s = max(d for d in range(1, step["factor"] + 1) if H % d == 0 and W % d == 0 and y0 % d == 0 and y1 % d == 0)
