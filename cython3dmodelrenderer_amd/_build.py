@@ -17,50 +17,38 @@ LIB_PATH = os.path.join(_HERE, "libcrender_hip.so")
 # model_ops.hip  rows f1-f4 of SURVEY 8f     abi.hip  plans, frames, swap chain (no kernels)
 SOURCES = ["abi.hip", "binning.hip", "raster.hip", "model_ops.hip"]
 HEADERS = ["common.h", "binning.h", "plan.h", "raster_math.h", os.path.join("..", "..", "include", "crender_hip.h")]
-# wireframe.hip  EdgeOnlyPixelBufferFiller (include/crender_wire.h).  Linked into the same library but
-# kept out of source_sha16(): that fingerprint names the kernels the committed profiles/*.json were
-# measured on, and the wireframe kernels are none of them.
-WIRE_SOURCES = ["wireframe.hip"]
-WIRE_HEADERS = [os.path.join("..", "..", "include", "crender_wire.h")]
-# pyfill.hip  the numpy filler of crender/py (include/crender_py.h); kept out of source_sha16() likewise.
-PY_SOURCES = ["pyfill.hip"]
-PY_HEADERS = [os.path.join("..", "..", "include", "crender_py.h")]
-# texture.hip  the deferred texture pass over the winner plane (include/crender_tex.h); kept out of
-# source_sha16() likewise.
-TEX_SOURCES = ["texture.hip"]
-TEX_HEADERS = [os.path.join("..", "..", "include", "crender_tex.h")]
-# texmip.hip  the mip chain and the trilinear texture pass (include/crender_mip.h); kept out of
-# source_sha16() likewise.
-MIP_SOURCES = ["texmip.hip"]
-MIP_HEADERS = [os.path.join("..", "..", "include", "crender_mip.h"), "mip_sample.h"]
-# texaniso.hip  the anisotropic texture pass (include/crender_aniso.h); kept out of source_sha16() likewise.
-# mip_sample.h is what it shares with texmip.hip: the chain's layout, the bilinear sample, uv at a pixel.
-ANISO_SOURCES = ["texaniso.hip"]
-ANISO_HEADERS = [os.path.join("..", "..", "include", "crender_aniso.h"), "mip_sample.h"]
-# resolve.hip  the supersampling resolve with the fused light and uint8 presentation (include/crender_ssaa.h);
-# kept out of source_sha16() likewise.
-SSAA_SOURCES = ["resolve.hip"]
-SSAA_HEADERS = [os.path.join("..", "..", "include", "crender_ssaa.h")]
-# shadow.hip  the deferred shadow-mapping pass over the winner plane (include/crender_shadow.h); kept out of
-# source_sha16() likewise.
-SHADOW_SOURCES = ["shadow.hip"]
-SHADOW_HEADERS = [os.path.join("..", "..", "include", "crender_shadow.h")]
-# phong.hip  the deferred Blinn-Phong lighting pass over the winner plane (include/crender_phong.h); kept out of
-# source_sha16() likewise.
-PHONG_SOURCES = ["phong.hip"]
-PHONG_HEADERS = [os.path.join("..", "..", "include", "crender_phong.h")]
-# ao.hip  the deferred ambient-occlusion pass over the z, winner and normal planes (include/crender_ao.h); kept out of
-# source_sha16() likewise.
-AO_SOURCES = ["ao.hip"]
-AO_HEADERS = [os.path.join("..", "..", "include", "crender_ao.h")]
-# winner_pass.h  what the deferred passes over the winner plane share (texture.hip, texmip.hip, texaniso.hip,
-# shadow.hip, phong.hip): the pixel frame, the corner gather, the store with the fused light, the texel fetches and the launch
-# geometry; a group of its own, so that each pass's header list stays its own; kept out of source_sha16() likewise.
-PASS_HEADERS = ["winner_pass.h"]
-# chain.hip  the swap chain's shared slot: one slot on the caller's stream (include/crender_chain.h; host code
-# only, over the pipeline handle of plan.h); kept out of source_sha16() likewise: it launches nothing.
-CHAIN_SOURCES = ["chain.hip"]
-CHAIN_HEADERS = [os.path.join("..", "..", "include", "crender_chain.h")]
+_INCLUDE = os.path.join("..", "..", "include")
+# The other units of the library, in link order: name -> (sources, headers).  All are linked into the same library
+# but kept out of source_sha16(): that fingerprint names the kernels the committed profiles/*.json were measured on,
+# and these kernels are none of them.  _capi.UNIT_SIGNATURES is keyed alike.
+UNITS = {
+    # wireframe.hip  EdgeOnlyPixelBufferFiller (include/crender_wire.h)
+    "wire": (["wireframe.hip"], [os.path.join(_INCLUDE, "crender_wire.h")]),
+    # pyfill.hip  the numpy filler of crender/py (include/crender_py.h)
+    "py": (["pyfill.hip"], [os.path.join(_INCLUDE, "crender_py.h")]),
+    # texture.hip  the deferred texture pass over the winner plane (include/crender_tex.h)
+    "tex": (["texture.hip"], [os.path.join(_INCLUDE, "crender_tex.h")]),
+    # texmip.hip  the mip chain and the trilinear texture pass (include/crender_mip.h)
+    "mip": (["texmip.hip"], [os.path.join(_INCLUDE, "crender_mip.h"), "mip_sample.h"]),
+    # texaniso.hip  the anisotropic texture pass (include/crender_aniso.h).  mip_sample.h is what it shares with
+    # texmip.hip: the chain's layout, the bilinear sample, uv at a pixel.
+    "aniso": (["texaniso.hip"], [os.path.join(_INCLUDE, "crender_aniso.h"), "mip_sample.h"]),
+    # resolve.hip  the supersampling resolve with the fused light and uint8 presentation (include/crender_ssaa.h)
+    "ssaa": (["resolve.hip"], [os.path.join(_INCLUDE, "crender_ssaa.h")]),
+    # shadow.hip  the deferred shadow-mapping pass over the winner plane (include/crender_shadow.h)
+    "shadow": (["shadow.hip"], [os.path.join(_INCLUDE, "crender_shadow.h")]),
+    # phong.hip  the deferred Blinn-Phong lighting pass over the winner plane (include/crender_phong.h)
+    "phong": (["phong.hip"], [os.path.join(_INCLUDE, "crender_phong.h")]),
+    # ao.hip  the deferred ambient-occlusion pass over the z, winner and normal planes (include/crender_ao.h)
+    "ao": (["ao.hip"], [os.path.join(_INCLUDE, "crender_ao.h")]),
+    # winner_pass.h  what the deferred passes over the winner plane share (texture.hip, texmip.hip, texaniso.hip,
+    # shadow.hip, phong.hip): the pixel frame, the corner gather, the store with the fused light, the texel fetches and
+    # the launch geometry; a unit of its own, without a source, so that each pass's header list stays its own.
+    "pass": ([], ["winner_pass.h"]),
+    # chain.hip  the swap chain's shared slot: one slot on the caller's stream (include/crender_chain.h; host code
+    # only, over the pipeline handle of plan.h): it launches nothing.
+    "chain": (["chain.hip"], [os.path.join(_INCLUDE, "crender_chain.h")]),
+}
 
 # Float parity with the reference depends on these (DESIGN.md "Numerics"):
 #   -ffp-contract=off                           no FMA contraction (hipcc defaults to fast)
@@ -102,18 +90,23 @@ def source_sha16() -> str:
     return h.hexdigest()[:16]
 
 
+def library_sources() -> list:
+    """The translation units of the library, in link order (which decides the library's bytes)."""
+    return SOURCES + [src for sources, _ in UNITS.values() for src in sources]
+
+
+def build_inputs() -> list:
+    """Paths of everything whose change makes the library stale: the fingerprinted sources and headers, every unit's
+    sources and headers, and this file (the flags).  A header that two units list is named once."""
+    names = SOURCES + HEADERS + [name for sources, headers in UNITS.values() for name in sources + headers]
+    return [os.path.join(SRC_DIR, name) for name in dict.fromkeys(names)] + [os.path.abspath(__file__)]
+
+
 def needs_build() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     built = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(SRC_DIR, s) for s in SOURCES + HEADERS + WIRE_SOURCES + WIRE_HEADERS +
-                                                PY_SOURCES + PY_HEADERS + TEX_SOURCES + TEX_HEADERS +
-                                                MIP_SOURCES + MIP_HEADERS + ANISO_SOURCES + ANISO_HEADERS +
-                                                SSAA_SOURCES + SSAA_HEADERS + SHADOW_SOURCES + SHADOW_HEADERS +
-                                                PHONG_SOURCES + PHONG_HEADERS + AO_SOURCES + AO_HEADERS + CHAIN_SOURCES + CHAIN_HEADERS +
-                                                PASS_HEADERS] + \
-        [os.path.abspath(__file__)]
-    return any(os.path.getmtime(d) > built for d in deps)
+    return any(os.path.getmtime(d) > built for d in build_inputs())
 
 
 def compile_library(out: str, extra_flags=(), sources=None, src_dir: str = SRC_DIR, verbose: bool = False,
@@ -122,8 +115,7 @@ def compile_library(out: str, extra_flags=(), sources=None, src_dir: str = SRC_D
     defines of diagnostic builds (-DCRENDER_STAMPS, ...)."""
     import tempfile
     from concurrent.futures import ThreadPoolExecutor
-    sources = list(sources or SOURCES + WIRE_SOURCES + PY_SOURCES + TEX_SOURCES + MIP_SOURCES + ANISO_SOURCES +
-                   SSAA_SOURCES + SHADOW_SOURCES + PHONG_SOURCES + AO_SOURCES + CHAIN_SOURCES)
+    sources = list(sources or library_sources())
     err = subprocess.DEVNULL if quiet else None
     with tempfile.TemporaryDirectory(prefix="crender_build_") as tmp:
         objs = [os.path.join(tmp, os.path.splitext(s)[0] + ".o") for s in sources]

@@ -78,16 +78,20 @@ SIGNATURES = {
     "crender_model_texture_colors": (_i32, [_vp, _i32, _i64, _vp, _i32, _i32, _vp, _vp]),
 }
 
+# The entry points of the library's other units, each bound from a table of its own beside its constants:
+# unit -> {name: (restype, argtypes)}, keyed like _build.UNITS (whose "pass" is a header without entry points).
+UNIT_SIGNATURES = {}
+
 # the wireframe filler's entry points (include/crender_wire.h), bound from a table of their own
 WIRE_DOTS, WIRE_FORCE_COLORS, WIRE_CLEAR = 1, 2, 4
-WIRE_SIGNATURES = {
+UNIT_SIGNATURES["wire"] = {
     "crender_wire_key_bytes": (_sz, [_i32, _i32]),
     "crender_wire_draw": (_i32, [_vp, _vp, _i64, _f32p, _vp, _vp, _vp, _vp, _i32, _i32, _u32, _vp, _vp]),
 }
 
 # the numpy filler's entry points (include/crender_py.h), bound from a table of their own
 PY_CLEAR = 1
-PY_SIGNATURES = {
+UNIT_SIGNATURES["py"] = {
     "crender_py_scratch_bytes": (_sz, [_i32, _i32, _i64]),
     "crender_py_draw": (_i32, [_vp, _vp, _vp, _i64, _f32p, _vp, _vp, _vp, _i32, _i32, _u32, _vp, _vp, _vp]),
     "crender_py_guro": (_i32, [_vp, _vp, _f32p, _i32, _i32, _vp]),
@@ -95,7 +99,7 @@ PY_SIGNATURES = {
 
 # the deferred texture pass (include/crender_tex.h), bound from a table of its own
 TEX_PERSPECTIVE, TEX_BILINEAR = 1, 2
-TEX_SIGNATURES = {
+UNIT_SIGNATURES["tex"] = {
     "crender_tex_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _i32, _vp, _f32p, _vp,
                                  _i32, _i32, _i32, _i32, _u32, _vp]),
 }
@@ -104,7 +108,7 @@ TEX_SIGNATURES = {
 MIP_PERSPECTIVE = 1
 MIP_MAX_LEVELS = 16
 _u64p = C.POINTER(C.c_uint64)
-MIP_SIGNATURES = {
+UNIT_SIGNATURES["mip"] = {
     "crender_mip_layout": (_i32, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _u64p, _u64p]),
     "crender_mip_build": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "crender_mip_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _i32, _vp, _f32p, _vp,
@@ -114,7 +118,7 @@ MIP_SIGNATURES = {
 # the anisotropic texture pass (include/crender_aniso.h), bound from a table of its own: crender_mip_shade's
 # arguments with max_aniso in front of the stream
 ANISO_MAX = 16
-ANISO_SIGNATURES = {
+UNIT_SIGNATURES["aniso"] = {
     "crender_aniso_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _i32, _vp, _f32p, _vp,
                                    _i32, _i32, _i32, _i32, _u32, _i32, _vp]),
 }
@@ -122,13 +126,13 @@ ANISO_SIGNATURES = {
 # the supersampling resolve (include/crender_ssaa.h), bound from a table of its own
 SSAA_U8, SSAA_FLIP = 1, 2
 SSAA_MAX = 8
-SSAA_SIGNATURES = {
+UNIT_SIGNATURES["ssaa"] = {
     "crender_ssaa_resolve": (_i32, [_vp, _vp, _f32p, _i32, _i32, _i32, _i32, _i32, _vp, _u32, _vp]),
 }
 
 # the deferred shadow pass (include/crender_shadow.h), bound from a table of its own
 SHADOW_PCF = (1, 3, 5)
-SHADOW_SIGNATURES = {
+UNIT_SIGNATURES["shadow"] = {
     "crender_shadow_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _f32p, _vp, _vp, _i32, _i32, C.c_float, C.c_float,
                                     _i32, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
 }
@@ -136,7 +140,7 @@ SHADOW_SIGNATURES = {
 # the deferred Phong pass (include/crender_phong.h), bound from a table of its own
 PHONG_MAX_LIGHTS = 4
 PHONG_MAX_SHININESS = 1 << 12
-PHONG_SIGNATURES = {
+UNIT_SIGNATURES["phong"] = {
     "crender_phong_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _f32p, _i32, _u32, C.c_float, _i32, _f32p, C.c_float,
                                    _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
 }
@@ -145,13 +149,13 @@ PHONG_SIGNATURES = {
 AO_ROTATE, AO_FACE_NORMALS = 1, 2
 AO_MAX_TAPS = 64
 AO_MAX_RADIUS_PX = 32
-AO_SIGNATURES = {
+UNIT_SIGNATURES["ao"] = {
     "crender_ao_shade": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _i32, C.c_float, C.c_float, C.c_float,
                                 C.c_float, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
 }
 
 # the swap chain's shared slot (include/crender_chain.h), bound from a table of its own
-CHAIN_SIGNATURES = {
+UNIT_SIGNATURES["chain"] = {
     "crender_pipeline_share_stream": (_i32, [_vp, _i32, _vp]),
     "crender_pipeline_unshare": (_i32, [_vp]),
     "crender_pipeline_shared_slot": (_i32, [_vp]),
@@ -181,13 +185,11 @@ def load():
             f"{path} is missing: build it with `python -m cython3dmodelrenderer_amd._build` "
             "(or __graft_entry__.build()).  There is no CPU fallback for the rasterizer.")
     L = C.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(WIRE_SIGNATURES.items()) + \
-            list(PY_SIGNATURES.items()) + list(TEX_SIGNATURES.items()) + list(MIP_SIGNATURES.items()) + \
-            list(ANISO_SIGNATURES.items()) + list(SSAA_SIGNATURES.items()) + list(SHADOW_SIGNATURES.items()) + \
-            list(PHONG_SIGNATURES.items()) + list(AO_SIGNATURES.items()) + list(CHAIN_SIGNATURES.items()):
-        fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
-        fn.restype = res
-        fn.argtypes = args
+    for table in (SIGNATURES, *UNIT_SIGNATURES.values()):
+        for name, (res, args) in table.items():
+            fn = getattr(L, name)      # AttributeError if the library lacks a declared symbol
+            fn.restype = res
+            fn.argtypes = args
     got = L.crender_abi_version()
     if got != ABI_VERSION:
         raise CrenderError(f"libcrender_hip.so ABI {got}, binding expects {ABI_VERSION}")

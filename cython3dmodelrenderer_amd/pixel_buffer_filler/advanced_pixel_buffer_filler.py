@@ -14,6 +14,9 @@ goes through the C ABI of libcrender_hip.so (include/crender_hip.h) — the per-
 same C entry points; plan management and the rarely used calls through ctypes.  torch supplies
 device memory and the HIP stream only.  There is no CPU path: without the HIP library, the
 extension or a GPU the constructor raises.
+This file is plans, staging slots and the swap chain; the deferred passes over the winner plane
+(``texture_pass``, ``shadow_pass``, ``phong_pass``, ``ao_pass`` and what they bind) are
+``_deferred_passes.DeferredPasses``.
 
 Behaviour kept from the reference
   * buffers persist across ``render_model`` calls and are never cleared, so successive
@@ -44,41 +47,8 @@ import numpy as np
 import torch
 
 from .. import _capi, _torch_ext
+from ._deferred_passes import DeferredPasses, _as_device_f32, _check_host_f32
 from ._device_planes import DevicePlanes
-
-
-def _host_f32(a):
-    """numpy view of a float32 host array, with what the reference raises for None (``None.copy()``)
-    and for another dtype (.pyx:94-96 binds ``float[:, :, :]``)."""
-    if a is None:
-        raise AttributeError("'NoneType' object has no attribute 'copy'")
-    arr = np.asarray(a)
-    if arr.dtype != np.float32:
-        kind = "double" if arr.dtype == np.float64 else str(arr.dtype)
-        raise ValueError(f"Buffer dtype mismatch, expected 'float' but got '{kind}'")
-    return arr
-
-
-def _check_host_f32(a, name):
-    """numpy view of a [T, 3, 3] float32 host array (any strides), with the reference's errors."""
-    arr = _host_f32(a)
-    if arr.ndim != 3 or arr.shape[1] != 3 or arr.shape[2] != 3:
-        raise ValueError(f"{name} must have shape [T, 3, 3], got {tuple(arr.shape)}")
-    return arr
-
-
-def _as_device_f32(a, name, device):
-    """[T, 3, 3] float32 contiguous tensor on `device` from numpy / torch input."""
-    if isinstance(a, torch.Tensor):
-        if a.dtype != torch.float32:
-            raise ValueError(f"Buffer dtype mismatch, expected 'float' but got '{a.dtype}' ({name})")
-        t = a.to(device=device).contiguous()
-    else:
-        t = torch.from_numpy(np.ascontiguousarray(_host_f32(a))).to(device)
-    if t.dim() != 3 or t.shape[1] != 3 or t.shape[2] != 3:
-        raise ValueError(f"{name} must have shape [T, 3, 3], got {tuple(t.shape)}")
-    return t
-
 
 # Handle of torch's current stream on a device, and the current device index: the private fast
 # paths when this torch has them (the public ones build a Stream object / go through Python
@@ -307,7 +277,7 @@ class _FramePipeline:
         return n.value, ms.value
 
 
-class AdvancedPixelBufferFiller(DevicePlanes):
+class AdvancedPixelBufferFiller(DevicePlanes, DeferredPasses):
     def __init__(self, h, w, fov=90.0, z_near=0.1, z_far=1000.0, n_threads=1, *,
                  device=None, tile=0, row_strip=None, track_winner=False, cache_inputs=False,
                  bin_capacity=0, direct_bins=True, pipeline=False, pipeline_depth=None,
@@ -370,9 +340,6 @@ class AdvancedPixelBufferFiller(DevicePlanes):
         self._order = None             # (orig_of, pos_of) int32 device tensors of the resident inputs
         self._plan_order = None        # what the single-stream plan currently holds
         self._fused_light = None       # (l0, l1, l2): illumination fused into cleared frames
-        self._texture = None           # (uv [T, 3, 2] float32, image [th, tw, 3] uint8) device tensors: bind_texture
-        self._mip = None               # (chain, [(h_k, w_k)], [byte offsets]) of that image: bind_texture(mipmaps=True)
-        self._shadow = None            # (the light's filler, its vertices [T, 3, 3] float32 on the device): bind_shadow_map
         self._plan_light = None        # what the single-stream plan currently holds
         self._pipeline = bool(pipeline)  # render_frame(): overlap consecutive frames (see _FramePipeline)
         # share_caller_stream: the chain's last slot runs on the caller's stream (_FramePipeline).  None = the
@@ -791,285 +758,6 @@ class AdvancedPixelBufferFiller(DevicePlanes):
         render)."""
         self._join_pipe()
         self._fused_light = None if light_direction is None else tuple(float(v) for v in light_direction)
-
-    def bind_texture(self, uv_by_triangles, texture, mipmaps=False):
-        """Keep a texture resident for ``texture_pass``: `uv_by_triangles` float32 [T, 3, 2] (u, v per corner,
-        in the caller's triangle order: ``Model.get_texture_coords_by_triangles()``) and `texture` uint8
-        [th, tw, 3] (``Model.get_texture()``), numpy arrays or device tensors.  With `mipmaps` the texture's
-        mip chain is built on the device as well (``crender_mip_build``, on torch's current stream), which
-        ``texture_pass(filter="trilinear")`` needs.  ``bind_texture(None, None)`` drops both."""
-        if uv_by_triangles is None and texture is None:
-            self._texture = self._mip = None
-            return
-        if uv_by_triangles is None or texture is None:
-            raise ValueError("bind_texture needs both the texture coordinates and the texture (or None, None)")
-        uv = uv_by_triangles if isinstance(uv_by_triangles, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(uv_by_triangles))
-        tex = texture if isinstance(texture, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(texture))
-        if uv.dtype != torch.float32 or uv.dim() != 3 or uv.shape[1] != 3 or uv.shape[2] != 2:
-            raise ValueError(f"uv_by_triangles must be float32 [T, 3, 2], got {uv.dtype} {tuple(uv.shape)}")
-        if tex.dtype != torch.uint8 or tex.dim() != 3 or tex.shape[2] < 3 or tex.shape[0] < 1 or tex.shape[1] < 1:
-            raise ValueError(f"texture must be uint8 [th, tw, 3], got {tex.dtype} {tuple(tex.shape)}")
-        bound = (uv.to(self.device).contiguous(), tex[:, :, :3].to(self.device).contiguous())
-        self._mip = self._build_mip_chain(bound[1]) if mipmaps else None
-        self._texture = bound
-
-    def _build_mip_chain(self, tex):
-        """(chain uint8 [total bytes], [(h_k, w_k)], [byte offset of level k]) of a device texture."""
-        th, tw = int(tex.shape[0]), int(tex.shape[1])
-        n = _capi.MIP_MAX_LEVELS
-        levels, total = C.c_int32(0), C.c_uint64(0)
-        hs, ws, offs = (C.c_int32 * n)(), (C.c_int32 * n)(), (C.c_uint64 * n)()
-        _capi.check(self._lib.crender_mip_layout(th, tw, C.byref(levels), hs, ws, offs, C.byref(total)),
-                    "crender_mip_layout")
-        chain = torch.empty(total.value, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _capi.check(self._lib.crender_mip_build(tex.data_ptr(), th, tw, chain.data_ptr(), self._stream()),
-                        "crender_mip_build")
-        L = levels.value
-        return chain, [(hs[k], ws[k]) for k in range(L)], [offs[k] for k in range(L)]
-
-    def mip_levels(self):
-        """[(h_k, w_k)] of the bound texture's mip chain, or None without one."""
-        return None if self._mip is None else list(self._mip[1])
-
-    def get_mip_level(self, k):
-        """Level `k` of the mip chain: a uint8 [h_k, w_k, 3] device tensor that views the chain."""
-        if self._mip is None:
-            raise ValueError("no mip chain is bound: bind_texture(..., mipmaps=True)")
-        chain, levels, offsets = self._mip
-        if not 0 <= k < len(levels):
-            raise IndexError(f"the chain has levels 0 .. {len(levels) - 1}, got {k}")
-        h, w = levels[k]
-        return chain[offsets[k]:offsets[k] + 3 * h * w].view(h, w, 3)
-
-    def texture_pass(self, perspective=False, filter="nearest", light_direction=None, anisotropy=1):
-        """Per-pixel texture mapping of the LAST frame's colour plane (``crender_tex_shade``,
-        include/crender_tex.h): every pixel a triangle won gets the bound texture's texel at its
-        interpolated (u, v) — affine like the reference's attributes, or perspective-correct; the nearest
-        texel or four of them — instead of the blend of three vertex colours.  ``filter="trilinear"``
-        (``crender_mip_shade``, include/crender_mip.h) picks a mip level per pixel from the screen-space
-        derivatives of (u, v) and blends the bilinear samples of two levels; it needs the chain of
-        ``bind_texture(..., mipmaps=True)``.  With `anisotropy` A from 2 to 16 on top of it
-        (``crender_aniso_shade``, include/crender_aniso.h) the level comes from the shorter of a pixel's two
-        texel-space steps, never more than A times shorter than the longer, and up to A trilinear samples
-        span the longer one: a surface seen at a grazing angle keeps its detail across the short axis.  Rows of
-        the filler's ``row_strip``, on torch's current stream.  With `light_direction` (the illumination object's own
-        flipped, normalised vector, as ``set_fused_illumination`` takes it) the pass also shades every
-        pixel of the rows: the same bits as the separate illumination pass afterwards, without its
-        traffic.
-
-        The frame is settled first (one stream synchronisation, as every getter does): a frame whose bin
-        lists overflowed is rendered again, and the pass must land on the frame that stays."""
-        if filter not in ("nearest", "bilinear", "trilinear"):
-            raise ValueError(f"filter must be 'nearest', 'bilinear' or 'trilinear', got {filter!r}")
-        if isinstance(anisotropy, bool) or not isinstance(anisotropy, int) or not 1 <= anisotropy <= _capi.ANISO_MAX:
-            raise ValueError(f"anisotropy must be an int from 1 to {_capi.ANISO_MAX}, got {anisotropy!r}")
-        if anisotropy > 1 and filter != "trilinear":
-            raise ValueError(f"anisotropy={anisotropy} needs filter=\"trilinear\" (and its mip chain), got {filter!r}")
-        if self._pipeline:
-            raise ValueError("texture_pass is not available on a swap chain (pipeline=True): per-slot passes are not implemented")
-        if self.winner_buffer is None:
-            raise ValueError("texture_pass needs the winner plane: construct the filler with track_winner=True")
-        if self._texture is None:
-            raise ValueError("texture_pass: no texture is bound (bind_texture)")
-        if filter == "trilinear" and self._mip is None:
-            raise ValueError("filter 'trilinear' needs a mip chain: bind_texture(..., mipmaps=True)")
-        if self._inputs is None:
-            raise ValueError("texture_pass: no frame has been rendered")
-        if not (self._last_flags & _capi.FUSED_CLEAR):
-            raise ValueError("texture_pass: the last frame did not start from cleared buffers (clear=True): the winner "
-                             "plane of a composite mixes the triangle indices of several models")
-        uv, tex = self._texture
-        tri = self._inputs[0]
-        T = tri.shape[0]
-        if uv.shape[0] != T:
-            raise ValueError(f"texture_pass: {uv.shape[0]} triangles of texture coordinates are bound, the last frame drew {T}")
-        light = None if light_direction is None else (C.c_float * 3)(*[float(v) for v in light_direction])
-        self._push_host_edits()
-        self._check_bins()             # nothing pending from here on: no later redo can undo the pass
-        pos_of = None if self._order is None else self._order[1].data_ptr()
-        more = ()
-        if filter == "trilinear":
-            shade, name, image = self._lib.crender_mip_shade, "crender_mip_shade", self._mip[0]
-            flags = _capi.MIP_PERSPECTIVE if perspective else 0
-            if anisotropy > 1:
-                shade, name, more = self._lib.crender_aniso_shade, "crender_aniso_shade", (anisotropy,)
-        else:
-            shade, name, image = self._lib.crender_tex_shade, "crender_tex_shade", tex
-            flags = (_capi.TEX_PERSPECTIVE if perspective else 0) | (_capi.TEX_BILINEAR if filter == "bilinear" else 0)
-        with torch.cuda.device(self.device):
-            _capi.check(shade(
-                self.winner_buffer.data_ptr(), tri.data_ptr() if T else None, T, pos_of, self._P,
-                uv.data_ptr() if T else None, image.data_ptr(), int(tex.shape[0]), int(tex.shape[1]),
-                None if light is None else self.normals_buffer.data_ptr(), light, self.color_buffer.data_ptr(),
-                self.h, self.w, self.y0, self.y1, flags, *more, self._stream()), name)
-        self._host_fresh = False       # views handed out earlier show the textured colours at the next getter call
-
-    def bind_shadow_map(self, light_filler, light_vertices):
-        """Name the shadow map of ``shadow_pass``: `light_filler`, another ``AdvancedPixelBufferFiller`` on the same
-        device (not a swap chain) into which the SAME triangles are rendered from the light, and `light_vertices`
-        float32 [T, 3, 3], numpy or a device tensor, in the caller's triangle order: the vertex array that filler
-        was given to draw (``shadow.light_arrays``).  The binding holds the filler object; its planes are read when
-        the pass runs.  ``bind_shadow_map(None, None)`` drops the binding."""
-        if light_filler is None and light_vertices is None:
-            self._shadow = None
-            return
-        if light_filler is None or light_vertices is None:
-            raise ValueError("bind_shadow_map needs both the light's filler and its vertices (or None, None)")
-        if not isinstance(light_filler, AdvancedPixelBufferFiller):
-            raise ValueError(f"bind_shadow_map: the light's filler must be an AdvancedPixelBufferFiller, "
-                             f"got {type(light_filler).__name__}")
-        if light_filler._pipeline:
-            raise ValueError("bind_shadow_map: the light's filler is a swap chain (pipeline=True): its planes rotate")
-        if light_filler.device != self.device:
-            raise ValueError(f"bind_shadow_map: the light's filler is on {light_filler.device}, this one on {self.device}")
-        self._shadow = (light_filler, _as_device_f32(light_vertices, "light_vertices", self.device))
-
-    def shadow_pass(self, bias=1e-3, pcf=1, ambient=0.25, use_winner=True):
-        """Shadow mapping of the LAST frame's colour plane (``crender_shadow_shade``, include/crender_shadow.h)
-        against the last frame of the filler bound with ``bind_shadow_map``: the surface point every covered pixel
-        shows is carried into the light's frame (perspective-correct) and projected into the light's z plane; the
-        pixel is shadowed where that plane holds something nearer by more than `bias` (in the light's projected z).
-        `pcf` K = 1, 3 or 5 averages the K x K texels around it; a fully shadowed pixel keeps `ambient` of its
-        colour, a fully lit one is not written at all.  With `use_winner` and a light filler that tracks its winner
-        plane, a texel the pixel's own triangle won is lit whatever the depths say, which removes the self-shadowing
-        of a surface on itself without a bias.  Rows of the filler's ``row_strip``, on torch's current stream.
-
-        Both frames are settled first (one stream synchronisation each, as every getter does): a frame whose bin
-        lists overflowed is rendered again, the pass must land on the camera frame that stays and see the light's
-        final z."""
-        if self._pipeline:
-            raise ValueError("shadow_pass is not available on a swap chain (pipeline=True): per-slot passes are not implemented")
-        if self.winner_buffer is None:
-            raise ValueError("shadow_pass needs the winner plane: construct the filler with track_winner=True")
-        if self._shadow is None:
-            raise ValueError("shadow_pass: no shadow map is bound (bind_shadow_map)")
-        light, ltri = self._shadow
-        for who, f in (("the camera's filler", self), ("the light's filler", light)):
-            if f._inputs is None:
-                raise ValueError(f"shadow_pass: no frame has been rendered by {who}")
-            if not (f._last_flags & _capi.FUSED_CLEAR):
-                raise ValueError(f"shadow_pass: the last frame of {who} did not start from cleared buffers (clear=True): "
-                                 "the planes of a composite mix several models")
-        tri = self._inputs[0]
-        T = tri.shape[0]
-        if not ltri.shape[0] == light._inputs[0].shape[0] == T:
-            raise ValueError(f"shadow_pass: {ltri.shape[0]} triangles of light-frame vertices are bound, the light's last "
-                             f"frame drew {light._inputs[0].shape[0]}, the camera's {T}")
-        if isinstance(pcf, bool) or pcf not in _capi.SHADOW_PCF:
-            raise ValueError(f"pcf must be 1, 3 or 5, got {pcf!r}")
-        self._push_host_edits()
-        light._push_host_edits()
-        light._check_bins()            # the map the pass reads is the light's final z
-        self._check_bins()             # nothing pending from here on: no later redo can undo the pass
-        pos_of = None if self._order is None else self._order[1].data_ptr()
-        lwinner = light.winner_buffer if use_winner else None
-        with torch.cuda.device(self.device):
-            _capi.check(self._lib.crender_shadow_shade(
-                self.winner_buffer.data_ptr(), tri.data_ptr() if T else None, T, pos_of, self._P,
-                ltri.data_ptr() if T else None, light._P, light.z_buffer.data_ptr(),
-                None if lwinner is None else lwinner.data_ptr(), light.h, light.w, float(bias), float(ambient), int(pcf),
-                self.color_buffer.data_ptr(), self.h, self.w, self.y0, self.y1, 0, self._stream()), "crender_shadow_shade")
-        self._host_fresh = False       # views handed out earlier show the shadowed colours at the next getter call
-
-    def phong_pass(self, lights, ambient=0.1, shininess=32, specular_color=(255, 255, 255), clamp=255.0):
-        """Per-pixel Blinn-Phong lighting of the LAST frame's colour plane (``crender_phong_shade``,
-        include/crender_phong.h): every covered pixel's colour c becomes ``min(c * F + Ws * specular_color, clamp)``
-        with ``F = ambient + sum kd_j * d_j`` and ``Ws = sum ks_j * sp_j ** shininess`` over the lights, d_j the
-        Guro factor of the pixel's stored normal under the unit vector towards light j, sp_j that of the half vector
-        between it and the direction to the camera, both taken at the surface point the pixel shows (the
-        perspective-correct blend of the winner's corners).  `lights` is a list of 1 to 4 dicts, each with exactly one
-        of ``position`` (a point in the camera's frame, where ``shadow.look_at(position=...)`` places a light) or
-        ``direction`` (the way the light travels, ``GuroIllumination``'s convention: flipped and normalised by that
-        class's own statements), and ``diffuse`` (kd) and ``specular`` (ks).  `shininess` is a power of two from 1 to
-        4096.  The background is not written.  Rows of the filler's ``row_strip``, on torch's current stream.
-
-        The frame is settled first (one stream synchronisation, as every getter does): a frame whose bin lists
-        overflowed is rendered again, and the pass must land on the frame that stays."""
-        from ..illumination.phong_illumination import light_rows, shininess_log2
-        if self._pipeline:
-            raise ValueError("phong_pass is not available on a swap chain (pipeline=True): per-slot passes are not implemented")
-        if self.winner_buffer is None:
-            raise ValueError("phong_pass needs the winner plane: construct the filler with track_winner=True")
-        rows, mask = light_rows(lights)
-        k = shininess_log2(shininess)
-        if self._inputs is None:
-            raise ValueError("phong_pass: no frame has been rendered")
-        if not (self._last_flags & _capi.FUSED_CLEAR):
-            raise ValueError("phong_pass: the last frame did not start from cleared buffers (clear=True): the winner "
-                             "plane of a composite mixes the triangle indices of several models")
-        tri = self._inputs[0]
-        T = tri.shape[0]
-        lights5 = (C.c_float * (5 * len(rows)))(*[v for row in rows for v in row])
-        spec = (C.c_float * 3)(*[float(v) for v in specular_color])
-        self._push_host_edits()
-        self._check_bins()             # nothing pending from here on: no later redo can undo the pass
-        pos_of = None if self._order is None else self._order[1].data_ptr()
-        with torch.cuda.device(self.device):
-            _capi.check(self._lib.crender_phong_shade(
-                self.winner_buffer.data_ptr(), tri.data_ptr() if T else None, T, pos_of, self._P,
-                self.normals_buffer.data_ptr(), lights5, len(rows), mask, float(ambient), k, spec, float(clamp),
-                self.color_buffer.data_ptr(), self.h, self.w, self.y0, self.y1, 0, self._stream()), "crender_phong_shade")
-        self._host_fresh = False       # views handed out earlier show the lit colours at the next getter call
-
-    def ao_pass(self, radius=0.03, radius_px=8, taps=16, min_cos=0.1, strength=2.0, floor=0.0, rotate=True, normals="plane"):
-        """Screen-space ambient occlusion of the LAST frame's colour plane (``crender_ao_shade``,
-        include/crender_ao.h): every covered pixel's colour is scaled by ``max(1 - strength * mean(o_i), floor)``,
-        where tap i looks at the covered pixel at its offset, takes the point that pixel shows (from the z plane) and
-        gives ``o_i = cos * (1 - (distance / radius) ** 2)`` if the point lies within `radius` (in the camera frame's
-        units) and the cosine between the pixel's normal and the way to it exceeds `min_cos`, else 0.  `taps` is a
-        count — the table ``ambient_occlusion.taps(radius_px, taps)`` — or an explicit list of (dx, dy) pairs, 1 to 64
-        of them within `radius_px` (1 to 32) in both coordinates.  With `rotate` a pixel turns the table by a quarter
-        turn picked by its parity, so that neighbours look in other directions.  `normals` is ``"plane"`` (the normal
-        plane the raster stored: interpolated vertex normals) or ``"face"`` (the winner's own geometric normal, turned
-        to the eye).  A pixel that nothing occludes is not written.  Rows of the filler's ``row_strip``, on torch's
-        current stream; the strip does not see across its edge.
-
-        The frame is settled first (one stream synchronisation, as every getter does): a frame whose bin lists
-        overflowed is rendered again, and the pass must land on the frame that stays."""
-        from .. import ambient_occlusion
-        if self._pipeline:
-            raise ValueError("ao_pass is not available on a swap chain (pipeline=True): per-slot passes are not implemented")
-        if self.winner_buffer is None:
-            raise ValueError("ao_pass needs the winner plane: construct the filler with track_winner=True")
-        if normals not in ("plane", "face"):
-            raise ValueError(f"normals must be 'plane' or 'face', got {normals!r}")
-        if isinstance(radius_px, bool) or not isinstance(radius_px, int) or not 1 <= radius_px <= _capi.AO_MAX_RADIUS_PX:
-            raise ValueError(f"radius_px must be an int from 1 to {_capi.AO_MAX_RADIUS_PX}, got {radius_px!r}")
-        if isinstance(taps, int) and not isinstance(taps, bool):
-            if not 1 <= taps <= _capi.AO_MAX_TAPS:
-                raise ValueError(f"taps must be a count from 1 to {_capi.AO_MAX_TAPS} or a list of (dx, dy) pairs, got {taps!r}")
-            table = ambient_occlusion.taps(radius_px, taps)
-        else:
-            try:
-                table = [(operator.index(dx), operator.index(dy)) for dx, dy in taps]
-            except (TypeError, ValueError):
-                raise ValueError(f"taps must be a count from 1 to {_capi.AO_MAX_TAPS} or a list of (dx, dy) pairs, "
-                                 f"got {taps!r}") from None
-            if not 1 <= len(table) <= _capi.AO_MAX_TAPS:
-                raise ValueError(f"taps must hold 1 to {_capi.AO_MAX_TAPS} pairs, got {len(table)}")
-            for dx, dy in table:
-                if max(abs(dx), abs(dy)) > radius_px or (dx, dy) == (0, 0):
-                    raise ValueError(f"the tap ({dx}, {dy}) is (0, 0) or reaches beyond radius_px={radius_px}")
-        if self._inputs is None:
-            raise ValueError("ao_pass: no frame has been rendered")
-        if not (self._last_flags & _capi.FUSED_CLEAR):
-            raise ValueError("ao_pass: the last frame did not start from cleared buffers (clear=True): the winner "
-                             "plane of a composite mixes the triangle indices of several models")
-        tri = self._inputs[0]
-        T = tri.shape[0]
-        taps2 = (C.c_int8 * (2 * len(table)))(*[v for pair in table for v in pair])
-        flags = (_capi.AO_ROTATE if rotate else 0) | (_capi.AO_FACE_NORMALS if normals == "face" else 0)
-        self._push_host_edits()
-        self._check_bins()             # nothing pending from here on: no later redo can undo the pass
-        pos_of = None if self._order is None else self._order[1].data_ptr()
-        with torch.cuda.device(self.device):
-            _capi.check(self._lib.crender_ao_shade(
-                self.winner_buffer.data_ptr(), self.z_buffer.data_ptr(), tri.data_ptr() if T else None, T, pos_of, self._P,
-                self.normals_buffer.data_ptr(), taps2, len(table), radius_px, float(radius), float(min_cos),
-                float(strength), float(floor), self.color_buffer.data_ptr(), self.h, self.w, self.y0, self.y1, flags,
-                self._stream()), "crender_ao_shade")
-        self._host_fresh = False       # views handed out earlier show the occluded colours at the next getter call
 
     def render_frame(self, pipelined=None):
         """One benchmark frame: clear + project + rasterize the resident model

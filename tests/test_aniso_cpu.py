@@ -13,7 +13,7 @@ import pytest
 
 import aniso_ref
 import mip_ref
-from util import assert_bit_equal
+from util import assert_bit_equal, other_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -48,34 +48,33 @@ def scenes_(oracle):
 def test_aniso_header_symbol_is_exported_and_bound(capi):
     header = open(os.path.join(ROOT, "include", "crender_aniso.h")).read()
     declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
-    assert declared == set(capi.ANISO_SIGNATURES) == {"crender_aniso_shade"}
-    assert not declared & (set(capi.SIGNATURES) | set(capi.WIRE_SIGNATURES) | set(capi.PY_SIGNATURES) |
-                           set(capi.TEX_SIGNATURES) | set(capi.MIP_SIGNATURES))
+    assert declared == set(capi.UNIT_SIGNATURES["aniso"]) == {"crender_aniso_shade"}
+    assert not declared & other_symbols(capi, "aniso")
     L = capi.load()
-    assert L.crender_aniso_shade.argtypes == capi.ANISO_SIGNATURES["crender_aniso_shade"][1]
+    assert L.crender_aniso_shade.argtypes == capi.UNIT_SIGNATURES["aniso"]["crender_aniso_shade"][1]
     out = subprocess.check_output(["nm", "-D", "--defined-only", capi.lib_path()], text=True)
     assert declared <= set(re.findall(r" T (crender_\w+)", out))
     assert capi.ANISO_MAX == 16 and re.search(rf"\bCRENDER_ANISO_MAX = {capi.ANISO_MAX}\b", header)
     assert aniso_ref.MAX_ANISO == capi.ANISO_MAX
     # crender_mip_shade's arguments in its order up to and including flags, then max_aniso, then the stream
-    mip = capi.MIP_SIGNATURES["crender_mip_shade"]
-    res, args = capi.ANISO_SIGNATURES["crender_aniso_shade"]
+    mip = capi.UNIT_SIGNATURES["mip"]["crender_mip_shade"]
+    res, args = capi.UNIT_SIGNATURES["aniso"]["crender_aniso_shade"]
     assert res == mip[0] and args == mip[1][:-1] + [C.c_int, mip[1][-1]]
     assert capi.ABI_VERSION == 6
 
 
 def test_aniso_sources_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert _build.ANISO_SOURCES == ["texaniso.hip"] and _build.MIP_SOURCES == ["texmip.hip"]
+    assert _build.UNITS["aniso"][0] == ["texaniso.hip"] and _build.UNITS["mip"][0] == ["texmip.hip"]
     fingerprinted = _build.SOURCES + _build.HEADERS
-    assert not set(_build.ANISO_SOURCES + _build.ANISO_HEADERS) & set(fingerprinted)
+    assert not set(_build.UNITS["aniso"][0] + _build.UNITS["aniso"][1]) & set(fingerprinted)
     assert not any("aniso" in name or "mip" in name for name in fingerprinted)
-    assert any(h.endswith("crender_aniso.h") for h in _build.ANISO_HEADERS)
+    assert any(h.endswith("crender_aniso.h") for h in _build.UNITS["aniso"][1])
     # what the pass shares with texmip.hip is watched by both and by nothing else
-    shared = set(_build.ANISO_HEADERS) & set(_build.MIP_HEADERS)
+    shared = set(_build.UNITS["aniso"][1]) & set(_build.UNITS["mip"][1])
     assert shared == {"mip_sample.h"}
-    assert not shared & set(_build.WIRE_HEADERS + _build.PY_HEADERS + _build.TEX_HEADERS)
-    for name in _build.ANISO_SOURCES + _build.ANISO_HEADERS:
+    assert not shared & set(_build.UNITS["wire"][1] + _build.UNITS["py"][1] + _build.UNITS["tex"][1])
+    for name in _build.UNITS["aniso"][0] + _build.UNITS["aniso"][1]:
         assert os.path.exists(os.path.join(_build.SRC_DIR, name)), name
 
 

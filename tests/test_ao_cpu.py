@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import ao_ref
-from util import assert_bit_equal
+from util import assert_bit_equal, other_symbols, unit_inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TABLE = [(1, 0), (-2, 2), (0, -3), (2, 3), (-4, -1), (4, -3), (-1, 5), (-3, -5), (5, 2), (-6, 2), (3, -6), (2, 6), (-6, -4),
@@ -32,16 +32,13 @@ def capi():
 def test_ao_header_symbol_is_exported_and_bound(capi):
     header = open(os.path.join(ROOT, "include", "crender_ao.h")).read()
     declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
-    assert declared == set(capi.AO_SIGNATURES) == {"crender_ao_shade"}
-    assert not declared & (set(capi.SIGNATURES) | set(capi.WIRE_SIGNATURES) | set(capi.PY_SIGNATURES) |
-                           set(capi.TEX_SIGNATURES) | set(capi.MIP_SIGNATURES) | set(capi.ANISO_SIGNATURES) |
-                           set(capi.SSAA_SIGNATURES) | set(capi.SHADOW_SIGNATURES) | set(capi.PHONG_SIGNATURES) |
-                           set(capi.CHAIN_SIGNATURES))
+    assert declared == set(capi.UNIT_SIGNATURES["ao"]) == {"crender_ao_shade"}
+    assert not declared & other_symbols(capi, "ao")
     L = capi.load()
-    assert L.crender_ao_shade.argtypes == capi.AO_SIGNATURES["crender_ao_shade"][1]
+    assert L.crender_ao_shade.argtypes == capi.UNIT_SIGNATURES["ao"]["crender_ao_shade"][1]
     # argument counts: the declaration's commas against the table
     decl = re.search(r"CRENDER_API int crender_ao_shade\((.*?)\);", header, re.S).group(1)
-    res, args = capi.AO_SIGNATURES["crender_ao_shade"]
+    res, args = capi.UNIT_SIGNATURES["ao"]["crender_ao_shade"]
     assert res == C.c_int and len(args) == len(decl.split(",")) == 21
     # the four floats of the declaration are the table's: radius, min_cos, strength and floor by value
     kinds = ["float" if re.match(r"\s*float \w+$", a) else "other" for a in decl.split(",")]
@@ -58,17 +55,17 @@ def test_ao_header_symbol_is_exported_and_bound(capi):
 
 def test_ao_sources_are_built_and_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert _build.AO_SOURCES == ["ao.hip"]
-    assert len(_build.AO_HEADERS) == 1 and _build.AO_HEADERS[0].endswith("crender_ao.h")
+    assert _build.UNITS["ao"][0] == ["ao.hip"]
+    assert len(_build.UNITS["ao"][1]) == 1 and _build.UNITS["ao"][1][0].endswith("crender_ao.h")
     fingerprinted = _build.SOURCES + _build.HEADERS
-    assert not set(_build.AO_SOURCES + _build.AO_HEADERS) & set(fingerprinted)
+    assert not set(_build.UNITS["ao"][0] + _build.UNITS["ao"][1]) & set(fingerprinted)
     assert not any("ao." in name for name in fingerprinted)
     assert _build.source_sha16() == "f3a47bfc1afb1a02"
-    for name in _build.AO_SOURCES + _build.AO_HEADERS:
+    for name in _build.UNITS["ao"][0] + _build.UNITS["ao"][1]:
         assert os.path.exists(os.path.join(_build.SRC_DIR, name)), name
     # the default build compiles the unit, and a change of it makes the library stale
-    assert "AO_SOURCES" in inspect.getsource(_build.compile_library)
-    assert "AO_SOURCES + AO_HEADERS" in inspect.getsource(_build.needs_build)
+    assert set(_build.UNITS["ao"][0]) <= set(_build.library_sources())
+    assert unit_inputs(_build, "ao") <= set(_build.build_inputs())
     # the kernel takes the shared pieces by inclusion, stages in LDS behind barriers and has no inline assembly
     unit = open(os.path.join(_build.SRC_DIR, "ao.hip")).read()
     for name in ("make_proj(", "wave_any(", "gather_corners("):

@@ -2,12 +2,13 @@
 the header against the library's exports and the ctypes table, the unit's place in the build, and the argument
 errors that return before anything touches the HIP runtime."""
 import ctypes as C
-import inspect
 import os
 import re
 import subprocess
 
 import pytest
+
+from util import other_symbols, unit_inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -22,40 +23,38 @@ def capi():
 def test_chain_header_symbols_are_exported_and_bound(capi):
     header = open(os.path.join(ROOT, "include", "crender_chain.h")).read()
     declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
-    assert declared == set(capi.CHAIN_SIGNATURES)
+    assert declared == set(capi.UNIT_SIGNATURES["chain"])
     assert {"crender_pipeline_share_stream", "crender_pipeline_unshare", "crender_pipeline_shared_slot"} <= declared
-    assert not declared & (set(capi.SIGNATURES) | set(capi.WIRE_SIGNATURES) | set(capi.PY_SIGNATURES) |
-                           set(capi.TEX_SIGNATURES) | set(capi.MIP_SIGNATURES) | set(capi.ANISO_SIGNATURES) |
-                           set(capi.SSAA_SIGNATURES) | set(capi.SHADOW_SIGNATURES))
+    assert not declared & other_symbols(capi, "chain")
     L = capi.load()
     out = subprocess.check_output(["nm", "-D", "--defined-only", capi.lib_path()], text=True)
     assert declared <= set(re.findall(r" T (crender_\w+)", out))
     kind = {"crender_pipeline *": C.c_void_p, "const crender_pipeline *": C.c_void_p, "void *": C.c_void_p, "int ": C.c_int}
     for name in declared:
-        res, args = capi.CHAIN_SIGNATURES[name]
+        res, args = capi.UNIT_SIGNATURES["chain"][name]
         fn = getattr(L, name)
         assert fn.restype == res == C.c_int and fn.argtypes == args, name
         # every parameter of the declaration, by its type, against the table
         decl = re.search(r"CRENDER_API int " + name + r"\((.*?)\);", header, re.S).group(1)
         want = [kind[re.match(r"\s*(.*?)\w+$", a).group(1)] for a in decl.split(",")]
         assert want == args, name
-    assert capi.CHAIN_SIGNATURES["crender_pipeline_share_stream"][1] == [C.c_void_p, C.c_int, C.c_void_p]
+    assert capi.UNIT_SIGNATURES["chain"]["crender_pipeline_share_stream"][1] == [C.c_void_p, C.c_int, C.c_void_p]
     assert capi.ABI_VERSION == 6
 
 
 def test_chain_sources_are_built_and_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert _build.CHAIN_SOURCES == ["chain.hip"]
-    assert len(_build.CHAIN_HEADERS) == 1 and _build.CHAIN_HEADERS[0].endswith("crender_chain.h")
+    assert _build.UNITS["chain"][0] == ["chain.hip"]
+    assert len(_build.UNITS["chain"][1]) == 1 and _build.UNITS["chain"][1][0].endswith("crender_chain.h")
     fingerprinted = _build.SOURCES + _build.HEADERS
-    assert not set(_build.CHAIN_SOURCES + _build.CHAIN_HEADERS) & set(fingerprinted)
+    assert not set(_build.UNITS["chain"][0] + _build.UNITS["chain"][1]) & set(fingerprinted)
     assert not any("chain" in name for name in fingerprinted)
     assert _build.source_sha16() == "f3a47bfc1afb1a02"
-    for name in _build.CHAIN_SOURCES + _build.CHAIN_HEADERS:
+    for name in _build.UNITS["chain"][0] + _build.UNITS["chain"][1]:
         assert os.path.exists(os.path.join(_build.SRC_DIR, name)), name
     # the default build compiles the unit, and a change of it makes the library stale
-    assert "CHAIN_SOURCES" in inspect.getsource(_build.compile_library)
-    assert "CHAIN_SOURCES + CHAIN_HEADERS" in inspect.getsource(_build.needs_build)
+    assert set(_build.UNITS["chain"][0]) <= set(_build.library_sources())
+    assert unit_inputs(_build, "chain") <= set(_build.build_inputs())
     # host code over the pipeline handle of plan.h: no kernel, no launch
     unit = open(os.path.join(_build.SRC_DIR, "chain.hip")).read()
     assert '#include "plan.h"' in unit

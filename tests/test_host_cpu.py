@@ -36,6 +36,40 @@ def test_library_exports_every_declared_symbol(capi):
     assert L.crender_abi_version() == capi.ABI_VERSION
 
 
+def test_library_units_are_one_table_for_the_build_and_the_binding():
+    from cython3dmodelrenderer_amd import _build, _capi
+    # link order decides the library's bytes
+    assert _build.library_sources() == ["abi.hip", "binning.hip", "raster.hip", "model_ops.hip", "wireframe.hip", "pyfill.hip",
+                                        "texture.hip", "texmip.hip", "texaniso.hip", "resolve.hip", "shadow.hip", "phong.hip",
+                                        "ao.hip", "chain.hip"]
+    assert list(_build.UNITS) == ["wire", "py", "tex", "mip", "aniso", "ssaa", "shadow", "phong", "ao", "pass", "chain"]
+    assert set(_capi.UNIT_SIGNATURES) == {unit for unit, (sources, _) in _build.UNITS.items() if sources}
+    bound = [name for table in (_capi.SIGNATURES, *_capi.UNIT_SIGNATURES.values()) for name in table]
+    assert len(bound) == len(set(bound))
+    inputs = _build.build_inputs()
+    assert len(inputs) == len(set(inputs))
+    for path in inputs:
+        assert os.path.isfile(path), path
+    want = _build.SOURCES + _build.HEADERS + [name for unit in _build.UNITS.values() for name in unit[0] + unit[1]]
+    assert set(inputs) == {os.path.join(_build.SRC_DIR, name) for name in want} | {os.path.abspath(_build.__file__)}
+
+
+def test_the_library_is_stale_when_any_build_input_is_newer(tmp_path, monkeypatch):
+    from cython3dmodelrenderer_amd import _build
+    lib = tmp_path / "libcrender_hip.so"
+    monkeypatch.setattr(_build, "LIB_PATH", str(lib))
+    assert _build.needs_build()                    # no library at all
+    lib.write_bytes(b"")
+    inputs = _build.build_inputs()
+    newest = max(os.path.getmtime(path) for path in inputs)
+    os.utime(lib, (newest + 1, newest + 1))
+    assert not _build.needs_build()
+    for path in inputs:
+        then = os.path.getmtime(path) - 1
+        os.utime(lib, (then, then))
+        assert _build.needs_build(), path
+
+
 def test_torch_extension_is_built_and_bound():
     """The torch C++ extension over the C ABI (csrc/crender_torch.cpp): builds in-tree without a
     GPU, loads, links the same libcrender_hip.so, and exposes the per-frame entry points."""

@@ -11,7 +11,7 @@ import pytest
 
 import mip_ref
 import tex_ref
-from util import assert_bit_equal
+from util import assert_bit_equal, other_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -90,30 +90,29 @@ def test_layout_refuses_an_empty_side_and_a_seventeenth_level(capi):
 def test_mip_header_symbols_are_exported_and_bound(capi):
     header = open(os.path.join(ROOT, "include", "crender_mip.h")).read()
     declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
-    assert declared == set(capi.MIP_SIGNATURES) == {"crender_mip_layout", "crender_mip_build", "crender_mip_shade"}
-    assert not declared & (set(capi.SIGNATURES) | set(capi.WIRE_SIGNATURES) | set(capi.PY_SIGNATURES) |
-                           set(capi.TEX_SIGNATURES))
+    assert declared == set(capi.UNIT_SIGNATURES["mip"]) == {"crender_mip_layout", "crender_mip_build", "crender_mip_shade"}
+    assert not declared & other_symbols(capi, "mip")
     L = capi.load()
     for name in declared:
-        assert getattr(L, name).argtypes == capi.MIP_SIGNATURES[name][1]
+        assert getattr(L, name).argtypes == capi.UNIT_SIGNATURES["mip"][name][1]
     out = subprocess.check_output(["nm", "-D", "--defined-only", capi.lib_path()], text=True)
     assert declared <= set(re.findall(r" T (crender_\w+)", out))
     assert re.search(rf"\bCRENDER_MIP_PERSPECTIVE = {capi.MIP_PERSPECTIVE}u\b", header)
     assert re.search(rf"\bCRENDER_MIP_MAX_LEVELS = {capi.MIP_MAX_LEVELS}\b", header)
     # the shade entry point takes crender_tex_shade's arguments
-    assert capi.MIP_SIGNATURES["crender_mip_shade"] == capi.TEX_SIGNATURES["crender_tex_shade"]
+    assert capi.UNIT_SIGNATURES["mip"]["crender_mip_shade"] == capi.UNIT_SIGNATURES["tex"]["crender_tex_shade"]
 
 
 def test_mip_sources_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert _build.MIP_SOURCES == ["texmip.hip"]
+    assert _build.UNITS["mip"][0] == ["texmip.hip"]
     fingerprinted = _build.SOURCES + _build.HEADERS
-    others = fingerprinted + _build.WIRE_SOURCES + _build.PY_SOURCES + _build.TEX_SOURCES + _build.WIRE_HEADERS + \
-        _build.PY_HEADERS + _build.TEX_HEADERS
-    assert not set(_build.MIP_SOURCES + _build.MIP_HEADERS) & set(others)
+    others = fingerprinted + _build.UNITS["wire"][0] + _build.UNITS["py"][0] + _build.UNITS["tex"][0] + _build.UNITS["wire"][1] + \
+        _build.UNITS["py"][1] + _build.UNITS["tex"][1]
+    assert not set(_build.UNITS["mip"][0] + _build.UNITS["mip"][1]) & set(others)
     assert not any("mip" in name for name in fingerprinted)
-    assert any(h.endswith("crender_mip.h") for h in _build.MIP_HEADERS)
-    for name in _build.MIP_SOURCES + _build.MIP_HEADERS:
+    assert any(h.endswith("crender_mip.h") for h in _build.UNITS["mip"][1])
+    for name in _build.UNITS["mip"][0] + _build.UNITS["mip"][1]:
         assert os.path.exists(os.path.join(_build.SRC_DIR, name)), name
 
 

@@ -2,7 +2,6 @@
 window decision of the passes, and every select of the Phong and occlusion passes, both ways, often enough and within one wavefront, before tests/test_pass_edges_gpu.py
 holds the kernels to them; and the float32 model of the scene is still the float64 form of its own statements where
 the operands are ordinary."""
-import inspect
 import os
 import re
 
@@ -17,6 +16,7 @@ import phong_ref
 import shadow_ref
 import tex_ref
 from test_texture_cpu import PERSPECTIVE_UV_BOUND
+from util import unit_inputs
 
 WAVE = 64
 
@@ -223,8 +223,8 @@ def test_the_tall_frame_needs_a_second_trip_of_the_row_block_loop(oracle):
 def test_the_passes_share_one_header_that_the_build_watches_and_the_fingerprint_does_not():
     from cython3dmodelrenderer_amd import _build
     assert os.path.exists(os.path.join(_build.SRC_DIR, "winner_pass.h"))
-    assert "winner_pass.h" in _build.PASS_HEADERS
-    assert "PASS_HEADERS" in inspect.getsource(_build.needs_build)
+    assert "winner_pass.h" in _build.UNITS["pass"][1]
+    assert unit_inputs(_build, "pass") <= set(_build.build_inputs())
     assert "winner_pass.h" not in _build.SOURCES + _build.HEADERS
     assert _build.source_sha16() == "f3a47bfc1afb1a02"
     units = ["texture.hip", "texmip.hip", "texaniso.hip", "shadow.hip"]

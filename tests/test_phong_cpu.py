@@ -3,7 +3,6 @@ checks, the host model the GPU tests compare with (tests/phong_ref.py) pinned on
 ``oracle.guro`` in the directional, diffuse-only case, by counts, by identities and against a float64 evaluation —
 and the ``PhongIllumination`` class."""
 import ctypes as C
-import inspect
 import os
 import re
 import subprocess
@@ -12,7 +11,7 @@ import numpy as np
 import pytest
 
 import phong_ref
-from util import assert_bit_equal
+from util import assert_bit_equal, other_symbols, unit_inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GURO = (0.3, -0.2, 1.0)              # what GuroIllumination is constructed with
@@ -32,15 +31,13 @@ def capi():
 def test_phong_header_symbol_is_exported_and_bound(capi):
     header = open(os.path.join(ROOT, "include", "crender_phong.h")).read()
     declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
-    assert declared == set(capi.PHONG_SIGNATURES) == {"crender_phong_shade"}
-    assert not declared & (set(capi.SIGNATURES) | set(capi.WIRE_SIGNATURES) | set(capi.PY_SIGNATURES) |
-                           set(capi.TEX_SIGNATURES) | set(capi.MIP_SIGNATURES) | set(capi.ANISO_SIGNATURES) |
-                           set(capi.SSAA_SIGNATURES) | set(capi.SHADOW_SIGNATURES) | set(capi.CHAIN_SIGNATURES))
+    assert declared == set(capi.UNIT_SIGNATURES["phong"]) == {"crender_phong_shade"}
+    assert not declared & other_symbols(capi, "phong")
     L = capi.load()
-    assert L.crender_phong_shade.argtypes == capi.PHONG_SIGNATURES["crender_phong_shade"][1]
+    assert L.crender_phong_shade.argtypes == capi.UNIT_SIGNATURES["phong"]["crender_phong_shade"][1]
     # argument counts: the declaration's commas against the table
     decl = re.search(r"CRENDER_API int crender_phong_shade\((.*?)\);", header, re.S).group(1)
-    res, args = capi.PHONG_SIGNATURES["crender_phong_shade"]
+    res, args = capi.UNIT_SIGNATURES["phong"]["crender_phong_shade"]
     assert res == C.c_int and len(args) == len(decl.split(",")) == 20
     # the two floats of the declaration are the table's: ambient and clamp by value, the host arrays as pointers
     kinds = ["float" if re.match(r"\s*float \w+$", a) else "other" for a in decl.split(",")]
@@ -56,17 +53,17 @@ def test_phong_header_symbol_is_exported_and_bound(capi):
 
 def test_phong_sources_are_built_and_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert _build.PHONG_SOURCES == ["phong.hip"]
-    assert len(_build.PHONG_HEADERS) == 1 and _build.PHONG_HEADERS[0].endswith("crender_phong.h")
+    assert _build.UNITS["phong"][0] == ["phong.hip"]
+    assert len(_build.UNITS["phong"][1]) == 1 and _build.UNITS["phong"][1][0].endswith("crender_phong.h")
     fingerprinted = _build.SOURCES + _build.HEADERS
-    assert not set(_build.PHONG_SOURCES + _build.PHONG_HEADERS) & set(fingerprinted)
+    assert not set(_build.UNITS["phong"][0] + _build.UNITS["phong"][1]) & set(fingerprinted)
     assert not any("phong" in name for name in fingerprinted)
     assert _build.source_sha16() == "f3a47bfc1afb1a02"
-    for name in _build.PHONG_SOURCES + _build.PHONG_HEADERS:
+    for name in _build.UNITS["phong"][0] + _build.UNITS["phong"][1]:
         assert os.path.exists(os.path.join(_build.SRC_DIR, name)), name
     # the default build compiles the unit, and a change of it makes the library stale
-    assert "PHONG_SOURCES" in inspect.getsource(_build.compile_library)
-    assert "PHONG_SOURCES + PHONG_HEADERS" in inspect.getsource(_build.needs_build)
+    assert set(_build.UNITS["phong"][0]) <= set(_build.library_sources())
+    assert unit_inputs(_build, "phong") <= set(_build.build_inputs())
     # the kernel takes the rasterizer's arithmetic and the passes' frame from the shared headers by inclusion
     unit = open(os.path.join(_build.SRC_DIR, "phong.hip")).read()
     for name in ("project_vertex(", "barycentric(", "guro_factor(", "make_proj(", "wave_any(", "winner_pixel(",

@@ -2,7 +2,6 @@
 checks, the host model the GPU tests compare with (tests/shadow_ref.py) pinned by hand on a floor under an occluder
 and on the oracle's frames of T-Rex, and the light-frame helpers of cython3dmodelrenderer_amd/shadow.py."""
 import ctypes as C
-import inspect
 import os
 import re
 import subprocess
@@ -11,7 +10,7 @@ import numpy as np
 import pytest
 
 import shadow_ref
-from util import assert_bit_equal
+from util import assert_bit_equal, other_symbols, unit_inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -28,15 +27,13 @@ def capi():
 def test_shadow_header_symbol_is_exported_and_bound(capi):
     header = open(os.path.join(ROOT, "include", "crender_shadow.h")).read()
     declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
-    assert declared == set(capi.SHADOW_SIGNATURES) == {"crender_shadow_shade"}
-    assert not declared & (set(capi.SIGNATURES) | set(capi.WIRE_SIGNATURES) | set(capi.PY_SIGNATURES) |
-                           set(capi.TEX_SIGNATURES) | set(capi.MIP_SIGNATURES) | set(capi.ANISO_SIGNATURES) |
-                           set(capi.SSAA_SIGNATURES))
+    assert declared == set(capi.UNIT_SIGNATURES["shadow"]) == {"crender_shadow_shade"}
+    assert not declared & other_symbols(capi, "shadow")
     L = capi.load()
-    assert L.crender_shadow_shade.argtypes == capi.SHADOW_SIGNATURES["crender_shadow_shade"][1]
+    assert L.crender_shadow_shade.argtypes == capi.UNIT_SIGNATURES["shadow"]["crender_shadow_shade"][1]
     # argument counts: the declaration's commas against the table
     decl = re.search(r"CRENDER_API int crender_shadow_shade\((.*?)\);", header, re.S).group(1)
-    res, args = capi.SHADOW_SIGNATURES["crender_shadow_shade"]
+    res, args = capi.UNIT_SIGNATURES["shadow"]["crender_shadow_shade"]
     assert res == C.c_int and len(args) == len(decl.split(",")) == 21
     # the three floats of the declaration are the table's: bias and ambient by value, the matrices as host pointers
     kinds = ["float" if re.match(r"\s*float \w+$", a) else "other" for a in decl.split(",")]
@@ -49,17 +46,17 @@ def test_shadow_header_symbol_is_exported_and_bound(capi):
 
 def test_shadow_sources_are_built_and_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert _build.SHADOW_SOURCES == ["shadow.hip"]
-    assert len(_build.SHADOW_HEADERS) == 1 and _build.SHADOW_HEADERS[0].endswith("crender_shadow.h")
+    assert _build.UNITS["shadow"][0] == ["shadow.hip"]
+    assert len(_build.UNITS["shadow"][1]) == 1 and _build.UNITS["shadow"][1][0].endswith("crender_shadow.h")
     fingerprinted = _build.SOURCES + _build.HEADERS
-    assert not set(_build.SHADOW_SOURCES + _build.SHADOW_HEADERS) & set(fingerprinted)
+    assert not set(_build.UNITS["shadow"][0] + _build.UNITS["shadow"][1]) & set(fingerprinted)
     assert not any("shadow" in name for name in fingerprinted)
     assert _build.source_sha16() == "f3a47bfc1afb1a02"
-    for name in _build.SHADOW_SOURCES + _build.SHADOW_HEADERS:
+    for name in _build.UNITS["shadow"][0] + _build.UNITS["shadow"][1]:
         assert os.path.exists(os.path.join(_build.SRC_DIR, name)), name
     # the default build compiles the unit, and a change of it makes the library stale
-    assert "SHADOW_SOURCES" in inspect.getsource(_build.compile_library)
-    assert "SHADOW_SOURCES + SHADOW_HEADERS" in inspect.getsource(_build.needs_build)
+    assert set(_build.UNITS["shadow"][0]) <= set(_build.library_sources())
+    assert unit_inputs(_build, "shadow") <= set(_build.build_inputs())
     # the kernel takes the rasterizer's arithmetic from the fingerprinted headers by inclusion
     unit = open(os.path.join(_build.SRC_DIR, "shadow.hip")).read()
     for name in ("project_vertex(", "barycentric(", "make_proj(", "wave_any("):

@@ -14,7 +14,7 @@ import pytest
 import torch
 
 import ssaa_ref
-from util import assert_bit_equal
+from util import assert_bit_equal, other_symbols, unit_inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -31,14 +31,13 @@ def capi():
 def test_ssaa_header_symbol_is_exported_and_bound(capi):
     header = open(os.path.join(ROOT, "include", "crender_ssaa.h")).read()
     declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
-    assert declared == set(capi.SSAA_SIGNATURES) == {"crender_ssaa_resolve"}
-    assert not declared & (set(capi.SIGNATURES) | set(capi.WIRE_SIGNATURES) | set(capi.PY_SIGNATURES) |
-                           set(capi.TEX_SIGNATURES) | set(capi.MIP_SIGNATURES) | set(capi.ANISO_SIGNATURES))
+    assert declared == set(capi.UNIT_SIGNATURES["ssaa"]) == {"crender_ssaa_resolve"}
+    assert not declared & other_symbols(capi, "ssaa")
     L = capi.load()
-    assert L.crender_ssaa_resolve.argtypes == capi.SSAA_SIGNATURES["crender_ssaa_resolve"][1]
+    assert L.crender_ssaa_resolve.argtypes == capi.UNIT_SIGNATURES["ssaa"]["crender_ssaa_resolve"][1]
     # argument counts: the declaration's commas against the table
     decl = re.search(r"CRENDER_API int crender_ssaa_resolve\((.*?)\);", header, re.S).group(1)
-    res, args = capi.SSAA_SIGNATURES["crender_ssaa_resolve"]
+    res, args = capi.UNIT_SIGNATURES["ssaa"]["crender_ssaa_resolve"]
     assert res == C.c_int and len(args) == len(decl.split(",")) == 11
     out = subprocess.check_output(["nm", "-D", "--defined-only", capi.lib_path()], text=True)
     assert declared <= set(re.findall(r" T (crender_\w+)", out))
@@ -52,19 +51,19 @@ def test_ssaa_header_symbol_is_exported_and_bound(capi):
 
 def test_ssaa_sources_are_built_and_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert _build.SSAA_SOURCES == ["resolve.hip"]
-    assert len(_build.SSAA_HEADERS) == 1 and _build.SSAA_HEADERS[0].endswith("crender_ssaa.h")
+    assert _build.UNITS["ssaa"][0] == ["resolve.hip"]
+    assert len(_build.UNITS["ssaa"][1]) == 1 and _build.UNITS["ssaa"][1][0].endswith("crender_ssaa.h")
     fingerprinted = _build.SOURCES + _build.HEADERS
-    assert not set(_build.SSAA_SOURCES + _build.SSAA_HEADERS) & set(fingerprinted)
+    assert not set(_build.UNITS["ssaa"][0] + _build.UNITS["ssaa"][1]) & set(fingerprinted)
     assert not any("ssaa" in name or "resolve" in name for name in fingerprinted)
     assert _build.source_sha16() == "f3a47bfc1afb1a02"
-    for name in _build.SSAA_SOURCES + _build.SSAA_HEADERS:
+    for name in _build.UNITS["ssaa"][0] + _build.UNITS["ssaa"][1]:
         assert os.path.exists(os.path.join(_build.SRC_DIR, name)), name
     # the default build compiles the unit, and a change of it makes the library stale
-    assert "SSAA_SOURCES" in inspect.getsource(_build.compile_library)
-    assert "SSAA_SOURCES + SSAA_HEADERS" in inspect.getsource(_build.needs_build)
+    assert set(_build.UNITS["ssaa"][0]) <= set(_build.library_sources())
+    assert unit_inputs(_build, "ssaa") <= set(_build.build_inputs())
     # the units the other passes pin stay as they were
-    assert _build.ANISO_SOURCES == ["texaniso.hip"] and _build.MIP_SOURCES == ["texmip.hip"]
+    assert _build.UNITS["aniso"][0] == ["texaniso.hip"] and _build.UNITS["mip"][0] == ["texmip.hip"]
     # the kernel takes the light's factor from raster_math.h by inclusion
     unit = open(os.path.join(_build.SRC_DIR, "resolve.hip")).read()
     assert "guro_factor(" in unit and "sqrtf" not in unit

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import tex_ref
-from util import assert_bit_equal, random_soup
+from util import assert_bit_equal, other_symbols, random_soup
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -196,11 +196,11 @@ def test_bilinear_statement_on_hand_computed_texels():
 def test_tex_header_symbols_are_exported_and_bound(capi):
     header = open(os.path.join(ROOT, "include", "crender_tex.h")).read()
     declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
-    assert declared == set(capi.TEX_SIGNATURES) == {"crender_tex_shade"}, declared ^ set(capi.TEX_SIGNATURES)
-    assert not declared & (set(capi.SIGNATURES) | set(capi.WIRE_SIGNATURES) | set(capi.PY_SIGNATURES))
+    assert declared == set(capi.UNIT_SIGNATURES["tex"]) == {"crender_tex_shade"}, declared ^ set(capi.UNIT_SIGNATURES["tex"])
+    assert not declared & other_symbols(capi, "tex")
     L = capi.load()
     for name in declared:
-        assert getattr(L, name).argtypes == capi.TEX_SIGNATURES[name][1]
+        assert getattr(L, name).argtypes == capi.UNIT_SIGNATURES["tex"][name][1]
     out = subprocess.check_output(["nm", "-D", "--defined-only", capi.lib_path()], text=True)
     assert declared <= set(re.findall(r" T (crender_\w+)", out))
     for flag, value in (("CRENDER_TEX_PERSPECTIVE", capi.TEX_PERSPECTIVE), ("CRENDER_TEX_BILINEAR", capi.TEX_BILINEAR)):
@@ -209,7 +209,7 @@ def test_tex_header_symbols_are_exported_and_bound(capi):
 
 def test_tex_sources_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert "texture.hip" in _build.TEX_SOURCES and "texture.hip" not in _build.SOURCES
+    assert "texture.hip" in _build.UNITS["tex"][0] and "texture.hip" not in _build.SOURCES
     assert not any("crender_tex" in h for h in _build.HEADERS)
     assert _build.source_sha16() == "f3a47bfc1afb1a02"         # the sources the committed profiles were measured on
 

@@ -11,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from util import sha
+from util import other_symbols, sha
 from wire_ref import HostImage, line_pixels, wire_plane
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -138,11 +138,11 @@ def test_host_model_equals_the_host_loop_on_random_soups():
 def test_wire_header_symbols_are_exported_and_bound(capi):
     header = open(os.path.join(ROOT, "include", "crender_wire.h")).read()
     declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
-    assert declared == set(capi.WIRE_SIGNATURES), declared ^ set(capi.WIRE_SIGNATURES)
-    assert not declared & set(capi.SIGNATURES)
+    assert declared == set(capi.UNIT_SIGNATURES["wire"]), declared ^ set(capi.UNIT_SIGNATURES["wire"])
+    assert not declared & other_symbols(capi, "wire")
     L = capi.load()
     for name in declared:
-        assert getattr(L, name).argtypes == capi.WIRE_SIGNATURES[name][1]
+        assert getattr(L, name).argtypes == capi.UNIT_SIGNATURES["wire"][name][1]
     out = subprocess.check_output(["nm", "-D", "--defined-only", capi.lib_path()], text=True)
     assert declared <= set(re.findall(r" T (crender_\w+)", out))
     for flag, value in (("CRENDER_WIRE_DOTS", capi.WIRE_DOTS), ("CRENDER_WIRE_FORCE_COLORS", capi.WIRE_FORCE_COLORS),
@@ -152,7 +152,7 @@ def test_wire_header_symbols_are_exported_and_bound(capi):
 
 def test_wire_sources_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert "wireframe.hip" in _build.WIRE_SOURCES and "wireframe.hip" not in _build.SOURCES
+    assert "wireframe.hip" in _build.UNITS["wire"][0] and "wireframe.hip" not in _build.SOURCES
     assert not any("crender_wire" in h for h in _build.HEADERS)
 
 

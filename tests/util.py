@@ -1,5 +1,6 @@
 """Shared helpers of the parity tests."""
 import hashlib
+import os
 
 import numpy as np
 
@@ -22,6 +23,21 @@ def assert_bit_equal(got, want, what):
         i = tuple(bad[0])
         raise AssertionError(f"{what}: {len(bad)} of {g.size} elements differ; first at {i}: "
                              f"got {np.asarray(got)[i]!r} want {np.asarray(want)[i]!r}")
+
+
+def other_symbols(capi, unit):
+    """Every symbol the binding declares outside `unit`'s own table: the core ABI's and all the other units'."""
+    names = set(capi.SIGNATURES)
+    for other, table in capi.UNIT_SIGNATURES.items():
+        if other != unit:
+            names |= set(table)
+    return names
+
+
+def unit_inputs(_build, unit):
+    """The paths of a unit's sources and headers, as _build.build_inputs() names them."""
+    sources, headers = _build.UNITS[unit]
+    return {os.path.join(_build.SRC_DIR, name) for name in sources + headers}
 
 
 def random_soup(rng, T, res, size_px=(1.0, 40.0), z=(0.5, 3.0), frac_backface=0.2, margin=0.3):
