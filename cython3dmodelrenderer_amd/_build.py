@@ -22,7 +22,7 @@ _INCLUDE = os.path.join("..", "..", "include")
 # but kept out of source_sha16(): that fingerprint names the kernels the committed profiles/*.json were measured on,
 # and these kernels are none of them.  _capi.UNIT_SIGNATURES is keyed alike.
 UNITS = {
-    # wireframe.hip  EdgeOnlyPixelBufferFiller (include/crender_wire.h)
+    # wireframe.hip  EdgeOnlyPixelBufferFiller, and the hidden-line overlay over the winner plane (include/crender_wire.h)
     "wire": (["wireframe.hip"], [os.path.join(_INCLUDE, "crender_wire.h")]),
     # pyfill.hip  the numpy filler of crender/py (include/crender_py.h)
     "py": (["pyfill.hip"], [os.path.join(_INCLUDE, "crender_py.h")]),
@@ -42,7 +42,7 @@ UNITS = {
     # ao.hip  the deferred ambient-occlusion pass over the z, winner and normal planes (include/crender_ao.h)
     "ao": (["ao.hip"], [os.path.join(_INCLUDE, "crender_ao.h")]),
     # winner_pass.h  what the deferred passes over the winner plane share (texture.hip, texmip.hip, texaniso.hip,
-    # shadow.hip, phong.hip): the pixel frame, the corner gather, the store with the fused light, the texel fetches and
+    # shadow.hip, phong.hip, wireframe.hip): the pixel frame, the corner gather, the store with the fused light, the texel fetches and
     # the launch geometry; a unit of its own, without a source, so that each pass's header list stays its own.
     "pass": ([], ["winner_pass.h"]),
     # chain.hip  the swap chain's shared slot: one slot on the caller's stream (include/crender_chain.h; host code

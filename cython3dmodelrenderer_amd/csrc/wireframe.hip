@@ -8,16 +8,23 @@
 // one's segment by a binary search over the workgroup's scan of the counts in LDS.  No device-wide
 // scan and no host round trip: a launch sizes nothing from another launch's result.
 //
+// Also here: the hidden-line overlay over the winner plane of AdvancedPixelBufferFiller (k_wire_overlay, at the end
+// of the file), a deferred pass of the shape of k_phong_shade.
+//
 // Order.  With one constant colour every writer of a pixel stores the same 12 bytes.  With
 // per-triangle colours the last write of the reference's sequence (triangle i, edge e) wins; a line
 // never visits a pixel twice (its major coordinate moves at every step), so the winner is the
 // segment with the largest 3 i + e: one launch takes the atomic maximum of 3 i + e + 1 per pixel in
 // a uint32 key plane, a second one walks the same pixels again and the segment that finds its own
 // key stores its colour and writes the key back to 0.
+#include <math.h>
+
 #include "common.h"
 #include "../../include/crender_wire.h"
 
 using namespace crender_detail;
+
+#include "winner_pass.h"     // WinnerPixel, gather_corners, pass_grid (k_wire_overlay)
 
 namespace {
 
@@ -188,6 +195,70 @@ __global__ __launch_bounds__(kThreads) void k_wire(const float *__restrict__ tri
     }
 }
 
+
+// ---- the hidden-line overlay (crender_wire_overlay) -------------------------------------------------------------
+// The shape of k_phong_shade (phong.hip): a pixel per work item, an 8 x 8 block of pixels per wavefront, a grid-stride
+// loop over row blocks; a wavefront whose 64 winners are all background leaves after its one load.  A pixel sees the
+// edges of its own winner only, so a line behind a nearer triangle is never drawn: no depth bias, no second look at z.
+
+// The line and the window of a call.
+struct WireStyle {
+    float line[3], fill[3];
+    float hi, feather, opacity;              // hi = width / 2 + feather / 2
+};
+
+// The statements "Per edge" of crender_wire.h: the distance of (fx, fy) to the line through a and b.
+CR_DEV float line_distance(const float a[3], const float b[3], float fx, float fy)
+{
+    const float l1 = a[0] - b[0], l2 = a[1] - b[1];
+    const float n = l1 * (fy - b[1]) - l2 * (fx - b[0]);
+    const float len = sqrtf(l1 * l1 + l2 * l2);
+    return fabsf(n) / len;
+}
+
+// FILL: every covered pixel is stored, over the fill colour; without it only the pixels on a line, over their own.
+template <bool FILL>
+__global__ __launch_bounds__(kThreads) void k_wire_overlay(const int32_t *__restrict__ win, const float *__restrict__ tri,
+                                                            int64_t T, const uint32_t *__restrict__ pos_of, ProjConst P,
+                                                            const uint8_t *__restrict__ edges, WireStyle S,
+                                                            float *__restrict__ cb, int W, int y0, int y1, int row_blocks)
+{
+    for (int rb = blockIdx.y; rb < row_blocks; rb += gridDim.y) {
+        const WinnerPixel px = winner_pixel(win, T, pos_of, W, y0, y1, rb);
+        if (!wave_any(px.covered)) continue;        // a scalar branch: the whole wavefront leaves
+        if (!px.covered) continue;
+        unsigned mask = 7u;
+        if (edges) mask = edges[px.orig];           // a scalar branch; the caller's order, as uv
+        float c[3][3];
+        gather_corners(tri, px.t, c[0], c[1], c[2]);
+        project_vertex(P, c[0]);
+        project_vertex(P, c[1]);
+        project_vertex(P, c[2]);
+        const float fx = (float)px.x, fy = (float)px.y;
+        float m = INFINITY;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            if (!((mask >> e) & 1u)) continue;
+            const float d = line_distance(c[e], c[(e + 1) % 3], fx, fy);
+            if (d < m) m = d;                       // (a NaN is never taken)
+        }
+        float a = (S.hi - m) / S.feather;
+        const bool on = a > 0.0f;
+        a = a > 1.0f ? 1.0f : a;
+        a = a * S.opacity;
+        float *cp = cb + px.pix * 3;
+        if (FILL) {
+            const float k = 1.0f - a;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) cp[j] = on ? S.fill[j] * k + S.line[j] * a : S.fill[j];
+        } else if (on) {
+            const float k = 1.0f - a;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) cp[j] = cp[j] * k + S.line[j] * a;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -235,6 +306,43 @@ int crender_wire_draw(const float *d_tri, const float *d_col, int64_t T, const f
     hipLaunchKernelGGL(k_wire<kResolve>, grid, dim3(kThreads), 0, st, d_tri, d_col, nseg, dots, 0.0f, 0.0f, 0.0f,
                        d_color, d_key, H, W, d_status);
     CR_LAUNCH_CHECK("k_wire<resolve>");
+    return CRENDER_OK;
+}
+
+int crender_wire_overlay(const int32_t *d_winner, const float *d_tri, int64_t T, const uint32_t *d_pos_of,
+                         const float *P16, const uint8_t *d_edges, const float *line3, const float *fill3, float width,
+                         float feather, float opacity, float *d_color, int H, int W, int y0, int y1, unsigned flags,
+                         void *stream)
+{
+    if (!d_winner || !P16 || !line3 || !d_color)
+        return fail(CRENDER_EINVAL, "crender_wire_overlay: d_winner, P16, line3 or d_color is NULL");
+    if (T < 0) return fail(CRENDER_EINVAL, "crender_wire_overlay: T is negative");
+    if (T > 0 && !d_tri) return fail(CRENDER_EINVAL, "crender_wire_overlay: d_tri is NULL with T > 0");
+    if (H < 1 || W < 1) return fail(CRENDER_EINVAL, "crender_wire_overlay: H or W is below 1");
+    if (y0 < 0 || y1 > H || y0 >= y1) return fail(CRENDER_EINVAL, "crender_wire_overlay: rows outside the frame");
+    if (!isfinite(width) || !(width > 0.0f && width <= (float)CRENDER_WIRE_MAX_WIDTH))
+        return fail(CRENDER_EINVAL, "crender_wire_overlay: width is not in (0, 64]");
+    if (!isfinite(feather) || !(feather > 0.0f && feather <= (float)CRENDER_WIRE_MAX_WIDTH))
+        return fail(CRENDER_EINVAL, "crender_wire_overlay: feather is not in (0, 64]");
+    if (!(opacity >= 0.0f && opacity <= 1.0f)) return fail(CRENDER_EINVAL, "crender_wire_overlay: opacity is not in [0, 1]");
+    bool finite = isfinite(line3[0]) && isfinite(line3[1]) && isfinite(line3[2]);
+    if (fill3) finite = finite && isfinite(fill3[0]) && isfinite(fill3[1]) && isfinite(fill3[2]);
+    if (!finite) return fail(CRENDER_EINVAL, "crender_wire_overlay: line3 or fill3 is not finite");
+    if (flags) return fail(CRENDER_EINVAL, "crender_wire_overlay: unknown flag bits");
+    if (T == 0) return CRENDER_OK;
+    WireStyle S{};
+    for (int j = 0; j < 3; ++j) {
+        S.line[j] = line3[j];
+        S.fill[j] = fill3 ? fill3[j] : 0.0f;
+    }
+    S.hi = width * 0.5f + feather * 0.5f;
+    S.feather = feather;
+    S.opacity = opacity;
+    static constexpr decltype(&k_wire_overlay<false>) kernels[2] = {k_wire_overlay<false>, k_wire_overlay<true>};
+    const PassGrid G = pass_grid(W, y0, y1);
+    hipLaunchKernelGGL(kernels[fill3 != nullptr], G.grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), d_winner,
+                       d_tri, T, d_pos_of, make_proj(P16, W, H), d_edges, S, d_color, W, y0, y1, G.row_blocks);
+    CR_LAUNCH_CHECK("k_wire_overlay");
     return CRENDER_OK;
 }
 

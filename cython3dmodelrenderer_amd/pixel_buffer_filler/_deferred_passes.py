@@ -1,5 +1,5 @@
 """The deferred passes of ``AdvancedPixelBufferFiller`` over the winner plane of its last frame: texture (nearest,
-bilinear, trilinear, anisotropic), shadow, Phong and ambient occlusion, with the texture and shadow-map bindings they
+bilinear, trilinear, anisotropic), shadow, Phong, ambient occlusion and the wireframe overlay, with the texture and shadow-map bindings they
 read.  A mixin beside ``_device_planes.DevicePlanes``: the filler supplies ``device, h, w, y0, y1, _lib, _P`` and
 its frame state (``_pipeline, _inputs, _order, _last_flags, _check_bins``).  What every pass has in common is here
 once: whom it refuses (``_pass_target``), which frame it accepts (``_pass_frame``), and how it is launched
@@ -300,3 +300,36 @@ class DeferredPasses:
         flags = (_capi.AO_ROTATE if rotate else 0) | (_capi.AO_FACE_NORMALS if normals == "face" else 0)
         self._run_pass("crender_ao_shade", tri, T, (self.normals_buffer, taps2, len(table), radius_px, float(radius),
                                                     float(min_cos), float(strength), float(floor)), flags, z=True)
+
+    def wire_pass(self, width=1.0, color=(255, 255, 255), feather=1.0, opacity=1.0, fill=None, edges=None):
+        """A hidden-line wireframe over the LAST frame's colour plane (``crender_wire_overlay``,
+        include/crender_wire.h): every covered pixel takes its distance in pixels to the nearest drawn edge of the
+        triangle that WON it, and is blended towards `color` by ``opacity * clip((width / 2 + feather / 2 - distance) /
+        feather, 0, 1)``.  A line behind a nearer triangle is never drawn, since its pixels name the nearer triangle:
+        no depth bias.  With `fill` (a colour) every covered pixel is first given that colour — lines on a flat body,
+        a hidden-line drawing; without it the lines lie over the shaded surface and a pixel off every line is not
+        written.  `edges` is None (all three edges of every triangle) or a uint8 array [T], numpy or a device tensor,
+        in the caller's triangle order: bit e of entry t draws the edge from corner e to corner (e + 1) % 3
+        (``wireframe.feature_edges`` picks creases and borders).  `width` and `feather` are in pixels, in (0, 64];
+        `opacity` in [0, 1].  The background is not written.  Rows of the filler's ``row_strip``, on torch's current
+        stream.
+
+        The frame is settled first (one stream synchronisation, as every getter does): a frame whose bin lists
+        overflowed is rendered again, and the pass must land on the frame that stays."""
+        self._pass_target("wire_pass")
+        for name, v in (("width", width), ("feather", feather)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 < float(v) <= _capi.WIRE_MAX_WIDTH:
+                raise ValueError(f"{name} must be a number of pixels above 0 and at most {_capi.WIRE_MAX_WIDTH}, got {v!r}")
+        if isinstance(opacity, bool) or not isinstance(opacity, (int, float, np.integer, np.floating)) or not 0 <= float(opacity) <= 1:
+            raise ValueError(f"opacity must be a number from 0 to 1, got {opacity!r}")
+        tri, T = self._pass_frame("wire_pass")
+        if edges is not None:
+            e = edges if isinstance(edges, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(edges))
+            if e.dtype != torch.uint8 or e.dim() != 1 or e.shape[0] != T:
+                raise ValueError(f"edges must be uint8 [T] with T = {T}, the triangles of the last frame, "
+                                 f"got {e.dtype} {tuple(e.shape)}")
+            edges = e.to(self.device).contiguous()
+        line3 = (C.c_float * 3)(*[float(v) for v in color])
+        fill3 = None if fill is None else (C.c_float * 3)(*[float(v) for v in fill])
+        self._run_pass("crender_wire_overlay", tri, T,
+                       (edges if T else None, line3, fill3, float(width), float(feather), float(opacity)))

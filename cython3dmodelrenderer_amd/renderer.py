@@ -22,7 +22,7 @@ def _device_form_is_the_same_shading(illumination):
 class Renderer:
     def __init__(self, pixel_buffer_filler, illumination, triangle_iterator_type=None,
                  image_height=512, image_width=512, use_tqdm=True, on_device=None, texture_pass=None,
-                 shadow=None, ambient_occlusion=None, supersample=None):
+                 shadow=None, ambient_occlusion=None, wireframe=None, supersample=None):
         self.pixel_buffer_filler = pixel_buffer_filler
         self.illumination = illumination
         self.triangle_iterator_type = triangle_iterator_type   # stored, unused (as in Version C)
@@ -91,6 +91,21 @@ class Renderer:
                 raise ValueError("Renderer(ambient_occlusion=...) needs a filler with an ambient-occlusion pass "
                                  f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no ao_pass()")
             self.ambient_occlusion = dict(ambient_occlusion)
+        # wireframe=None (default): no lines.  A dict of AdvancedPixelBufferFiller.wire_pass's arguments ({} = its defaults:
+        # every edge, one pixel wide, white) and, optionally, ``feature_angle``: the edge mask is then
+        # ``wireframe.feature_edges(the model's triangles, feature_angle)``, computed once per model.  Every frame starts
+        # from cleared buffers (one model per frame, as "fused").  The lines are an overlay and are NOT lit: the pass
+        # runs after everything that shades — the illumination in whichever form, the shadow pass under a
+        # PhongIllumination — and before the resolve.  With ``supersample=s`` it runs on the supersampled frame, ``width``
+        # counts that frame's pixels, and the light cannot ride in the resolve (it would shade the lines): the
+        # illumination's device form runs over the supersampled frame, then the wire pass, then the plain resolve.
+        self.wireframe = None
+        self._wired = None             # (weak reference to the model, its feature-edge mask)
+        if wireframe is not None:
+            if not hasattr(pixel_buffer_filler, "wire_pass"):
+                raise ValueError("Renderer(wireframe=...) needs a filler with a wireframe pass "
+                                 f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no wire_pass()")
+            self.wireframe = dict(wireframe)
         # A PhongIllumination is a deferred pass of the filler over its winner plane (``phong_pass``): every frame
         # starts from cleared buffers (one model per frame, as "fused"); the draw, then the texture pass (unlit) if
         # asked for, then the Phong pass, then the shadow pass — AFTER the light here, since the specular term is
@@ -109,11 +124,11 @@ class Renderer:
                                  f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no phong_pass()")
 
     def _draw(self, model, light=None, shadows=True, **kw):
-        """``render_model``; with a texture pass, ambient occlusion or a shadow map, a cleared frame and the passes on
-        top of it."""
+        """``render_model``; with a texture pass, ambient occlusion, a shadow map or a wireframe, a cleared frame and
+        the passes on top of it (but the wireframe's, which follows the light: ``_draw_wire``)."""
         filler = self.pixel_buffer_filler
         if self.texture_pass is None:
-            if self.shadow is None and self.ambient_occlusion is None:
+            if self.shadow is None and self.ambient_occlusion is None and self.wireframe is None:
                 return filler.render_model(model, **kw)
             if not kw.get("clear"):        # (the "fused" caller asks for the cleared frame itself: its raster kernel shades)
                 filler.set_fused_illumination(None)
@@ -156,6 +171,25 @@ class Renderer:
         self.pixel_buffer_filler.bind_shadow_map(light_filler, ltri)
         self.pixel_buffer_filler.shadow_pass(**opts)
 
+    def _draw_wire(self, model):
+        """The wire pass over the frame as it stands (host edits included), if a wireframe was asked for."""
+        if self.wireframe is None:
+            return
+        opts = dict(self.wireframe)
+        angle = opts.pop("feature_angle", None)
+        if angle is not None:
+            if self._wired is None or self._wired[0]() is not model:     # once per model, not per frame
+                from .wireframe import feature_edges
+                tri = model._vertices_by_triangles
+                mask = feature_edges(tri.cpu().numpy() if hasattr(tri, "cpu") else tri, angle)
+                device = getattr(self.pixel_buffer_filler, "device", None)
+                if device is not None:
+                    import torch
+                    mask = torch.from_numpy(mask).to(device)
+                self._wired = (weakref.ref(model), mask)
+            opts["edges"] = self._wired[1]
+        self.pixel_buffer_filler.wire_pass(**opts)
+
     def render(self, model, normalize_model=False, random_colors=True):
         if normalize_model:
             # fit the model into the image (reference: renderer.py:41-46)
@@ -172,9 +206,11 @@ class Renderer:
             if self.texture_pass is not None:
                 # the texture pass carries the light
                 self._draw(model, light=self.illumination.light_direction)
+                self._draw_wire(model)
                 return filler.get_color_tensor()
             self.illumination.fuse_into(filler)
             self._draw(model, clear=True)
+            self._draw_wire(model)
             return filler.get_color_tensor()
         device_form = getattr(self.illumination, "draw_illumination_device", None)
         if self.on_device is None and not _device_form_is_the_same_shading(self.illumination):
@@ -185,10 +221,12 @@ class Renderer:
             # (the views handed out so far are refreshed by the getter below, after the shading)
             self._draw(model, refresh_views=False)
             if device_form(filler):
+                self._draw_wire(model)
                 return filler.get_color_tensor() if self.on_device is True else filler.get_color_buffer()
         else:
             self._draw(model)
         self.illumination.draw_illumination(filler.get_color_buffer(), filler.get_normals_buffer())
+        self._draw_wire(model)         # (carries the host edits to the device; the view shows the lines)
         return filler.get_color_buffer()
 
     def _render_phong(self, model):
@@ -204,6 +242,7 @@ class Renderer:
         self.illumination.draw_illumination_device(filler)
         if self.shadow is not None:
             self._cast_shadows(model)
+        self._draw_wire(model)
         if self.supersample is not None:
             image = filler.resolve(self.supersample)
             return image if self.on_device is True else image.cpu().numpy()
@@ -218,6 +257,7 @@ class Renderer:
             else:
                 self.illumination.fuse_into(filler)
                 self._draw(model, clear=True)
+            self._draw_wire(model)
             return filler.resolve(s)
         light = getattr(self.illumination, "light_direction", None)
         device_form = getattr(self.illumination, "draw_illumination_device", None)
@@ -226,10 +266,18 @@ class Renderer:
         if self.on_device is not False and device_form is not None and light is not None:
             # the resolve carries the light: the supersampled colour plane is read once and stays unshaded
             self._draw(model, refresh_views=False)
-            image = filler.resolve(s, light_direction=light)
+            if self.wireframe is None:
+                image = filler.resolve(s, light_direction=light)
+            else:
+                # the lines are not lit: the light as a pass of its own over the supersampled frame, then the lines
+                if not device_form(filler):
+                    self.illumination.draw_illumination(filler.get_color_buffer(), filler.get_normals_buffer())
+                self._draw_wire(model)
+                image = filler.resolve(s)
             return image if self.on_device is True else image.cpu().numpy()
         self._draw(model)
         self.illumination.draw_illumination(filler.get_color_buffer(), filler.get_normals_buffer())
+        self._draw_wire(model)
         return filler.resolve(s).cpu().numpy()
 
     def reset_buffers(self):

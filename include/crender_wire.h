@@ -1,6 +1,7 @@
 /*
  * crender_wire.h — C ABI of the wireframe filler (EdgeOnlyPixelBufferFiller) of
- * libcrender_hip.so.  Same conventions as crender_hip.h: raw device pointers, an int
+ * libcrender_hip.so, and of the hidden-line overlay over AdvancedPixelBufferFiller's winner plane
+ * (crender_wire_overlay, at the end).  Same conventions as crender_hip.h: raw device pointers, an int
  * status (CRENDER_OK or a CRENDER_E* code, text in crender_last_error()), work enqueued
  * on `stream` and nothing synchronised.  Reference files cited below are in the
  * reference's crender/py/ (the crender/cy/ copies are identical but for one import).
@@ -62,6 +63,72 @@ CRENDER_API size_t crender_wire_key_bytes(int H, int W);
 CRENDER_API int crender_wire_draw(const float *d_tri, const float *d_col, int64_t T, const float *line_bgr3,
                                   float *d_z, float *d_color, float *d_normal, uint32_t *d_key, int H, int W,
                                   unsigned flags, int32_t *d_status, void *stream);
+
+/*
+ * The hidden-line overlay: a deferred pass over the winner plane a raster launch left (crender_render_model with a
+ * d_winner), as crender_phong_shade is.  It draws the edges of every triangle on the pixels that triangle WON, so a
+ * line behind a nearer triangle is never drawn: hidden-line removal without a depth bias.
+ *
+ * Result contract.  For every pixel (x, y) with y0 <= y < y1 and t = d_winner[y][x]:
+ *
+ *   Arithmetic   every step below is ONE float32 operation, rounded once, with IEEE division and square root (no
+ *                contraction into fused multiply-adds, no reciprocal, denormals kept).
+ *   Background   t < 0, t >= T, or d_pos_of[t] >= T: the pixel is not written.  Nothing is ever read out of bounds,
+ *                whatever the winner plane holds.
+ *   Corners      the three vertices of triangle t -- d_tri[t], or d_tri[d_pos_of[t]] with a d_pos_of -- projected as
+ *                crender_project projects them (.pyx:116-130): (x_k, y_k), k = 0, 1, 2.
+ *   Edge mask    bits = d_edges[t] (indexed by t itself, the caller's order, whatever d_pos_of says), or 7 without
+ *                d_edges.  Bit e draws edge e, from corner e to corner (e + 1) % 3: p0->p1, p1->p2, p2->p0, the
+ *                numbering of crender_wire_draw's lines.  Bits 3 to 7 are ignored.
+ *   Per edge     fx = (float)x, fy = (float)y, m = +inf; for e = 0, 1, 2 in order, if bit e is set, with a = corner e
+ *                and b = corner (e + 1) % 3:
+ *                  l1 = xa - xb,   l2 = ya - yb
+ *                  n  = l1 * (fy - yb) - l2 * (fx - xb)      (the numerator of the barycentric b3, b1, b2 of
+ *                                                             math_utils.pyx:8-34 for e = 0, 1, 2)
+ *                  len = sqrtf(l1 * l1 + l2 * l2)
+ *                  d  = fabsf(n) / len
+ *                  if (d < m) m = d
+ *                The distance is to the edge's LINE, not to its segment.  A NaN (an edge of no length, a NaN or
+ *                infinite corner) is never taken.
+ *   Window       hi = width * 0.5f + feather * 0.5f (once, on the host, in float32);
+ *                  a  = (hi - m) / feather
+ *                  on = a > 0                                 (false for a NaN and for m = +inf)
+ *                  a  = a > 1 ? 1 : a
+ *                  a  = a * opacity
+ *                A pixel within (width - feather) / 2 of a line gets all of `opacity`, one beyond
+ *                (width + feather) / 2 none; the ramp between them is linear.
+ *   Colour       base = fill3 if given, else the pixel's own colour.  If on, per channel j:
+ *                  k = 1.0f - a,   colour_j = base_j * k + line3_j * a
+ *                If not on: the pixel is stored with fill3 if it is given, and otherwise NOT written: it keeps its
+ *                bits.  With finite colours no NaN reaches a pixel that is on or filled.
+ *   Other planes z, normals and the winner plane are only read.
+ *
+ * Only the winner's side of an edge draws it: the line of a silhouette or border edge is width / 2 wide.  Widths are
+ * in pixels; no dashes, no fading with depth.
+ */
+#define CRENDER_WIRE_MAX_WIDTH 64
+
+/* Overlay the colour plane d_color float32 [H][W][3] over rows y0 <= y < y1.
+ *   d_winner   int32 [H][W]: the caller's index of the triangle whose fragment won, -1 = background
+ *   d_tri      float32 [T][3][3], UNPROJECTED camera-frame vertices (may be NULL if T == 0)
+ *   d_pos_of   NULL, or uint32 [T]: triangle t sits at d_tri[d_pos_of[t]] (the tile-coherent copy of
+ *              crender_plan_set_triangle_order); an entry >= T makes t background
+ *   P16        HOST float[16], the camera's projection matrix (crender_projection_matrix)
+ *   d_edges    NULL (all three edges of every triangle), or uint8 [T] in the CALLER's triangle order
+ *   line3      HOST float[3], the colour of the lines
+ *   fill3      NULL, or HOST float[3]: the colour every covered pixel is given under the lines (a hidden-line drawing)
+ *   width      of a line in pixels, in (0, CRENDER_WIRE_MAX_WIDTH]
+ *   feather    the width of the ramp at each side of a line in pixels, in (0, CRENDER_WIRE_MAX_WIDTH]
+ *   opacity    of the lines, in [0, 1]
+ *   flags      0
+ * CRENDER_EINVAL, before anything is dereferenced or launched, for: a NULL d_winner, P16, line3 or d_color, T < 0,
+ * T > 0 without d_tri, H or W < 1, rows outside the frame (y0 < 0, y1 > H, y0 >= y1), a width or feather that is not
+ * finite or not in (0, CRENDER_WIRE_MAX_WIDTH], an opacity not in [0, 1], a line3 or fill3 component that is not
+ * finite, any flag bit.  T == 0 returns CRENDER_OK without a launch.  One launch; no synchronisation. */
+CRENDER_API int crender_wire_overlay(const int32_t *d_winner, const float *d_tri, int64_t T, const uint32_t *d_pos_of,
+                                     const float *P16, const uint8_t *d_edges, const float *line3, const float *fill3,
+                                     float width, float feather, float opacity, float *d_color,
+                                     int H, int W, int y0, int y1, unsigned flags, void *stream);
 
 #ifdef __cplusplus
 }
