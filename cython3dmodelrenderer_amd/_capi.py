@@ -85,12 +85,17 @@ UNIT_SIGNATURES = {}
 # the wireframe filler's entry points (include/crender_wire.h), bound from a table of their own
 WIRE_DOTS, WIRE_FORCE_COLORS, WIRE_CLEAR = 1, 2, 4
 WIRE_MAX_WIDTH = 64
+WIRE_OUTLINE_MAX_RADIUS = 8
 UNIT_SIGNATURES["wire"] = {
     "crender_wire_key_bytes": (_sz, [_i32, _i32]),
     "crender_wire_draw": (_i32, [_vp, _vp, _i64, _f32p, _vp, _vp, _vp, _vp, _i32, _i32, _u32, _vp, _vp]),
     # the hidden-line overlay over the winner plane: a deferred pass (DeferredPasses.wire_pass)
     "crender_wire_overlay": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _f32p, _f32p, C.c_float, C.c_float, C.c_float, _vp,
                                     _i32, _i32, _i32, _i32, _u32, _vp]),
+    # the same lines at full width, from the winners of a pixel's neighbourhood (DeferredPasses.wire_pass(outline=True)):
+    # the overlay's arguments with d_z after d_winner, and depth_bias and radius_px after the opacity
+    "crender_wire_outline": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, _f32p, _f32p, C.c_float, C.c_float, C.c_float,
+                                    C.c_float, _i32, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
 }
 
 # the numpy filler's entry points (include/crender_py.h), bound from a table of their own

@@ -9,7 +9,8 @@
 // scan and no host round trip: a launch sizes nothing from another launch's result.
 //
 // Also here: the hidden-line overlay over the winner plane of AdvancedPixelBufferFiller (k_wire_overlay, at the end
-// of the file), a deferred pass of the shape of k_phong_shade.
+// of the file), a deferred pass of the shape of k_phong_shade, and after it the outline (k_wire_outline): the same
+// lines at full width from a neighbourhood pass over the winner plane staged in LDS, of the shape of k_ao_shade.
 //
 // Order.  With one constant colour every writer of a pixel stores the same 12 bytes.  With
 // per-triangle colours the last write of the reference's sequence (triangle i, edge e) wins; a line
@@ -259,6 +260,154 @@ __global__ __launch_bounds__(kThreads) void k_wire_overlay(const int32_t *__rest
     }
 }
 
+// ---- the outline (crender_wire_outline) -------------------------------------------------------------------------
+// The overlay's lines at full width: a pixel also sees the edges of the triangles that won its NEIGHBOURS, so the
+// outer half of a silhouette is drawn, on a farther surface or on the background, and a line is not cut where its
+// triangle ends.  A neighbourhood pass over the winner plane, of the shape of k_ao_shade (ao.hip), but with a workgroup
+// per tile and no loop over tiles (the loop's state cost scalar registers the kernel does not have): a workgroup owns a
+// tile of kTile x kTile pixels and stages the VALIDATED winner — the caller's index, or -1 for background, off the
+// frame, outside the strip, t >= T or d_pos_of[t] >= T — of the tile plus a halo of radius_px on every side into LDS
+// once, with unit-stride loads along rows; a tap is then one ds_read_b32 and needs no second look at T or d_pos_of.
+//
+// Geometry.  256 work items are 32 x 8 pixels; a wavefront is two rows of 32 and walks the tile's 32 rows in four
+// steps of 8.  ds_read_b32 is served in two lane groups of 32 lanes over 32 banks of 4 bytes: a lane group is ONE row
+// of 32 consecutive words, so a tap's read — every lane at its own base plus the same offset — is free of bank
+// conflicts under any pitch, and the pitch is simply kTile + 2 R: (32 + 2 R)^2 words, 4.6 KB at R = 1, 9.2 KB at
+// R = 8, plus one word per staged row that says whether the row holds a winner at all.
+//
+// Work.  A pixel handles its own winner first, then walks the (2 R + 1)^2 taps, four reads in flight at a time
+// (a tap's decision waits for its read: one tap at a time the loop is bound by the latency of the LDS), and skips a
+// tap that is -1, its own winner, or one of the four triangles it handled last: a wavefront pays for a candidate
+// whenever one of its lanes takes one, and a window that straddles two or three triangles would otherwise take them
+// again at every row.  Where triangles are larger than the window nearly every group of four is skipped after its reads.  A new candidate costs the corner gather, the projection (nine divisions) and a division
+// and a square root per drawn edge.  The minimum is exact, so the order of the taps does not matter.  A wavefront
+// whose two rows' window holds no winner leaves after one read per staged row of it; a workgroup over background alone
+// is four such wavefronts.
+constexpr int kTile = 32;                       // pixels along each side of a workgroup's tile
+constexpr int kTileRows = kThreads / kTile;     // rows of it the 256 work items cover at a time
+
+// The statements "Per candidate" of crender_wire_outline: the distances of (fx, fy) to the drawn edge SEGMENTS of the
+// triangle at d_tri[pos], each taken into m if it counts there (`always`, or nearer than zp by the bias).
+CR_DEV void outline_candidate(const float *__restrict__ tri, int64_t pos, const ProjConst &P, unsigned mask, float fx,
+                              float fy, bool always, float bias, float zp, float &m)
+{
+    float c[3][3];
+    gather_corners(tri, pos, c[0], c[1], c[2]);
+    project_vertex(P, c[0]);
+    project_vertex(P, c[1]);
+    project_vertex(P, c[2]);
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        if (!((mask >> e) & 1u)) continue;
+        const float *a = c[e], *b = c[(e + 1) % 3];
+        const float ex = b[0] - a[0], ey = b[1] - a[1];
+        const float px = fx - a[0], py = fy - a[1];
+        float s = (px * ex + py * ey) / (ex * ex + ey * ey);
+        s = s < 0.0f ? 0.0f : s;                    // (selects: a NaN passes both)
+        s = s > 1.0f ? 1.0f : s;
+        const float qx = a[0] + s * ex, qy = a[1] + s * ey;
+        const float cx = fx - qx, cy = fy - qy;
+        const float d = sqrtf(cx * cx + cy * cy);
+        const float ze = a[2] + s * (b[2] - a[2]);
+        const bool counts = always || (ze - bias) < zp;
+        if (counts && d < m) m = d;                 // (a NaN is never taken)
+    }
+}
+
+// FILL: every covered pixel is stored, over the fill colour; a background pixel, and without FILL every pixel, only
+// on a line, over its own colour.
+template <bool FILL>
+__global__ __launch_bounds__(kThreads) void k_wire_outline(const int32_t *__restrict__ win, const float *__restrict__ zb,
+                                                            const float *__restrict__ tri, int64_t T,
+                                                            const uint32_t *__restrict__ pos_of, ProjConst P,
+                                                            const uint8_t *__restrict__ edges, WireStyle S, float bias,
+                                                            int R, float *__restrict__ cb, int W, int y0, int y1,
+                                                            int tiles_x)
+{
+    extern __shared__ int32_t s_win[];          // [kTile + 2R][kTile + 2R], then s_row[kTile + 2R]
+    const int side = 2 * R + 1, pitch = kTile + 2 * R;
+    int32_t *s_row = s_win + pitch * pitch;     // 1 if the staged row holds a winner
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lx = threadIdx.x & (kTile - 1), ly = threadIdx.x >> 5;
+    const int tile = blockIdx.x, ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int x0 = tx * kTile, ty0 = y0 + ty * kTile;
+    // ---- stage the validated winners of the tile and its halo: a wavefront per row, 64 columns at a time
+    for (int sy = wave; sy < pitch; sy += kThreads / 64) {
+        const int gy = ty0 - R + sy;
+        const bool row_in = gy >= y0 && gy < y1;
+        bool in_row = false;
+        for (int sx = lane; sx < pitch; sx += 64) {
+            const int gx = x0 - R + sx;
+            int32_t v = -1;
+            if (row_in && gx >= 0 && gx < W) {
+                const int32_t w = win[(size_t)gy * (size_t)W + (size_t)gx];
+                if (w >= 0 && w < T && (!pos_of || pos_of[w] < T)) v = w;
+            }
+            s_win[sy * pitch + sx] = v;
+            in_row |= v >= 0;
+        }
+        in_row = wave_any(in_row);
+        if (lane == 0) s_row[sy] = in_row ? 1 : 0;
+    }
+    __syncthreads();
+    // ---- the tile's pixels, 32 x 8 at a time
+#pragma unroll 1
+    for (int k = 0; k < kTile / kTileRows; ++k) {
+        const int row = ly + k * kTileRows;
+        // the staged rows this wavefront's two rows can reach: (row of lane 0) .. + 1 + 2R
+        const int first = row - (lane >> 5);
+        int reach = 0;
+        for (int r = first; r <= first + 1 + 2 * R; ++r) reach |= s_row[r];
+        if (!wave_any(reach != 0)) continue;        // a scalar branch: the whole wavefront skips
+        const int x = x0 + lx, y = ty0 + row;
+        if (!(x < W && y < y1)) continue;
+        const size_t pix = (size_t)y * (size_t)W + (size_t)x;
+        const int base = (row + R) * pitch + lx + R;
+        const int32_t own = s_win[base];
+        const float zp = zb[pix];
+        const float fx = (float)x, fy = (float)y;
+        float m = INFINITY;
+        // the pixel's own winner first, then the window row by row, four taps in flight at a time
+        if (own >= 0)
+            outline_candidate(tri, pos_of ? (int64_t)pos_of[own] : (int64_t)own, P, edges ? edges[own] : 7u, fx, fy, true,
+                              bias, zp, m);
+        int32_t h0 = -1, h1 = -1, h2 = -1, h3 = -1;     // the four candidates handled last
+        for (int dy = -R; dy <= R; ++dy) {
+            const int32_t *rp = s_win + (base + dy * pitch - R);
+            for (int j = 0; j < side; j += 4) {
+                // (a word past the row's end is still inside the allocation, s_row follows the tile, and is not used)
+                const int32_t t0 = rp[j], r1 = rp[j + 1], r2 = rp[j + 2], r3 = rp[j + 3];
+                const int32_t t1 = j + 1 < side ? r1 : -1, t2 = j + 2 < side ? r2 : -1, t3 = j + 3 < side ? r3 : -1;
+                const bool fresh = (t0 >= 0 && t0 != own) || (t1 >= 0 && t1 != own) || (t2 >= 0 && t2 != own) ||
+                                   (t3 >= 0 && t3 != own);
+                if (!fresh) continue;
+#pragma unroll 1
+                for (int k = 0; k < 4; ++k) {
+                    const int32_t t = k == 0 ? t0 : k == 1 ? t1 : k == 2 ? t2 : t3;
+                    if (t < 0 || t == own || t == h0 || t == h1 || t == h2 || t == h3) continue;
+                    h3 = h2; h2 = h1; h1 = h0; h0 = t;
+                    outline_candidate(tri, pos_of ? (int64_t)pos_of[t] : (int64_t)t, P, edges ? edges[t] : 7u, fx, fy,
+                                      own < 0, bias, zp, m);
+                }
+            }
+        }
+        float a = (S.hi - m) / S.feather;
+        const bool on = a > 0.0f;
+        a = a > 1.0f ? 1.0f : a;
+        a = a * S.opacity;
+        float *cp = cb + pix * 3;
+        if (FILL && own >= 0) {
+            const float kk = 1.0f - a;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) cp[j] = on ? S.fill[j] * kk + S.line[j] * a : S.fill[j];
+        } else if (on) {
+            const float kk = 1.0f - a;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) cp[j] = cp[j] * kk + S.line[j] * a;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -343,6 +492,51 @@ int crender_wire_overlay(const int32_t *d_winner, const float *d_tri, int64_t T,
     hipLaunchKernelGGL(kernels[fill3 != nullptr], G.grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), d_winner,
                        d_tri, T, d_pos_of, make_proj(P16, W, H), d_edges, S, d_color, W, y0, y1, G.row_blocks);
     CR_LAUNCH_CHECK("k_wire_overlay");
+    return CRENDER_OK;
+}
+
+int crender_wire_outline(const int32_t *d_winner, const float *d_z, const float *d_tri, int64_t T,
+                         const uint32_t *d_pos_of, const float *P16, const uint8_t *d_edges, const float *line3,
+                         const float *fill3, float width, float feather, float opacity, float depth_bias, int radius_px,
+                         float *d_color, int H, int W, int y0, int y1, unsigned flags, void *stream)
+{
+    if (!d_winner || !d_z || !P16 || !line3 || !d_color)
+        return fail(CRENDER_EINVAL, "crender_wire_outline: d_winner, d_z, P16, line3 or d_color is NULL");
+    if (T < 0) return fail(CRENDER_EINVAL, "crender_wire_outline: T is negative");
+    if (T > 0 && !d_tri) return fail(CRENDER_EINVAL, "crender_wire_outline: d_tri is NULL with T > 0");
+    if (H < 1 || W < 1) return fail(CRENDER_EINVAL, "crender_wire_outline: H or W is below 1");
+    if (y0 < 0 || y1 > H || y0 >= y1) return fail(CRENDER_EINVAL, "crender_wire_outline: rows outside the frame");
+    if (!isfinite(width) || !(width > 0.0f && width <= (float)CRENDER_WIRE_MAX_WIDTH))
+        return fail(CRENDER_EINVAL, "crender_wire_outline: width is not in (0, 64]");
+    if (!isfinite(feather) || !(feather > 0.0f && feather <= (float)CRENDER_WIRE_MAX_WIDTH))
+        return fail(CRENDER_EINVAL, "crender_wire_outline: feather is not in (0, 64]");
+    if (!(opacity >= 0.0f && opacity <= 1.0f)) return fail(CRENDER_EINVAL, "crender_wire_outline: opacity is not in [0, 1]");
+    if (!isfinite(depth_bias)) return fail(CRENDER_EINVAL, "crender_wire_outline: depth_bias is not finite");
+    if (radius_px < 0 || radius_px > CRENDER_WIRE_OUTLINE_MAX_RADIUS)
+        return fail(CRENDER_EINVAL, "crender_wire_outline: radius_px is not 0 .. 8");
+    bool finite = isfinite(line3[0]) && isfinite(line3[1]) && isfinite(line3[2]);
+    if (fill3) finite = finite && isfinite(fill3[0]) && isfinite(fill3[1]) && isfinite(fill3[2]);
+    if (!finite) return fail(CRENDER_EINVAL, "crender_wire_outline: line3 or fill3 is not finite");
+    if (flags) return fail(CRENDER_EINVAL, "crender_wire_outline: unknown flag bits");
+    if (T == 0) return CRENDER_OK;
+    const int tiles_x = (W + kTile - 1) / kTile;
+    const int64_t tiles = (int64_t)tiles_x * (int64_t)((y1 - y0 + kTile - 1) / kTile);
+    if (tiles > 0x7FFFFFFF) return fail(CRENDER_EINVAL, "crender_wire_outline: H or W is too large");
+    WireStyle S{};
+    for (int j = 0; j < 3; ++j) {
+        S.line[j] = line3[j];
+        S.fill[j] = fill3 ? fill3[j] : 0.0f;
+    }
+    S.hi = width * 0.5f + feather * 0.5f;
+    S.feather = feather;
+    S.opacity = opacity;
+    const int side = kTile + 2 * radius_px;
+    static constexpr decltype(&k_wire_outline<false>) kernels[2] = {k_wire_outline<false>, k_wire_outline<true>};
+    hipLaunchKernelGGL(kernels[fill3 != nullptr], dim3((unsigned)tiles), dim3(kThreads),
+                       (size_t)(side * side + side) * sizeof(int32_t), static_cast<hipStream_t>(stream), d_winner, d_z,
+                       d_tri, T, d_pos_of, make_proj(P16, W, H), d_edges, S, depth_bias, radius_px, d_color, W, y0, y1,
+                       tiles_x);
+    CR_LAUNCH_CHECK("k_wire_outline");
     return CRENDER_OK;
 }
 

@@ -301,7 +301,8 @@ class DeferredPasses:
         self._run_pass("crender_ao_shade", tri, T, (self.normals_buffer, taps2, len(table), radius_px, float(radius),
                                                     float(min_cos), float(strength), float(floor)), flags, z=True)
 
-    def wire_pass(self, width=1.0, color=(255, 255, 255), feather=1.0, opacity=1.0, fill=None, edges=None):
+    def wire_pass(self, width=1.0, color=(255, 255, 255), feather=1.0, opacity=1.0, fill=None, edges=None, outline=False,
+                  depth_bias=1e-3, radius_px=None):
         """A hidden-line wireframe over the LAST frame's colour plane (``crender_wire_overlay``,
         include/crender_wire.h): every covered pixel takes its distance in pixels to the nearest drawn edge of the
         triangle that WON it, and is blended towards `color` by ``opacity * clip((width / 2 + feather / 2 - distance) /
@@ -314,6 +315,15 @@ class DeferredPasses:
         `opacity` in [0, 1].  The background is not written.  Rows of the filler's ``row_strip``, on torch's current
         stream.
 
+        With `outline` (``crender_wire_outline``) the lines have their full width: a pixel takes its distance to the
+        nearest drawn edge SEGMENT of every triangle that won a pixel within `radius_px` of it (0 to 8; None:
+        ``ceil((width + feather) / 2) + 1``, which holds a whole line and so limits ``width + feather`` to 14), the strip
+        not seeing across its edge.  The outer half of a silhouette, a border or an occlusion boundary is then drawn as
+        well, with its ramp: on the background, which is written only where a line lies and never filled, and on a
+        farther surface, where an edge counts if its projected depth at its closest point, less `depth_bias` (in the z
+        plane's units, as ``shadow_pass``'s bias), is nearer than what the pixel shows.  A line behind the surface a
+        pixel shows is not drawn.
+
         The frame is settled first (one stream synchronisation, as every getter does): a frame whose bin lists
         overflowed is rendered again, and the pass must land on the frame that stays."""
         self._pass_target("wire_pass")
@@ -322,6 +332,18 @@ class DeferredPasses:
                 raise ValueError(f"{name} must be a number of pixels above 0 and at most {_capi.WIRE_MAX_WIDTH}, got {v!r}")
         if isinstance(opacity, bool) or not isinstance(opacity, (int, float, np.integer, np.floating)) or not 0 <= float(opacity) <= 1:
             raise ValueError(f"opacity must be a number from 0 to 1, got {opacity!r}")
+        if outline:
+            top = _capi.WIRE_OUTLINE_MAX_RADIUS
+            if isinstance(depth_bias, bool) or not isinstance(depth_bias, (int, float, np.integer, np.floating)) \
+                    or not np.isfinite(float(depth_bias)):
+                raise ValueError(f"depth_bias must be a finite number, got {depth_bias!r}")
+            if radius_px is None:
+                radius_px = int(np.ceil((float(width) + float(feather)) / 2.0)) + 1
+                if radius_px > top:
+                    raise ValueError(f"outline=True: width + feather = {float(width) + float(feather):g} needs radius_px = "
+                                     f"{radius_px}, above the largest, {top}: width + feather may be at most {2 * (top - 1)}")
+            elif isinstance(radius_px, bool) or not isinstance(radius_px, (int, np.integer)) or not 0 <= radius_px <= top:
+                raise ValueError(f"radius_px must be None or an int from 0 to {top}, got {radius_px!r}")
         tri, T = self._pass_frame("wire_pass")
         if edges is not None:
             e = edges if isinstance(edges, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(edges))
@@ -331,5 +353,10 @@ class DeferredPasses:
             edges = e.to(self.device).contiguous()
         line3 = (C.c_float * 3)(*[float(v) for v in color])
         fill3 = None if fill is None else (C.c_float * 3)(*[float(v) for v in fill])
+        if outline:
+            self._run_pass("crender_wire_outline", tri, T,
+                           (edges if T else None, line3, fill3, float(width), float(feather), float(opacity),
+                            float(depth_bias), int(radius_px)), z=True)
+            return
         self._run_pass("crender_wire_overlay", tri, T,
                        (edges if T else None, line3, fill3, float(width), float(feather), float(opacity)))

@@ -1,7 +1,7 @@
 /*
  * crender_wire.h — C ABI of the wireframe filler (EdgeOnlyPixelBufferFiller) of
  * libcrender_hip.so, and of the hidden-line overlay over AdvancedPixelBufferFiller's winner plane
- * (crender_wire_overlay, at the end).  Same conventions as crender_hip.h: raw device pointers, an int
+ * (crender_wire_overlay, and crender_wire_outline for lines at full width, at the end).  Same conventions as crender_hip.h: raw device pointers, an int
  * status (CRENDER_OK or a CRENDER_E* code, text in crender_last_error()), work enqueued
  * on `stream` and nothing synchronised.  Reference files cited below are in the
  * reference's crender/py/ (the crender/cy/ copies are identical but for one import).
@@ -128,6 +128,70 @@ CRENDER_API int crender_wire_draw(const float *d_tri, const float *d_col, int64_
 CRENDER_API int crender_wire_overlay(const int32_t *d_winner, const float *d_tri, int64_t T, const uint32_t *d_pos_of,
                                      const float *P16, const uint8_t *d_edges, const float *line3, const float *fill3,
                                      float width, float feather, float opacity, float *d_color,
+                                     int H, int W, int y0, int y1, unsigned flags, void *stream);
+
+/*
+ * The outline: the overlay's lines at FULL width.  A pixel also sees the edges of the triangles that won its
+ * neighbours, so the outer half of a silhouette, a border or an occlusion boundary is drawn — on the farther surface
+ * or on the background, with the same ramp as inside — and a line is not cut where the triangle that carries it ends.
+ * A neighbourhood pass over the winner plane, as crender_ao_shade is; it needs the z plane of the same frame.
+ *
+ * Result contract.  For every pixel p = (x, y) with y0 <= y < y1:
+ *
+ *   Arithmetic   every step below is ONE float32 operation, rounded once, with IEEE division and square root (no
+ *                contraction into fused multiply-adds, no reciprocal, denormals kept).
+ *   Winners      the winner of a pixel q is VALID if t = d_winner[q] has 0 <= t < T and, with a d_pos_of,
+ *                d_pos_of[t] < T.  p is COVERED if its own winner is valid, else it is background.  Nothing is ever
+ *                read out of bounds, whatever the planes hold.
+ *   Candidates   the valid winners of the pixels q with |qx - x| <= radius_px and |qy - y| <= radius_px that lie on
+ *                the frame and in rows y0 <= qy < y1: a strip does not see across its edge.  p itself is among them.
+ *   Corners      of candidate t: d_tri[t], or d_tri[d_pos_of[t]] with a d_pos_of, projected as crender_project
+ *                projects them: (x_k, y_k, z_k), k = 0, 1, 2 — x and y in pixels, z the projected depth.
+ *   Edge mask    the overlay's: bits = d_edges[t] in the caller's order, or 7 without d_edges; bit e draws the edge
+ *                from corner e to corner (e + 1) % 3.
+ *   Per edge     fx = (float)x, fy = (float)y; for a candidate t and a drawn edge e, a = corner e, b = corner (e + 1) % 3:
+ *                  ex = xb - xa,   ey = yb - ya,   px = fx - xa,   py = fy - ya
+ *                  s  = (px * ex + py * ey) / (ex * ex + ey * ey)
+ *                  s  = s < 0 ? 0 : s;   s = s > 1 ? 1 : s        (selects: a NaN passes both)
+ *                  qx = xa + s * ex,   qy = ya + s * ey           (the closest point of the SEGMENT)
+ *                  cx = fx - qx,   cy = fy - qy
+ *                  d  = sqrtf(cx * cx + cy * cy)
+ *                  ze = za + s * (zb - za)                        (projected z is affine on the screen: the edge's
+ *                                                                  depth at the closest point)
+ *   Hidden lines (t, e) COUNTS at p if t is p's own winner (the same index), or p is background, or
+ *                (ze - depth_bias) < d_z[p].  A line behind the surface p shows is never drawn; a silhouette in front
+ *                of a farther surface draws its outer half on it.  (False for a NaN: such an edge does not count.)
+ *   Minimum      m = +inf; for every (t, e) that counts: if (d < m) m = d.  A NaN (an edge of no length, a corner
+ *                that is not finite) is never taken.  A minimum is exact and does not depend on the order: the result
+ *                is a function of the SET of candidates.  The kernel visits the taps in an order of its own and skips
+ *                a tap whose winner it has just handled.
+ *   Window       crender_wire_overlay's statements, unchanged: hi, a, on, the clamp and the opacity.
+ *   Colour       a covered pixel: base = fill3 if given, else its own colour; if on, colour_j = base_j * k + line3_j * a
+ *                with k = 1.0f - a; if not on, it is stored with fill3 if given and otherwise not written.
+ *                A BACKGROUND pixel: base is always its own colour, and it is written only if it is on.
+ *                With finite colours no NaN reaches a pixel that is written.
+ *   Other planes z, normals and the winner plane are only read.  The colour is read and written at p alone.
+ *
+ * Limits.  An edge is seen only through pixels its triangle WON within radius_px of p: a sliver that won nothing
+ * nearby draws nothing there, as in the overlay, and a line wider than radius_px allows is cut.  For the whole ramp of
+ * a line radius_px >= ceil((width + feather) / 2) + 1: the extra pixel is for the won pixel nearest to the closest
+ * point.  radius_px = 0 sees the own winner alone (segments instead of the overlay's lines).
+ */
+#define CRENDER_WIRE_OUTLINE_MAX_RADIUS 8
+
+/* Outline the colour plane d_color float32 [H][W][3] over rows y0 <= y < y1.  crender_wire_overlay's arguments, and
+ *   d_z        float32 [H][W]: the z plane of the frame that left d_winner (projected depth, smaller = nearer)
+ *   depth_bias finite; in the units of d_z (projected z)
+ *   radius_px  0 .. CRENDER_WIRE_OUTLINE_MAX_RADIUS: how far, in pixels, a pixel looks for candidates
+ *   flags      0
+ * CRENDER_EINVAL, before anything is dereferenced or launched, for every cause of crender_wire_overlay's, a NULL d_z,
+ * a depth_bias that is not finite, a radius_px outside 0 .. CRENDER_WIRE_OUTLINE_MAX_RADIUS, any flag bit.  T == 0
+ * returns CRENDER_OK without a launch.  One launch with (32 + 2 radius_px)^2 + 32 + 2 radius_px words of LDS; no
+ * synchronisation. */
+CRENDER_API int crender_wire_outline(const int32_t *d_winner, const float *d_z, const float *d_tri, int64_t T,
+                                     const uint32_t *d_pos_of, const float *P16, const uint8_t *d_edges,
+                                     const float *line3, const float *fill3, float width, float feather, float opacity,
+                                     float depth_bias, int radius_px, float *d_color,
                                      int H, int W, int y0, int y1, unsigned flags, void *stream);
 
 #ifdef __cplusplus

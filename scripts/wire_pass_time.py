@@ -1,6 +1,9 @@
 """Device time of the hidden-line overlay (csrc/wireframe.hip, k_wire_overlay): crender_wire_overlay between two HIP
-events, mean of 50 passes over the same frame, for T-Rex at 1024^2 and at 4096^2: all edges and the 30-degree feature
-mask, with and without a fill, at width 1 and width 3 (feather 1).  (Without a fill the pass blends the lines over what
+events, mean of 50 passes over the same frame, for T-Rex at 256^2 (where nearly every tap of the outline is a new
+triangle), at 1024^2 and at 4096^2: all edges and the 30-degree feature mask, with and without a fill, at width 1 and
+width 3 (feather 1).  Next to it, in the same run, the outline (k_wire_outline, crender_wire_outline) at radius 2
+(width 1), 4 and 8 (width 3) under the same masks and fills: every outline row carries its ratio to the overlay row of
+the same mask, fill and width as `vs_overlay`.  (Without a fill the pass blends the lines over what
 it finds, so the colour under a line converges to the line's colour from pass to pass; the work per pass does not depend
 on the colours.)
 
@@ -25,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 REPS, WARMUP, ROUNDS = 50, 5, 3
-SCENES = {"trex1024": 1024, "trex4096": 4096}
+SCENES = {"trex256": 256, "trex1024": 1024, "trex4096": 4096}
 CHILD_SECONDS = 240
 
 
@@ -94,6 +97,7 @@ def measure(name):
                                                   size, 0, size, st), "crender_guro_illumination")
     guro_us = row("illumination_pass_alone", _timed(stream, guro))
 
+    overlay_us = {}
     for edges_name, edges in (("all", None), ("feature30", feature)):
         for fill_name, fill in (("over", None), ("fill", grey)):
             for width in (1.0, 3.0):
@@ -103,7 +107,21 @@ def measure(name):
                         None if edges is None else edges.data_ptr(), white, fill, width, 1.0, 1.0, f.color_buffer.data_ptr(),
                         size, size, 0, size, 0, st), "crender_wire_overlay")
                 us, spread = _timed(stream, launch)
+                overlay_us[edges_name, fill_name, width] = us
                 row(f"wire_{edges_name}_{fill_name}_w{int(width)}", (us, spread), vs_tex=round(us / tex_us, 2),
+                    vs_guro=round(us / guro_us, 2))
+
+    for edges_name, edges in (("all", None), ("feature30", feature)):
+        for fill_name, fill in (("over", None), ("fill", grey)):
+            for radius, width in ((2, 1.0), (4, 3.0), (8, 3.0)):
+                def launch():
+                    _capi.check(lib.crender_wire_outline(
+                        f.winner_buffer.data_ptr(), f.z_buffer.data_ptr(), f._inputs[0].data_ptr(), T, None, f._P,
+                        None if edges is None else edges.data_ptr(), white, fill, width, 1.0, 1.0, 1e-3, radius,
+                        f.color_buffer.data_ptr(), size, size, 0, size, 0, st), "crender_wire_outline")
+                us, spread = _timed(stream, launch)
+                row(f"outline_{edges_name}_{fill_name}_r{radius}_w{int(width)}", (us, spread),
+                    vs_overlay=round(us / overlay_us[edges_name, fill_name, width], 2), vs_tex=round(us / tex_us, 2),
                     vs_guro=round(us / guro_us, 2))
 
 
