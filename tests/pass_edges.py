@@ -16,12 +16,18 @@ n == 0) the full `/` is used."):
 `classify` restates them in numpy float32 from the host model's own operands; no kernel code is imported.
 
 The Phong and the occlusion pass take no such shortcut; what they add to the scenes (`_lit`, at the end: a z plane,
-tap tables, light sets) is drawn after everything else, so that the arrays of the four older passes stay what they were."""
+tap tables, light sets) is drawn after everything else, so that the arrays of the four older passes stay what they were.
+
+Nor do the two wire passes (the overlay and the outline).  `_wired`, after `_lit`, gives the scenes an edge mask — and
+the tall frame a z plane — from generators of its own; and three frames at the end are theirs alone: `tie_scene` (the
+hidden-line test at equality, the three sides of the clamp, the NaN), `sparse_frames` and `sparse_strip` (lone winners
+on the seams of the outline's 32 x 32 tiles, for the rows a wavefront skips)."""
 import functools
 
 import numpy as np
 
 import ao_ref
+import outline_ref
 import phong_ref
 import shadow_ref
 import tex_ref
@@ -295,7 +301,7 @@ def shadow_points(s, winner, bias=BIAS):
 
 @functools.lru_cache(maxsize=None)
 def scene():
-    return _lit(_build(), 20244)
+    return _wired(_lit(_build(), 20244), 20246)
 
 
 def classify(s, winner=None, dtype=np.float32):
@@ -365,7 +371,7 @@ def mini_scene():
     s.normals = nrm
     s.lz = rng.uniform(0.3, 1.0, (HL, WL)).astype(np.float32)
     s.lwinner = rng.integers(-1, T, (HL, WL)).astype(np.int32)
-    return _lit(s, 20245)
+    return _wired(_lit(s, 20245), 20247)
 
 
 # ---- the tall frame: more 8-row blocks than a grid is tall ----------------------------------------------------------
@@ -404,7 +410,7 @@ def tall_scene():
     s.lz = rng.uniform(0.3, 1.0, (HL, WL)).astype(np.float32)
     s.lwinner = rng.integers(-1, T, (HL, WL)).astype(np.int32)
     s.lights = light_sets(s, None)
-    return s
+    return _wired(s, 20248, z=True)
 
 
 # ---- what the Phong and the occlusion pass need: drawn after everything above, from generators of their own ----------
@@ -470,3 +476,206 @@ def _lit(s, seed):
     s.on_corner = (int(t[at[0]]), int(corner[0])) if len(at) else None
     s.lights = light_sets(s, s.tri[s.on_corner] if len(at) else None)
     return s
+
+
+# ---- what the two wire passes need: drawn after everything above, from generators of their own -----------------------
+
+SPARSE_H, SPARSE_W = 97, 101          # the outline's tiles of 32: three whole ones each way, then one row and five columns
+TILE = 32
+SPARSE_COLUMNS = (0, 31, 32, 63, 64, 95, 96, 100)
+SPARSE_RADII = (1, 8)
+SPARSE_STRIP = (37, 75)               # rows of the strip frame: neither end a multiple of 32
+
+
+def _wired(s, seed, z=False):
+    """An edge mask in the caller's order, bits 3 to 7 set at random (they are ignored); with `z` a z plane for a scene
+    that has none (the tall frame): projected depths of the range its triangles have, a tenth of it NaN or infinite."""
+    rng = np.random.default_rng(seed)
+    s.edges = rng.integers(0, 256, s.T).astype(np.uint8)
+    if z:
+        plane = rng.uniform(0.4, 1.0, (s.H, s.W)).astype(np.float32)
+        odd = rng.uniform(size=plane.shape) < 0.1
+        plane[odd] = rng.choice(np.float32([np.nan, np.inf, -np.inf, 1e6]), int(odd.sum()))
+        s.z = plane
+    return s
+
+
+# ---- the tie of the hidden-line test, the clamp of s and the depth ze: two triangles and a degenerate third ----------
+
+TIE_H, TIE_W, TIE_RADIUS, TIE_BIAS = 40, 40, 3, 1e-3
+TIE_A, TIE_B, TIE_A2 = 0, 1, 2
+TIE_KINDS = ("exact", "above", "below")
+
+
+def tie_operands(proj, t, e, xs, ys, bias=TIE_BIAS):
+    """(s before the clamp, s, d, ze, ze - bias) of crender_wire_outline's "Per edge" for edge e of triangle t at the
+    pixels (xs, ys): the model's own float32 statements (tests/outline_ref.py), one operation per step."""
+    d_ = np.float32
+    a, b = proj[t, e], proj[t, (e + 1) % 3]
+    fx, fy = xs.astype(d_), ys.astype(d_)
+    with np.errstate(all="ignore"):
+        ex, ey = b[0] - a[0], b[1] - a[1]
+        px, py = fx - a[0], fy - a[1]
+        raw = (px * ex + py * ey) / (ex * ex + ey * ey)
+        s = np.where(raw < 0, d_(0), raw)
+        s = np.where(s > 1, d_(1), s)
+        qx, qy = a[0] + s * ex, a[1] + s * ey
+        cx, cy = fx - qx, fy - qy
+        d = np.sqrt(cx * cx + cy * cy)
+        ze = a[2] + s * (b[2] - a[2])
+        return raw, s, d, ze, ze - d_(np.float32(bias))
+
+
+def near(mask, radius):
+    """The pixels within `radius` (in both coordinates) of a pixel of `mask`."""
+    h, w = mask.shape
+    pad = np.zeros((h + 2 * radius, w + 2 * radius), bool)
+    pad[radius:radius + h, radius:radius + w] = mask
+    out = np.zeros_like(mask)
+    for dy in range(2 * radius + 1):
+        for dx in range(2 * radius + 1):
+            out |= pad[dy:dy + h, dx:dx + w]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def tie_scene():
+    """A near triangle A whose edge 0 alone is drawn, over a far triangle B that covers the frame and draws nothing; A2,
+    a copy of A whose edge 0 has no length (s is 0 / 0), painted as a small patch of its own.  The winner plane is
+    painted: A's pixels are those inside it, so that B's pixels within TIE_RADIUS of them lie along the drawn edge
+    (0 <= s <= 1), beyond its two ends (s < 0, s > 1) and around the two other edges.  At those pixels the window holds
+    A and B only and whether A's edge counts is a function of one (t, e): d_z[p] there is, by the residue of x + 2 y,
+    exactly ze - depth_bias (computed with the model's statements for that pixel), one ulp above it or one below — the
+    scheme of the shadow map in `_build`."""
+    d = np.float32
+    s = Scene()
+    s.H, s.W, s.T = TIE_H, TIE_W, 3
+    corners = np.float64([(12.3, 9.6), (25.7, 14.2), (15.1, 27.4)])
+    zs = [1.0, 1.3, 1.15]
+    A = unproject(corners[:, 0], corners[:, 1], zs, TIE_W, TIE_H)
+    B = unproject(np.float64([-10, 100, -10]), np.float64([-10, -10, 100]), 2.0, TIE_W, TIE_H)
+    A2 = A.copy()
+    A2[1] = A2[0]
+    s.tri = np.ascontiguousarray(np.stack([A, B, A2]), np.float32)
+    s.edges = np.uint8([1, 0, 1])
+    ys, xs = np.mgrid[0:TIE_H, 0:TIE_W]
+    inside = np.ones((TIE_H, TIE_W), bool)
+    for k in range(3):                                         # (painted: any rule will do, this one is exact in float64)
+        (ax, ay), (bx, by) = corners[k], corners[(k + 1) % 3]
+        inside &= (bx - ax) * (ys - ay) - (by - ay) * (xs - ax) >= 0
+    winner = np.full((TIE_H, TIE_W), TIE_B, np.int32)
+    winner[inside] = TIE_A
+    winner[32:37, 31:36] = TIE_A2
+    s.winner = winner
+    s.is_a, s.is_a2 = winner == TIE_A, winner == TIE_A2
+    assert not (near(s.is_a, 2 * TIE_RADIUS + 1) & s.is_a2).any()        # no window holds both
+    s.ring = (winner == TIE_B) & near(s.is_a, TIE_RADIUS)
+    s.ring2 = (winner == TIE_B) & near(s.is_a2, TIE_RADIUS)
+    rng = np.random.default_rng(20249)
+    s.color = rng.uniform(0, 255, (TIE_H, TIE_W, 3)).astype(d)
+    z = np.full((TIE_H, TIE_W), d(0.875), d)                   # B's own projected depth; A's pixels never ask
+    s.proj = tex_ref.project(s.tri, P, TIE_W, TIE_H)
+    ry, rx = np.nonzero(s.ring)
+    at = tie_operands(s.proj, TIE_A, 0, rx, ry)[4]
+    kind = (rx + 2 * ry) % 3
+    up, down = np.nextafter(at, d(np.inf), dtype=d), np.nextafter(at, d(-np.inf), dtype=d)
+    z[ry, rx] = np.where(kind == 0, at, np.where(kind == 1, up, down))
+    s.z = z
+    s.kind = np.full((TIE_H, TIE_W), -1)
+    s.kind[ry, rx] = kind
+    return s
+
+
+# ---- lone winners on a frame of background: the rows a wavefront of the outline skips, and the seams of its tiles ----
+
+def _lone_triangle(x, y, direction):
+    """A triangle with edge 0 through the pixel (x, y), a quarter of a pixel off its centre and 100 px long both ways:
+    vertical ("v": the pixels above and below in column x are 0.25 px from it) or horizontal ("h")."""
+    if direction == "v":
+        pts = [(x + 0.25, y - 100), (x + 0.25, y + 100), (x + 50, y)]
+    else:
+        pts = [(x - 100, y + 0.25), (x + 100, y + 0.25), (x, y + 50)]
+    pts = np.float64(pts)
+    return unproject(pts[:, 0], pts[:, 1], 1.0, SPARSE_W, SPARSE_H)
+
+
+def tiles_that_stage(x, radius):
+    """The tile columns (or rows) whose staged span, the tile and `radius` of halo either side, holds coordinate x."""
+    return {k for k in range(-(-max(SPARSE_H, SPARSE_W) // TILE)) if k * TILE - radius <= x < (k + 1) * TILE + radius}
+
+
+def sparse_winners():
+    """[(x, y, direction)]: a "v" winner at every row 0 .. 96 and an "h" winner at every one of SPARSE_COLUMNS.  The
+    columns of the "v" winners: an even row takes one staged by the two left tile columns alone, the odd row after it one
+    that no tile stages together with it (the two share a frame); in the first tile row both lie just left of a seam."""
+    out = []
+    for y in range(SPARSE_H):
+        ty, k = y // TILE, (y // 2) % 2
+        if y % 2 == 0:
+            x = (31, 0, 32, 0)[ty]
+        else:
+            x = (95, (64, 63)[k], (100, 96)[k])[ty]
+        out.append((x, y, "v"))
+    for k, x in enumerate(SPARSE_COLUMNS):
+        out.append((x, (7 + 23 * k) % SPARSE_H, "h"))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def sparse_frames(radius):
+    """The lone winners of `sparse_winners` packed into frames, first fit: two winners share a frame only if no tile
+    stages both or their rows are 2 radius + 2 or more apart — the rows a wavefront of k_wire_outline reaches, its own
+    two and `radius` either side, then hold at most one winner, and no pixel sees two.  Each frame: a Scene with
+    tri [T, 3, 3], edges (edge 0 alone), winner, z, colour and `lone`, the [(x, y, direction)] of triangles 0 .. T - 1."""
+    frames = []
+    span = 2 * radius + 2                                      # ("v" rows a span apart, and each with the next row, first)
+    for x, y, direction in sorted(sparse_winners(), key=lambda w: (w[2] == "h", w[1] % span // 2, w[1])):
+        cols = tiles_that_stage(x, radius)
+        for lone in frames:
+            if all(abs(y - y2) >= span or not (cols & tiles_that_stage(x2, radius)) for x2, y2, _ in lone):
+                lone.append((x, y, direction))
+                break
+        else:
+            frames.append([(x, y, direction)])
+    return [_sparse_scene(lone, 20250 + 100 * radius + k) for k, lone in enumerate(frames)]
+
+
+def _sparse_scene(lone, seed):
+    rng = np.random.default_rng(seed)
+    s = Scene()
+    s.H, s.W, s.T, s.lone = SPARSE_H, SPARSE_W, len(lone), list(lone)
+    s.tri = np.ascontiguousarray(np.stack([_lone_triangle(*w) for w in lone]), np.float32)
+    s.edges = np.full(s.T, 1, np.uint8)
+    s.winner = np.full((SPARSE_H, SPARSE_W), -1, np.int32)
+    for t, (x, y, _) in enumerate(lone):
+        s.winner[y, x] = t
+    s.z = rng.uniform(0.4, 1.0, (SPARSE_H, SPARSE_W)).astype(np.float32)
+    s.color = rng.uniform(0, 255, (SPARSE_H, SPARSE_W, 3)).astype(np.float32)
+    return s
+
+
+def extreme_taps(s, radius):
+    """[(t, x, y, px, py)]: for every lone winner t at (x, y) of a sparse frame, the in-frame pixels (px, py) exactly
+    `radius` rows ("v") or columns ("h") from it, both signs, in the winner's own column (row) and in the next one:
+    0.25 px and 0.75 px from the edge, on a line of width 1 and feather 1 both."""
+    out = []
+    for t, (x, y, direction) in enumerate(s.lone):
+        for sign in (-1, 1):
+            for side in (0, 1):
+                px, py = (x + side, y + sign * radius) if direction == "v" else (x + sign * radius, y + side)
+                if 0 <= px < s.W and 0 <= py < s.H:
+                    out.append((t, x, y, px, py))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def sparse_strip():
+    """A frame for the rows SPARSE_STRIP: lone "v" winners on the row above the strip and on the first row below it,
+    whose lines would cross the strip's outermost rows, and one inside it, which the pass does see."""
+    y0, y1 = SPARSE_STRIP
+    return _sparse_scene([(20, y0 - 1, "v"), (70, y1, "v"), (45, (y0 + y1) // 2, "v")], 20259)
+
+
+def outline_model(s, winner=None, edges=None, field=None, **kw):
+    """tests/outline_ref.py's wire_pass on a scene's own planes."""
+    return outline_ref.wire_pass(s.color, s.winner if winner is None else winner, s.z, s.tri, P, edges=edges, field=field, **kw)

@@ -3,15 +3,17 @@ deferred passes.  A pure function of the seed — `plan(seed)` returns the fille
 dict that says everything the runner does and whether a pass in it is legal — so that tests/test_pass_edges_cpu.py can
 dry-run the default seeds without a GPU and hold the generator to its coverage floors.
 
-Two families of sessions.  The default one, "passes", draws texture and shadow passes; "lit" draws the Phong and
+Three families of sessions.  The default one, "passes", draws texture and shadow passes; "lit" draws the Phong and
 the occlusion pass among them as well, from generators, ops, weights and instances of its own, and chains up to four
-passes on one frame.  The default family is the same function of the seed it was before the second one existed:
-tests/test_pass_sessions_cpu.py pins a digest of every default plan.
+passes on one frame; "wired" adds the wire pass, overlay and outline, to those of "lit", again from a seed base, ops,
+weights and instances of its own, and chains up to five.  The two older families are the same functions of the seed
+they were before the third one existed: tests/test_pass_sessions_cpu.py pins a digest of every plan of theirs.
 
 The generator keeps the little state that decides legality, as the filler documents it: a pass needs a last frame that
 started from cleared buffers (``clear()`` afterwards empties the planes but leaves the pass legal: it finds background
 only); a texture pass needs uv of the last frame's triangle count bound, and a mip chain for "trilinear"; a Phong or
-an occlusion pass needs the frame alone, and its own arguments well formed."""
+an occlusion pass needs the frame alone, and its own arguments well formed; so does a wire pass, whose edge mask
+must have the last frame's triangle count."""
 import numpy as np
 
 SEEDS = 12
@@ -28,7 +30,7 @@ WEIGHTS = (4, 2, 1, 1, 3, 1, 13, 7, 5, 2, 2, 2)
 # frame, on every seed of a soak as well.
 CAMERA_OVERFLOWS = (4, 9)
 
-FAMILIES = ("passes", "lit")
+FAMILIES = ("passes", "lit", "wired")
 # The "lit" family: a pass of each kind as an op of its own, "chain" (two to four passes on one frame) for "two passes".
 LIT_OPS = ("cleared frame", "render_frame", "composite", "clear", "bind", "unbind", "texture_pass", "shadow_pass",
            "phong_pass", "ao_pass", "chain", "edit then pass", "resolve", "getters")
@@ -52,9 +54,25 @@ AO_RADIUS = {1: 0.03, 4: 0.05, 8: 0.1, 32: 0.4}       # the world radius grows w
 AO_TAP_COUNTS = {1: (1, 8), 4: (4, 16, 64), 8: (1, 16, 64), 32: (16, 64)}
 
 
+# The "wired" family: the ops of "lit" and the wire pass as an op of its own.
+WIRED_OPS = LIT_OPS + ("wire_pass",)
+# (tuned on the dry run of the default seeds, as WEIGHTS is)
+WIRED_WEIGHTS = (16, 6, 1, 7, 3, 4, 18, 5, 1, 2, 58, 6, 4, 6, 9)
+WIRED_KINDS = (0.41, 0.02, 0.23, 0.21, 0.13)          # texture, shadow, phong, ao, wire
+WIRED_SEED = 38000
+# The session 4 (modulo SEEDS) opens with an overlay on its overflowed frame, the session 9 — presorted, with a row
+# strip — with an outline.
+WIRED_OPENING = {4: False, 9: True}
+WIRE_WIDTHS = (0.25, 1.0, 3.0, 10.0)
+WIRE_FILLS = (None, (30.0, 35.0, 40.0), (0.0, 0.0, 0.0))
+WIRE_LINES = ((255.0, 255.0, 255.0), (250.0, 240.0, 20.0), (0.0, 0.0, 0.0))
+WIRE_RADII = (None, 0, 1, 3, 8)
+WIRE_MALFORMED = ("width 0", "radius_px 9", "width + feather over 14", "edges of another length", "opacity 1.5")
+
+
 def options(seed, family="passes"):
     """The filler's construction options and the frame's size."""
-    rng = np.random.default_rng((17000 if family == "passes" else 27000) + seed)
+    rng = np.random.default_rng({"passes": 17000, "lit": 27000, "wired": 37000}[family] + seed)
     H = int(rng.choice([96, 128, 97, 111])) if seed % 3 else int(rng.choice([97, 111, 127]))
     W = int(rng.choice([160, 128, 131, 159])) if seed % 3 else int(rng.choice([131, 159, 105]))
     kw = {"tile": int(rng.choice([16, 32]))}
@@ -63,7 +81,7 @@ def options(seed, family="passes"):
     if seed % 5 == 2:
         a = 4 * int(rng.integers(0, H // 8))
         kw["row_strip"] = (a, min(H, a + 4 * int(rng.integers(4, H // 4))))
-    if family == "lit" and seed % SEEDS == 9:                          # a row strip, presorted and overflowing at once
+    if family != "passes" and seed % SEEDS == 9:                          # a row strip, presorted and overflowing at once
         a = 4 * int(rng.integers(1, H // 8))
         kw["row_strip"] = (a, min(H, a + 4 * int(rng.integers(6, H // 4))))
     if seed % SEEDS in CAMERA_OVERFLOWS:
@@ -137,8 +155,38 @@ def _ao_mode(rng):
     return mode
 
 
+def _wire_mode(rng, outline=None):
+    """A random mode of wire_pass; about one in eight is malformed (WIRE_MALFORMED).  `edges`: None, or how the mask —
+    random bytes drawn from `seed`, of the last frame's triangle count unless `wrong` — is handed over."""
+    outline = bool(rng.integers(0, 2)) if outline is None else outline
+    width = float(rng.choice(WIRE_WIDTHS))
+    feather = float(rng.choice([0.25, 1.0, 3.0, 14.0 - width]))
+    edges = [None, "numpy", "tensor"][int(rng.integers(0, 3))]
+    mode = dict(kind="wire", outline=outline, fill=WIRE_FILLS[int(rng.integers(0, len(WIRE_FILLS)))],
+                color=WIRE_LINES[int(rng.integers(0, len(WIRE_LINES)))], width=width, feather=feather,
+                opacity=float(rng.choice([0.0, 0.5, 1.0])),
+                edges=None if edges is None else dict(form=edges, seed=int(rng.integers(0, 2 ** 31)), wrong=False),
+                depth_bias=float(rng.choice([0.0, 1e-3, -2e-3])), radius_px=WIRE_RADII[int(rng.integers(0, len(WIRE_RADII)))],
+                malformed=None)
+    if rng.uniform() < 0.125:
+        mode["malformed"] = bad = str(rng.choice(WIRE_MALFORMED))
+        if bad == "width 0":
+            mode["width"] = 0.0
+        elif bad == "radius_px 9":
+            mode.update(outline=True, radius_px=9)
+        elif bad == "width + feather over 14":
+            mode.update(outline=True, radius_px=None, width=10.0, feather=4.5)
+        elif bad == "edges of another length":
+            mode["edges"] = dict(form=str(rng.choice(["numpy", "tensor"])), seed=int(rng.integers(0, 2 ** 31)), wrong=True)
+        else:
+            mode["opacity"] = 1.5
+    return mode
+
+
 def instance(mode):
     """The kernel instance a legal pass runs."""
+    if mode["kind"] == "wire":
+        return ("wire", mode["outline"], mode["fill"] is not None)
     if mode["kind"] == "phong":
         return ("phong", len(mode["lights"]) == 1, mode["shininess"] > 1)
     if mode["kind"] == "ao":
@@ -156,22 +204,26 @@ INSTANCES = [("tex", p, b, l) for p in (False, True) for b in (False, True) for 
             [("shadow", K, w) for K in (1, 3, 5) for w in (False, True)]
 LIT_INSTANCES = INSTANCES + [("phong", one, squared) for one in (False, True) for squared in (False, True)] + \
                 [("ao", face, rotate, R) for face in (False, True) for rotate in (False, True) for R in (1, 8, 32)]
+WIRED_INSTANCES = LIT_INSTANCES + [("wire", outline, fill) for outline in (False, True) for fill in (False, True)]
 
 
 def plan(seed, steps=STEPS, family="passes"):
     """(options, [step]) of a session.  Each step: op, its parameters, and for every pass in it `legal`."""
-    lit = family == "lit"
     assert family in FAMILIES
+    wired = family == "wired"
+    lit = family == "lit" or wired                             # what "wired" shares with "lit"
     opt = options(seed, family)
-    rng = np.random.default_rng((LIT_SEED if lit else 18000) + seed)
-    ops, weights = (LIT_OPS, LIT_WEIGHTS) if lit else (OPS, WEIGHTS)
+    rng = np.random.default_rng({"passes": 18000, "lit": LIT_SEED, "wired": WIRED_SEED}[family] + seed)
+    ops, weights = {"passes": (OPS, WEIGHTS), "lit": (LIT_OPS, LIT_WEIGHTS), "wired": (WIRED_OPS, WIRED_WEIGHTS)}[family]
     soup = None            # the soup of the last render
     cleared = False        # that render started from cleared buffers
     bound = None           # (soup whose uv are bound, mipmaps)
     out = []
 
     def a_pass(kind=None):
-        if lit:
+        if wired:
+            kind = kind or str(rng.choice(["texture", "shadow", "phong", "ao", "wire"], p=WIRED_KINDS))
+        elif lit:
             kind = kind or str(rng.choice(["texture", "shadow", "phong", "ao"], p=LIT_KINDS))
         else:
             kind = "texture" if rng.uniform() < 0.62 else "shadow"
@@ -182,7 +234,7 @@ def plan(seed, steps=STEPS, family="passes"):
             mode = _shadow_mode(rng)
             legal = soup is not None and cleared and not mode["wrong"]
         else:                          # the frame alone: the empty soup is legal and writes nothing
-            mode = _phong_mode(rng) if kind == "phong" else _ao_mode(rng)
+            mode = _phong_mode(rng) if kind == "phong" else _ao_mode(rng) if kind == "ao" else _wire_mode(rng)
             legal = soup is not None and cleared and mode["malformed"] is None
         return dict(mode, legal=bool(legal))
 
@@ -200,7 +252,7 @@ def plan(seed, steps=STEPS, family="passes"):
     # filler (the light's).  The rest of the session is drawn as everywhere.
     opening = []
     if opt["kw"].get("bin_capacity"):
-        opening += [LIT_OPENING[seed % SEEDS]] if lit else ["bind", "texture_pass"]
+        opening += ["wire_pass"] if wired else [LIT_OPENING[seed % SEEDS]] if lit else ["bind", "texture_pass"]
     if opt["light_kw"].get("bin_capacity"):
         opening += ["shadow_pass"]
     opening = ["cleared frame"] + opening if opening else []
@@ -224,6 +276,11 @@ def plan(seed, steps=STEPS, family="passes"):
                 mode = None
                 while mode is None or mode["malformed"]:               # (a well-formed one)
                     mode = _phong_mode(rng) if op == "phong_pass" else dict(_ao_mode(rng), normals="face")
+                step["mode"] = dict(mode, legal=True)
+            elif op == "wire_pass":
+                mode = None
+                while mode is None or mode["malformed"]:
+                    mode = _wire_mode(rng, WIRED_OPENING[seed % SEEDS])
                 step["mode"] = dict(mode, legal=True)
             else:
                 step["mode"] = dict(_shadow_mode(rng), own=False, wrong=False, legal=True)
@@ -254,20 +311,24 @@ def plan(seed, steps=STEPS, family="passes"):
             if (p["kind"] == "texture") != (op == "texture_pass"):
                 p = a_pass() if rng.uniform() < 0.5 else p
             step.update(op="texture_pass" if p["kind"] == "texture" else "shadow_pass", mode=p)
-        elif op in ("phong_pass", "ao_pass"):
+        elif op in ("phong_pass", "ao_pass", "wire_pass"):
             step["mode"] = a_pass(op[:-5])
         elif op == "two passes":
             step["modes"] = [a_pass(), a_pass()]
         elif op == "chain":
             if rng.uniform() < 0.6:                                     # a texture first, a shadow last, lights between
                 kinds = ["texture"] + [str(k) for k in rng.choice(["phong", "ao"], int(rng.integers(1, 3)))] + ["shadow"]
+                if wired:                                               # (and the lines over the lit surface, under the shadow)
+                    kinds[-1:] = ["wire", "shadow"] if rng.uniform() < 0.6 else ["wire"]
             else:
                 kinds = [None] * int(rng.integers(2, 5))
             step["modes"] = [a_pass(kind) for kind in kinds]
         elif op == "edit then pass":
-            step.update(rows=[float(v) for v in rng.uniform(0, 1, 2)], value=float(rng.uniform(1, 200)), mode=a_pass())
+            step.update(rows=[float(v) for v in rng.uniform(0, 1, 2)], value=float(rng.uniform(1, 200)),
+                        mode=a_pass("wire" if wired and rng.uniform() < 0.5 else None))
             if lit:                    # under an occlusion pass: covered pixels of the rows pushed towards the eye as well
-                step["z_edit"] = bool(rng.integers(0, 2)) and step["mode"]["kind"] == "ao"
+                mode = step["mode"]
+                step["z_edit"] = bool(rng.integers(0, 2)) and (mode["kind"] == "ao" or bool(mode.get("outline")))
         elif op == "resolve":
             step.update(factor=int(rng.integers(1, 5)), light=bool(rng.integers(0, 2)))
         out.append(step)
@@ -283,7 +344,7 @@ def passes(steps):
     for s in steps:
         if s["op"] == "composite":
             yield s["then"]
-        elif s["op"] in ("texture_pass", "shadow_pass", "phong_pass", "ao_pass", "edit then pass"):
+        elif s["op"] in ("texture_pass", "shadow_pass", "phong_pass", "ao_pass", "wire_pass", "edit then pass"):
             yield s["mode"]
         elif s["op"] in ("two passes", "chain"):
             yield from s["modes"]
@@ -297,7 +358,7 @@ def first_to_settle(steps):
     live = False
     for s in steps:
         op = s["op"]
-        modes = [s["mode"]] if op in ("texture_pass", "shadow_pass", "phong_pass", "ao_pass") else s.get("modes", [])
+        modes = [s["mode"]] if op in ("texture_pass", "shadow_pass", "phong_pass", "ao_pass", "wire_pass") else s.get("modes", [])
         if op == "cleared frame":
             live = count(s["soup"]) > 0
         elif op == "clear":
@@ -325,9 +386,9 @@ def light_meets_a_pass(steps):
     return False
 
 
-def lit_between(steps):
-    """The chains of a session that hold a legal Phong or occlusion pass after a legal texture pass and before a legal
-    shadow pass of the same chain, or before a resolve as the next step."""
+def lit_between(steps, between=("phong", "ao")):
+    """The chains of a session that hold a legal Phong or occlusion pass (or one of the kinds `between`) after a legal
+    texture pass and before a legal shadow pass of the same chain, or before a resolve as the next step."""
     n = 0
     for k, s in enumerate(steps):
         if s["op"] != "chain":
@@ -335,7 +396,7 @@ def lit_between(steps):
         kinds = [m["kind"] if m["legal"] else None for m in s["modes"]]
         resolve_next = k + 1 < len(steps) and steps[k + 1]["op"] == "resolve"
         for i, kind in enumerate(kinds):
-            if kind in ("phong", "ao") and "texture" in kinds[:i] and ("shadow" in kinds[i + 1:] or resolve_next):
+            if kind in between and "texture" in kinds[:i] and ("shadow" in kinds[i + 1:] or resolve_next):
                 n += 1
                 break
     return n

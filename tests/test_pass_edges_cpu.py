@@ -1,7 +1,12 @@
 """Conditions on the hand-built scenes of tests/pass_edges.py, checked on the host model alone: the scenes take every
 window decision of the passes, and every select of the Phong and occlusion passes, both ways, often enough and within one wavefront, before tests/test_pass_edges_gpu.py
 holds the kernels to them; and the float32 model of the scene is still the float64 form of its own statements where
-the operands are ordinary."""
+the operands are ordinary.
+
+The two wire passes, at the end: floors on what the overlay's and the outline's models do on the painted scene; the
+hand-built frame that holds the hidden-line test at equality, the clamp of s on its three sides and the depth at the
+closest point, with three mutants of the model that it tells apart; and the frames of lone winners, where the model
+lights the pixel exactly radius_px rows or columns from a winner and no nearer radius does."""
 import os
 import re
 
@@ -11,6 +16,8 @@ import pytest
 import aniso_ref
 import ao_ref
 import mip_ref
+import outline_ref
+import overlay_ref
 import pass_edges as E
 import phong_ref
 import shadow_ref
@@ -435,3 +442,221 @@ def test_ao_on_the_small_frame(oracle):
             assert not np.isnan(out).any()
             assert counts["occluded"] >= 16 and counts["covered"] - counts["occluded"] >= 16 and counts["taps_taken"] > 0
     assert m.H < 32 and m.W < 32                                                 # inside one tile, smaller than the halo
+
+
+# ---- the wire passes: the overlay and the outline -----------------------------------------------------------------------
+
+def _overlay(s, **kw):
+    counts = {}
+    out = overlay_ref.wire_pass(s.color, s.winner, s.tri, E.P, counts=counts, **kw)
+    assert not np.isnan(out).any()
+    on = (out.view(np.uint32) != s.color.view(np.uint32)).any(2)
+    return out, counts, on
+
+
+def _outline(s, **kw):
+    counts = {}
+    out = E.outline_model(s, counts=counts, **kw)
+    assert not np.isnan(out).any()
+    return out, counts
+
+
+def test_the_scenes_gain_an_edge_mask_and_the_tall_frame_a_z_plane(scene):
+    """What `_wired` adds: an edge mask with every value of the three low bits and bits above them, and a z plane on
+    the tall frame alone (the other two keep the occlusion pass's)."""
+    for s in (scene, E.mini_scene(), E.tall_scene()):
+        assert s.edges.dtype == np.uint8 and s.edges.shape == (s.T,) and s.z.shape == (s.H, s.W) and s.z.dtype == np.float32
+    assert set((scene.edges & 7).tolist()) == set(range(8)) and (scene.edges > 7).sum() > scene.T // 2
+    t = E.tall_scene()
+    assert np.isnan(t.z[t.rows]).any() and np.isinf(t.z[t.rows]).any()
+
+
+def test_the_overlay_on_the_edge_scene(scene):
+    s = scene
+    _, c, _ = _overlay(s)
+    print(f"overlay, defaults: {c}")
+    assert c["covered"] == 7844 and (c["full"], c["partial"], c["nan"]) == (84, 205, 1309)
+    assert c["full"] + c["partial"] >= 200 and c["nan"] >= 1000
+    ys, xs, t, m, _ = overlay_ref.distances(s.winner, s.tri, E.P)
+    with np.errstate(all="ignore"):
+        on = (np.float32(1.0) - m) / np.float32(1.0) > 0
+    for name, ids in s.classes.items():
+        mine = np.isin(t, ids)
+        print(f"overlay, {name}: {int((mine & on).sum())} on, {int((mine & ~on).sum())} off")
+        if name != "aniso":                  # (its corners lie 100 px outside the frame: no pixel is near an edge)
+            assert (mine & on).any() and (mine & ~on).any(), name
+    assert _overlay(s, width=3.0, feather=0.5)[1]["full"] + _overlay(s, width=3.0, feather=0.5)[1]["partial"] == 528
+    out, c, on = _overlay(s, width=64.0, feather=64.0, fill=(30.0, 35.0, 40.0))
+    assert (c["full"] + c["partial"], c["off"]) == (6450, 1394) and c["full"] == 85       # the ramp: hi / feather is 1, the cap is met ON a line alone
+    _, c, _ = _overlay(s, edges=s.edges)
+    assert 100 <= c["full"] + c["partial"] < 289                                           # the mask takes edges away
+    # d_pos_of: the model on the winner plane without the triangle that is sent beyond T
+    out, _, _ = _overlay(s)
+    gone = overlay_ref.wire_pass(s.color, s.winner_without_gone, s.tri, E.P)
+    assert (out != gone).any()
+
+
+def test_the_outline_on_the_edge_scene(scene):
+    s = scene
+    background = ~((s.winner >= 0) & (s.winner < s.T))
+    _, c = _outline(s, radius_px=2)
+    print(f"outline, r = 2: {c}")
+    assert (c["background_on"], c["covered_on"], c["nan"]) == (83, 668, 3559)
+    assert c["background_on"] >= 50 and c["nan"] > 3000
+    out, c = _outline(s, radius_px=0)
+    assert (c["background_on"], c["covered_on"]) == (0, 218)
+    assert (out[background] == s.color[background]).all()
+    _, c = _outline(s, width=3.0, feather=0.5, radius_px=3)
+    assert (c["background_on"], c["covered_on"]) == (176, 1556)
+    _, c = _outline(s, width=3.0, radius_px=8, depth_bias=0.0, fill=(30.0, 35.0, 40.0))
+    assert (c["background_on"], c["covered_on"], c["nan"]) == (331, 3129, 7815)
+    out, c = _outline(s, width=64.0, feather=64.0, radius_px=8, fill=(30.0, 35.0, 40.0))
+    assert 0 < c["full"] < 500 and c["covered_on"] > 6000          # the ramp; the cap at the segments' own pixels alone
+    # the depth comparison falls both ways: against a bias under which every edge counts, and one under which no
+    # foreign edge does
+    m = outline_ref.distances(s.winner, s.z, s.tri, E.P, radius_px=3, depth_bias=1e-3)[0]
+    every = outline_ref.distances(s.winner, s.z, s.tri, E.P, radius_px=3, depth_bias=1e6)[0]
+    none = outline_ref.distances(s.winner, s.z, s.tri, E.P, radius_px=3, depth_bias=-1e6)[0]
+    print(f"the distance field differs at {int((m != every).sum())} pixels from every edge counting, at {int((m != none).sum())} from none")
+    assert ((m != every).sum(), (m != none).sum()) == (4376, 4607)
+    assert (m != every).sum() > 2000 and (m != none).sum() > 2000
+    _, c = _outline(s, radius_px=2, edges=s.edges)
+    assert 0 < c["background_on"] < 83
+    # the small frame: a halo wider than the frame is tall
+    mini = E.mini_scene()
+    _, c = _outline(mini, radius_px=8)
+    assert c["background_on"] >= 8 and c["covered_on"] >= 16 and mini.H < 2 * 8 + 8
+    t = E.tall_scene()
+    out, c = _outline(t, radius_px=2, y0=E.TALL_Y0)
+    changed = np.nonzero((out != t.color).any((1, 2)))[0]
+    assert c["covered_on"] >= 16 and set(changed.tolist()) <= set(t.rows.tolist()) and changed.max() >= E.TALL_H - 16
+    assert (-(-E.TALL_W // E.TILE)) * (-(-(E.TALL_H - E.TALL_Y0) // E.TILE)) == 16385      # a workgroup per tile
+
+
+# ---- the tie of the hidden-line test, the clamp and the depth at the closest point ------------------------------------
+
+def _tie_field(s, less=np.less, clamp=True, ze_at_corner=False):
+    """The distance field of the outline on `tie_scene`, restated for what that frame is: B draws nothing, every window
+    holds A or A2 beside B and never both, and the one drawn edge is edge 0.  A pixel of A (A2) takes the edge whatever
+    the depths; a pixel of B within the radius of one takes it if it counts.  The mutants: `less` (the comparison of
+    the depth test), `clamp` False (the distance to the LINE, s as it comes), `ze_at_corner` (the depth of corner a)."""
+    d_ = np.float32
+    m = np.full((s.H, s.W), np.inf, d_)
+    ys, xs = np.mgrid[0:s.H, 0:s.W]
+    for t, own, ring in ((E.TIE_A, s.is_a, s.ring), (E.TIE_A2, s.is_a2, s.ring2)):
+        raw, _, d, ze, _ = E.tie_operands(s.proj, t, 0, xs.reshape(-1), ys.reshape(-1))
+        a, b = s.proj[t, 0], s.proj[t, 1]
+        with np.errstate(all="ignore"):
+            if not clamp:
+                qx, qy = a[0] + raw * (b[0] - a[0]), a[1] + raw * (b[1] - a[1])
+                cx, cy = xs.reshape(-1).astype(d_) - qx, ys.reshape(-1).astype(d_) - qy
+                d = np.sqrt(cx * cx + cy * cy)
+                ze = a[2] + raw * (b[2] - a[2])
+            if ze_at_corner:
+                ze = np.broadcast_to(a[2], ze.shape)
+            counts = less(ze - d_(np.float32(E.TIE_BIAS)), s.z.reshape(-1))
+            take = (own.reshape(-1) | (ring.reshape(-1) & counts)) & (d < np.inf)
+        m.reshape(-1)[take] = d[take]
+    return m
+
+
+def test_the_tie_frame_holds_the_depth_test_at_equality_and_the_clamp_on_three_sides(oracle):
+    s = E.tie_scene()
+    assert s.H <= 40 and s.W <= 40 and s.edges.tolist() == [1, 0, 1]
+    assert s.is_a.sum() >= 64 and s.is_a2.sum() == 25 and s.ring2.sum() >= 40
+    ry, rx = np.nonzero(s.ring)
+    raw, sc, d, ze, at = E.tie_operands(s.proj, E.TIE_A, 0, rx, ry)
+    kind = s.kind[ry, rx]
+    z = s.z[ry, rx]
+    f32 = np.float32
+    assert (z[kind == 0] == at[kind == 0]).all()
+    assert (z[kind == 1] == np.nextafter(at[kind == 1], f32(np.inf), dtype=f32)).all()
+    assert (z[kind == 2] == np.nextafter(at[kind == 2], f32(-np.inf), dtype=f32)).all()
+    sides = [(raw < 0), (raw >= 0) & (raw <= 1), (raw > 1)]
+    print(f"ring: {np.bincount(kind).tolist()} pixels exact / above / below; s < 0, inside, > 1: {[int(v.sum()) for v in sides]}")
+    assert (np.bincount(kind, minlength=3) >= 20).all() and all(v.sum() >= 10 for v in sides)
+    for side in sides:                                         # every side of the clamp meets every kind of depth
+        assert set(kind[side].tolist()) == {0, 1, 2}
+    assert len(np.unique(ze)) > 50 and (sc[sides[0]] == 0).all() and (sc[sides[2]] == 1).all()
+    # the model takes the edge at "one ulp above" only
+    m, own, nan = outline_ref.distances(s.winner, s.z, s.tri, E.P, s.edges, E.TIE_RADIUS, E.TIE_BIAS)
+    taken = np.isfinite(m[ry, rx])
+    assert taken[kind == 1].all() and not taken[kind != 1].any()
+    assert (m[ry, rx][taken] == d[taken]).all()
+    assert np.isfinite(m[s.is_a]).all() and np.isinf(m[(own == E.TIE_B) & ~s.ring]).all()
+    # the edge of no length: s is 0 / 0, its distance a NaN that is never taken, its depth one that never counts
+    r2 = E.tie_operands(s.proj, E.TIE_A2, 0, *np.nonzero(s.ring2 | s.is_a2)[::-1])
+    assert np.isnan(r2[0]).all() and np.isnan(r2[2]).all() and np.isnan(r2[3]).all()
+    assert np.isinf(m[s.is_a2 | s.ring2]).all() and nan[s.is_a2 | s.ring2].all()
+    # the restatement is the model on this frame, and each mutant is not
+    assert np.array_equal(_tie_field(s), m)
+    for name, kw, where in (("<= for <", dict(less=np.less_equal), s.kind == 0), ("no clamp", dict(clamp=False), None),
+                            ("ze at corner a", dict(ze_at_corner=True), s.ring)):
+        differ = _tie_field(s, **kw) != m
+        print(f"mutant {name}: differs at {int(differ.sum())} pixels")
+        assert differ.sum() >= 10, name
+        if where is not None:
+            assert not (differ & ~where).any(), name
+    assert (_tie_field(s, less=np.less_equal) != m)[s.kind == 0].all()
+    # and in the colours, under a line wide enough to reach every pixel that takes the edge
+    for fill in (None, (30.0, 35.0, 40.0)):
+        out, c = _outline(s, width=64.0, feather=64.0, radius_px=E.TIE_RADIUS, depth_bias=E.TIE_BIAS, edges=s.edges, fill=fill)
+        lit = (out != s.color).any(2)
+        assert lit[s.ring & (s.kind == 1)].all() and (fill is not None or not lit[s.ring & (s.kind != 1)].any())
+
+
+# ---- lone winners: the rows a wavefront skips, and the seams of the tiles ----------------------------------------------
+
+@pytest.mark.parametrize("radius", E.SPARSE_RADII)
+def test_lone_winners_light_the_pixel_exactly_radius_px_away_and_no_nearer_radius_does(oracle, radius):
+    frames = E.sparse_frames(radius)
+    assert len(frames) <= 16 and (E.SPARSE_H, E.SPARSE_W) == (97, 101)
+    rows, cols, crossing = set(), set(), set()
+    residues = {ty: set() for ty in range(3)}
+    taps = 0
+    for s in frames:
+        # what the packing promises: the rows one wavefront reaches hold at most one winner of the tiles that stage it
+        for i, (x, y, _) in enumerate(s.lone):
+            for x2, y2, _ in s.lone[i + 1:]:
+                assert abs(y - y2) >= 2 * radius + 2 or not (E.tiles_that_stage(x, radius) & E.tiles_that_stage(x2, radius))
+        assert ((s.winner >= 0).sum(), s.T) == (len(s.lone), len(s.lone))
+        out, c = _outline(s, radius_px=radius, edges=s.edges)
+        nearer, _ = _outline(s, radius_px=radius - 1, edges=s.edges)
+        lit, lit_nearer = (out != s.color).any(2), (nearer != s.color).any(2)
+        assert c["covered"] == s.T and c["nan"] == 0
+        for t, x, y, px, py in E.extreme_taps(s, radius):
+            assert lit[py, px] and not lit_nearer[py, px], (radius, s.lone[t], px, py)
+            taps += 1
+            if s.lone[t][2] == "v" and (px // E.TILE, py // E.TILE) != (x // E.TILE, y // E.TILE):
+                crossing.add(y % E.TILE)
+        # nothing beyond the radius: every lit pixel is within it of its winner, rows and columns both
+        ys, xs = np.nonzero(lit)
+        for py, px in zip(ys, xs):
+            assert any(abs(py - y) <= radius and abs(px - x) <= radius for x, y, _ in s.lone)
+        for x, y, direction in s.lone:
+            if direction == "v":
+                rows.add(y)
+                if y < 96:
+                    residues[y // E.TILE].add(y % E.TILE)
+            else:
+                cols.add(x)
+    assert rows == set(range(E.SPARSE_H)) and cols == set(E.SPARSE_COLUMNS)
+    assert all(r == set(range(E.TILE)) for r in residues.values())
+    assert {x for s in frames for x, _, d in s.lone if d == "v"} == set(E.SPARSE_COLUMNS)
+    assert crossing == set(range(E.TILE)), sorted(set(range(E.TILE)) - crossing)
+    print(f"radius {radius}: {len(frames)} frames, {taps} extreme taps lit")
+    assert taps >= 2 * (E.SPARSE_H - radius) + 8                 # (each row's winner both ways where the frame allows)
+
+
+def test_the_strip_frame_keeps_its_outside_winners_out_of_sight(oracle):
+    s = E.sparse_strip()
+    y0, y1 = E.SPARSE_STRIP
+    assert y0 % 32 and y1 % 32 and [w[1] for w in s.lone] == [y0 - 1, y1, (y0 + y1) // 2]
+    for radius in E.SPARSE_RADII:
+        whole, _ = _outline(s, radius_px=radius, edges=s.edges)
+        strip, _ = _outline(s, radius_px=radius, edges=s.edges, y0=y0, y1=y1)
+        seen, lit = (whole != s.color).any(2), (strip != s.color).any(2)
+        (xa, ya, _), (xb, yb, _), (xc, yc, _) = s.lone
+        assert seen[y0:y0 + radius, xa].all() and seen[y1 - radius:y1, xb].all()         # the whole frame sees them
+        assert not lit[:, :xc - radius].any() and not lit[:, xc + radius + 1:].any()    # the strip does not
+        assert lit[yc - radius:yc + radius + 1, xc].all() and not lit[:y0].any() and not lit[y1:].any()

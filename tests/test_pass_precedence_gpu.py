@@ -1,5 +1,5 @@
-"""Which refusal of a deferred pass wins when several apply: for each of texture_pass, shadow_pass, phong_pass and
-ao_pass the state in which every precondition is violated at once (as far as they can coexist), then one violation
+"""Which refusal of a deferred pass wins when several apply: for each of texture_pass, shadow_pass, phong_pass,
+ao_pass and wire_pass the state in which every precondition is violated at once (as far as they can coexist), then one violation
 repaired at a time, down to a call that succeeds.  Every refusal is asserted by its whole message.  16 x 16 fillers,
 one triangle, an 8 x 8 texture: the refused calls never reach the library, and each pass launches once at the end."""
 import numpy as np
@@ -133,3 +133,43 @@ def test_ao_pass_refusals_in_order():
     before = _covered(f)
     f.ao_pass(**kw)                                        # (one flat triangle: nothing occludes it)
     assert np.array_equal(_covered(f), before)
+
+
+def test_wire_pass_refusals_in_order():
+    """wire_pass asks whom it serves first (the swap chain, the winner plane), then reads its own arguments in the order
+    width, feather, opacity, depth_bias, radius_px — the last two with `outline` alone — then the frame, and `edges`
+    last, as it is measured against the frame's triangle count."""
+    chain, nowin, f = _fillers()
+    number = "must be a number of pixels above 0 and at most 64, got "
+    kw = dict(outline=True, width=0.0, feather=65.0, opacity=1.5, depth_bias=float("nan"), radius_px=9,
+              edges=np.zeros(2, np.int32))
+    _refused("wire_pass is not available on a swap chain (pipeline=True): per-slot passes are not implemented", chain.wire_pass, **kw)
+    _refused("wire_pass needs the winner plane: construct the filler with track_winner=True", nowin.wire_pass, **kw)
+    _refused("width " + number + "0.0", f.wire_pass, **kw)
+    kw["width"] = 10.0
+    _refused("feather " + number + "65.0", f.wire_pass, **kw)
+    kw["feather"] = 4.5
+    _refused("opacity must be a number from 0 to 1, got 1.5", f.wire_pass, **kw)
+    kw["opacity"] = 0.5
+    _refused("depth_bias must be a finite number, got nan", f.wire_pass, **kw)
+    kw["depth_bias"] = 1e-3
+    _refused("radius_px must be None or an int from 0 to 8, got 9", f.wire_pass, **kw)
+    kw["radius_px"] = None
+    _refused("outline=True: width + feather = 14.5 needs radius_px = 9, above the largest, 8: width + feather may be at most 14",
+             f.wire_pass, **kw)
+    kw["feather"] = 4.0                                    # (the widest line the default radius holds)
+    # an overlay does not look at the outline's two arguments
+    _refused("wire_pass: no frame has been rendered", f.wire_pass, **dict(kw, outline=False, depth_bias=float("nan"), radius_px=9))
+    _frames(f, "wire_pass", f.wire_pass, **kw)
+    _refused("edges must be uint8 [T] with T = 1, the triangles of the last frame, got torch.int32 (2,)", f.wire_pass, **kw)
+    kw["edges"] = np.zeros(2, np.uint8)
+    _refused("edges must be uint8 [T] with T = 1, the triangles of the last frame, got torch.uint8 (2,)", f.wire_pass, **kw)
+    kw["edges"] = np.full(1, 7, np.uint8)
+    before = _covered(f)
+    f.wire_pass(**dict(kw, outline=False))
+    assert (_covered(f) != before).any()
+    f.render_arrays(TRI, COL, NRM, clear=True)
+    f.wire_pass(**kw)                                      # (the outline writes the background too: the outer half of a line)
+    color = f.get_color_tensor().cpu().numpy()
+    covered = f.get_winner_tensor().cpu().numpy() >= 0
+    assert (color[covered] != before).any() and (color[~covered] != 0).any()

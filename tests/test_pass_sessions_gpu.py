@@ -5,8 +5,10 @@ every mode, shadow passes against a second filler that renders the light's view 
 two passes on one frame, edits of a colour view carried into a pass, resolves and getters — against an oracle frame and
 the host models of the passes (tests/tex_ref.py, mip_ref.py, aniso_ref.py, shadow_ref.py, ssaa_ref.py) applied to it
 in the same order.  The sessions of the "lit" family draw Phong and occlusion passes among them (tests/phong_ref.py,
-ao_ref.py), chain up to four passes on one frame and edit the z view under an occlusion pass.  Every comparison is bit
-for bit."""
+ao_ref.py), chain up to four passes on one frame and edit the z view under an occlusion pass.  Those of the "wired"
+family draw the wire pass as well, overlay and outline (tests/overlay_ref.py, outline_ref.py): between other passes on
+one frame, over edited colours and an edited z view, first on a frame whose bin lists overflowed, after clear(), and
+refused after a composite or for its own arguments.  Every comparison is bit for bit."""
 import os
 
 import numpy as np
@@ -15,6 +17,8 @@ import pytest
 import aniso_ref
 import ao_ref
 import mip_ref
+import outline_ref
+import overlay_ref
 import pass_sessions as S
 import phong_ref
 import shadow_ref
@@ -113,6 +117,17 @@ def test_fuzz_a_filler_through_its_passes(oracle, pool, family, seed):
         if k % 2:
             f.debug_check()
 
+    def wire_edges(mode):
+        """The edge mask of a wire mode, in the caller's order: random bytes of the last frame's triangle count, or of
+        another soup's."""
+        e = mode["edges"]
+        if e is None:
+            return None
+        T = S.count(state["soup"]) if state["soup"] is not None else 0
+        if e["wrong"]:
+            T = next(S.count(n) for n in S.SOUPS if S.count(n) != T)
+        return np.random.default_rng(e["seed"]).integers(0, 256, T).astype(np.uint8)
+
     def host_pass(mode):
         """The host model of a legal pass, applied to the oracle's colour plane."""
         tri, col, nrm = pool.host[state["soup"]]
@@ -139,6 +154,16 @@ def test_fuzz_a_filler_through_its_passes(oracle, pool, family, seed):
             out = ao_ref.ao_pass(ref.color_buffer, ref.z_buffer, ref.winner, tri, ref.proj_mat, ref.normals_buffer, table,
                                  radius=mode["radius"], radius_px=mode["radius_px"], strength=mode["strength"],
                                  floor=mode["floor"], rotate=mode["rotate"], face=mode["normals"] == "face", y0=y0, y1=y1)
+        elif mode["kind"] == "wire":
+            kw = dict(width=mode["width"], line=mode["color"], feather=mode["feather"], opacity=mode["opacity"], fill=mode["fill"],
+                      edges=wire_edges(mode), y0=y0, y1=y1)
+            if len(tri) == 0:          # the empty soup: legal, and nothing is written
+                out = ref.color_buffer.copy()
+            elif mode["outline"]:
+                out = outline_ref.wire_pass(ref.color_buffer, ref.winner, ref.z_buffer, tri, ref.proj_mat,
+                                            depth_bias=mode["depth_bias"], radius_px=mode["radius_px"], **kw)
+            else:
+                out = overlay_ref.wire_pass(ref.color_buffer, ref.winner, tri, ref.proj_mat, **kw)
         else:
             if mode["own"]:
                 ltri, PL, lz, lw = tri, ref.proj_mat, ref.z_buffer, ref.winner
@@ -160,6 +185,13 @@ def test_fuzz_a_filler_through_its_passes(oracle, pool, family, seed):
         elif mode["kind"] == "ao":
             f.ao_pass(radius=mode["radius"], radius_px=mode["radius_px"], taps=mode["taps"], strength=mode["strength"],
                       floor=mode["floor"], rotate=mode["rotate"], normals=mode["normals"])
+        elif mode["kind"] == "wire":
+            edges = wire_edges(mode)
+            if edges is not None and mode["edges"]["form"] == "tensor":
+                edges = torch.from_numpy(edges).cuda()
+            f.wire_pass(width=mode["width"], color=mode["color"], feather=mode["feather"], opacity=mode["opacity"],
+                        fill=mode["fill"], edges=edges, outline=mode["outline"], depth_bias=mode["depth_bias"],
+                        radius_px=mode["radius_px"])
         else:
             f.shadow_pass(bias=mode["bias"], pcf=mode["pcf"], ambient=mode["ambient"], use_winner=mode["use_winner"])
 
@@ -244,7 +276,7 @@ def test_fuzz_a_filler_through_its_passes(oracle, pool, family, seed):
         elif op == "unbind":
             f.bind_texture(None, None)
             state["bound"] = None
-        elif op in ("texture_pass", "shadow_pass", "phong_pass", "ao_pass"):
+        elif op in ("texture_pass", "shadow_pass", "phong_pass", "ao_pass", "wire_pass"):
             a_pass(k, step["mode"])
             continue
         elif op in ("two passes", "chain"):
