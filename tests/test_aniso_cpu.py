@@ -13,28 +13,17 @@ import pytest
 
 import aniso_ref
 import mip_ref
+from pass_scenes import capi, trex_textured  # noqa: F401 (fixtures)
 from util import assert_bit_equal, other_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from cython3dmodelrenderer_amd import _build, _capi
-    _build.build()           # hipcc cross-compiles for gfx950 without a GPU
-    return _capi
 
 
 @pytest.fixture(scope="module")
 def scenes_(oracle):
     """name -> (oracle frame, tri, uv, texture, chain): T-Rex at 256^2 and the floor at 64^2, rendered once."""
-    from cython3dmodelrenderer_amd import scenes
-    tri, col, nrm = scenes.load_fixture("trex_inputs.npz")
-    with np.load(os.path.join(GOLDEN, "trex_uv.npz")) as z:
-        uv = np.ascontiguousarray(z["uv"][z["faces_uv"]], dtype=np.float32)
     out = {}
-    for name, size, (tri, col, nrm, uv), tex_side in (("trex256", 256, (tri, col, nrm, uv), 709),
+    for name, size, (tri, col, nrm, uv), tex_side in (("trex256", 256, trex_textured(), 709),
                                                        ("floor64", 64, aniso_ref.floor_scene(), 256)):
         f = oracle.OracleFiller(size, size, fov=45.0)
         f.render_arrays(tri, col, nrm)

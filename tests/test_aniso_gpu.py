@@ -1,55 +1,17 @@
 """Anisotropic filtering on the GPU (csrc/texaniso.hip through texture_pass(filter="trilinear", anisotropy=A) and
 Renderer(texture_pass=...)), bit for bit against the host model of tests/aniso_ref.py evaluated on the oracle's
 frame (itself pinned in tests/test_aniso_cpu.py)."""
-import os
-
 import numpy as np
 import pytest
 
 import aniso_ref
 import mip_ref
-from util import assert_bit_equal, random_soup
+from pass_scenes import filler, host, oracle_frame, planes_only_read, soup_textured, texture, textured_model, trex_textured
+from util import assert_bit_equal
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 LIGHT = (0.3, -0.2, 1.0)             # what GuroIllumination is constructed with
-
-
-def _texture(seed, th, tw):
-    return np.random.default_rng(seed).integers(0, 256, (th, tw, 3), dtype=np.uint8)
-
-
-def _trex():
-    from cython3dmodelrenderer_amd import scenes
-    tri, col, nrm = scenes.load_fixture("trex_inputs.npz")
-    with np.load(os.path.join(GOLDEN, "trex_uv.npz")) as z:
-        uv = np.ascontiguousarray(z["uv"][z["faces_uv"]], dtype=np.float32)
-    return tri, col, nrm, uv
-
-
-def _soup(seed, T, res, **kw):
-    rng = np.random.default_rng(seed)
-    tri, col, nrm = random_soup(rng, T, res, **kw)
-    uv = rng.uniform(-1.5, 2.5, (T, 3, 2)).astype(np.float32)        # beyond [0, 1]: the clamp is part of the rule
-    return tri, col, nrm, uv
-
-
-def _filler(H, W, **kw):
-    from cython3dmodelrenderer_amd.pixel_buffer_filler import AdvancedPixelBufferFiller
-    kw.setdefault("track_winner", True)
-    return AdvancedPixelBufferFiller(H, W, fov=45.0, device="cuda:0", **kw)
-
-
-def _frame(oracle, tri, col, nrm, H, W, y0=0, y1=None):
-    ref = oracle.OracleFiller(H, W, fov=45.0)
-    ref.render_arrays(tri, col, nrm, y0=y0, y1=y1)
-    return ref
-
-
-def _host(t):
-    return t.cpu().numpy()
 
 
 def _want(ref, tri, uv, tex, persp, A, **kw):
@@ -66,8 +28,8 @@ def _check_both_modes(oracle, scene, tex, H, W, what, levels, check=None, **fill
     """The pass at each A of `levels`, affine and perspective, against the host model; `check(counts, persp, A)`
     judges the sample counts."""
     tri, col, nrm, uv = scene
-    ref = _frame(oracle, tri, col, nrm, H, W)
-    f = _filler(H, W, **filler_kw)
+    ref = oracle_frame(oracle, tri, col, nrm, H, W)
+    f = filler(H, W, **filler_kw)
     f.bind_texture(uv, tex, mipmaps=True)
     chain = mip_ref.build_chain(tex)
     constant = (chain[0] == chain[0][0, 0]).all()      # (a 1 x 1 texture: every filter gives its one texel)
@@ -78,13 +40,10 @@ def _check_both_modes(oracle, scene, tex, H, W, what, levels, check=None, **fill
             f.texture_pass(perspective=persp, filter="trilinear", anisotropy=A)
             want = _want(ref, tri, uv, tex, persp, A, chain=chain)
             assert not np.isnan(want).any(), (what, persp, A)
-            assert_bit_equal(_host(f.get_color_tensor()), want, f"{what} colour, perspective={persp}, A={A}")
+            assert_bit_equal(host(f.get_color_tensor()), want, f"{what} colour, perspective={persp}, A={A}")
             if not constant:
                 assert (want.view(np.uint32) != trilinear.view(np.uint32)).any(), (what, A, "no pixel differs from trilinear")
-            # z, normals and the winner plane are only read
-            assert_bit_equal(_host(f.get_z_tensor()), ref.z_buffer, f"{what} z")
-            assert_bit_equal(_host(f.get_normals_tensor()), ref.normals_buffer, f"{what} normals")
-            assert_bit_equal(_host(f.get_winner_tensor()), ref.winner, f"{what} winner")
+            planes_only_read(f, ref, what)
             counts = _counts(ref, tri, uv, tex, persp, A)
             print(f"{what}, perspective={persp}, A={A}: {int(counts.sum())} covered, N histogram {counts[1:].tolist()}")
             if check is not None:
@@ -100,7 +59,7 @@ def test_the_floor_reaches_every_sample_count(oracle):
         if persp:
             assert counts[1] >= 500                  # the near rows are magnified: the plain trilinear path
 
-    _check_both_modes(oracle, aniso_ref.floor_scene(), _texture(1, 256, 256), 64, 64, "floor64", (2, 4, 5, 16), check)
+    _check_both_modes(oracle, aniso_ref.floor_scene(), texture(1, 256, 256), 64, 64, "floor64", (2, 4, 5, 16), check)
 
 
 @pytest.mark.parametrize("size", [256, 1024])
@@ -112,7 +71,7 @@ def test_trex_against_the_host_model(oracle, size):
             # a wavefront mixes lanes that take one sample with lanes that take up to sixteen
             assert counts[1] >= 100000 and counts[2:].sum() >= 50000 and counts[16] >= 1
 
-    _check_both_modes(oracle, _trex(), _texture(1, 709, 709), size, size, f"trex{size}", (4, 16), check)
+    _check_both_modes(oracle, trex_textured(), texture(1, 709, 709), size, size, f"trex{size}", (4, 16), check)
 
 
 @pytest.mark.parametrize("seed,T,H,W,th,tw,size_px", [(34, 60, 64, 41, 2, 5, (1.0, 60.0)),
@@ -120,7 +79,7 @@ def test_trex_against_the_host_model(oracle, size):
                                                       (32, 2500, 333, 512, 3, 1000, (1.0, 60.0)),
                                                       (35, 1500, 128, 119, 64, 97, (2, 40))])
 def test_random_soups_with_uv_beyond_the_unit_square(oracle, seed, T, H, W, th, tw, size_px):
-    scene = _soup(seed, T, max(H, W), size_px=size_px)
+    scene = soup_textured(seed, T, max(H, W), size_px=size_px)
 
     def check(counts, persp, A):
         if seed == 32:
@@ -130,26 +89,26 @@ def test_random_soups_with_uv_beyond_the_unit_square(oracle, seed, T, H, W, th, 
         if seed == 34:
             assert counts.sum() == 1886 and counts[2:5].sum() >= 100 and not counts[5:].any()
 
-    _check_both_modes(oracle, scene, _texture(seed, th, tw), H, W, f"soup{seed}", (3, 5, 16), check)
+    _check_both_modes(oracle, scene, texture(seed, th, tw), H, W, f"soup{seed}", (3, 5, 16), check)
 
 
 def test_nan_and_infinite_uv_follow_the_statement(oracle):
-    tri, col, nrm, uv = _soup(12, 1500, 160, size_px=(4.0, 40.0))
+    tri, col, nrm, uv = soup_textured(12, 1500, 160, size_px=(4.0, 40.0))
     rng = np.random.default_rng(12)
     odd = np.float32([np.nan, np.inf, -np.inf, 3e38, -3e38, 2147483648.0, -2147483904.0, 1e-42])
     hit = rng.uniform(size=uv.shape) < 0.15
     uv[hit] = rng.choice(odd, int(hit.sum()))
-    tex = _texture(12, 5, 7)
-    ref = _frame(oracle, tri, col, nrm, 160, 160)
+    tex = texture(12, 5, 7)
+    ref = oracle_frame(oracle, tri, col, nrm, 160, 160)
     assert int((ref.winner >= 0).sum()) == 25325
-    f = _filler(160, 160)
+    f = filler(160, 160)
     f.bind_texture(uv, tex, mipmaps=True)
     for persp in (False, True):
         trilinear = mip_ref.texture_pass(ref.color_buffer, ref.winner, tri, ref.proj_mat, uv, tex, persp)
         for A in (5, 16):
             f.render_arrays(tri, col, nrm, clear=True)
             f.texture_pass(perspective=persp, filter="trilinear", anisotropy=A)
-            got = _host(f.get_color_tensor())
+            got = host(f.get_color_tensor())
             want = _want(ref, tri, uv, tex, persp, A)
             # (IEEE 754 leaves the sign and payload of a generated NaN open: x86 and gfx950 differ there)
             nan = np.isnan(want)
@@ -164,9 +123,9 @@ def test_nan_and_infinite_uv_follow_the_statement(oracle):
 
 def test_one_sample_through_the_entry_point_is_the_trilinear_pass(oracle):
     from cython3dmodelrenderer_amd import _capi
-    tri, col, nrm, uv = _trex()
-    tex = _texture(1, 709, 709)
-    f, g = _filler(256, 256), _filler(256, 256)
+    tri, col, nrm, uv = trex_textured()
+    tex = texture(1, 709, 709)
+    f, g = filler(256, 256), filler(256, 256)
     for x in (f, g):
         x.bind_texture(uv, tex, mipmaps=True)
     for persp in (False, True):
@@ -174,33 +133,33 @@ def test_one_sample_through_the_entry_point_is_the_trilinear_pass(oracle):
         f.texture_pass(perspective=persp, filter="trilinear")
         g.render_arrays(tri, col, nrm, clear=True)
         g.synchronize()
-        before = _host(g.get_color_tensor()).copy()
+        before = host(g.get_color_tensor()).copy()
         d_uv, _ = g._texture
         _capi.check(g._lib.crender_aniso_shade(
             g.winner_buffer.data_ptr(), g._inputs[0].data_ptr(), len(tri), None, g._P, d_uv.data_ptr(),
             g._mip[0].data_ptr(), 709, 709, None, None, g.color_buffer.data_ptr(), 256, 256, 0, 256,
             _capi.MIP_PERSPECTIVE if persp else 0, 1, g._stream()), "crender_aniso_shade")
         g.synchronize()
-        got = _host(g.color_buffer)
+        got = host(g.color_buffer)
         assert (got != before).any()
-        assert_bit_equal(got, _host(f.get_color_tensor()), f"max_aniso = 1 vs crender_mip_shade, perspective={persp}")
+        assert_bit_equal(got, host(f.get_color_tensor()), f"max_aniso = 1 vs crender_mip_shade, perspective={persp}")
 
 
 def test_presort_gives_the_same_bits(oracle):
-    scene = _soup(41, 20000, 512, size_px=(2.0, 30.0))
-    f = _check_both_modes(oracle, scene, _texture(41, 64, 97), 512, 512, "presorted soup", (16,), presort=True)
+    scene = soup_textured(41, 20000, 512, size_px=(2.0, 30.0))
+    f = _check_both_modes(oracle, scene, texture(41, 64, 97), 512, 512, "presorted soup", (16,), presort=True)
     assert f._order is not None          # the resident inputs are the tile-coherent copy: the pass went through pos_of
 
 
 def test_fused_light_equals_the_pass_plus_the_illumination(oracle):
-    tri, col, nrm, uv = _trex()
-    tex = _texture(5, 709, 709)
+    tri, col, nrm, uv = trex_textured()
+    tex = texture(5, 709, 709)
     chain = mip_ref.build_chain(tex)
     H = W = 512
     A = 16
-    ref = _frame(oracle, tri, col, nrm, H, W)
+    ref = oracle_frame(oracle, tri, col, nrm, H, W)
     light = [float(v) for v in oracle.guro_light(LIGHT)]
-    f, g = _filler(H, W), _filler(H, W)
+    f, g = filler(H, W), filler(H, W)
     f.bind_texture(uv, tex, mipmaps=True)
     g.bind_texture(uv, tex, mipmaps=True)
     for persp in (False, True):
@@ -210,11 +169,11 @@ def test_fused_light_equals_the_pass_plus_the_illumination(oracle):
         g.texture_pass(perspective=persp, filter="trilinear", anisotropy=A)
         g.synchronize()
         g.shade_guro(light)
-        got = _host(f.get_color_tensor())
-        assert_bit_equal(got, _host(g.get_color_tensor()), f"fused light vs pass + illumination, {persp}")
+        got = host(f.get_color_tensor())
+        assert_bit_equal(got, host(g.get_color_tensor()), f"fused light vs pass + illumination, {persp}")
         want = _want(ref, tri, uv, tex, persp, A, chain=chain, normals=ref.normals_buffer, light_direction=LIGHT)
         assert_bit_equal(got, want, f"fused light vs oracle.guro of the host model, {persp}")
-        assert_bit_equal(_host(f.get_normals_tensor()), ref.normals_buffer, "normals")
+        assert_bit_equal(host(f.get_normals_tensor()), ref.normals_buffer, "normals")
         lit_trilinear = mip_ref.texture_pass(ref.color_buffer, ref.winner, tri, ref.proj_mat, uv, tex, persp, chain=chain,
                                              normals=ref.normals_buffer, light_direction=LIGHT)
         assert (want != lit_trilinear).any()
@@ -230,20 +189,20 @@ def test_fused_light_equals_the_pass_plus_the_illumination(oracle):
     want = aniso_ref.texture_pass(c, ref.winner, tri, ref.proj_mat, uv, tex, False, A, chain=chain, normals=n,
                                   light_direction=LIGHT)
     assert ref.winner[0, 0] < 0 and want[0, 0, 0] != 0.0 and want[0, 0, 0] != 3.0
-    assert_bit_equal(_host(f.get_color_tensor()), want, "background under the fused light")
+    assert_bit_equal(host(f.get_color_tensor()), want, "background under the fused light")
 
 
 def test_row_strip_leaves_the_other_rows_alone(oracle):
-    tri, col, nrm, uv = _trex()
-    tex = _texture(6, 709, 709)
+    tri, col, nrm, uv = trex_textured()
+    tex = texture(6, 709, 709)
     chain = mip_ref.build_chain(tex)
     H = W = 512
     A = 16
     y0, y1 = 135, 301                    # not multiples of the kernel's 8-row blocks
-    ref = _frame(oracle, tri, col, nrm, H, W, y0=y0, y1=y1)
+    ref = oracle_frame(oracle, tri, col, nrm, H, W, y0=y0, y1=y1)
     light = [float(v) for v in oracle.guro_light(LIGHT)]
     for with_light in (False, True):
-        f = _filler(H, W, row_strip=(y0, y1))
+        f = filler(H, W, row_strip=(y0, y1))
         f.bind_texture(uv, tex, mipmaps=True)
         f.render_arrays(tri, col, nrm, clear=True)
         f.synchronize()
@@ -253,7 +212,7 @@ def test_row_strip_leaves_the_other_rows_alone(oracle):
         f.winner_buffer[:y0] = 0
         f.winner_buffer[y1:] = 1
         f.texture_pass(filter="trilinear", light_direction=light if with_light else None, anisotropy=A)
-        got = _host(f.get_color_tensor())
+        got = host(f.get_color_tensor())
         assert (got[:y0] == 7.5).all() and (got[y1:] == -2.25).all()
         kw = dict(normals=ref.normals_buffer, light_direction=LIGHT) if with_light else {}
         want = _want(ref, tri, uv, tex, False, A, chain=chain, y0=y0, y1=y1, **kw)
@@ -263,31 +222,21 @@ def test_row_strip_leaves_the_other_rows_alone(oracle):
         assert (want[y0:y1] != trilinear[y0:y1]).any()
 
 
-def _textured_model(seed=8):
-    from cython3dmodelrenderer_amd.data_structures.model import Model
-    tri, col, nrm, uv = _soup(seed, 3000, 256, size_px=(3.0, 50.0))
-    T = len(tri)
-    idx = np.arange(3 * T, dtype=np.int32).reshape(T, 3)
-    tex = _texture(seed, 37, 53)
-    m = Model(tri.reshape(-1, 3), idx, uv.reshape(-1, 2), idx, tex, nrm.reshape(-1, 3), idx, recalculate_normals=False)
-    return m, tex
-
-
 @pytest.mark.parametrize("on_device", [None, False, True, "fused"])
 def test_renderer_under_every_on_device(oracle, on_device):
     from cython3dmodelrenderer_amd.illumination.guro_illumination import GuroIllumination
     from cython3dmodelrenderer_amd.renderer import Renderer
-    m, tex = _textured_model()
+    m, tex = textured_model()
     tri, col, nrm = m._vertices_by_triangles, m._colors_by_triangles, m._normals_by_triangles
     uv = m.get_texture_coords_by_triangles()
     H = W = 256
-    ref = _frame(oracle, tri, col, nrm, H, W)
+    ref = oracle_frame(oracle, tri, col, nrm, H, W)
     assert int((ref.winner >= 0).sum()) > 10000
     want = _want(ref, tri, uv, tex, True, 8, normals=ref.normals_buffer, light_direction=LIGHT)
     trilinear = mip_ref.texture_pass(ref.color_buffer, ref.winner, tri, ref.proj_mat, uv, tex, True,
                                      normals=ref.normals_buffer, light_direction=LIGHT)
     assert (want != trilinear).any()
-    f = _filler(H, W)
+    f = filler(H, W)
     binds = []
     bind = f.bind_texture
     f.bind_texture = lambda *a, **kw: (binds.append(kw), bind(*a, **kw))[1]
@@ -295,18 +244,18 @@ def test_renderer_under_every_on_device(oracle, on_device):
                  texture_pass={"filter": "trilinear", "perspective": True, "anisotropy": 8})
     for _ in range(2):                             # every frame starts from cleared buffers: the same image twice
         out = r.render(m)
-        got = _host(out) if on_device in (True, "fused") else np.array(out)
+        got = host(out) if on_device in (True, "fused") else np.array(out)
         assert_bit_equal(got, want, f"Renderer(on_device={on_device!r})")
     assert binds == [{"mipmaps": True}]            # the texture went up once per model, with its chain
     assert f.mip_levels() == mip_ref.layout(37, 53)[0]
-    assert_bit_equal(_host(f.get_normals_tensor()), ref.normals_buffer, "normals")
+    assert_bit_equal(host(f.get_normals_tensor()), ref.normals_buffer, "normals")
 
 
 def test_errors_name_their_cause(oracle):
     from cython3dmodelrenderer_amd import _capi
-    tri, col, nrm, uv = _soup(13, 300, 64)
-    tex = _texture(13, 8, 8)
-    f = _filler(64, 64)
+    tri, col, nrm, uv = soup_textured(13, 300, 64)
+    tex = texture(13, 8, 8)
+    f = filler(64, 64)
     f.bind_texture(uv, tex, mipmaps=True)
     f.render_arrays(tri, col, nrm, clear=True)
     f.texture_pass(filter="trilinear", anisotropy=4)
@@ -327,7 +276,7 @@ def test_errors_name_their_cause(oracle):
     f.bind_texture(uv, tex)
     with pytest.raises(ValueError, match="filter 'trilinear' needs a mip chain"):
         f.texture_pass(filter="trilinear", anisotropy=4)
-    chain = _filler(64, 64, pipeline=True)
+    chain = filler(64, 64, pipeline=True)
     chain.bind_texture(uv, tex, mipmaps=True)
     with pytest.raises(ValueError, match="swap chain"):
         chain.texture_pass(filter="trilinear", anisotropy=4)

@@ -12,19 +12,13 @@ import numpy as np
 import pytest
 
 import ao_ref
+from pass_scenes import Frame, capi, trex_fixture  # noqa: F401 (fixtures)
 from util import assert_bit_equal, other_symbols, unit_inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TABLE = [(1, 0), (-2, 2), (0, -3), (2, 3), (-4, -1), (4, -3), (-1, 5), (-3, -5), (5, 2), (-6, 2), (3, -6), (2, 6), (-6, -4),
          (7, -2), (-4, 6), (-1, -8)]
 TREX_KW = dict(radius=0.03, radius_px=8, min_cos=0.1, strength=1.0, floor=0.0)
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from cython3dmodelrenderer_amd import _build, _capi
-    _build.build()           # hipcc cross-compiles for gfx950 without a GPU
-    return _capi
 
 
 # ---- the host side of the ABI ----------------------------------------------------------------------------------
@@ -197,14 +191,7 @@ def test_a_depth_step_darkens_the_far_side_only(oracle, rotate):
 
 # ---- the model on the oracle's frame of T-Rex ------------------------------------------------------------------
 
-class _Frame:
-    def __init__(self, oracle):
-        from cython3dmodelrenderer_amd import scenes
-        self.tri, self.col, self.nrm = scenes.load_fixture("trex_inputs.npz")
-        self.cam = oracle.OracleFiller(256, 256, fov=45.0)
-        self.cam.render_arrays(self.tri, self.col, self.nrm)
-        self.covered = self.cam.winner >= 0
-
+class _Frame(Frame):
     def run(self, taps=TABLE, **kw):
         for k, v in TREX_KW.items():
             kw.setdefault(k, v)
@@ -212,11 +199,7 @@ class _Frame:
                               self.cam.normals_buffer, taps, **kw)
 
 
-@pytest.fixture(scope="module")
-def trex(oracle):
-    f = _Frame(oracle)
-    assert int(f.covered.sum()) == 15801
-    return f
+trex = trex_fixture(_Frame)
 
 
 @pytest.mark.parametrize("rotate,occluded,taken", [(True, 7102, 22461), (False, 7245, 22514)])

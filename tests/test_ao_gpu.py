@@ -10,26 +10,15 @@ import pytest
 import ao_ref
 import phong_ref
 import shadow_ref
+from pass_scenes import GOLDEN, Scene, filler, host, soup_fixture, trex_arrays, trex_fixture
 from util import assert_bit_equal, random_soup
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 GURO = (0.3, -0.2, 1.0)
 TABLE = [(1, 0), (-2, 2), (0, -3), (2, 3), (-4, -1), (4, -3), (-1, 5), (-3, -5), (5, 2), (-6, 2), (3, -6), (2, 6), (-6, -4),
          (7, -2), (-4, 6), (-1, -8)]
 SOUP_KW = dict(radius=0.05, radius_px=8, strength=3.0, floor=0.25)
-
-
-def _filler(H, W, fov=45.0, **kw):
-    from cython3dmodelrenderer_amd.pixel_buffer_filler import AdvancedPixelBufferFiller
-    kw.setdefault("track_winner", True)
-    return AdvancedPixelBufferFiller(H, W, fov=fov, device="cuda:0", **kw)
-
-
-def _host(t):
-    return t.cpu().numpy()
 
 
 def _table(kw):
@@ -47,16 +36,7 @@ def _model_kw(kw):
     return m
 
 
-class _Scene:
-    """A model and the oracle's frame of it: computed once, only read afterwards."""
-
-    def __init__(self, oracle, arrays, H, W, y0=0, y1=None):
-        self.tri, self.col, self.nrm = arrays
-        self.H, self.W = H, W
-        self.cam = oracle.OracleFiller(H, W, fov=45.0)
-        self.cam.render_arrays(self.tri, self.col, self.nrm, y0=y0, y1=y1)
-        self.covered = int((self.cam.winner >= 0).sum())
-
+class _Scene(Scene):
     def want(self, color=None, counts=None, y0=0, y1=None, **kw):
         out = ao_ref.ao_pass(self.cam.color_buffer if color is None else color, self.cam.z_buffer, self.cam.winner,
                              self.tri, self.cam.proj_mat, self.cam.normals_buffer, _table(kw), y0=y0, y1=y1, counts=counts,
@@ -64,38 +44,23 @@ class _Scene:
         assert not np.isnan(out).any()
         return out
 
-    def draw(self, f):
-        f.render_arrays(self.tri, self.col, self.nrm, clear=True)
-
-    def check_planes(self, f, what):
-        """z, normals and the winner plane are only read."""
-        assert_bit_equal(_host(f.get_z_tensor()), self.cam.z_buffer, f"{what}: z")
-        assert_bit_equal(_host(f.get_normals_tensor()), self.cam.normals_buffer, f"{what}: normals")
-        assert_bit_equal(_host(f.get_winner_tensor()), self.cam.winner, f"{what}: winner")
-
     def check(self, f, what, counts=None, **kw):
         self.draw(f)
         f.ao_pass(**kw)
         want = self.want(counts=counts, **kw)
-        assert (want.view(np.uint32) != self.cam.color_buffer.view(np.uint32)).any(), (what, "the pass changed nothing")
-        assert_bit_equal(_host(f.get_color_tensor()), want, f"{what} colour")
+        self.assert_changed(want, what)
+        assert_bit_equal(host(f.get_color_tensor()), want, f"{what} colour")
         self.check_planes(f, what)
         return want
 
 
-def _trex_arrays():
-    from cython3dmodelrenderer_amd import scenes
-    return scenes.load_fixture("trex_inputs.npz")
-
-
-@pytest.fixture(scope="module")
-def trex256(oracle):
-    return _Scene(oracle, _trex_arrays(), 256, 256)
+trex256 = trex_fixture(_Scene)
+soup256 = soup_fixture(_Scene)
 
 
 @pytest.fixture(scope="module")
 def filler256():
-    return _filler(256, 256)
+    return filler(256, 256)
 
 
 # ---- 1. T-Rex ------------------------------------------------------------------------------------------------------
@@ -138,8 +103,8 @@ def test_trex_the_corners_and_the_edges_of_the_halo(trex256, filler256, R):
 
 def test_a_row_strip_of_an_odd_frame_leaves_the_other_rows_alone(oracle):
     y0, y1 = 40, 136
-    s = _Scene(oracle, _trex_arrays(), 200, 173, y0=y0, y1=y1)
-    f = _filler(200, 173, row_strip=(y0, y1))
+    s = _Scene(oracle, trex_arrays(), 200, 173, y0=y0, y1=y1)
+    f = filler(200, 173, row_strip=(y0, y1))
     near = float(s.cam.z_buffer[s.cam.winner >= 0].min()) - 1e-3
     for normals in ("plane", "face"):
         s.draw(f)
@@ -153,19 +118,19 @@ def test_a_row_strip_of_an_odd_frame_leaves_the_other_rows_alone(oracle):
         f.z_buffer[y1:] = near
         kw = dict(taps=TABLE, radius=0.2, strength=1.0, normals=normals)
         f.ao_pass(**kw)
-        got = _host(f.get_color_tensor())
+        got = host(f.get_color_tensor())
         assert (got[:y0] == 7.5).all() and (got[y1:] == -2.25).all()
         want = s.want(y0=y0, y1=y1, **kw)
         assert (want[y0:y1].view(np.uint32) != s.cam.color_buffer[y0:y1].view(np.uint32)).any()
         assert_bit_equal(got[y0:y1], want[y0:y1], f"strip rows, {normals}")
         # the poison works: a pass that looked across the strip's edge would give other colours
-        poisoned_w, poisoned_z = _host(f.get_winner_tensor()), _host(f.get_z_tensor())
+        poisoned_w, poisoned_z = host(f.get_winner_tensor()), host(f.get_z_tensor())
         seen = ao_ref.ao_pass(s.cam.color_buffer, poisoned_z, poisoned_w, s.tri, s.cam.proj_mat, s.cam.normals_buffer, TABLE,
                               **_model_kw(kw))
         assert (seen[y0:y1] != want[y0:y1]).any()
         assert_bit_equal(poisoned_w[y0:y1], s.cam.winner[y0:y1], "winner")
         assert_bit_equal(poisoned_z[y0:y1], s.cam.z_buffer[y0:y1], "z")
-        assert_bit_equal(_host(f.get_normals_tensor()), s.cam.normals_buffer, "normals")
+        assert_bit_equal(host(f.get_normals_tensor()), s.cam.normals_buffer, "normals")
 
 
 class _Planes:
@@ -203,8 +168,8 @@ class _Planes:
         import torch
         from cython3dmodelrenderer_amd import _capi
         lib = _capi.load()
-        host = {k: np.ascontiguousarray(planes.get(k, getattr(self, k))) for k in ("winner", "z", "normal", "tri", "color")}
-        dev = {k: torch.from_numpy(v).cuda() for k, v in host.items()}
+        kept = {k: np.ascontiguousarray(planes.get(k, getattr(self, k))) for k in ("winner", "z", "normal", "tri", "color")}
+        dev = {k: torch.from_numpy(v).cuda() for k, v in kept.items()}
         T = self.T if T is None else T
         d_pos = None if pos_of is None else torch.from_numpy(np.ascontiguousarray(pos_of).view(np.int32)).cuda()
         taps2 = (C.c_int8 * (2 * len(table)))(*[v for p in table for v in p])
@@ -215,9 +180,9 @@ class _Planes:
             None if d_pos is None else d_pos.data_ptr(), _capi.f32_16(self.P), dev["normal"].data_ptr(), taps2, len(table),
             radius_px, self.radius if radius is None else radius, min_cos, strength, floor, dev["color"].data_ptr(),
             self.H, self.W, y0, self.H if y1 is None else y1, flags, st), "crender_ao_shade")
-        got = _host(dev["color"])
+        got = host(dev["color"])
         for k in ("winner", "z", "normal", "tri"):
-            assert_bit_equal(_host(dev[k]), host[k], f"{k} is only read")
+            assert_bit_equal(host(dev[k]), kept[k], f"{k} is only read")
         return got
 
     def check(self, what, table=TABLE + [(0, 1), (-1, 0), (0, -1), (1, 0)], **kw):
@@ -268,7 +233,7 @@ SOUP52 = {"plane": (253911, 208585, 13112), "face": (253911, 42730, 330)}
 ])
 def test_random_soups(oracle, seed, T, H, W, kw, presort, pinned):
     s = _Scene(oracle, random_soup(np.random.default_rng(seed), T, max(H, W), **kw), H, W)
-    f = _filler(H, W, presort=presort)
+    f = filler(H, W, presort=presort)
     for normals in ("plane", "face"):
         counts = {}
         s.check(f, f"soup{seed}, {normals}", counts=counts, normals=normals, **SOUP_KW)
@@ -332,23 +297,6 @@ def test_special_values_through_the_c_entry(oracle):
 
 # ---- 5. the filler -------------------------------------------------------------------------------------------------
 
-class _Soup:
-    """What a filler reads off a model."""
-
-    def __init__(self, seed=71, T=3000, res=256):
-        self._vertices_by_triangles, self._colors_by_triangles, self._normals_by_triangles = \
-            random_soup(np.random.default_rng(seed), T, res, size_px=(3.0, 50.0))
-
-
-@pytest.fixture(scope="module")
-def soup256(oracle):
-    m = _Soup()
-    s = _Scene(oracle, (m._vertices_by_triangles, m._colors_by_triangles, m._normals_by_triangles), 256, 256)
-    s.model = m
-    assert s.covered > 10000
-    return s
-
-
 def test_host_views_show_the_pass_and_their_edits_reach_it(soup256, filler256):
     s, f = soup256, filler256
     s.draw(f)
@@ -382,7 +330,7 @@ def test_host_views_show_the_pass_and_their_edits_reach_it(soup256, filler256):
                             _table(SOUP_KW), **_model_kw(SOUP_KW))
     assert (want_z != want).any()
     assert_bit_equal(f.get_color_buffer(), want_z, "under an edited z")
-    assert_bit_equal(_host(f.get_winner_tensor()), s.cam.winner, "winner")
+    assert_bit_equal(host(f.get_winner_tensor()), s.cam.winner, "winner")
 
 
 def test_numpy_torch_and_device_model_inputs_agree(oracle):
@@ -399,19 +347,19 @@ def test_numpy_torch_and_device_model_inputs_agree(oracle):
     kw = dict(normals="face", strength=1.0)
     want = s.want(**kw)
     assert (want != s.cam.color_buffer).any()
-    f = _filler(256, 256)                          # numpy
+    f = filler(256, 256)                          # numpy
     s.draw(f)
     f.ao_pass(**kw)
-    assert_bit_equal(_host(f.get_color_tensor()), want, "numpy inputs")
+    assert_bit_equal(host(f.get_color_tensor()), want, "numpy inputs")
     s.check_planes(f, "numpy inputs")
-    f = _filler(256, 256)                          # caller's device tensors
+    f = filler(256, 256)                          # caller's device tensors
     f.render_arrays(*[torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (tri, col, nrm)], clear=True)
     f.ao_pass(**kw)
-    assert_bit_equal(_host(f.get_color_tensor()), want, "torch inputs")
-    f = _filler(256, 256)                          # the device-resident model
+    assert_bit_equal(host(f.get_color_tensor()), want, "torch inputs")
+    f = filler(256, 256)                          # the device-resident model
     f.render_model(DeviceModel(m), clear=True)
     f.ao_pass(**kw)
-    assert_bit_equal(_host(f.get_color_tensor()), want, "DeviceModel inputs")
+    assert_bit_equal(host(f.get_color_tensor()), want, "DeviceModel inputs")
     s.check_planes(f, "DeviceModel inputs")
 
 
@@ -432,17 +380,17 @@ def test_renderer_with_guro_illumination(oracle, soup256, on_device):
         want = s.want(color=oracle.guro(s.cam.color_buffer.copy(), s.cam.normals_buffer, GURO), **AO)
     else:
         want = oracle.guro(occluded.copy(), s.cam.normals_buffer, GURO)
-    f = _filler(256, 256)
+    f = filler(256, 256)
     r = Renderer(f, GuroIllumination(GURO), on_device=on_device, ambient_occlusion=AO)
     for _ in range(2):                             # every frame starts from cleared buffers
         out = r.render(s.model)
         assert isinstance(out, np.ndarray) == (on_device is None)
-        got = np.array(out) if on_device is None else _host(out)
+        got = np.array(out) if on_device is None else host(out)
         assert np.array_equal(got, want)           # as values: the light leaves -0 on the background
         covered = s.cam.winner >= 0
         assert_bit_equal(got[covered], want[covered], f"Renderer(on_device={on_device!r}, ambient_occlusion=...)")
     s.check_planes(f, "after Renderer")
-    plain = _host(Renderer(_filler(256, 256), GuroIllumination(GURO), on_device=True).render(s.model))
+    plain = host(Renderer(filler(256, 256), GuroIllumination(GURO), on_device=True).render(s.model))
     assert (plain != want).any()
 
 
@@ -460,16 +408,16 @@ def test_renderer_occludes_before_the_phong_pass(soup256):
     want = lit(s.want(**AO))
     other = s.want(color=lit(s.cam.color_buffer), **AO)
     assert (want != other).any()                   # the two orders differ on this scene: the test can tell them apart
-    f = _filler(256, 256)
+    f = filler(256, 256)
     r = Renderer(f, PhongIllumination(lights=PHONG_LIGHTS, **PHONG_KW), on_device=True, ambient_occlusion=AO)
-    got = _host(r.render(s.model))
+    got = host(r.render(s.model))
     assert_bit_equal(got, want, "Renderer(PhongIllumination, ambient_occlusion=...)")
     # and by hand
-    a = _filler(256, 256)
+    a = filler(256, 256)
     s.draw(a)
     a.ao_pass(**AO)
     a.phong_pass(PHONG_LIGHTS, **PHONG_KW)
-    assert_bit_equal(got, _host(a.get_color_tensor()), "ao_pass, then phong_pass")
+    assert_bit_equal(got, host(a.get_color_tensor()), "ao_pass, then phong_pass")
     s.check_planes(a, "ao_pass, then phong_pass")
 
 
@@ -488,22 +436,22 @@ def test_renderer_with_shadow_texture_and_supersampling(oracle, soup256):
     want = shadow_ref.shadow_pass(occluded, s.cam.winner, s.tri, s.cam.proj_mat, ltri, lig.proj_mat, lig.z_buffer, lig.winner,
                                   bias=2e-3, ambient=0.125, pcf=3)
     assert (want != occluded).any()
-    f, g = _filler(256, 256), _filler(128, 160)
+    f, g = filler(256, 256), filler(128, 160)
     r = Renderer(f, GuroIllumination(GURO), on_device="fused", ambient_occlusion=AO,
                  shadow=dict(filler=g, R=R, t=t, bias=2e-3, pcf=3, ambient=0.125))
-    a, b = _filler(256, 256), _filler(128, 160)
+    a, b = filler(256, 256), filler(128, 160)
     a.set_fused_illumination(GuroIllumination(GURO).light_direction)
     s.draw(a)
     b.render_arrays(ltri, s.col, lnrm, clear=True)
     a.bind_shadow_map(b, ltri)
     a.ao_pass(**AO)
     a.shadow_pass(bias=2e-3, pcf=3, ambient=0.125)
-    assert_bit_equal(_host(r.render(s.model)), _host(a.get_color_tensor()), "ao_pass, then shadow_pass, under the fused light")
+    assert_bit_equal(host(r.render(s.model)), host(a.get_color_tensor()), "ao_pass, then shadow_pass, under the fused light")
     a.set_fused_illumination(None)
     s.draw(a)
     a.ao_pass(**AO)
     a.shadow_pass(bias=2e-3, pcf=3, ambient=0.125)
-    assert_bit_equal(_host(a.get_color_tensor()), want, "ao_pass, then shadow_pass")
+    assert_bit_equal(host(a.get_color_tensor()), want, "ao_pass, then shadow_pass")
     # the texture pass before it
     rng = np.random.default_rng(72)
     T = len(s.tri)
@@ -511,25 +459,25 @@ def test_renderer_with_shadow_texture_and_supersampling(oracle, soup256):
     uv = rng.uniform(0, 1, (T, 3, 2)).astype(np.float32)
     tex = rng.integers(0, 256, (37, 53, 3), dtype=np.uint8)
     m = Model(s.tri.reshape(-1, 3), idx, uv.reshape(-1, 2), idx, tex, s.nrm.reshape(-1, 3), idx, recalculate_normals=False)
-    f = _filler(256, 256)
-    got = _host(Renderer(f, GuroIllumination(GURO), on_device="fused", texture_pass={"perspective": True},
+    f = filler(256, 256)
+    got = host(Renderer(f, GuroIllumination(GURO), on_device="fused", texture_pass={"perspective": True},
                          ambient_occlusion=AO).render(m))
-    a = _filler(256, 256)
+    a = filler(256, 256)
     a.bind_texture(m.get_texture_coords_by_triangles(), tex)
     a.render_model(m, clear=True)
     a.texture_pass(perspective=True, light_direction=GuroIllumination(GURO).light_direction)
-    textured = _host(a.get_color_tensor())
+    textured = host(a.get_color_tensor())
     assert (textured != s.cam.color_buffer).any()
     assert_bit_equal(got, s.want(color=textured, **AO), "the texture with its light, then the occlusion")
     # supersampling: the pass runs on the supersampled frame, the resolve afterwards
-    f = _filler(256, 256)
+    f = filler(256, 256)
     out = Renderer(f, GuroIllumination(GURO), None, 128, 128, on_device=True, supersample=2, ambient_occlusion=AO).render(s.model)
     assert tuple(out.shape) == (128, 128, 3)
-    assert_bit_equal(_host(f.get_color_tensor()), occluded, "the supersampled frame, occluded and unshaded")
-    a = _filler(256, 256)
+    assert_bit_equal(host(f.get_color_tensor()), occluded, "the supersampled frame, occluded and unshaded")
+    a = filler(256, 256)
     s.draw(a)
     a.ao_pass(**AO)
-    assert_bit_equal(_host(out), _host(a.resolve(2, light_direction=GuroIllumination(GURO).light_direction)),
+    assert_bit_equal(host(out), host(a.resolve(2, light_direction=GuroIllumination(GURO).light_direction)),
                      "Renderer(supersample=2, ambient_occlusion=...)")
     s.check_planes(f, "after the supersampled frame")
 
@@ -539,11 +487,11 @@ def test_renderer_with_shadow_texture_and_supersampling(oracle, soup256):
 def test_errors_name_their_cause(soup256):
     from cython3dmodelrenderer_amd import _capi
     s = soup256
-    f = _filler(256, 256, track_winner=False)
+    f = filler(256, 256, track_winner=False)
     s.draw(f)
     with pytest.raises(ValueError, match="winner plane"):
         f.ao_pass()
-    f = _filler(256, 256)
+    f = filler(256, 256)
     with pytest.raises(ValueError, match="no frame has been rendered"):
         f.ao_pass()
     s.draw(f)
@@ -551,7 +499,7 @@ def test_errors_name_their_cause(soup256):
     with pytest.raises(ValueError, match="did not start from cleared buffers"):
         f.ao_pass()
     with pytest.raises(ValueError, match="swap chain"):
-        _filler(64, 64, pipeline=True).ao_pass()
+        filler(64, 64, pipeline=True).ao_pass()
     s.draw(f)
     with pytest.raises(ValueError, match="normals must be 'plane' or 'face', got 'vertex'"):
         f.ao_pass(normals="vertex")
@@ -581,11 +529,11 @@ def test_errors_name_their_cause(soup256):
         f.ao_pass(strength=-1.0)
     with pytest.raises(_capi.CrenderError, match="floor is not 0 .. 1"):
         f.ao_pass(floor=1.5)
-    assert_bit_equal(_host(f.get_color_tensor()), s.cam.color_buffer, "nothing was written")
+    assert_bit_equal(host(f.get_color_tensor()), s.cam.color_buffer, "nothing was written")
     f.ao_pass(**SOUP_KW)                           # and works again
     want = s.want(**SOUP_KW)
     assert (want != s.cam.color_buffer).any()
-    assert_bit_equal(_host(f.get_color_tensor()), want, "after the errors")
+    assert_bit_equal(host(f.get_color_tensor()), want, "after the errors")
     s.check_planes(f, "after the errors")
 
 
@@ -599,11 +547,11 @@ def test_a_frame_redrawn_after_a_bin_overflow_ends_occluded(oracle):
     want = s.want(**kw)
     assert (want != s.cam.color_buffer).any()
     for more in (dict(), dict(presort=True)):
-        f = _filler(512, 512, tile=32, bin_capacity=500, direct_bins=False, **more)
+        f = filler(512, 512, tile=32, bin_capacity=500, direct_bins=False, **more)
         s.draw(f)
         need, cap = f.bin_usage()
         assert cap == 500 and need > cap and len(f._pending) == 1     # dropped fragments, nobody has looked yet
         f.ao_pass(**kw)
         assert not f._pending                                          # grown and redone before the pass
-        assert_bit_equal(_host(f.get_color_tensor()), want, f"a redone frame, {more}")
+        assert_bit_equal(host(f.get_color_tensor()), want, f"a redone frame, {more}")
         s.check_planes(f, "a redone frame")

@@ -6,18 +6,10 @@ import os
 import re
 import subprocess
 
-import pytest
-
+from pass_scenes import capi  # noqa: F401 (fixtures)
 from util import other_symbols, unit_inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from cython3dmodelrenderer_amd import _build, _capi
-    _build.build()           # hipcc cross-compiles for gfx950 without a GPU
-    return _capi
 
 
 def test_chain_header_symbols_are_exported_and_bound(capi):

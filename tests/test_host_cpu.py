@@ -10,16 +10,10 @@ import sys
 import numpy as np
 import pytest
 
+from pass_scenes import capi  # noqa: F401 (fixtures)
 from util import assert_bit_equal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from cython3dmodelrenderer_amd import _build, _capi
-    _build.build()           # hipcc cross-compiles for gfx950 without a GPU
-    return _capi
 
 
 def test_library_exports_every_declared_symbol(capi):

@@ -11,27 +11,11 @@ import pytest
 
 import mip_ref
 import tex_ref
+from pass_scenes import capi, texture, trex_uv as trex  # noqa: F401 (fixtures)
 from util import assert_bit_equal, other_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 SIZES = [(1, 1), (1, 7), (2, 5), (3, 1000), (709, 709), (64, 97), (1025, 513)]
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from cython3dmodelrenderer_amd import _build, _capi
-    _build.build()           # hipcc cross-compiles for gfx950 without a GPU
-    return _capi
-
-
-@pytest.fixture(scope="module")
-def trex():
-    from cython3dmodelrenderer_amd import scenes
-    tri, col, nrm = scenes.load_fixture("trex_inputs.npz")
-    with np.load(os.path.join(GOLDEN, "trex_uv.npz")) as z:
-        uv = np.ascontiguousarray(z["uv"][z["faces_uv"]], dtype=np.float32)
-    return tri, col, nrm, uv
 
 
 @pytest.fixture(scope="module")
@@ -46,10 +30,6 @@ def frames(oracle, trex):
             made[size].render_arrays(tri, col, nrm)
         return made[size]
     return frame
-
-
-def _texture(seed, th, tw):
-    return np.random.default_rng(seed).integers(0, 256, (th, tw, 3), dtype=np.uint8)
 
 
 def _c_layout(capi, th, tw):
@@ -158,7 +138,7 @@ def test_filler_and_renderer_carry_the_option():
 
 def test_chain_properties():
     for th, tw in SIZES:
-        tex = _texture(th * 1000 + tw, th, tw)
+        tex = texture(th * 1000 + tw, th, tw)
         chain = mip_ref.build_chain(tex)
         levels, offsets, total = mip_ref.layout(th, tw)
         assert [c.shape for c in chain] == [(h, w, 3) for h, w in levels]
@@ -205,7 +185,7 @@ def test_level_rule_by_hand():
 def test_magnified_pixels_are_the_bilinear_ones(trex, frames, perspective):
     tri, _, _, uv = trex
     f = frames(1024)
-    tex = _texture(1, 709, 709)
+    tex = texture(1, 709, 709)
     base = np.zeros((1024, 1024, 3), np.float32)
     got = mip_ref.texture_pass(base, f.winner, tri, f.proj_mat, uv, tex, perspective=perspective)
     ys, xs, u, v, rho, l0, w = mip_ref.pixel_levels(f.winner, tri, f.proj_mat, uv, 709, 709, perspective)

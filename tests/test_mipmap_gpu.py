@@ -1,56 +1,18 @@
 """Mipmaps and trilinear filtering on the GPU (csrc/texmip.hip through bind_texture(..., mipmaps=True),
 texture_pass(filter="trilinear") and Renderer(texture_pass=...)), bit for bit against the host model of
 tests/mip_ref.py evaluated on the oracle's frame (itself pinned in tests/test_mipmap_cpu.py)."""
-import os
-
 import numpy as np
 import pytest
 
 import mip_ref
 import tex_ref
-from util import assert_bit_equal, random_soup
+from pass_scenes import filler, host, oracle_frame, planes_only_read, soup_textured, texture, textured_model, trex_textured
+from util import assert_bit_equal
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 LIGHT = (0.3, -0.2, 1.0)             # what GuroIllumination is constructed with
 SIZES = [(1, 1), (1, 7), (2, 5), (3, 1000), (709, 709), (64, 97), (1025, 513)]
-
-
-def _texture(seed, th, tw):
-    return np.random.default_rng(seed).integers(0, 256, (th, tw, 3), dtype=np.uint8)
-
-
-def _trex():
-    from cython3dmodelrenderer_amd import scenes
-    tri, col, nrm = scenes.load_fixture("trex_inputs.npz")
-    with np.load(os.path.join(GOLDEN, "trex_uv.npz")) as z:
-        uv = np.ascontiguousarray(z["uv"][z["faces_uv"]], dtype=np.float32)
-    return tri, col, nrm, uv
-
-
-def _soup(seed, T, res, **kw):
-    rng = np.random.default_rng(seed)
-    tri, col, nrm = random_soup(rng, T, res, **kw)
-    uv = rng.uniform(-1.5, 2.5, (T, 3, 2)).astype(np.float32)        # beyond [0, 1]: the clamp is part of the rule
-    return tri, col, nrm, uv
-
-
-def _filler(H, W, **kw):
-    from cython3dmodelrenderer_amd.pixel_buffer_filler import AdvancedPixelBufferFiller
-    kw.setdefault("track_winner", True)
-    return AdvancedPixelBufferFiller(H, W, fov=45.0, device="cuda:0", **kw)
-
-
-def _frame(oracle, tri, col, nrm, H, W, y0=0, y1=None):
-    ref = oracle.OracleFiller(H, W, fov=45.0)
-    ref.render_arrays(tri, col, nrm, y0=y0, y1=y1)
-    return ref
-
-
-def _host(t):
-    return t.cpu().numpy()
 
 
 def _want(ref, tri, uv, tex, persp=False, **kw):
@@ -64,10 +26,10 @@ def _levels(ref, tri, uv, tex, persp):
 def _check_both_modes(oracle, scene, tex, H, W, what, min_covered=1, check=None, **filler_kw):
     """The trilinear pass, affine and perspective, against the host model; `check(l0, L)` judges the levels."""
     tri, col, nrm, uv = scene
-    ref = _frame(oracle, tri, col, nrm, H, W)
+    ref = oracle_frame(oracle, tri, col, nrm, H, W)
     covered = int((ref.winner >= 0).sum())
     assert covered >= min_covered, (what, covered)
-    f = _filler(H, W, **filler_kw)
+    f = filler(H, W, **filler_kw)
     f.bind_texture(uv, tex, mipmaps=True)
     chain = mip_ref.build_chain(tex)
     for persp in (False, True):
@@ -75,12 +37,9 @@ def _check_both_modes(oracle, scene, tex, H, W, what, min_covered=1, check=None,
         f.texture_pass(perspective=persp, filter="trilinear")
         want = _want(ref, tri, uv, tex, persp, chain=chain)
         assert not np.isnan(want).any(), (what, persp)
-        assert_bit_equal(_host(f.get_color_tensor()), want, f"{what} colour, perspective={persp}")
+        assert_bit_equal(host(f.get_color_tensor()), want, f"{what} colour, perspective={persp}")
         assert (want.view(np.uint32) != ref.color_buffer.view(np.uint32)).any(), (what, "the pass changed nothing")
-        # z, normals and the winner plane are only read
-        assert_bit_equal(_host(f.get_z_tensor()), ref.z_buffer, f"{what} z")
-        assert_bit_equal(_host(f.get_normals_tensor()), ref.normals_buffer, f"{what} normals")
-        assert_bit_equal(_host(f.get_winner_tensor()), ref.winner, f"{what} winner")
+        planes_only_read(f, ref, what)
         if check is not None:
             l0 = _levels(ref, tri, uv, tex, persp)
             print(f"{what}, perspective={persp}: levels {np.bincount(l0, minlength=len(chain)).tolist()}")
@@ -91,8 +50,8 @@ def _check_both_modes(oracle, scene, tex, H, W, what, min_covered=1, check=None,
 @pytest.mark.parametrize("th,tw", SIZES)
 def test_chain_equals_the_host_model(th, tw):
     import torch
-    tex = _texture(th * 1000 + tw, th, tw)
-    f = _filler(16, 16)
+    tex = texture(th * 1000 + tw, th, tw)
+    f = filler(16, 16)
     assert f.mip_levels() is None
     f.bind_texture(np.zeros((1, 3, 2), np.float32), tex, mipmaps=True)
     chain = mip_ref.build_chain(tex)
@@ -100,19 +59,19 @@ def test_chain_equals_the_host_model(th, tw):
     for k, want in enumerate(chain):
         got = f.get_mip_level(k)
         assert got.is_cuda and got.dtype == torch.uint8 and tuple(got.shape) == want.shape
-        assert np.array_equal(_host(got), want), f"{th} x {tw}, level {k}"
-    assert np.array_equal(_host(f._mip[0]), mip_ref.pack_chain(chain))          # packed tightly, in order
+        assert np.array_equal(host(got), want), f"{th} x {tw}, level {k}"
+    assert np.array_equal(host(f._mip[0]), mip_ref.pack_chain(chain))          # packed tightly, in order
     assert f.get_mip_level(0).data_ptr() == f._mip[0].data_ptr()                # a view, not a copy
     uv, image = f._texture                                                      # still the (uv, image) pair
-    assert np.array_equal(_host(image), tex) and tuple(uv.shape) == (1, 3, 2)
+    assert np.array_equal(host(image), tex) and tuple(uv.shape) == (1, 3, 2)
     with pytest.raises(IndexError):
         f.get_mip_level(len(chain))
 
 
 @pytest.mark.parametrize("size", [256, 1024])
 def test_trex_against_the_host_model(oracle, size):
-    tri, col, nrm, uv = _trex()
-    tex = _texture(1, 709, 709)
+    tri, col, nrm, uv = trex_textured()
+    tex = texture(1, 709, 709)
 
     def check(l0, L, want, ref, persp):
         bilinear = tex_ref.texture_pass(ref.color_buffer, ref.winner, tri, ref.proj_mat, uv, tex, perspective=persp,
@@ -127,7 +86,7 @@ def test_trex_against_the_host_model(oracle, size):
 @pytest.mark.parametrize("seed,T,H,W,th,tw", [(31, 4000, 200, 173, 1, 1), (32, 2500, 333, 512, 3, 1000),
                                               (33, 30000, 512, 509, 709, 709), (34, 60, 64, 41, 2, 5)])
 def test_random_soups_with_uv_beyond_the_unit_square(oracle, seed, T, H, W, th, tw):
-    scene = _soup(seed, T, max(H, W), size_px=(1.0, 60.0))
+    scene = soup_textured(seed, T, max(H, W), size_px=(1.0, 60.0))
 
     def check(l0, L, want, ref, persp):
         assert L == len(mip_ref.layout(th, tw)[0])
@@ -138,23 +97,23 @@ def test_random_soups_with_uv_beyond_the_unit_square(oracle, seed, T, H, W, th, 
         if seed == 34:
             assert L == 3                                    # the tiny chain: 2 x 5, 1 x 2, 1 x 1
 
-    _check_both_modes(oracle, scene, _texture(seed, th, tw), H, W, f"soup{seed}", min_covered=H * W // 20, check=check)
+    _check_both_modes(oracle, scene, texture(seed, th, tw), H, W, f"soup{seed}", min_covered=H * W // 20, check=check)
 
 
 def test_presort_gives_the_same_bits(oracle):
-    scene = _soup(41, 20000, 512, size_px=(2.0, 30.0))
-    f = _check_both_modes(oracle, scene, _texture(41, 64, 97), 512, 512, "presorted soup", presort=True)
+    scene = soup_textured(41, 20000, 512, size_px=(2.0, 30.0))
+    f = _check_both_modes(oracle, scene, texture(41, 64, 97), 512, 512, "presorted soup", presort=True)
     assert f._order is not None          # the resident inputs are the tile-coherent copy: the pass went through pos_of
 
 
 def test_fused_light_equals_the_pass_plus_the_illumination(oracle):
-    tri, col, nrm, uv = _trex()
-    tex = _texture(5, 709, 709)
+    tri, col, nrm, uv = trex_textured()
+    tex = texture(5, 709, 709)
     chain = mip_ref.build_chain(tex)
     H = W = 512
-    ref = _frame(oracle, tri, col, nrm, H, W)
+    ref = oracle_frame(oracle, tri, col, nrm, H, W)
     light = [float(v) for v in oracle.guro_light(LIGHT)]
-    f, g = _filler(H, W), _filler(H, W)
+    f, g = filler(H, W), filler(H, W)
     f.bind_texture(uv, tex, mipmaps=True)
     g.bind_texture(uv, tex, mipmaps=True)
     for persp in (False, True):
@@ -164,11 +123,11 @@ def test_fused_light_equals_the_pass_plus_the_illumination(oracle):
         g.texture_pass(perspective=persp, filter="trilinear")
         g.synchronize()
         g.shade_guro(light)
-        got = _host(f.get_color_tensor())
-        assert_bit_equal(got, _host(g.get_color_tensor()), f"fused light vs pass + illumination, {persp}")
+        got = host(f.get_color_tensor())
+        assert_bit_equal(got, host(g.get_color_tensor()), f"fused light vs pass + illumination, {persp}")
         want = _want(ref, tri, uv, tex, persp, chain=chain, normals=ref.normals_buffer, light_direction=LIGHT)
         assert_bit_equal(got, want, f"fused light vs oracle.guro of the host model, {persp}")
-        assert_bit_equal(_host(f.get_normals_tensor()), ref.normals_buffer, "normals")
+        assert_bit_equal(host(f.get_normals_tensor()), ref.normals_buffer, "normals")
     # the background is shaded too: a colour written there beforehand comes out multiplied
     f.render_arrays(tri, col, nrm, clear=True)
     plane = f.get_color_tensor()
@@ -180,19 +139,19 @@ def test_fused_light_equals_the_pass_plus_the_illumination(oracle):
     n = ref.normals_buffer.copy(); n[0, 0, 2] = -2.0
     want = mip_ref.texture_pass(c, ref.winner, tri, ref.proj_mat, uv, tex, chain=chain, normals=n, light_direction=LIGHT)
     assert ref.winner[0, 0] < 0 and want[0, 0, 0] != 0.0 and want[0, 0, 0] != 3.0
-    assert_bit_equal(_host(f.get_color_tensor()), want, "background under the fused light")
+    assert_bit_equal(host(f.get_color_tensor()), want, "background under the fused light")
 
 
 def test_row_strip_leaves_the_other_rows_alone(oracle):
-    tri, col, nrm, uv = _trex()
-    tex = _texture(6, 709, 709)
+    tri, col, nrm, uv = trex_textured()
+    tex = texture(6, 709, 709)
     chain = mip_ref.build_chain(tex)
     H = W = 512
     y0, y1 = 135, 301                    # not multiples of the kernel's 8-row blocks
-    ref = _frame(oracle, tri, col, nrm, H, W, y0=y0, y1=y1)
+    ref = oracle_frame(oracle, tri, col, nrm, H, W, y0=y0, y1=y1)
     light = [float(v) for v in oracle.guro_light(LIGHT)]
     for with_light in (False, True):
-        f = _filler(H, W, row_strip=(y0, y1))
+        f = filler(H, W, row_strip=(y0, y1))
         f.bind_texture(uv, tex, mipmaps=True)
         f.render_arrays(tri, col, nrm, clear=True)
         f.synchronize()
@@ -202,7 +161,7 @@ def test_row_strip_leaves_the_other_rows_alone(oracle):
         f.winner_buffer[:y0] = 0
         f.winner_buffer[y1:] = 1
         f.texture_pass(filter="trilinear", light_direction=light if with_light else None)
-        got = _host(f.get_color_tensor())
+        got = host(f.get_color_tensor())
         assert (got[:y0] == 7.5).all() and (got[y1:] == -2.25).all()
         kw = dict(normals=ref.normals_buffer, light_direction=LIGHT) if with_light else {}
         want = _want(ref, tri, uv, tex, False, chain=chain, y0=y0, y1=y1, **kw)
@@ -210,19 +169,19 @@ def test_row_strip_leaves_the_other_rows_alone(oracle):
 
 
 def test_nan_and_infinite_uv_follow_the_statement(oracle):
-    tri, col, nrm, uv = _soup(12, 1500, 160, size_px=(4.0, 40.0))
+    tri, col, nrm, uv = soup_textured(12, 1500, 160, size_px=(4.0, 40.0))
     rng = np.random.default_rng(12)
     odd = np.float32([np.nan, np.inf, -np.inf, 3e38, -3e38, 2147483648.0, -2147483904.0, 1e-42])
     hit = rng.uniform(size=uv.shape) < 0.15
     uv[hit] = rng.choice(odd, int(hit.sum()))
-    tex = _texture(12, 5, 7)
-    ref = _frame(oracle, tri, col, nrm, 160, 160)
-    f = _filler(160, 160)
+    tex = texture(12, 5, 7)
+    ref = oracle_frame(oracle, tri, col, nrm, 160, 160)
+    f = filler(160, 160)
     f.bind_texture(uv, tex, mipmaps=True)
     for persp in (False, True):
         f.render_arrays(tri, col, nrm, clear=True)
         f.texture_pass(perspective=persp, filter="trilinear")
-        got = _host(f.get_color_tensor())
+        got = host(f.get_color_tensor())
         want = _want(ref, tri, uv, tex, persp)
         # (IEEE 754 leaves the sign and payload of a generated NaN open: x86 and gfx950 differ there)
         nan = np.isnan(want)
@@ -231,49 +190,39 @@ def test_nan_and_infinite_uv_follow_the_statement(oracle):
         assert nan.any() and not nan.all()
 
 
-def _textured_model(seed=8):
-    from cython3dmodelrenderer_amd.data_structures.model import Model
-    tri, col, nrm, uv = _soup(seed, 3000, 256, size_px=(3.0, 50.0))
-    T = len(tri)
-    idx = np.arange(3 * T, dtype=np.int32).reshape(T, 3)
-    tex = _texture(seed, 37, 53)
-    m = Model(tri.reshape(-1, 3), idx, uv.reshape(-1, 2), idx, tex, nrm.reshape(-1, 3), idx, recalculate_normals=False)
-    return m, tex
-
-
 @pytest.mark.parametrize("on_device", [None, False, True, "fused"])
 def test_renderer_under_every_on_device(oracle, on_device):
     from cython3dmodelrenderer_amd.illumination.guro_illumination import GuroIllumination
     from cython3dmodelrenderer_amd.renderer import Renderer
-    m, tex = _textured_model()
+    m, tex = textured_model()
     tri, col, nrm = m._vertices_by_triangles, m._colors_by_triangles, m._normals_by_triangles
     uv = m.get_texture_coords_by_triangles()
     H = W = 256
-    ref = _frame(oracle, tri, col, nrm, H, W)
+    ref = oracle_frame(oracle, tri, col, nrm, H, W)
     assert int((ref.winner >= 0).sum()) > 10000
     want = _want(ref, tri, uv, tex, True, normals=ref.normals_buffer, light_direction=LIGHT)
     bilinear = tex_ref.texture_pass(ref.color_buffer, ref.winner, tri, ref.proj_mat, uv, tex, perspective=True,
                                     bilinear_filter=True, normals=ref.normals_buffer, light_direction=LIGHT)
     assert (want != bilinear).any()
-    f = _filler(H, W)
+    f = filler(H, W)
     binds = []
     bind = f.bind_texture
     f.bind_texture = lambda *a, **kw: (binds.append(kw), bind(*a, **kw))[1]
     r = Renderer(f, GuroIllumination(LIGHT), on_device=on_device, texture_pass={"filter": "trilinear", "perspective": True})
     for _ in range(2):                             # every frame starts from cleared buffers: the same image twice
         out = r.render(m)
-        got = _host(out) if on_device in (True, "fused") else np.array(out)
+        got = host(out) if on_device in (True, "fused") else np.array(out)
         assert_bit_equal(got, want, f"Renderer(on_device={on_device!r})")
     assert binds == [{"mipmaps": True}]            # the texture went up once per model, with its chain
     assert f.mip_levels() == mip_ref.layout(37, 53)[0]
-    assert_bit_equal(_host(f.get_normals_tensor()), ref.normals_buffer, "normals")
+    assert_bit_equal(host(f.get_normals_tensor()), ref.normals_buffer, "normals")
 
 
 def test_errors_name_their_cause(oracle):
     from cython3dmodelrenderer_amd import _capi
-    tri, col, nrm, uv = _soup(13, 300, 64)
-    tex = _texture(13, 8, 8)
-    f = _filler(64, 64)
+    tri, col, nrm, uv = soup_textured(13, 300, 64)
+    tex = texture(13, 8, 8)
+    f = filler(64, 64)
     f.bind_texture(uv, tex, mipmaps=True)
     assert f.mip_levels() == [(8, 8), (4, 4), (2, 2), (1, 1)]
     f.render_arrays(tri, col, nrm, clear=True)
@@ -301,7 +250,7 @@ def test_errors_name_their_cause(oracle):
         f.texture_pass(filter="trilinear")
     with pytest.raises(ValueError, match="filter"):
         f.texture_pass(filter="anisotropic")
-    chain = _filler(64, 64, pipeline=True)
+    chain = filler(64, 64, pipeline=True)
     chain.bind_texture(uv, tex, mipmaps=True)
     with pytest.raises(ValueError, match="swap chain"):
         chain.texture_pass(filter="trilinear")

@@ -23,6 +23,7 @@ import pass_edges as E
 import phong_ref
 import shadow_ref
 import tex_ref
+from pass_scenes import lib, light3, stream  # noqa: F401 (lib is a fixture)
 from util import assert_bit_equal
 
 pytestmark = pytest.mark.gpu
@@ -68,24 +69,11 @@ class _Texture:
         self.chain = mip_ref.build_chain(tex)
         self.d_tex = _dev(tex)
         self.d_chain = torch.empty(mip_ref.layout(self.th, self.tw)[2], dtype=torch.uint8, device="cuda")
-        _capi.check(lib.crender_mip_build(self.d_tex.data_ptr(), self.th, self.tw, self.d_chain.data_ptr(), _stream()),
+        _capi.check(lib.crender_mip_build(self.d_tex.data_ptr(), self.th, self.tw, self.d_chain.data_ptr(), stream()),
                     "crender_mip_build")
 
 
-def _stream():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 SHAPES = {"1x1": (1, 1), "3x1000": (3, 1000), "64x97": (64, 97), "1x65535": (1, 65535), "40000x2": (40000, 2)}
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import torch                     # (before the library: the two then share one HIP runtime, torch's)
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    from cython3dmodelrenderer_amd import _capi
-    return _capi.load()
 
 
 @pytest.fixture(scope="module")
@@ -109,10 +97,6 @@ def tall(oracle):
     return _Device(E.tall_scene())
 
 
-def _light3(oracle):
-    return (C.c_float * 3)(*[float(v) for v in oracle.guro_light(E.LIGHT)])
-
-
 def _texture_family(lib, oracle, D, kind, tx, persp, light, y0=0, y1=None, pos_of=False, bilinear=False, A=1):
     """(got, want): one call of a texture entry on a fresh copy of the scene's colour plane, and the host model's answer."""
     from cython3dmodelrenderer_amd import _capi
@@ -121,20 +105,20 @@ def _texture_family(lib, oracle, D, kind, tx, persp, light, y0=0, y1=None, pos_o
     color = _dev(s.color)
     head = (D.winner.data_ptr(), (D.moved if pos_of else D.tri).data_ptr(), s.T, D.pos_of.data_ptr() if pos_of else None,
             _capi.f32_16(E.P), D.uv.data_ptr())
-    tail = (D.normals.data_ptr() if light else None, _light3(oracle) if light else None, color.data_ptr(), s.H, s.W, y0, y1)
+    tail = (D.normals.data_ptr() if light else None, light3(oracle) if light else None, color.data_ptr(), s.H, s.W, y0, y1)
     winner = s.winner_without_gone if pos_of else s.winner
     lit = dict(normals=s.normals, light_direction=E.LIGHT) if light else {}
     if kind == "tex":
         flags = (_capi.TEX_PERSPECTIVE if persp else 0) | (_capi.TEX_BILINEAR if bilinear else 0)
-        _capi.check(lib.crender_tex_shade(*head, tx.d_tex.data_ptr(), tx.th, tx.tw, *tail, flags, _stream()), "crender_tex_shade")
+        _capi.check(lib.crender_tex_shade(*head, tx.d_tex.data_ptr(), tx.th, tx.tw, *tail, flags, stream()), "crender_tex_shade")
         want = tex_ref.texture_pass(s.color, winner, s.tri, E.P, s.uv, tx.tex, persp, bilinear, y0=y0, y1=y1, **lit)
     elif kind == "mip":
         _capi.check(lib.crender_mip_shade(*head, tx.d_chain.data_ptr(), tx.th, tx.tw, *tail, _capi.MIP_PERSPECTIVE if persp else 0,
-                                          _stream()), "crender_mip_shade")
+                                          stream()), "crender_mip_shade")
         want = mip_ref.texture_pass(s.color, winner, s.tri, E.P, s.uv, None, persp, y0=y0, y1=y1, chain=tx.chain, **lit)
     else:
         _capi.check(lib.crender_aniso_shade(*head, tx.d_chain.data_ptr(), tx.th, tx.tw, *tail, _capi.MIP_PERSPECTIVE if persp else 0,
-                                            A, _stream()), "crender_aniso_shade")
+                                            A, stream()), "crender_aniso_shade")
         want = aniso_ref.texture_pass(s.color, winner, s.tri, E.P, s.uv, None, persp, A, y0=y0, y1=y1, chain=tx.chain, **lit)
     return color.cpu().numpy(), want
 
@@ -208,7 +192,7 @@ def _shadow(lib, D, K, use_winner, y0=0, y1=None, pos_of=False, ambient=AMBIENT)
     _capi.check(lib.crender_shadow_shade(
         D.winner.data_ptr(), (D.moved if pos_of else D.tri).data_ptr(), s.T, D.pos_of.data_ptr() if pos_of else None,
         _capi.f32_16(E.P), D.ltri.data_ptr(), _capi.f32_16(E.P), D.lz.data_ptr(), D.lwinner.data_ptr() if use_winner else None,
-        Hl, Wl, E.BIAS, ambient, K, color.data_ptr(), s.H, s.W, y0, y1, 0, _stream()), "crender_shadow_shade")
+        Hl, Wl, E.BIAS, ambient, K, color.data_ptr(), s.H, s.W, y0, y1, 0, stream()), "crender_shadow_shade")
     want = shadow_ref.shadow_pass(s.color, s.winner_without_gone if pos_of else s.winner, s.tri, E.P, s.ltri, E.P, s.lz,
                                   s.lwinner if use_winner else None, bias=E.BIAS, ambient=ambient, pcf=K, y0=y0, y1=y1)
     return color.cpu().numpy(), want
@@ -248,7 +232,7 @@ def _phong(lib, D, lights, shininess=32, y0=0, y1=None, pos_of=False, ambient=AM
     _capi.check(lib.crender_phong_shade(
         D.winner.data_ptr(), (D.moved if pos_of else D.tri).data_ptr(), s.T, D.pos_of.data_ptr() if pos_of else None,
         _capi.f32_16(E.P), D.normals.data_ptr(), (C.c_float * L5.size)(*L5.reshape(-1).tolist()), len(lights), mask, ambient,
-        int(shininess).bit_length() - 1, (C.c_float * 3)(*spec), clamp, color.data_ptr(), s.H, s.W, y0, y1, 0, _stream()),
+        int(shininess).bit_length() - 1, (C.c_float * 3)(*spec), clamp, color.data_ptr(), s.H, s.W, y0, y1, 0, stream()),
         "crender_phong_shade")
     want = phong_ref.phong_pass(s.color, s.winner_without_gone if pos_of else s.winner, s.tri, E.P, s.normals, lights,
                                 ambient=ambient, shininess=shininess, specular_color=spec, clamp=clamp, y0=y0, y1=y1)
@@ -298,7 +282,7 @@ def _ao(lib, D, table, face, rotate, radius_px, radius, y0=0, y1=None, pos_of=Fa
     _capi.check(lib.crender_ao_shade(
         D.winner.data_ptr(), D.z.data_ptr(), (D.moved if pos_of else D.tri).data_ptr(), s.T,
         D.pos_of.data_ptr() if pos_of else None, _capi.f32_16(E.P), D.normals.data_ptr(), taps2, len(table), radius_px, radius,
-        0.1, strength, floor, color.data_ptr(), s.H, s.W, y0, y1, flags, _stream()), "crender_ao_shade")
+        0.1, strength, floor, color.data_ptr(), s.H, s.W, y0, y1, flags, stream()), "crender_ao_shade")
     model_pos_of = pos_of if want_pos_of is None else want_pos_of
     counts = {}
     want = ao_ref.ao_pass(s.color, s.z, s.winner, s.moved if model_pos_of else s.tri, E.P, s.normals, table, radius=radius,
@@ -375,14 +359,14 @@ def _wire(lib, D, outline, fill=None, masked=False, y0=0, y1=None, pos_of=False,
     kw = dict(width=width, line=LINE, feather=feather, opacity=opacity, fill=fill, edges=s.edges if masked else None, y0=y0, y1=y1)
     if outline:
         _capi.check(lib.crender_wire_outline(D.winner.data_ptr(), D.z.data_ptr(), *head, depth_bias, radius_px,
-                                             color.data_ptr(), s.H, s.W, y0, y1, 0, _stream()), "crender_wire_outline")
+                                             color.data_ptr(), s.H, s.W, y0, y1, 0, stream()), "crender_wire_outline")
         key = (id(s), masked, pos_of, radius_px, depth_bias, y0, y1)
         if key not in _FIELDS:
             _FIELDS[key] = outline_ref.distances(winner, s.z, s.tri, E.P, kw["edges"], radius_px, depth_bias, y0, y1)
         want = outline_ref.wire_pass(s.color, winner, s.z, s.tri, E.P, depth_bias=depth_bias, radius_px=radius_px,
                                      field=_FIELDS[key], **kw)
     else:
-        _capi.check(lib.crender_wire_overlay(D.winner.data_ptr(), *head, color.data_ptr(), s.H, s.W, y0, y1, 0, _stream()),
+        _capi.check(lib.crender_wire_overlay(D.winner.data_ptr(), *head, color.data_ptr(), s.H, s.W, y0, y1, 0, stream()),
                     "crender_wire_overlay")
         want = overlay_ref.wire_pass(s.color, winner, s.tri, E.P, **kw)
     assert not np.isnan(want).any()

@@ -11,19 +11,13 @@ import numpy as np
 import pytest
 
 import phong_ref
+from pass_scenes import Frame, capi, trex_fixture  # noqa: F401 (fixtures)
 from util import assert_bit_equal, other_symbols, unit_inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GURO = (0.3, -0.2, 1.0)              # what GuroIllumination is constructed with
 POINT = (-0.8, -0.5, -0.2)           # a point light up and to the left of the camera, a little behind it
 SECOND = (1.5, -2.0, -0.5)           # and one far to the right: a third of the model faces away from it
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from cython3dmodelrenderer_amd import _build, _capi
-    _build.build()           # hipcc cross-compiles for gfx950 without a GPU
-    return _capi
 
 
 # ---- the host side of the ABI ----------------------------------------------------------------------------------
@@ -134,24 +128,13 @@ def test_phong_argument_errors_without_a_gpu(capi):
 
 # ---- the model on the oracle's frame of T-Rex ------------------------------------------------------------------
 
-class _Frame:
-    def __init__(self, oracle):
-        from cython3dmodelrenderer_amd import scenes
-        self.tri, self.col, self.nrm = scenes.load_fixture("trex_inputs.npz")
-        self.cam = oracle.OracleFiller(256, 256, fov=45.0)
-        self.cam.render_arrays(self.tri, self.col, self.nrm)
-        self.covered = self.cam.winner >= 0
-
+class _Frame(Frame):
     def run(self, lights, **kw):
         return phong_ref.phong_pass(self.cam.color_buffer, self.cam.winner, self.tri, self.cam.proj_mat,
                                     self.cam.normals_buffer, lights, **kw)
 
 
-@pytest.fixture(scope="module")
-def trex(oracle):
-    f = _Frame(oracle)
-    assert int(f.covered.sum()) == 15801
-    return f
+trex = trex_fixture(_Frame)
 
 
 def _point(pos=POINT, kd=0.9, ks=0.5):

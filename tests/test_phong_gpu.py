@@ -9,12 +9,11 @@ import pytest
 
 import phong_ref
 import shadow_ref
+from pass_scenes import GOLDEN, Scene, filler, host, soup_fixture, trex_arrays, trex_fixture
 from util import assert_bit_equal, random_soup
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 GURO = (0.3, -0.2, 1.0)              # what GuroIllumination is constructed with
 POINT = (-0.8, -0.5, -0.2)
 SECOND = (1.5, -2.0, -0.5)
@@ -25,59 +24,25 @@ FOUR = [dict(position=POINT, diffuse=0.6, specular=0.5), dict(direction=GURO, di
 LIGHTS = {"point": ONE_POINT, "direction": ONE_DIRECTION, "four": FOUR}
 
 
-def _filler(H, W, fov=45.0, **kw):
-    from cython3dmodelrenderer_amd.pixel_buffer_filler import AdvancedPixelBufferFiller
-    kw.setdefault("track_winner", True)
-    return AdvancedPixelBufferFiller(H, W, fov=fov, device="cuda:0", **kw)
-
-
-def _host(t):
-    return t.cpu().numpy()
-
-
-class _Scene:
-    """A model and the oracle's frame of it: computed once, only read afterwards."""
-
-    def __init__(self, oracle, arrays, H, W, y0=0, y1=None):
-        self.tri, self.col, self.nrm = arrays
-        self.H, self.W = H, W
-        self.cam = oracle.OracleFiller(H, W, fov=45.0)
-        self.cam.render_arrays(self.tri, self.col, self.nrm, y0=y0, y1=y1)
-        self.covered = int((self.cam.winner >= 0).sum())
-
+class _Scene(Scene):
     def want(self, lights, color=None, **kw):
         out = phong_ref.phong_pass(self.cam.color_buffer if color is None else color, self.cam.winner, self.tri,
                                    self.cam.proj_mat, self.cam.normals_buffer, lights, **kw)
         assert not np.isnan(out).any()
         return out
 
-    def draw(self, f):
-        f.render_arrays(self.tri, self.col, self.nrm, clear=True)
-
-    def check_planes(self, f, what):
-        """z, normals and the winner plane are only read."""
-        assert_bit_equal(_host(f.get_z_tensor()), self.cam.z_buffer, f"{what}: z")
-        assert_bit_equal(_host(f.get_normals_tensor()), self.cam.normals_buffer, f"{what}: normals")
-        assert_bit_equal(_host(f.get_winner_tensor()), self.cam.winner, f"{what}: winner")
-
     def check(self, f, lights, what, **kw):
         self.draw(f)
         f.phong_pass(lights, **kw)
         want = self.want(lights, **kw)
-        assert (want.view(np.uint32) != self.cam.color_buffer.view(np.uint32)).any(), (what, "the pass changed nothing")
-        assert_bit_equal(_host(f.get_color_tensor()), want, f"{what} colour")
+        self.assert_changed(want, what)
+        assert_bit_equal(host(f.get_color_tensor()), want, f"{what} colour")
         self.check_planes(f, what)
         return want
 
 
-def _trex_arrays():
-    from cython3dmodelrenderer_amd import scenes
-    return scenes.load_fixture("trex_inputs.npz")
-
-
-@pytest.fixture(scope="module")
-def trex256(oracle):
-    return _Scene(oracle, _trex_arrays(), 256, 256)
+trex256 = trex_fixture(_Scene)
+soup256 = soup_fixture(_Scene)
 
 
 # ---- 1. T-Rex ------------------------------------------------------------------------------------------------------
@@ -87,12 +52,12 @@ def trex256(oracle):
 def test_trex_every_instance(trex256, kind, shininess):
     s = trex256
     assert s.covered == 15801
-    s.check(_filler(256, 256), LIGHTS[kind], f"trex256, {kind}, shininess {shininess}", shininess=shininess)
+    s.check(filler(256, 256), LIGHTS[kind], f"trex256, {kind}, shininess {shininess}", shininess=shininess)
 
 
 def test_trex_other_coefficients(trex256):
     s = trex256
-    f = _filler(256, 256)
+    f = filler(256, 256)
     s.check(f, ONE_POINT + [dict(position=SECOND, diffuse=0.9, specular=0.5)], "two points, no clamp",
             ambient=0.0, shininess=128, specular_color=(3.0, 200.0, 17.5), clamp=float("inf"))
     s.check(f, ONE_POINT, "clamp 100", ambient=0.25, shininess=2, clamp=100.0)
@@ -100,10 +65,10 @@ def test_trex_other_coefficients(trex256):
 
 def test_one_directional_diffuse_light_is_guro(oracle, trex256):
     s = trex256
-    f = _filler(256, 256)
+    f = filler(256, 256)
     s.draw(f)
     f.phong_pass([dict(direction=GURO, diffuse=1.0, specular=0.0)], ambient=0.0, clamp=float("inf"))
-    got = _host(f.get_color_tensor())
+    got = host(f.get_color_tensor())
     want = oracle.guro(s.cam.color_buffer.copy(), s.cam.normals_buffer, GURO)
     covered = s.cam.winner >= 0
     assert np.array_equal(got[covered], want[covered])                       # as values: -0 against +0 is allowed
@@ -114,8 +79,8 @@ def test_one_directional_diffuse_light_is_guro(oracle, trex256):
 
 def test_a_row_strip_of_an_odd_frame_leaves_the_other_rows_alone(oracle):
     y0, y1 = 40, 136
-    s = _Scene(oracle, _trex_arrays(), 200, 173, y0=y0, y1=y1)
-    f = _filler(200, 173, row_strip=(y0, y1))
+    s = _Scene(oracle, trex_arrays(), 200, 173, y0=y0, y1=y1)
+    f = filler(200, 173, row_strip=(y0, y1))
     for kind in ("point", "four"):
         s.draw(f)
         f.synchronize()
@@ -125,7 +90,7 @@ def test_a_row_strip_of_an_odd_frame_leaves_the_other_rows_alone(oracle):
         f.winner_buffer[:y0] = 0
         f.winner_buffer[y1:] = 1
         f.phong_pass(LIGHTS[kind])
-        got = _host(f.get_color_tensor())
+        got = host(f.get_color_tensor())
         assert (got[:y0] == 7.5).all() and (got[y1:] == -2.25).all()
         want = s.want(LIGHTS[kind], y0=y0, y1=y1)
         assert (want[y0:y1].view(np.uint32) != s.cam.color_buffer[y0:y1].view(np.uint32)).any()
@@ -155,7 +120,7 @@ def test_random_soups(oracle, seed, T, H, W, kw, presort, counts):
     assert (got["covered"], [(l["lit"], l["unlit"]) for l in got["lights"]]) == counts
     for l in got["lights"]:
         assert min(l["lit"], l["unlit"]) >= 0.02 * got["covered"]
-    f = _filler(H, W, presort=presort)
+    f = filler(H, W, presort=presort)
     s.check(f, SOUP_LIGHTS, f"soup{seed}")
     s.check(f, SOUP_LIGHTS[:1], f"soup{seed}, one light", shininess=4)
     if presort:
@@ -177,7 +142,7 @@ def _shade(lib, winner, tri, P, normal, lights, color, ambient=0.1, shininess=32
         normal.data_ptr(), (C.c_float * L5.size)(*L5.reshape(-1).tolist()), len(lights), mask, ambient,
         int(shininess).bit_length() - 1, (C.c_float * 3)(*spec), clamp, color.data_ptr(), H, W, 0, H, 0, st),
         "crender_phong_shade")
-    return _host(color)
+    return host(color)
 
 
 def test_special_values_through_the_c_entry(oracle):
@@ -262,40 +227,23 @@ def test_numpy_torch_and_device_model_inputs_agree(oracle):
     tri, col, nrm = m._vertices_by_triangles, m._colors_by_triangles, m._normals_by_triangles
     s = _Scene(oracle, (tri, col, nrm), 256, 256)
     want = s.want(FOUR)
-    f = _filler(256, 256)                          # numpy
+    f = filler(256, 256)                          # numpy
     s.draw(f)
     f.phong_pass(FOUR)
-    assert_bit_equal(_host(f.get_color_tensor()), want, "numpy inputs")
-    f = _filler(256, 256)                          # caller's device tensors
+    assert_bit_equal(host(f.get_color_tensor()), want, "numpy inputs")
+    f = filler(256, 256)                          # caller's device tensors
     f.render_arrays(*[torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (tri, col, nrm)], clear=True)
     f.phong_pass(FOUR)
-    assert_bit_equal(_host(f.get_color_tensor()), want, "torch inputs")
-    f = _filler(256, 256)                          # the device-resident model
+    assert_bit_equal(host(f.get_color_tensor()), want, "torch inputs")
+    f = filler(256, 256)                          # the device-resident model
     f.render_model(DeviceModel(m), clear=True)
     f.phong_pass(FOUR)
-    assert_bit_equal(_host(f.get_color_tensor()), want, "DeviceModel inputs")
-
-
-class _Soup:
-    """What a filler reads off a model."""
-
-    def __init__(self, seed=71, T=3000, res=256):
-        self._vertices_by_triangles, self._colors_by_triangles, self._normals_by_triangles = \
-            random_soup(np.random.default_rng(seed), T, res, size_px=(3.0, 50.0))
-
-
-@pytest.fixture(scope="module")
-def soup256(oracle):
-    m = _Soup()
-    s = _Scene(oracle, (m._vertices_by_triangles, m._colors_by_triangles, m._normals_by_triangles), 256, 256)
-    s.model = m
-    assert s.covered > 10000
-    return s
+    assert_bit_equal(host(f.get_color_tensor()), want, "DeviceModel inputs")
 
 
 def test_host_views_show_the_lit_colours_at_the_next_getter_call(soup256):
     s = soup256
-    f = _filler(256, 256)
+    f = filler(256, 256)
     s.draw(f)
     view = f.get_color_buffer()
     assert_bit_equal(view, s.cam.color_buffer, "before the pass")
@@ -329,17 +277,17 @@ def test_renderer_renders_the_same_image_twice(soup256, on_device):
     from cython3dmodelrenderer_amd.renderer import Renderer
     s = soup256
     want = s.want(SOUP_LIGHTS, **PHONG_KW)
-    f = _filler(256, 256)
+    f = filler(256, 256)
     r = Renderer(f, _phong(), on_device=on_device)
     for _ in range(2):                             # every frame starts from cleared buffers
         out = r.render(s.model)
         assert isinstance(out, np.ndarray) == (on_device is None)
-        assert_bit_equal(np.array(out) if on_device is None else _host(out), want, f"Renderer(on_device={on_device!r})")
+        assert_bit_equal(np.array(out) if on_device is None else host(out), want, f"Renderer(on_device={on_device!r})")
     s.check_planes(f, "after Renderer")
     # one light through position=
     from cython3dmodelrenderer_amd.illumination import PhongIllumination
     out = Renderer(f, PhongIllumination(position=POINT), on_device=True).render(s.model)
-    assert_bit_equal(_host(out), s.want(ONE_POINT), "PhongIllumination(position=...)")
+    assert_bit_equal(host(out), s.want(ONE_POINT), "PhongIllumination(position=...)")
 
 
 def test_renderer_with_a_texture_pass(soup256):
@@ -354,13 +302,13 @@ def test_renderer_with_a_texture_pass(soup256):
     m = Model(s.tri.reshape(-1, 3), idx, uv.reshape(-1, 2), idx, tex, s.nrm.reshape(-1, 3), idx, recalculate_normals=False)
     assert_bit_equal(m._vertices_by_triangles, s.tri, "the model's triangles")
     assert_bit_equal(m._normals_by_triangles, s.nrm, "the model's normals")
-    f = _filler(256, 256)
-    got = _host(Renderer(f, _phong(), on_device=True, texture_pass={"perspective": True}).render(m))
-    a = _filler(256, 256)
+    f = filler(256, 256)
+    got = host(Renderer(f, _phong(), on_device=True, texture_pass={"perspective": True}).render(m))
+    a = filler(256, 256)
     a.bind_texture(m.get_texture_coords_by_triangles(), tex)
     a.render_model(m, clear=True)
     a.texture_pass(perspective=True)
-    textured = _host(a.get_color_tensor())
+    textured = host(a.get_color_tensor())
     assert (textured != s.cam.color_buffer).any()
     assert_bit_equal(got, s.want(SOUP_LIGHTS, color=textured, **PHONG_KW), "the texture unlit, then the light")
 
@@ -380,34 +328,34 @@ def test_renderer_casts_the_shadow_after_the_light(oracle, soup256):
     want = shadowed(s.want(SOUP_LIGHTS, **PHONG_KW))
     other = s.want(SOUP_LIGHTS, color=shadowed(s.cam.color_buffer), **PHONG_KW)
     assert (want != other).any()                   # the two orders differ on this scene: the test can tell them apart
-    f, g = _filler(256, 256), _filler(128, 160)
+    f, g = filler(256, 256), filler(128, 160)
     r = Renderer(f, _phong(), on_device=True, shadow=dict(filler=g, R=R, t=t, bias=2e-3, pcf=3, ambient=0.125))
-    got = _host(r.render(s.model))
+    got = host(r.render(s.model))
     assert_bit_equal(got, want, "Renderer(PhongIllumination, shadow=...)")
     # and by hand
-    a, b = _filler(256, 256), _filler(128, 160)
+    a, b = filler(256, 256), filler(128, 160)
     s.draw(a)
     b.render_arrays(ltri, s.col, lnrm, clear=True)
     a.bind_shadow_map(b, ltri)
     a.phong_pass(SOUP_LIGHTS, **PHONG_KW)
     a.shadow_pass(bias=2e-3, pcf=3, ambient=0.125)
-    assert_bit_equal(got, _host(a.get_color_tensor()), "phong_pass, then shadow_pass")
+    assert_bit_equal(got, host(a.get_color_tensor()), "phong_pass, then shadow_pass")
 
 
 @pytest.mark.parametrize("on_device", [None, True])
 def test_renderer_with_supersampling(soup256, on_device):
     from cython3dmodelrenderer_amd.renderer import Renderer
     s = soup256
-    f = _filler(256, 256)
+    f = filler(256, 256)
     out = Renderer(f, _phong(), None, 128, 128, on_device=on_device, supersample=2).render(s.model)
     assert isinstance(out, np.ndarray) == (on_device is None)
-    got = out if on_device is None else _host(out)
+    got = out if on_device is None else host(out)
     assert got.shape == (128, 128, 3)
-    a = _filler(256, 256)
+    a = filler(256, 256)
     s.draw(a)
     a.phong_pass(SOUP_LIGHTS, **PHONG_KW)
-    assert_bit_equal(_host(a.get_color_tensor()), s.want(SOUP_LIGHTS, **PHONG_KW), "the supersampled frame, lit")
-    assert_bit_equal(got, _host(a.resolve(2)), "Renderer(supersample=2)")
+    assert_bit_equal(host(a.get_color_tensor()), s.want(SOUP_LIGHTS, **PHONG_KW), "the supersampled frame, lit")
+    assert_bit_equal(got, host(a.resolve(2)), "Renderer(supersample=2)")
 
 
 # ---- 7. errors -----------------------------------------------------------------------------------------------------
@@ -415,11 +363,11 @@ def test_renderer_with_supersampling(soup256, on_device):
 def test_errors_name_their_cause(soup256):
     from cython3dmodelrenderer_amd import _capi
     s = soup256
-    f = _filler(256, 256, track_winner=False)
+    f = filler(256, 256, track_winner=False)
     s.draw(f)
     with pytest.raises(ValueError, match="winner plane"):
         f.phong_pass(ONE_POINT)
-    f = _filler(256, 256)
+    f = filler(256, 256)
     with pytest.raises(ValueError, match="no frame has been rendered"):
         f.phong_pass(ONE_POINT)
     s.draw(f)
@@ -427,7 +375,7 @@ def test_errors_name_their_cause(soup256):
     with pytest.raises(ValueError, match="did not start from cleared buffers"):
         f.phong_pass(ONE_POINT)
     with pytest.raises(ValueError, match="swap chain"):
-        _filler(64, 64, pipeline=True).phong_pass(ONE_POINT)
+        filler(64, 64, pipeline=True).phong_pass(ONE_POINT)
     s.draw(f)
     with pytest.raises(ValueError, match="1 to 4 dicts, got 0"):
         f.phong_pass([])
@@ -443,9 +391,9 @@ def test_errors_name_their_cause(soup256):
         f.phong_pass(ONE_POINT, ambient=float("nan"))
     with pytest.raises(_capi.CrenderError, match="negative"):
         f.phong_pass([dict(position=POINT, diffuse=-1.0, specular=0.0)])
-    assert_bit_equal(_host(f.get_color_tensor()), s.cam.color_buffer, "nothing was written")
+    assert_bit_equal(host(f.get_color_tensor()), s.cam.color_buffer, "nothing was written")
     f.phong_pass(ONE_POINT)                        # and works again
-    assert_bit_equal(_host(f.get_color_tensor()), s.want(ONE_POINT), "after the errors")
+    assert_bit_equal(host(f.get_color_tensor()), s.want(ONE_POINT), "after the errors")
 
 
 # ---- 8. bin overflow -----------------------------------------------------------------------------------------------
@@ -456,11 +404,11 @@ def test_a_frame_redrawn_after_a_bin_overflow_ends_lit(oracle):
     s = _Scene(oracle, random_soup(np.random.default_rng(21), 400, 512, size_px=(150, 400), frac_backface=0.0), 512, 512)
     want = s.want(SOUP_LIGHTS)
     for kw in (dict(), dict(presort=True)):
-        f = _filler(512, 512, tile=32, bin_capacity=500, direct_bins=False, **kw)
+        f = filler(512, 512, tile=32, bin_capacity=500, direct_bins=False, **kw)
         s.draw(f)
         need, cap = f.bin_usage()
         assert cap == 500 and need > cap and len(f._pending) == 1     # dropped fragments, nobody has looked yet
         f.phong_pass(SOUP_LIGHTS)
         assert not f._pending                                          # grown and redone before the pass
-        assert_bit_equal(_host(f.get_color_tensor()), want, f"a redone frame, {kw}")
+        assert_bit_equal(host(f.get_color_tensor()), want, f"a redone frame, {kw}")
         s.check_planes(f, "a redone frame")

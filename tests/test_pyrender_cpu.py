@@ -1,7 +1,6 @@
 """The numpy path on the host: the key rule, the BLAS orders it relies on, the random stream, the
 iterators, the host filler and Renderer against the reference's fixtures (scripts/make_py_golden.py),
 the vectorised model tests/py_ref.py, Buffer and the uint8 Guro."""
-import hashlib
 import json
 import os
 
@@ -16,28 +15,13 @@ from cython3dmodelrenderer_amd.triangle_iterator import DepthIterator, SimpleIte
 from cython3dmodelrenderer_amd import scenes
 
 import py_ref
+from pass_scenes import TriangleModel as Soup
+from util import sha
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 with open(os.path.join(GOLDEN, "py_golden.json")) as _fh:
     DOC = json.load(_fh)
 SOUPS = np.load(os.path.join(GOLDEN, "py_soups.npz"))
-
-
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
-
-
-class Soup:
-    def __init__(self, tri, col, nrm):
-        self._vertices_by_triangles, self._colors_by_triangles, self._normals_by_triangles = tri, col, nrm
-
-    def n_triangles(self):
-        return len(self._vertices_by_triangles)
-
-    def get_triangle(self, i):
-        return (self._vertices_by_triangles[i],
-                None if self._colors_by_triangles is None else self._colors_by_triangles[i],
-                self._normals_by_triangles[i])
 
 
 def soup(s):

@@ -2,7 +2,6 @@
 the C ABI, random near-tie soups and T-Rex at 4096^2 against tests/py_ref.py, culls, single-pixel
 triangles, custom iterators and fillers, the device Guro and the domain errors."""
 import ctypes as C
-import hashlib
 import json
 import os
 
@@ -17,6 +16,8 @@ from cython3dmodelrenderer_amd.py.pixel_buffer_filler import AdvancedPixelBuffer
 from cython3dmodelrenderer_amd.triangle_iterator import DepthIterator, SimpleIterator, TriangleIterator
 
 import py_ref
+from pass_scenes import TriangleModel as Soup
+from util import sha
 
 pytestmark = pytest.mark.gpu
 
@@ -25,23 +26,6 @@ with open(os.path.join(GOLDEN, "py_golden.json")) as _fh:
     DOC = json.load(_fh)
 SOUPS = np.load(os.path.join(GOLDEN, "py_soups.npz"))
 ITERS = {"simple": SimpleIterator, "depth": DepthIterator}
-
-
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
-
-
-class Soup:
-    def __init__(self, tri, col, nrm):
-        self._vertices_by_triangles, self._colors_by_triangles, self._normals_by_triangles = tri, col, nrm
-
-    def n_triangles(self):
-        return len(self._vertices_by_triangles)
-
-    def get_triangle(self, i):
-        return (self._vertices_by_triangles[i],
-                None if self._colors_by_triangles is None else self._colors_by_triangles[i],
-                self._normals_by_triangles[i])
 
 
 def renderer(h, w, it, fov, light=False):

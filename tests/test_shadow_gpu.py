@@ -8,41 +8,27 @@ import numpy as np
 import pytest
 
 import shadow_ref
+from pass_scenes import GOLDEN, Scene, Soup, filler, host, planes_only_read, trex_arrays
 from util import assert_bit_equal, random_soup
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 EVERY = [(K, w) for K in (1, 3, 5) for w in (False, True)]
 LIGHT = (0.3, -0.2, 1.0)             # what GuroIllumination is constructed with
 BIAS, AMBIENT = 1e-3, 0.25
 
 
-def _filler(H, W, fov=45.0, **kw):
-    from cython3dmodelrenderer_amd.pixel_buffer_filler import AdvancedPixelBufferFiller
-    kw.setdefault("track_winner", True)
-    return AdvancedPixelBufferFiller(H, W, fov=fov, device="cuda:0", **kw)
-
-
-def _host(t):
-    return t.cpu().numpy()
-
-
-class _Scene:
+class _Scene(Scene):
     """A model, its light-frame arrays and the oracle's two frames of it: computed once, only read afterwards."""
 
     def __init__(self, oracle, arrays, H, W, Hl, Wl, R, t, light_fov=45.0, y0=0, y1=None):
         from cython3dmodelrenderer_amd import shadow
-        self.tri, self.col, self.nrm = arrays
-        self.H, self.W, self.Hl, self.Wl, self.light_fov = H, W, Hl, Wl, light_fov
+        super().__init__(oracle, arrays, H, W, y0, y1)
+        self.Hl, self.Wl, self.light_fov = Hl, Wl, light_fov
         self.R, self.t = R, t
         self.ltri, self.lnrm = shadow.light_arrays(self.tri, self.nrm, R, t)
-        self.cam = oracle.OracleFiller(H, W, fov=45.0)
-        self.cam.render_arrays(self.tri, self.col, self.nrm, y0=y0, y1=y1)
         self.lig = oracle.OracleFiller(Hl, Wl, fov=light_fov)
         self.lig.render_arrays(self.ltri, self.col, self.lnrm)
-        self.covered = int((self.cam.winner >= 0).sum())
 
     def want(self, K=1, use_winner=True, bias=BIAS, ambient=AMBIENT, color=None, counts=None, **kw):
         return shadow_ref.shadow_pass(self.cam.color_buffer if color is None else color, self.cam.winner, self.tri,
@@ -51,19 +37,17 @@ class _Scene:
                                       counts=counts, **kw)
 
     def fillers(self, camera_kw=None, light_kw=None):
-        return _filler(self.H, self.W, **(camera_kw or {})), _filler(self.Hl, self.Wl, fov=self.light_fov, **(light_kw or {}))
+        return filler(self.H, self.W, **(camera_kw or {})), filler(self.Hl, self.Wl, fov=self.light_fov, **(light_kw or {}))
 
     def draw(self, f, g):
-        f.render_arrays(self.tri, self.col, self.nrm, clear=True)
+        super().draw(f)
         g.render_arrays(self.ltri, self.col, self.lnrm, clear=True)
         f.bind_shadow_map(g, self.ltri)
 
     def check_planes(self, f, g, what):
         """z, normals and the winner planes of both fillers are only read."""
-        for filler, ref, who in ((f, self.cam, "camera"), (g, self.lig, "light")):
-            assert_bit_equal(_host(filler.get_z_tensor()), ref.z_buffer, f"{what}: {who}'s z")
-            assert_bit_equal(_host(filler.get_normals_tensor()), ref.normals_buffer, f"{what}: {who}'s normals")
-            assert_bit_equal(_host(filler.get_winner_tensor()), ref.winner, f"{what}: {who}'s winner")
+        planes_only_read(f, self.cam, f"{what}: the camera")
+        planes_only_read(g, self.lig, f"{what}: the light")
 
     def off_the_map(self):
         """(share of the covered pixels whose texel is off the map, share whose surface point is behind the light)."""
@@ -84,16 +68,11 @@ class _Scene:
             f.shadow_pass(bias=BIAS, pcf=K, ambient=AMBIENT, use_winner=use_winner, **pass_kw)
             want = self.want(K, use_winner)
             assert not np.isnan(want).any()
-            assert_bit_equal(_host(f.get_color_tensor()), want, f"{what} colour, K={K}, use_winner={use_winner}")
+            assert_bit_equal(host(f.get_color_tensor()), want, f"{what} colour, K={K}, use_winner={use_winner}")
             if changes:
-                assert (want.view(np.uint32) != self.cam.color_buffer.view(np.uint32)).any(), (what, "the pass changed nothing")
+                self.assert_changed(want, what)
             self.check_planes(f, g, what)
         return f, g
-
-
-def _trex_arrays():
-    from cython3dmodelrenderer_amd import scenes
-    return scenes.load_fixture("trex_inputs.npz")
 
 
 @pytest.fixture(scope="module")
@@ -101,7 +80,7 @@ def trex256(oracle):
     """T-Rex at 256 x 256 with a 256 x 256 map, both fov 45; the light's frame holds the model turned about the
     float32 mean of its corners by the y block [[cos 40, -sin 40], [sin 40, cos 40]]: ``Model.rotate((0, -40, 0))`` in
     that method's own sign convention, the frame of the figures in tests/test_shadow_cpu.py."""
-    arrays = _trex_arrays()
+    arrays = trex_arrays()
     return _Scene(oracle, arrays, 256, 256, 256, 256, *shadow_ref.rotation_frame(arrays[0], (0, -40, 0)))
 
 
@@ -109,7 +88,7 @@ def trex256(oracle):
 def odd_trex(oracle):
     """T-Rex 200 x 173 under a 96 x 80 map of a light of fov 30 turned by (-25, 50, 0) in ``Model.rotate``'s convention
     (the blocks [[cos, -sin], [sin, cos]] of 25 and -50 degrees): most of the scene falls off the map."""
-    arrays = _trex_arrays()
+    arrays = trex_arrays()
     return _Scene(oracle, arrays, 200, 173, 96, 80, *shadow_ref.rotation_frame(arrays[0], (-25, 50, 0)), light_fov=30.0)
 
 
@@ -131,7 +110,7 @@ def test_trex_every_instance(trex256, K, use_winner):
 def test_trex_turned_the_other_way(oracle):
     """The same scene with the y block of ``Model.rotate((0, 40, 0))``: the light on the model's other side.
     The host model gives 67.6 % untouched, 32.4 % fully shadowed."""
-    arrays = _trex_arrays()
+    arrays = trex_arrays()
     s = _Scene(oracle, arrays, 256, 256, 256, 256, *shadow_ref.rotation_frame(arrays[0], (0, 40, 0)))
     s.check([(1, True)], "trex256, +40")
     counts = {}
@@ -146,7 +125,7 @@ def test_without_a_bias_the_winner_rule_lights_strictly_more(trex256):
     for use_winner in (False, True):
         s.draw(f, g)
         f.shadow_pass(bias=0.0, pcf=1, ambient=AMBIENT, use_winner=use_winner)
-        got = _host(f.get_color_tensor())
+        got = host(f.get_color_tensor())
         counts = {}
         assert_bit_equal(got, s.want(1, use_winner, bias=0.0, counts=counts), f"bias 0, use_winner={use_winner}")
         untouched = (got.view(np.uint32) == s.cam.color_buffer.view(np.uint32)).all(2) & (s.cam.winner >= 0)
@@ -160,11 +139,11 @@ def test_without_a_bias_the_winner_rule_lights_strictly_more(trex256):
 
 def test_the_light_at_the_camera_shadows_nothing(trex256):
     s = trex256
-    f = _filler(256, 256)
+    f = filler(256, 256)
     f.render_arrays(s.tri, s.col, s.nrm, clear=True)
     f.bind_shadow_map(f, s.tri)          # R = I, t = 0, the same projection: the frame's own z and winner planes are the map
     f.shadow_pass(bias=0.0, pcf=1, use_winner=True)
-    assert_bit_equal(_host(f.get_color_tensor()), s.cam.color_buffer, "bias 0 with the winner rule: 15 801 of 15 801 lit")
+    assert_bit_equal(host(f.get_color_tensor()), s.cam.color_buffer, "bias 0 with the winner rule: 15 801 of 15 801 lit")
 
     def model(bias, lwinner):
         counts = {}
@@ -175,11 +154,11 @@ def test_the_light_at_the_camera_shadows_nothing(trex256):
     f.shadow_pass(bias=0.0, pcf=1, ambient=AMBIENT, use_winner=False)
     want, lit = model(0.0, None)
     assert lit == 10703
-    assert_bit_equal(_host(f.get_color_tensor()), want, "bias 0 without the rule")
+    assert_bit_equal(host(f.get_color_tensor()), want, "bias 0 without the rule")
     f.render_arrays(s.tri, s.col, s.nrm, clear=True)
     f.shadow_pass(bias=1e-5, pcf=1, use_winner=False)
     assert model(1e-5, None)[1] == 15801
-    assert_bit_equal(_host(f.get_color_tensor()), s.cam.color_buffer, "bias 1e-5 without the rule")
+    assert_bit_equal(host(f.get_color_tensor()), s.cam.color_buffer, "bias 1e-5 without the rule")
 
 
 # ---- 3. odd shapes and the map's edge ------------------------------------------------------------------------------
@@ -213,7 +192,7 @@ def test_a_row_strip_leaves_the_other_rows_alone(oracle, odd_trex):
         f.winner_buffer[:y0] = 0
         f.winner_buffer[y1:] = 1
         f.shadow_pass(bias=BIAS, pcf=K, ambient=AMBIENT)
-        got = _host(f.get_color_tensor())
+        got = host(f.get_color_tensor())
         assert (got[:y0] == 7.5).all() and (got[y1:] == -2.25).all()
         want = s.want(K, True, y0=y0, y1=y1)
         assert (want[y0:y1].view(np.uint32) != s.cam.color_buffer[y0:y1].view(np.uint32)).any()
@@ -278,7 +257,7 @@ def _shade(lib, winner, tri, ltri, P, PL, lz, lwinner, color, bias=BIAS, ambient
         winner.data_ptr(), tri.data_ptr() if T else None, T, None if pos_of is None else pos_of.data_ptr(), _capi.f32_16(P),
         ltri.data_ptr() if T else None, _capi.f32_16(PL), lz.data_ptr(), None if lwinner is None else lwinner.data_ptr(),
         Hl, Wl, bias, ambient, pcf, color.data_ptr(), H, W, 0, H, 0, st), "crender_shadow_shade")
-    return _host(color)
+    return host(color)
 
 
 def test_special_values_through_the_c_entry(oracle):
@@ -373,18 +352,18 @@ def test_numpy_torch_and_device_model_inputs_agree(oracle):
     f, g = s.fillers()                             # numpy
     s.draw(f, g)
     f.shadow_pass(pcf=3)
-    assert_bit_equal(_host(f.get_color_tensor()), want, "numpy inputs")
+    assert_bit_equal(host(f.get_color_tensor()), want, "numpy inputs")
 
     f, g = s.fillers()                             # caller's device tensors, the light's arrays made on the device
     dev = [torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (tri, col, nrm)]
     dl, dn = shadow.light_arrays(dev[0], dev[2], R, t)
     assert dl.is_cuda
-    assert_bit_equal(_host(dl), s.ltri, "light_arrays on the device")
+    assert_bit_equal(host(dl), s.ltri, "light_arrays on the device")
     f.render_arrays(*dev, clear=True)
     g.render_arrays(dl, dev[1], dn, clear=True)
     f.bind_shadow_map(g, dl)
     f.shadow_pass(pcf=3)
-    assert_bit_equal(_host(f.get_color_tensor()), want, "torch inputs")
+    assert_bit_equal(host(f.get_color_tensor()), want, "torch inputs")
 
     f, g = s.fillers()                             # the device-resident model
     dm = DeviceModel(m)
@@ -393,24 +372,16 @@ def test_numpy_torch_and_device_model_inputs_agree(oracle):
     g.render_arrays(dl, dm._colors_by_triangles, dn, clear=True)
     f.bind_shadow_map(g, dl)
     f.shadow_pass(pcf=3)
-    assert_bit_equal(_host(f.get_color_tensor()), want, "DeviceModel inputs")
+    assert_bit_equal(host(f.get_color_tensor()), want, "DeviceModel inputs")
     # dropping the binding
     f.bind_shadow_map(None, None)
     with pytest.raises(ValueError, match="no shadow map is bound"):
         f.shadow_pass()
 
 
-class _Soup:
-    """What a filler reads off a model."""
-
-    def __init__(self, seed=71, T=3000, res=256):
-        self._vertices_by_triangles, self._colors_by_triangles, self._normals_by_triangles = \
-            random_soup(np.random.default_rng(seed), T, res, size_px=(3.0, 50.0))
-
-
 @pytest.fixture(scope="module")
 def soup256(oracle):
-    m = _Soup()
+    m = Soup()
     arrays = (m._vertices_by_triangles, m._colors_by_triangles, m._normals_by_triangles)
     s = _Scene(oracle, arrays, 256, 256, 128, 160, *shadow_ref.rotation_frame(arrays[0], (10, -20, 0)))
     s.model = m
@@ -435,7 +406,7 @@ def test_renderer_under_every_on_device(oracle, soup256, on_device):
     r = Renderer(f, GuroIllumination(LIGHT), on_device=on_device, shadow=dict(filler=g, R=s.R, t=s.t, **opts))
     for _ in range(2):                             # every frame starts from cleared buffers: the same image twice
         out = r.render(s.model)
-        got = _host(out) if on_device in (True, "fused") else np.array(out)
+        got = host(out) if on_device in (True, "fused") else np.array(out)
         assert_bit_equal(got, want, f"Renderer(on_device={on_device!r}, shadow=...)")
     s.check_planes(f, g, "after Renderer")
 
@@ -449,14 +420,14 @@ def test_renderer_with_supersampling_and_with_a_texture_pass(oracle, soup256):
     # the pass runs on the supersampled frame, and the resolve carries the light over the shadowed colours
     f, g = s.fillers()
     r = Renderer(f, GuroIllumination(LIGHT), None, 128, 128, on_device=True, supersample=2, shadow=dict(filler=g, R=s.R, t=s.t, pcf=5))
-    got = _host(r.render(s.model))
+    got = host(r.render(s.model))
     assert got.shape == (128, 128, 3)
     a, b = s.fillers()
     s.draw(a, b)
     a.shadow_pass(pcf=5)
-    assert_bit_equal(_host(a.get_color_tensor()), s.want(5, True), "the supersampled frame, shadowed")
-    assert_bit_equal(_host(f.get_color_tensor()), s.want(5, True), "the Renderer's frame stays unshaded")
-    assert_bit_equal(got, _host(a.resolve(2, light_direction=light)), "Renderer(supersample=2, shadow=...)")
+    assert_bit_equal(host(a.get_color_tensor()), s.want(5, True), "the supersampled frame, shadowed")
+    assert_bit_equal(host(f.get_color_tensor()), s.want(5, True), "the Renderer's frame stays unshaded")
+    assert_bit_equal(got, host(a.resolve(2, light_direction=light)), "Renderer(supersample=2, shadow=...)")
     # after a texture pass: the shadow falls on the texture's colours
     rng = np.random.default_rng(72)
     T = len(s.tri)
@@ -468,12 +439,12 @@ def test_renderer_with_supersampling_and_with_a_texture_pass(oracle, soup256):
     assert_bit_equal(m._normals_by_triangles, s.nrm, "the model's normals")
     f, g = s.fillers()
     r = Renderer(f, GuroIllumination(LIGHT), on_device=True, texture_pass={"perspective": True}, shadow=dict(filler=g, R=s.R, t=s.t))
-    got = _host(r.render(m))
+    got = host(r.render(m))
     a, b = s.fillers()
     a.bind_texture(m.get_texture_coords_by_triangles(), tex)
     a.render_model(m, clear=True)
     a.texture_pass(perspective=True)
-    textured = _host(a.get_color_tensor())
+    textured = host(a.get_color_tensor())
     want = oracle.guro(s.want(1, True, color=textured), s.cam.normals_buffer, LIGHT)
     assert_bit_equal(got, want, "Renderer(texture_pass=..., shadow=...)")
 
@@ -537,20 +508,20 @@ def test_errors_name_their_cause(soup256):
     with pytest.raises(_capi.CrenderError, match="bias is not finite"):
         f.shadow_pass(bias=float("nan"))
     f.shadow_pass()                                # and works again
-    assert_bit_equal(_host(f.get_color_tensor()), s.want(), "after the errors")
+    assert_bit_equal(host(f.get_color_tensor()), s.want(), "after the errors")
     # a light filler without a winner plane: use_winner=True falls back to the depths alone
-    g2 = _filler(s.Hl, s.Wl, track_winner=False)
+    g2 = filler(s.Hl, s.Wl, track_winner=False)
     f.render_arrays(s.tri, s.col, s.nrm, clear=True)
     g2.render_arrays(s.ltri, s.col, s.lnrm, clear=True)
     f.bind_shadow_map(g2, s.ltri)
     f.shadow_pass(use_winner=True)
-    assert_bit_equal(_host(f.get_color_tensor()), s.want(1, False), "a light without a winner plane")
+    assert_bit_equal(host(f.get_color_tensor()), s.want(1, False), "a light without a winner plane")
     for bad in ((None, s.ltri), (g, None), (object(), s.ltri), (g, s.ltri.astype(np.float64)), (g, s.ltri[:, :, :2])):
         with pytest.raises(ValueError):
             f.bind_shadow_map(*bad)
     with pytest.raises(ValueError, match="swap chain"):
-        f.bind_shadow_map(_filler(64, 64, pipeline=True), s.ltri)
-    chain = _filler(64, 64, pipeline=True)
+        f.bind_shadow_map(filler(64, 64, pipeline=True), s.ltri)
+    chain = filler(64, 64, pipeline=True)
     chain.bind_shadow_map(g, s.ltri)
     with pytest.raises(ValueError, match="swap chain"):
         chain.shadow_pass()
@@ -577,5 +548,5 @@ def test_a_frame_redrawn_after_a_bin_overflow_ends_shadowed(oracle):
                 assert cap == 500 and need > cap and len(filler._pending) == 1     # dropped fragments, nobody has looked yet
         f.shadow_pass(pcf=3)
         assert not f._pending and not g._pending                                   # grown and redone before the pass
-        assert_bit_equal(_host(f.get_color_tensor()), want, f"redone frames, {camera_kw}, {light_kw}")
+        assert_bit_equal(host(f.get_color_tensor()), want, f"redone frames, {camera_kw}, {light_kw}")
         s.check_planes(f, g, "redone frames")

@@ -14,16 +14,10 @@ import pytest
 import torch
 
 import ssaa_ref
+from pass_scenes import capi  # noqa: F401 (fixtures)
 from util import assert_bit_equal, other_symbols, unit_inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from cython3dmodelrenderer_amd import _build, _capi
-    _build.build()           # hipcc cross-compiles for gfx950 without a GPU
-    return _capi
 
 
 # ---- the host side of the ABI ----------------------------------------------------------------------------------

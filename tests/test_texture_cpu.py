@@ -10,31 +10,15 @@ import numpy as np
 import pytest
 
 import tex_ref
+from pass_scenes import capi, trex_uv as trex  # noqa: F401 (fixtures)
 from util import assert_bit_equal, other_symbols, random_soup
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 # Largest |u32 - u64| and |v32 - v64| over the covered pixels of T-Rex at 1024^2, perspective mode, where u64 /
 # v64 are the statements of include/crender_tex.h evaluated in float64 from the same float32 inputs (projection
 # included): measured 2.173e-06 (u) and 2.492e-06 (v) on 252 539 pixels.  Four times the larger, for other scenes' rounding.
 PERSPECTIVE_UV_BOUND = 4 * 2.492e-06
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from cython3dmodelrenderer_amd import _build, _capi
-    _build.build()           # hipcc cross-compiles for gfx950 without a GPU
-    return _capi
-
-
-@pytest.fixture(scope="module")
-def trex():
-    from cython3dmodelrenderer_amd import scenes
-    tri, col, nrm = scenes.load_fixture("trex_inputs.npz")
-    with np.load(os.path.join(GOLDEN, "trex_uv.npz")) as z:
-        uv = np.ascontiguousarray(z["uv"][z["faces_uv"]], dtype=np.float32)
-    return tri, col, nrm, uv
 
 
 def _oracle_frame(oracle, tri, col, nrm, size):

@@ -7,49 +7,13 @@ import numpy as np
 import pytest
 
 import tex_ref
+from pass_scenes import GOLDEN, filler, host, oracle_frame, planes_only_read, soup_textured, texture, textured_model, trex_textured
 from util import assert_bit_equal, random_soup
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 MODES = [(False, "nearest"), (True, "nearest"), (False, "bilinear"), (True, "bilinear")]
 LIGHT = (0.3, -0.2, 1.0)             # what GuroIllumination is constructed with
-
-
-def _texture(seed, th, tw):
-    return np.random.default_rng(seed).integers(0, 256, (th, tw, 3), dtype=np.uint8)
-
-
-def _trex():
-    from cython3dmodelrenderer_amd import scenes
-    tri, col, nrm = scenes.load_fixture("trex_inputs.npz")
-    with np.load(os.path.join(GOLDEN, "trex_uv.npz")) as z:
-        uv = np.ascontiguousarray(z["uv"][z["faces_uv"]], dtype=np.float32)
-    return tri, col, nrm, uv
-
-
-def _soup(seed, T, res, **kw):
-    rng = np.random.default_rng(seed)
-    tri, col, nrm = random_soup(rng, T, res, **kw)
-    uv = rng.uniform(-1.5, 2.5, (T, 3, 2)).astype(np.float32)        # beyond [0, 1]: the clamp is part of the rule
-    return tri, col, nrm, uv
-
-
-def _filler(H, W, **kw):
-    from cython3dmodelrenderer_amd.pixel_buffer_filler import AdvancedPixelBufferFiller
-    kw.setdefault("track_winner", True)
-    return AdvancedPixelBufferFiller(H, W, fov=45.0, device="cuda:0", **kw)
-
-
-def _frame(oracle, tri, col, nrm, H, W, y0=0, y1=None):
-    ref = oracle.OracleFiller(H, W, fov=45.0)
-    ref.render_arrays(tri, col, nrm, y0=y0, y1=y1)
-    return ref
-
-
-def _host(t):
-    return t.cpu().numpy()
 
 
 def _want(ref, tri, uv, tex, persp=False, filt="nearest", **kw):
@@ -59,58 +23,55 @@ def _want(ref, tri, uv, tex, persp=False, filt="nearest", **kw):
 
 def _check_every_mode(oracle, scene, tex, H, W, what, min_covered=1, **filler_kw):
     tri, col, nrm, uv = scene
-    ref = _frame(oracle, tri, col, nrm, H, W)
+    ref = oracle_frame(oracle, tri, col, nrm, H, W)
     covered = int((ref.winner >= 0).sum())
     assert covered >= min_covered, (what, covered)
-    f = _filler(H, W, **filler_kw)
+    f = filler(H, W, **filler_kw)
     f.bind_texture(uv, tex)
     for persp, filt in MODES:
         f.render_arrays(tri, col, nrm, clear=True)
         f.texture_pass(perspective=persp, filter=filt)
         want = _want(ref, tri, uv, tex, persp, filt)
         assert not np.isnan(want).any(), (what, persp, filt)
-        assert_bit_equal(_host(f.get_color_tensor()), want, f"{what} colour, perspective={persp}, {filt}")
+        assert_bit_equal(host(f.get_color_tensor()), want, f"{what} colour, perspective={persp}, {filt}")
         if covered:
             assert (want.view(np.uint32) != ref.color_buffer.view(np.uint32)).any(), (what, "the pass changed nothing")
-        # z, normals and the winner plane are only read
-        assert_bit_equal(_host(f.get_z_tensor()), ref.z_buffer, f"{what} z")
-        assert_bit_equal(_host(f.get_normals_tensor()), ref.normals_buffer, f"{what} normals")
-        assert_bit_equal(_host(f.get_winner_tensor()), ref.winner, f"{what} winner")
+        planes_only_read(f, ref, what)
     return f
 
 
 @pytest.mark.parametrize("size", [256, 1024, 4096])
 def test_trex_every_mode(oracle, size):
-    _check_every_mode(oracle, _trex(), _texture(1, 709, 709), size, size, f"trex{size}", min_covered=15000)
+    _check_every_mode(oracle, trex_textured(), texture(1, 709, 709), size, size, f"trex{size}", min_covered=15000)
 
 
 def test_cube_every_mode(oracle):
     from cython3dmodelrenderer_amd import scenes
     tri, col, nrm = scenes.load_fixture("cube_inputs.npz")
     uv = np.random.default_rng(2).uniform(-0.5, 1.5, (len(tri), 3, 2)).astype(np.float32)
-    _check_every_mode(oracle, (tri, col, nrm, uv), _texture(2, 3, 1000), 256, 256, "cube256", min_covered=1000)
+    _check_every_mode(oracle, (tri, col, nrm, uv), texture(2, 3, 1000), 256, 256, "cube256", min_covered=1000)
 
 
 @pytest.mark.parametrize("seed,T,H,W,th,tw", [(31, 4000, 200, 173, 1, 1), (32, 2500, 333, 512, 3, 1000),
                                               (33, 30000, 512, 509, 709, 709), (34, 60, 64, 41, 2, 5)])
 def test_random_soups_with_uv_beyond_the_unit_square(oracle, seed, T, H, W, th, tw):
-    scene = _soup(seed, T, max(H, W), size_px=(1.0, 60.0))
-    _check_every_mode(oracle, scene, _texture(seed, th, tw), H, W, f"soup{seed}", min_covered=H * W // 20)
+    scene = soup_textured(seed, T, max(H, W), size_px=(1.0, 60.0))
+    _check_every_mode(oracle, scene, texture(seed, th, tw), H, W, f"soup{seed}", min_covered=H * W // 20)
 
 
 def test_presort_gives_the_same_bits(oracle):
-    scene = _soup(41, 20000, 512, size_px=(2.0, 30.0))
-    f = _check_every_mode(oracle, scene, _texture(41, 64, 97), 512, 512, "presorted soup", presort=True)
+    scene = soup_textured(41, 20000, 512, size_px=(2.0, 30.0))
+    f = _check_every_mode(oracle, scene, texture(41, 64, 97), 512, 512, "presorted soup", presort=True)
     assert f._order is not None          # the resident inputs are the tile-coherent copy: the pass went through pos_of
 
 
 def test_fused_light_equals_the_pass_plus_the_illumination(oracle):
-    tri, col, nrm, uv = _trex()
-    tex = _texture(5, 709, 709)
+    tri, col, nrm, uv = trex_textured()
+    tex = texture(5, 709, 709)
     H = W = 1024
-    ref = _frame(oracle, tri, col, nrm, H, W)
+    ref = oracle_frame(oracle, tri, col, nrm, H, W)
     light = [float(v) for v in oracle.guro_light(LIGHT)]
-    f, g = _filler(H, W), _filler(H, W)
+    f, g = filler(H, W), filler(H, W)
     f.bind_texture(uv, tex)
     g.bind_texture(uv, tex)
     for persp, filt in MODES:
@@ -120,11 +81,11 @@ def test_fused_light_equals_the_pass_plus_the_illumination(oracle):
         g.texture_pass(perspective=persp, filter=filt)
         g.synchronize()
         g.shade_guro(light)
-        got = _host(f.get_color_tensor())
-        assert_bit_equal(got, _host(g.get_color_tensor()), f"fused light vs pass + illumination, {persp}, {filt}")
+        got = host(f.get_color_tensor())
+        assert_bit_equal(got, host(g.get_color_tensor()), f"fused light vs pass + illumination, {persp}, {filt}")
         want = _want(ref, tri, uv, tex, persp, filt, normals=ref.normals_buffer, light_direction=LIGHT)
         assert_bit_equal(got, want, f"fused light vs oracle.guro of the reference, {persp}, {filt}")
-        assert_bit_equal(_host(f.get_normals_tensor()), ref.normals_buffer, "normals")
+        assert_bit_equal(host(f.get_normals_tensor()), ref.normals_buffer, "normals")
     # the background is shaded too: a colour written there beforehand comes out multiplied
     f.render_arrays(tri, col, nrm, clear=True)
     plane = f.get_color_tensor()
@@ -136,18 +97,18 @@ def test_fused_light_equals_the_pass_plus_the_illumination(oracle):
     n = ref.normals_buffer.copy(); n[0, 0, 2] = -2.0
     want = tex_ref.texture_pass(c, ref.winner, tri, ref.proj_mat, uv, tex, normals=n, light_direction=LIGHT)
     assert want[0, 0, 0] != 0.0 and want[0, 0, 0] != 3.0
-    assert_bit_equal(_host(f.get_color_tensor()), want, "background under the fused light")
+    assert_bit_equal(host(f.get_color_tensor()), want, "background under the fused light")
 
 
 def test_row_strip_leaves_the_other_rows_alone(oracle):
-    tri, col, nrm, uv = _trex()
-    tex = _texture(6, 709, 709)
+    tri, col, nrm, uv = trex_textured()
+    tex = texture(6, 709, 709)
     H = W = 512
     y0, y1 = 135, 301                    # not multiples of the kernel's 8-row blocks
-    ref = _frame(oracle, tri, col, nrm, H, W, y0=y0, y1=y1)
+    ref = oracle_frame(oracle, tri, col, nrm, H, W, y0=y0, y1=y1)
     light = [float(v) for v in oracle.guro_light(LIGHT)]
     for with_light in (False, True):
-        f = _filler(H, W, row_strip=(y0, y1))
+        f = filler(H, W, row_strip=(y0, y1))
         f.bind_texture(uv, tex)
         f.render_arrays(tri, col, nrm, clear=True)
         f.synchronize()
@@ -157,7 +118,7 @@ def test_row_strip_leaves_the_other_rows_alone(oracle):
         f.winner_buffer[:y0] = 0
         f.winner_buffer[y1:] = 1
         f.texture_pass(filter="bilinear", light_direction=light if with_light else None)
-        got = _host(f.get_color_tensor())
+        got = host(f.get_color_tensor())
         assert (got[:y0] == 7.5).all() and (got[y1:] == -2.25).all()
         kw = dict(normals=ref.normals_buffer, light_direction=LIGHT) if with_light else {}
         want = _want(ref, tri, uv, tex, False, "bilinear", y0=y0, y1=y1, **kw)
@@ -173,40 +134,40 @@ def test_numpy_torch_and_device_model_inputs_agree(oracle):
         vertices, faces = z["vertices"], z["faces"]
     with np.load(os.path.join(GOLDEN, "trex_uv.npz")) as z:
         uv_pool, faces_uv = z["uv"], z["faces_uv"]
-    tex = _texture(7, 709, 709)
+    tex = texture(7, 709, 709)
     m = Model(vertices, faces, uv_pool, faces_uv, tex)
     scenes.fit_model(m)
     H = W = 512
     tri, col, nrm = m._vertices_by_triangles, m._colors_by_triangles, m._normals_by_triangles
     uv = m.get_texture_coords_by_triangles()
     assert uv.shape == (len(tri), 3, 2) and uv.dtype == np.float32 and m.get_texture() is m._texture
-    ref = _frame(oracle, tri, col, nrm, H, W)
+    ref = oracle_frame(oracle, tri, col, nrm, H, W)
     assert int((ref.winner >= 0).sum()) > 5000
     want = _want(ref, tri, uv, tex, True, "bilinear")
 
-    a = _filler(H, W)                              # numpy
+    a = filler(H, W)                              # numpy
     a.bind_texture(uv, tex)
     a.render_model(m, clear=True)
     a.texture_pass(perspective=True, filter="bilinear")
-    assert_bit_equal(_host(a.get_color_tensor()), want, "numpy inputs")
+    assert_bit_equal(host(a.get_color_tensor()), want, "numpy inputs")
 
-    b = _filler(H, W)                              # caller's device tensors
+    b = filler(H, W)                              # caller's device tensors
     dev = [torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (tri, col, nrm)]
     b.bind_texture(torch.from_numpy(uv).cuda(), torch.from_numpy(tex).cuda())
     b.render_arrays(*dev, clear=True)
     b.texture_pass(perspective=True, filter="bilinear")
-    assert_bit_equal(_host(b.get_color_tensor()), want, "torch inputs")
+    assert_bit_equal(host(b.get_color_tensor()), want, "torch inputs")
 
     dm = DeviceModel(m)                            # the device-resident model's own uv and texture
     duv, dtex = dm.get_texture_coords_by_triangles(), dm.get_texture()
     assert duv.is_cuda and dtex.is_cuda and duv.dtype == torch.float32 and dtex.dtype == torch.uint8
-    assert_bit_equal(_host(duv), uv, "DeviceModel uv")
-    assert np.array_equal(_host(dtex), tex)
-    c = _filler(H, W)
+    assert_bit_equal(host(duv), uv, "DeviceModel uv")
+    assert np.array_equal(host(dtex), tex)
+    c = filler(H, W)
     c.bind_texture(duv, dtex)
     c.render_model(dm, clear=True)
     c.texture_pass(perspective=True, filter="bilinear")
-    assert_bit_equal(_host(c.get_color_tensor()), want, "DeviceModel inputs")
+    assert_bit_equal(host(c.get_color_tensor()), want, "DeviceModel inputs")
     # dropping the texture
     c.bind_texture(None, None)
     with pytest.raises(ValueError, match="no texture is bound"):
@@ -215,52 +176,42 @@ def test_numpy_torch_and_device_model_inputs_agree(oracle):
     assert untextured.get_texture_coords_by_triangles() is None and untextured.get_texture() is None
 
 
-def _textured_model(seed=8):
-    from cython3dmodelrenderer_amd.data_structures.model import Model
-    tri, col, nrm, uv = _soup(seed, 3000, 256, size_px=(3.0, 50.0))
-    T = len(tri)
-    idx = np.arange(3 * T, dtype=np.int32).reshape(T, 3)
-    tex = _texture(seed, 37, 53)
-    m = Model(tri.reshape(-1, 3), idx, uv.reshape(-1, 2), idx, tex, nrm.reshape(-1, 3), idx, recalculate_normals=False)
-    return m, tex
-
-
 @pytest.mark.parametrize("on_device", [None, False, True, "fused"])
 def test_renderer_under_every_on_device(oracle, on_device):
     from cython3dmodelrenderer_amd.illumination.guro_illumination import GuroIllumination
     from cython3dmodelrenderer_amd.renderer import Renderer
-    m, tex = _textured_model()
+    m, tex = textured_model()
     tri, col, nrm = m._vertices_by_triangles, m._colors_by_triangles, m._normals_by_triangles
     uv = m.get_texture_coords_by_triangles()
     H = W = 256
-    ref = _frame(oracle, tri, col, nrm, H, W)
+    ref = oracle_frame(oracle, tri, col, nrm, H, W)
     assert int((ref.winner >= 0).sum()) > 10000
     want = _want(ref, tri, uv, tex, True, "bilinear", normals=ref.normals_buffer, light_direction=LIGHT)
-    f = _filler(H, W)
+    f = filler(H, W)
     binds = []
     bind = f.bind_texture
     f.bind_texture = lambda *a: (binds.append(1), bind(*a))[1]
     r = Renderer(f, GuroIllumination(LIGHT), on_device=on_device, texture_pass={"perspective": True, "filter": "bilinear"})
     for _ in range(2):                             # every frame starts from cleared buffers: the same image twice
         out = r.render(m)
-        got = _host(out) if on_device in (True, "fused") else np.array(out)
+        got = host(out) if on_device in (True, "fused") else np.array(out)
         assert_bit_equal(got, want, f"Renderer(on_device={on_device!r})")
     assert len(binds) == 1                         # the texture went up once per model, not per frame
-    assert_bit_equal(_host(f.get_normals_tensor()), ref.normals_buffer, "normals")
+    assert_bit_equal(host(f.get_normals_tensor()), ref.normals_buffer, "normals")
     # the default stays the reference's image
-    plain = Renderer(_filler(H, W), GuroIllumination(LIGHT), on_device=on_device)
+    plain = Renderer(filler(H, W), GuroIllumination(LIGHT), on_device=on_device)
     out = plain.render(m)
-    got = _host(out) if on_device in (True, "fused") else np.array(out)
+    got = host(out) if on_device in (True, "fused") else np.array(out)
     c = ref.color_buffer.copy()
     oracle.guro(c, ref.normals_buffer, LIGHT)
     assert_bit_equal(got, c, f"Renderer(on_device={on_device!r}) without a texture pass")
 
 
 def test_host_views_show_the_textured_colours_at_the_next_getter_call(oracle):
-    tri, col, nrm, uv = _soup(9, 2000, 128, size_px=(3.0, 40.0))
-    tex = _texture(9, 16, 16)
-    ref = _frame(oracle, tri, col, nrm, 128, 128)
-    f = _filler(128, 128)
+    tri, col, nrm, uv = soup_textured(9, 2000, 128, size_px=(3.0, 40.0))
+    tex = texture(9, 16, 16)
+    ref = oracle_frame(oracle, tri, col, nrm, 128, 128)
+    f = filler(128, 128)
     f.bind_texture(uv, tex)
     f.render_arrays(tri, col, nrm, clear=True)
     view = f.get_color_buffer()
@@ -273,37 +224,37 @@ def test_host_views_show_the_textured_colours_at_the_next_getter_call(oracle):
 
 def test_a_frame_without_triangles_keeps_its_cleared_colours(oracle):
     e = np.zeros((0, 3, 3), np.float32)
-    f = _filler(96, 80)
-    f.bind_texture(np.zeros((0, 3, 2), np.float32), _texture(10, 4, 4))
+    f = filler(96, 80)
+    f.bind_texture(np.zeros((0, 3, 2), np.float32), texture(10, 4, 4))
     light = [float(v) for v in oracle.guro_light(LIGHT)]
     for kw in ({}, {"light_direction": light}, {"perspective": True, "filter": "bilinear"}):
         f.render_arrays(e, e, e, clear=True)
         f.texture_pass(**kw)
-        assert (_host(f.get_color_tensor()).view(np.uint32) == 0).all(), kw
-        assert (_host(f.get_winner_tensor()) == -1).all()
+        assert (host(f.get_color_tensor()).view(np.uint32) == 0).all(), kw
+        assert (host(f.get_winner_tensor()) == -1).all()
     # and a frame whose triangles all miss the view
-    tri, col, nrm, uv = _soup(10, 50, 96)
+    tri, col, nrm, uv = soup_textured(10, 50, 96)
     tri[..., 0] += 100.0
-    f.bind_texture(uv, _texture(10, 4, 4))
+    f.bind_texture(uv, texture(10, 4, 4))
     f.render_arrays(tri, col, nrm, clear=True)
     f.texture_pass(filter="bilinear")
-    assert (_host(f.get_color_tensor()).view(np.uint32) == 0).all()
+    assert (host(f.get_color_tensor()).view(np.uint32) == 0).all()
 
 
 def test_nan_and_infinite_uv_follow_the_statement(oracle):
-    tri, col, nrm, uv = _soup(12, 1500, 160, size_px=(4.0, 40.0))
+    tri, col, nrm, uv = soup_textured(12, 1500, 160, size_px=(4.0, 40.0))
     rng = np.random.default_rng(12)
     odd = np.float32([np.nan, np.inf, -np.inf, 3e38, -3e38, 2147483648.0, -2147483904.0, 1e-42])
     hit = rng.uniform(size=uv.shape) < 0.15
     uv[hit] = rng.choice(odd, int(hit.sum()))
-    tex = _texture(12, 5, 7)
-    ref = _frame(oracle, tri, col, nrm, 160, 160)
-    f = _filler(160, 160)
+    tex = texture(12, 5, 7)
+    ref = oracle_frame(oracle, tri, col, nrm, 160, 160)
+    f = filler(160, 160)
     f.bind_texture(uv, tex)
     for persp, filt in MODES:
         f.render_arrays(tri, col, nrm, clear=True)
         f.texture_pass(perspective=persp, filter=filt)
-        got = _host(f.get_color_tensor())
+        got = host(f.get_color_tensor())
         want = _want(ref, tri, uv, tex, persp, filt)
         # (IEEE 754 leaves the sign and payload of a generated NaN open: x86 and gfx950 differ there)
         nan = np.isnan(want)
@@ -319,14 +270,14 @@ def test_errors_name_their_cause(oracle):
     from cython3dmodelrenderer_amd.data_structures.model import Model
     from cython3dmodelrenderer_amd.illumination.guro_illumination import GuroIllumination
     from cython3dmodelrenderer_amd.renderer import Renderer
-    tri, col, nrm, uv = _soup(13, 300, 64)
-    tex = _texture(13, 8, 8)
-    f = _filler(64, 64, track_winner=False)
+    tri, col, nrm, uv = soup_textured(13, 300, 64)
+    tex = texture(13, 8, 8)
+    f = filler(64, 64, track_winner=False)
     f.bind_texture(uv, tex)
     f.render_arrays(tri, col, nrm, clear=True)
     with pytest.raises(ValueError, match="winner plane"):
         f.texture_pass()
-    f = _filler(64, 64)
+    f = filler(64, 64)
     with pytest.raises(ValueError, match="no frame has been rendered|no texture is bound"):
         f.texture_pass()
     f.render_arrays(tri, col, nrm, clear=True)
@@ -347,7 +298,7 @@ def test_errors_name_their_cause(oracle):
                 (uv, tex[:, :, :2])):
         with pytest.raises(ValueError):
             f.bind_texture(*bad)
-    chain = _filler(64, 64, pipeline=True)
+    chain = filler(64, 64, pipeline=True)
     chain.bind_texture(uv, tex)
     with pytest.raises(ValueError, match="swap chain"):
         chain.texture_pass()
@@ -356,7 +307,7 @@ def test_errors_name_their_cause(oracle):
     plain = Model(tri.reshape(-1, 3), idx, normals=nrm.reshape(-1, 3), triangles_normals=idx, recalculate_normals=False)
     plain.set_uniform_color()
     with pytest.raises(ValueError, match="textured model"):
-        Renderer(_filler(64, 64), GuroIllumination(LIGHT), texture_pass={}).render(plain)
+        Renderer(filler(64, 64), GuroIllumination(LIGHT), texture_pass={}).render(plain)
 
 
 def test_a_frame_redrawn_after_a_bin_overflow_ends_textured(oracle):
@@ -365,16 +316,16 @@ def test_a_frame_redrawn_after_a_bin_overflow_ends_textured(oracle):
     rng = np.random.default_rng(21)
     tri, col, nrm = random_soup(rng, 400, 512, size_px=(150, 400), frac_backface=0.0)
     uv = rng.uniform(-0.5, 1.5, (400, 3, 2)).astype(np.float32)
-    tex = _texture(21, 31, 17)
-    ref = _frame(oracle, tri, col, nrm, 512, 512)
+    tex = texture(21, 31, 17)
+    ref = oracle_frame(oracle, tri, col, nrm, 512, 512)
     for presort in (False, True):
-        f = _filler(512, 512, tile=32, bin_capacity=500, direct_bins=False, presort=presort)
+        f = filler(512, 512, tile=32, bin_capacity=500, direct_bins=False, presort=presort)
         f.bind_texture(uv, tex)
         f.render_arrays(tri, col, nrm, clear=True)
         need, cap = f.bin_usage()
         assert cap == 500 and need > cap and len(f._pending) == 1      # this frame dropped fragments, nobody has looked yet
         f.texture_pass(perspective=True)
         assert not f._pending and f.bin_usage()[1] >= need             # grown and redone before the pass
-        assert_bit_equal(_host(f.get_color_tensor()), _want(ref, tri, uv, tex, True), f"redone frame, presort={presort}")
-        assert_bit_equal(_host(f.get_winner_tensor()), ref.winner, "winner")
-        assert_bit_equal(_host(f.get_z_tensor()), ref.z_buffer, "z")
+        assert_bit_equal(host(f.get_color_tensor()), _want(ref, tri, uv, tex, True), f"redone frame, presort={presort}")
+        assert_bit_equal(host(f.get_winner_tensor()), ref.winner, "winner")
+        assert_bit_equal(host(f.get_z_tensor()), ref.z_buffer, "z")

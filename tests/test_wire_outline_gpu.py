@@ -11,36 +11,21 @@ import outline_ref
 import overlay_ref
 import phong_ref
 import shadow_ref
+from pass_scenes import GOLDEN, Scene, edge_mask, filler, host, soup_fixture, trex_arrays, trex_fixture
 from util import assert_bit_equal, random_soup
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 GURO = (0.3, -0.2, 1.0)              # what GuroIllumination is constructed with
 LINE = (250.0, 240.0, 20.0)
 FILL = (30.0, 35.0, 40.0)
 
 
-def _filler(H, W, fov=45.0, **kw):
-    from cython3dmodelrenderer_amd.pixel_buffer_filler import AdvancedPixelBufferFiller
-    kw.setdefault("track_winner", True)
-    return AdvancedPixelBufferFiller(H, W, fov=fov, device="cuda:0", **kw)
+class _Scene(Scene):
+    """The model's distance fields are kept by (mask, radius, bias, rows): they do not depend on the line's style."""
 
-
-def _host(t):
-    return t.cpu().numpy()
-
-
-class _Scene:
-    """A model and the oracle's frame of it: computed once, only read afterwards.  The model's distance fields are
-    kept by (mask, radius, bias, rows): they do not depend on the line's style."""
-
-    def __init__(self, oracle, arrays, H, W, y0=0, y1=None):
-        self.tri, self.col, self.nrm = arrays
-        self.H, self.W = H, W
-        self.cam = oracle.OracleFiller(H, W, fov=45.0)
-        self.cam.render_arrays(self.tri, self.col, self.nrm, y0=y0, y1=y1)
-        self.covered = int((self.cam.winner >= 0).sum())
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
         self._fields = {}
 
     def want(self, base=None, mask_key=None, **kw):
@@ -62,43 +47,18 @@ class _Scene:
         return outline_ref.wire_pass(self.cam.color_buffer if base is None else base, self.cam.winner, self.cam.z_buffer,
                                      self.tri, self.cam.proj_mat, field=field, **kw)
 
-    def draw(self, f):
-        f.render_arrays(self.tri, self.col, self.nrm, clear=True)
-
-    def check_planes(self, f, what):
-        """z, normals and the winner plane are only read."""
-        assert_bit_equal(_host(f.get_z_tensor()), self.cam.z_buffer, f"{what}: z")
-        assert_bit_equal(_host(f.get_normals_tensor()), self.cam.normals_buffer, f"{what}: normals")
-        assert_bit_equal(_host(f.get_winner_tensor()), self.cam.winner, f"{what}: winner")
-
     def check(self, f, what, mask_key=None, **kw):
         self.draw(f)
         f.wire_pass(outline=True, **kw)
         want = self.want(mask_key=mask_key, **kw)
-        changed = (want.view(np.uint32) != self.cam.color_buffer.view(np.uint32)).any(2)
-        assert changed.any(), (what, "the pass changed nothing")
-        assert_bit_equal(_host(f.get_color_tensor()), want, f"{what} colour")
+        changed = self.assert_changed(want, what)
+        assert_bit_equal(host(f.get_color_tensor()), want, f"{what} colour")
         self.check_planes(f, what)
         return want, changed
 
 
-def _trex_arrays():
-    from cython3dmodelrenderer_amd import scenes
-    return scenes.load_fixture("trex_inputs.npz")
-
-
-@pytest.fixture(scope="module")
-def trex256(oracle):
-    return _Scene(oracle, _trex_arrays(), 256, 256)
-
-
-def _mask(kind, tri, seed=9):
-    from cython3dmodelrenderer_amd.wireframe import feature_edges
-    if kind == "all":
-        return None
-    if kind == "feature":
-        return feature_edges(tri, 30.0)
-    return np.random.default_rng(seed).integers(0, 256, len(tri)).astype(np.uint8)       # bits 3 to 7 are ignored
+trex256 = trex_fixture(_Scene)
+soup256 = soup_fixture(_Scene)
 
 
 # ---- 1. T-Rex ------------------------------------------------------------------------------------------------------
@@ -108,8 +68,8 @@ def _mask(kind, tri, seed=9):
 def test_trex_every_instance(trex256, fill, edges):
     s = trex256
     assert s.covered == 15801
-    f = _filler(256, 256)
-    mask = _mask(edges, s.tri)
+    f = filler(256, 256)
+    mask = edge_mask(edges, s.tri)
     background = s.cam.winner < 0
     for radius_px in (1, 2, 8):
         for width in (1.0, 3.0):
@@ -128,7 +88,7 @@ def test_frames_that_do_not_fit_the_tiles(oracle, H, W, T, size, radii):
     """One pixel past a tile both ways; and a frame smaller than the halo."""
     s = _Scene(oracle, random_soup(np.random.default_rng(H), T, max(H, W), size_px=size), H, W)
     assert s.covered > 3
-    f = _filler(H, W)
+    f = filler(H, W)
     for radius_px in radii:
         for fill in (None, FILL):
             s.check(f, f"{H} x {W}, radius {radius_px}, fill {fill}", color=LINE, fill=fill, radius_px=radius_px, width=3.0)
@@ -136,8 +96,8 @@ def test_frames_that_do_not_fit_the_tiles(oracle, H, W, T, size, radii):
 
 def test_a_row_strip_of_an_odd_frame_leaves_the_other_rows_alone(oracle):
     y0, y1 = 40, 136
-    s = _Scene(oracle, _trex_arrays(), 200, 173, y0=y0, y1=y1)
-    f = _filler(200, 173, row_strip=(y0, y1))
+    s = _Scene(oracle, trex_arrays(), 200, 173, y0=y0, y1=y1)
+    f = filler(200, 173, row_strip=(y0, y1))
     for fill in (None, FILL):
         for radius_px in (3, 8):
             s.draw(f)
@@ -148,7 +108,7 @@ def test_a_row_strip_of_an_odd_frame_leaves_the_other_rows_alone(oracle):
             f.winner_buffer[:y0] = 0
             f.winner_buffer[y1:] = 1
             f.wire_pass(width=3.0, color=LINE, fill=fill, outline=True, radius_px=radius_px)
-            got = _host(f.get_color_tensor())
+            got = host(f.get_color_tensor())
             assert (got[:y0] == 7.5).all() and (got[y1:] == -2.25).all()
             want = s.want(width=3.0, color=LINE, fill=fill, radius_px=radius_px, y0=y0, y1=y1)
             assert (want[y0:y1].view(np.uint32) != s.cam.color_buffer[y0:y1].view(np.uint32)).any()
@@ -163,10 +123,10 @@ def test_a_row_strip_of_an_odd_frame_leaves_the_other_rows_alone(oracle):
 ])
 def test_random_soups(oracle, seed, T, H, W, size, presort):
     s = _Scene(oracle, random_soup(np.random.default_rng(seed), T, max(H, W), size_px=size), H, W)
-    f = _filler(H, W, presort=presort)
+    f = filler(H, W, presort=presort)
     # the mask is indexed in the caller's order while the corners are fetched through d_pos_of: a random mask tells
     # a mix-up of the two orders
-    mask = _mask("random", s.tri, seed)
+    mask = edge_mask("random", s.tri, seed)
     s.check(f, f"soup{seed}", color=LINE)
     s.check(f, f"soup{seed}, masked", mask_key="random", color=LINE, edges=mask, width=2.0)
     s.check(f, f"soup{seed}, masked and filled", mask_key="random", color=LINE, edges=mask, fill=FILL, width=2.0, feather=0.5)
@@ -190,7 +150,7 @@ def _outline(lib, winner, z, tri, P, color, width=1.0, feather=1.0, opacity=1.0,
         _capi.f32_16(P), None if edges is None else edges.data_ptr(), (C.c_float * 3)(*line),
         None if fill is None else (C.c_float * 3)(*fill), width, feather, opacity, depth_bias, radius_px, color.data_ptr(),
         H, W, 0, H, 0, st), "crender_wire_outline")
-    return _host(color)
+    return host(color)
 
 
 def test_special_values_through_the_c_entry(oracle):
@@ -251,7 +211,7 @@ def test_special_values_through_the_c_entry(oracle):
         nans = max(nans, counts["nan"])
     assert touched > 500 and nans > 50 and outside > 20
     for name in ("winner", "z", "tri"):
-        assert_bit_equal(_host(dev[name]), dict(winner=winner, z=z, tri=tri)[name], f"{name} is only read")
+        assert_bit_equal(host(dev[name]), dict(winner=winner, z=z, tri=tri)[name], f"{name} is only read")
     # an entry of d_pos_of beyond T makes its triangle background, as a pixel's own winner and as a neighbour's; the
     # others are found where it says, their edge bits where the caller put them
     perm = rng.permutation(T).astype(np.uint32)
@@ -277,23 +237,6 @@ def test_special_values_through_the_c_entry(oracle):
 
 # ---- 5. inputs and host views --------------------------------------------------------------------------------------
 
-class _Soup:
-    """What a filler reads off a model."""
-
-    def __init__(self, seed=71, T=3000, res=256):
-        self._vertices_by_triangles, self._colors_by_triangles, self._normals_by_triangles = \
-            random_soup(np.random.default_rng(seed), T, res, size_px=(3.0, 50.0))
-
-
-@pytest.fixture(scope="module")
-def soup256(oracle):
-    m = _Soup()
-    s = _Scene(oracle, (m._vertices_by_triangles, m._colors_by_triangles, m._normals_by_triangles), 256, 256)
-    s.model = m
-    assert s.covered > 10000
-    return s
-
-
 def test_numpy_torch_and_device_model_inputs_agree(oracle):
     import torch
     from cython3dmodelrenderer_amd import scenes
@@ -308,24 +251,24 @@ def test_numpy_torch_and_device_model_inputs_agree(oracle):
     kw = dict(width=2.0, color=LINE, fill=FILL)
     want = s.want(mask_key="all", **kw)
     assert (want != s.cam.color_buffer).any()
-    f = _filler(256, 256)                          # numpy
+    f = filler(256, 256)                          # numpy
     s.draw(f)
     f.wire_pass(outline=True, **kw)
-    assert_bit_equal(_host(f.get_color_tensor()), want, "numpy inputs")
-    f = _filler(256, 256)                          # caller's device tensors
+    assert_bit_equal(host(f.get_color_tensor()), want, "numpy inputs")
+    f = filler(256, 256)                          # caller's device tensors
     f.render_arrays(*[torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (tri, col, nrm)], clear=True)
     f.wire_pass(outline=True, **kw)
-    assert_bit_equal(_host(f.get_color_tensor()), want, "torch inputs")
-    f = _filler(256, 256)                          # the device-resident model
+    assert_bit_equal(host(f.get_color_tensor()), want, "torch inputs")
+    f = filler(256, 256)                          # the device-resident model
     f.render_model(DeviceModel(m), clear=True)
     f.wire_pass(outline=True, **kw)
-    assert_bit_equal(_host(f.get_color_tensor()), want, "DeviceModel inputs")
+    assert_bit_equal(host(f.get_color_tensor()), want, "DeviceModel inputs")
     s.check_planes(f, "DeviceModel inputs")
 
 
 def test_host_views_show_the_lines_at_the_next_getter_call(soup256):
     s = soup256
-    f = _filler(256, 256)
+    f = filler(256, 256)
     s.draw(f)
     view = f.get_color_buffer()
     assert_bit_equal(view, s.cam.color_buffer, "before the pass")
@@ -356,22 +299,22 @@ def test_renderer_with_supersampling(soup256):
     from cython3dmodelrenderer_amd.renderer import Renderer
     s = soup256
     ill = GuroIllumination(GURO)
-    f = _filler(256, 256)
+    f = filler(256, 256)
     out = Renderer(f, ill, None, 128, 128, on_device=True, wireframe=WIRE, supersample=2).render(s.model)
-    got = _host(out)
+    got = host(out)
     assert got.shape == (128, 128, 3)
-    a = _filler(256, 256)
+    a = filler(256, 256)
     a.render_model(s.model, clear=True)
     ill.draw_illumination_device(a)
-    lit = _host(a.get_color_tensor()).copy()
+    lit = host(a.get_color_tensor()).copy()
     a.wire_pass(**WIRE)
-    assert_bit_equal(_host(f.get_color_tensor()), s.want(base=lit, mask_key="all", **WIRE), "the supersampled frame is the model's")
-    assert_bit_equal(got, _host(a.resolve(2)), "the illumination pass, wire_pass, resolve(2)")
-    b = _filler(256, 256)
+    assert_bit_equal(host(f.get_color_tensor()), s.want(base=lit, mask_key="all", **WIRE), "the supersampled frame is the model's")
+    assert_bit_equal(got, host(a.resolve(2)), "the illumination pass, wire_pass, resolve(2)")
+    b = filler(256, 256)
     b.render_model(s.model, clear=True)
     ill.draw_illumination_device(b)
     b.wire_pass(**dict(WIRE, outline=False))
-    assert (got != _host(b.resolve(2))).any()      # the options reached the pass
+    assert (got != host(b.resolve(2))).any()      # the options reached the pass
     s.check_planes(f, "after the supersampled frame")
 
 
@@ -393,19 +336,19 @@ def test_renderer_draws_the_outline_after_the_shadow(oracle, soup256):
     want = s.want(base=shadowed(lit), mask_key="all", **WIRE)
     other = shadowed(s.want(base=lit, mask_key="all", **WIRE))
     assert (want != other).any()                   # lines inside a shadow: the two orders differ on this scene
-    f, g = _filler(256, 256), _filler(128, 160)
+    f, g = filler(256, 256), filler(128, 160)
     r = Renderer(f, PhongIllumination(lights=SOUP_LIGHTS, **PHONG_KW), on_device=True,
                  shadow=dict(filler=g, R=R, t=t, bias=2e-3, pcf=3, ambient=0.125), wireframe=WIRE)
-    got = _host(r.render(s.model))
+    got = host(r.render(s.model))
     assert_bit_equal(got, want, "Renderer(PhongIllumination, shadow=..., wireframe={outline...})")
-    a, b = _filler(256, 256), _filler(128, 160)    # and by hand
+    a, b = filler(256, 256), filler(128, 160)    # and by hand
     s.draw(a)
     b.render_arrays(ltri, s.col, lnrm, clear=True)
     a.bind_shadow_map(b, ltri)
     a.phong_pass(SOUP_LIGHTS, **PHONG_KW)
     a.shadow_pass(bias=2e-3, pcf=3, ambient=0.125)
     a.wire_pass(**WIRE)
-    assert_bit_equal(got, _host(a.get_color_tensor()), "phong_pass, shadow_pass, wire_pass")
+    assert_bit_equal(got, host(a.get_color_tensor()), "phong_pass, shadow_pass, wire_pass")
 
 
 def test_renderer_with_a_texture_pass(soup256):
@@ -419,29 +362,29 @@ def test_renderer_with_a_texture_pass(soup256):
     uv = rng.uniform(0, 1, (T, 3, 2)).astype(np.float32)
     tex = rng.integers(0, 256, (37, 53, 3), dtype=np.uint8)
     m = Model(s.tri.reshape(-1, 3), idx, uv.reshape(-1, 2), idx, tex, s.nrm.reshape(-1, 3), idx, recalculate_normals=False)
-    f = _filler(256, 256)
-    got = _host(Renderer(f, GuroIllumination(GURO), on_device="fused", texture_pass={"perspective": True},
+    f = filler(256, 256)
+    got = host(Renderer(f, GuroIllumination(GURO), on_device="fused", texture_pass={"perspective": True},
                          wireframe=WIRE).render(m))
-    a = _filler(256, 256)
+    a = filler(256, 256)
     a.bind_texture(m.get_texture_coords_by_triangles(), tex)
     a.render_model(m, clear=True)
     a.texture_pass(perspective=True, light_direction=GuroIllumination(GURO).light_direction)
-    textured = _host(a.get_color_tensor()).copy()
+    textured = host(a.get_color_tensor()).copy()
     assert (textured != s.cam.color_buffer).any()
     assert_bit_equal(got, s.want(base=textured, mask_key="all", **WIRE), "the texture with its light, then the outline")
     a.wire_pass(**WIRE)
-    assert_bit_equal(got, _host(a.get_color_tensor()), "texture_pass, wire_pass")
+    assert_bit_equal(got, host(a.get_color_tensor()), "texture_pass, wire_pass")
 
 
 # ---- 7. errors -----------------------------------------------------------------------------------------------------
 
 def test_errors_name_their_cause(soup256):
     s = soup256
-    f = _filler(256, 256, track_winner=False)
+    f = filler(256, 256, track_winner=False)
     s.draw(f)
     with pytest.raises(ValueError, match="winner plane"):
         f.wire_pass(outline=True)
-    f = _filler(256, 256)
+    f = filler(256, 256)
     with pytest.raises(ValueError, match="no frame has been rendered"):
         f.wire_pass(outline=True)
     s.draw(f)
@@ -449,7 +392,7 @@ def test_errors_name_their_cause(soup256):
     with pytest.raises(ValueError, match="did not start from cleared buffers"):
         f.wire_pass(outline=True)
     with pytest.raises(ValueError, match="swap chain"):
-        _filler(64, 64, pipeline=True).wire_pass(outline=True)
+        filler(64, 64, pipeline=True).wire_pass(outline=True)
     s.draw(f)
     T = len(s.tri)
     for kw, word in ((dict(radius_px=-1), "radius_px must be"), (dict(radius_px=9), "radius_px must be"),
@@ -461,12 +404,12 @@ def test_errors_name_their_cause(soup256):
             f.wire_pass(outline=True, **kw)
     with pytest.raises(ValueError, match=rf"T = {T}.*\({T - 1},\)"):
         f.wire_pass(outline=True, edges=np.zeros(T - 1, np.uint8))
-    assert_bit_equal(_host(f.get_color_tensor()), s.cam.color_buffer, "nothing was written")
+    assert_bit_equal(host(f.get_color_tensor()), s.cam.color_buffer, "nothing was written")
     f.wire_pass(outline=True, width=10.0, feather=4.0)                 # the widest line that fits: radius 8
-    assert_bit_equal(_host(f.get_color_tensor()), s.want(width=10.0, feather=4.0), "the widest line")
+    assert_bit_equal(host(f.get_color_tensor()), s.want(width=10.0, feather=4.0), "the widest line")
     s.draw(f)
     f.wire_pass(**WIRE)                            # and works again
-    assert_bit_equal(_host(f.get_color_tensor()), s.want(mask_key="all", **WIRE), "after the errors")
+    assert_bit_equal(host(f.get_color_tensor()), s.want(mask_key="all", **WIRE), "after the errors")
 
 
 # ---- 8. bin overflow -----------------------------------------------------------------------------------------------
@@ -477,11 +420,11 @@ def test_a_frame_redrawn_after_a_bin_overflow_ends_outlined(oracle):
     s = _Scene(oracle, random_soup(np.random.default_rng(21), 400, 512, size_px=(150, 400), frac_backface=0.0), 512, 512)
     want = s.want(width=3.0, color=LINE)
     for kw in (dict(), dict(presort=True)):
-        f = _filler(512, 512, tile=32, bin_capacity=500, direct_bins=False, **kw)
+        f = filler(512, 512, tile=32, bin_capacity=500, direct_bins=False, **kw)
         s.draw(f)
         need, cap = f.bin_usage()
         assert cap == 500 and need > cap and len(f._pending) == 1     # dropped fragments, nobody has looked yet
         f.wire_pass(width=3.0, color=LINE, outline=True)
         assert not f._pending                                          # grown and redone before the pass
-        assert_bit_equal(_host(f.get_color_tensor()), want, f"a redone frame, {kw}")
+        assert_bit_equal(host(f.get_color_tensor()), want, f"a redone frame, {kw}")
         s.check_planes(f, "a redone frame")

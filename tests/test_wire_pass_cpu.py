@@ -12,19 +12,13 @@ import numpy as np
 import pytest
 
 import overlay_ref
-from util import assert_bit_equal, other_symbols, random_soup, unit_inputs
+from pass_scenes import Frame, capi, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
+from util import assert_bit_equal, other_symbols, unit_inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OVERLAY_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.POINTER(C.c_float),
                     C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                     C.c_uint, C.c_void_p]
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from cython3dmodelrenderer_amd import _build, _capi
-    _build.build()           # hipcc cross-compiles for gfx950 without a GPU
-    return _capi
 
 
 # ---- the host side of the ABI ----------------------------------------------------------------------------------
@@ -113,15 +107,7 @@ def test_overlay_argument_errors_without_a_gpu(capi):
 
 # ---- the model on the oracle's frames --------------------------------------------------------------------------
 
-class _Frame:
-    """A model and the oracle's frame of it: computed once, only read afterwards."""
-
-    def __init__(self, oracle, arrays, H, W):
-        self.tri, self.col, self.nrm = arrays
-        self.cam = oracle.OracleFiller(H, W, fov=45.0)
-        self.cam.render_arrays(self.tri, self.col, self.nrm)
-        self.covered = (self.cam.winner >= 0) & (self.cam.winner < len(self.tri))
-
+class _Frame(Frame):
     def run(self, **kw):
         return overlay_ref.wire_pass(self.cam.color_buffer, self.cam.winner, self.tri, self.cam.proj_mat, **kw)
 
@@ -132,16 +118,8 @@ class _Frame:
 SOUPS = {61: (300, 40, 37, (3.0, 25.0)), 51: (4000, 200, 173, (1.0, 40.0)), 71: (3000, 256, 256, (3.0, 50.0))}
 
 
-@pytest.fixture(scope="module")
-def soups(oracle):
-    return {seed: _Frame(oracle, random_soup(np.random.default_rng(seed), T, max(H, W), size_px=size), H, W)
-            for seed, (T, H, W, size) in SOUPS.items()}
-
-
-@pytest.fixture(scope="module")
-def trex(oracle):
-    from cython3dmodelrenderer_amd import scenes
-    return _Frame(oracle, scenes.load_fixture("trex_inputs.npz"), 256, 256)
+soups = soups_fixture(_Frame, SOUPS)
+trex = trex_fixture(_Frame)
 
 
 # (covered, (a >= 1, 0 < a < 1, off) at width 1 / feather 1, the same at width 3 / feather 0.5) from the host model

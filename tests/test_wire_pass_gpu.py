@@ -9,6 +9,7 @@ import pytest
 import overlay_ref
 import phong_ref
 import shadow_ref
+from pass_scenes import Scene, Soup, edge_mask, filler, host, soup_fixture, trex_arrays, trex_fixture
 from util import assert_bit_equal, random_soup
 
 pytestmark = pytest.mark.gpu
@@ -20,26 +21,7 @@ FILL = (30.0, 35.0, 40.0)
 STYLES = [dict(width=1.0, feather=1.0), dict(width=3.0, feather=0.5), dict(width=0.5, feather=0.25, opacity=0.5)]
 
 
-def _filler(H, W, fov=45.0, **kw):
-    from cython3dmodelrenderer_amd.pixel_buffer_filler import AdvancedPixelBufferFiller
-    kw.setdefault("track_winner", True)
-    return AdvancedPixelBufferFiller(H, W, fov=fov, device="cuda:0", **kw)
-
-
-def _host(t):
-    return t.cpu().numpy()
-
-
-class _Scene:
-    """A model and the oracle's frame of it: computed once, only read afterwards."""
-
-    def __init__(self, oracle, arrays, H, W, y0=0, y1=None):
-        self.tri, self.col, self.nrm = arrays
-        self.H, self.W = H, W
-        self.cam = oracle.OracleFiller(H, W, fov=45.0)
-        self.cam.render_arrays(self.tri, self.col, self.nrm, y0=y0, y1=y1)
-        self.covered = int((self.cam.winner >= 0).sum())
-
+class _Scene(Scene):
     def want(self, base=None, **kw):
         """The model's frame after ``wire_pass(**kw)`` over `base` (the oracle's colours if None)."""
         kw = dict(kw)
@@ -47,42 +29,18 @@ class _Scene:
         return overlay_ref.wire_pass(self.cam.color_buffer if base is None else base, self.cam.winner, self.tri,
                                      self.cam.proj_mat, **kw)
 
-    def draw(self, f):
-        f.render_arrays(self.tri, self.col, self.nrm, clear=True)
-
-    def check_planes(self, f, what):
-        """z, normals and the winner plane are only read."""
-        assert_bit_equal(_host(f.get_z_tensor()), self.cam.z_buffer, f"{what}: z")
-        assert_bit_equal(_host(f.get_normals_tensor()), self.cam.normals_buffer, f"{what}: normals")
-        assert_bit_equal(_host(f.get_winner_tensor()), self.cam.winner, f"{what}: winner")
-
     def check(self, f, what, **kw):
         self.draw(f)
         f.wire_pass(**kw)
         want = self.want(**kw)
-        assert (want.view(np.uint32) != self.cam.color_buffer.view(np.uint32)).any(), (what, "the pass changed nothing")
-        assert_bit_equal(_host(f.get_color_tensor()), want, f"{what} colour")
+        self.assert_changed(want, what)
+        assert_bit_equal(host(f.get_color_tensor()), want, f"{what} colour")
         self.check_planes(f, what)
         return want
 
 
-def _trex_arrays():
-    from cython3dmodelrenderer_amd import scenes
-    return scenes.load_fixture("trex_inputs.npz")
-
-
-@pytest.fixture(scope="module")
-def trex256(oracle):
-    return _Scene(oracle, _trex_arrays(), 256, 256)
-
-
-def _mask(kind, tri, seed=9):
-    from cython3dmodelrenderer_amd.wireframe import feature_edges
-    if kind == "all":
-        return None
-    if kind == "feature":
-        return feature_edges(tri, 30.0)
-    return np.random.default_rng(seed).integers(0, 256, len(tri)).astype(np.uint8)       # bits 3 to 7 are ignored
+trex256 = trex_fixture(_Scene)
+soup256 = soup_fixture(_Scene)
 
 
 # ---- 1. T-Rex ------------------------------------------------------------------------------------------------------
@@ -93,14 +51,14 @@ def test_trex_every_instance(trex256, fill, edges):
     import torch
     s = trex256
     assert s.covered == 15801
-    f = _filler(256, 256)
-    mask = _mask(edges, s.tri)
+    f = filler(256, 256)
+    mask = edge_mask(edges, s.tri)
     for style in STYLES:
         s.check(f, f"trex256, fill {fill}, {edges} edges, {style}", color=LINE, fill=fill, edges=mask, **style)
     if mask is not None:            # a device tensor is taken as it is
         s.draw(f)
         f.wire_pass(color=LINE, fill=fill, edges=torch.from_numpy(mask).cuda(), **STYLES[1])
-        assert_bit_equal(_host(f.get_color_tensor()), s.want(color=LINE, fill=fill, edges=mask, **STYLES[1]), "a device mask")
+        assert_bit_equal(host(f.get_color_tensor()), s.want(color=LINE, fill=fill, edges=mask, **STYLES[1]), "a device mask")
 
 
 # ---- 2. random soups -----------------------------------------------------------------------------------------------
@@ -112,10 +70,10 @@ def test_trex_every_instance(trex256, fill, edges):
 ])
 def test_random_soups(oracle, seed, T, H, W, size, presort):
     s = _Scene(oracle, random_soup(np.random.default_rng(seed), T, max(H, W), size_px=size), H, W)
-    f = _filler(H, W, presort=presort)
+    f = filler(H, W, presort=presort)
     # the mask is indexed in the caller's order while the corners are fetched through d_pos_of: a random mask tells
     # a mix-up of the two orders
-    mask = _mask("random", s.tri, seed)
+    mask = edge_mask("random", s.tri, seed)
     for style in STYLES[:2]:
         s.check(f, f"soup{seed}", color=LINE, **style)
         s.check(f, f"soup{seed}, masked", color=LINE, edges=mask, **style)
@@ -128,8 +86,8 @@ def test_random_soups(oracle, seed, T, H, W, size, presort):
 
 def test_a_row_strip_of_an_odd_frame_leaves_the_other_rows_alone(oracle):
     y0, y1 = 40, 136
-    s = _Scene(oracle, _trex_arrays(), 200, 173, y0=y0, y1=y1)
-    f = _filler(200, 173, row_strip=(y0, y1))
+    s = _Scene(oracle, trex_arrays(), 200, 173, y0=y0, y1=y1)
+    f = filler(200, 173, row_strip=(y0, y1))
     for fill in (None, FILL):
         s.draw(f)
         f.synchronize()
@@ -139,7 +97,7 @@ def test_a_row_strip_of_an_odd_frame_leaves_the_other_rows_alone(oracle):
         f.winner_buffer[:y0] = 0
         f.winner_buffer[y1:] = 1
         f.wire_pass(width=3.0, color=LINE, fill=fill)
-        got = _host(f.get_color_tensor())
+        got = host(f.get_color_tensor())
         assert (got[:y0] == 7.5).all() and (got[y1:] == -2.25).all()
         want = s.want(width=3.0, color=LINE, fill=fill, y0=y0, y1=y1)
         assert (want[y0:y1].view(np.uint32) != s.cam.color_buffer[y0:y1].view(np.uint32)).any()
@@ -159,7 +117,7 @@ def _overlay(lib, winner, tri, P, color, width=1.0, feather=1.0, opacity=1.0, li
         winner.data_ptr(), tri.data_ptr() if T else None, T, None if pos_of is None else pos_of.data_ptr(), _capi.f32_16(P),
         None if edges is None else edges.data_ptr(), (C.c_float * 3)(*line), None if fill is None else (C.c_float * 3)(*fill),
         width, feather, opacity, color.data_ptr(), H, W, 0, H, 0, st), "crender_wire_overlay")
-    return _host(color)
+    return host(color)
 
 
 def test_special_values_through_the_c_entry(oracle):
@@ -280,26 +238,9 @@ def test_the_windows_two_decisions_taken_both_ways():
 
 # ---- 4. host views -------------------------------------------------------------------------------------------------
 
-class _Soup:
-    """What a filler reads off a model."""
-
-    def __init__(self, seed=71, T=3000, res=256):
-        self._vertices_by_triangles, self._colors_by_triangles, self._normals_by_triangles = \
-            random_soup(np.random.default_rng(seed), T, res, size_px=(3.0, 50.0))
-
-
-@pytest.fixture(scope="module")
-def soup256(oracle):
-    m = _Soup()
-    s = _Scene(oracle, (m._vertices_by_triangles, m._colors_by_triangles, m._normals_by_triangles), 256, 256)
-    s.model = m
-    assert s.covered > 10000
-    return s
-
-
 def test_host_views_show_the_lines_at_the_next_getter_call(soup256):
     s = soup256
-    f = _filler(256, 256)
+    f = filler(256, 256)
     s.draw(f)
     view = f.get_color_buffer()
     assert_bit_equal(view, s.cam.color_buffer, "before the pass")
@@ -327,7 +268,7 @@ WIRE = dict(width=2.0, color=LINE, feather=0.5)
 def _by_hand(s, on_device, **wire):
     """draw, the illumination in the form `on_device` names, then the wire pass."""
     from cython3dmodelrenderer_amd.illumination import GuroIllumination
-    a = _filler(256, 256)
+    a = filler(256, 256)
     ill = GuroIllumination(GURO)
     if on_device == "fused":
         ill.fuse_into(a)
@@ -336,9 +277,9 @@ def _by_hand(s, on_device, **wire):
         ill.draw_illumination(a.get_color_buffer(), a.get_normals_buffer())
     elif on_device != "fused":
         ill.draw_illumination_device(a)
-    lit = _host(a.get_color_tensor()).copy() if on_device is not False else None
+    lit = host(a.get_color_tensor()).copy() if on_device is not False else None
     a.wire_pass(**wire)
-    return _host(a.get_color_tensor()), lit
+    return host(a.get_color_tensor()), lit
 
 
 @pytest.mark.parametrize("on_device", [None, True, False, "fused"])
@@ -350,12 +291,12 @@ def test_renderer_draws_the_lines_over_the_light(soup256, on_device):
     if lit is not None:                            # and the hand composition is the model's: unlit lines over the lit frame
         assert_bit_equal(want, s.want(base=lit, **WIRE), "the hand composition")
         assert (want != lit).any()
-    f = _filler(256, 256)
+    f = filler(256, 256)
     r = Renderer(f, GuroIllumination(GURO), on_device=on_device, wireframe=WIRE)
     for _ in range(2):                             # every frame starts from cleared buffers
         out = r.render(s.model)
         assert isinstance(out, np.ndarray) == (on_device in (None, False))
-        assert_bit_equal(np.array(out) if isinstance(out, np.ndarray) else _host(out), want, f"Renderer(on_device={on_device!r})")
+        assert_bit_equal(np.array(out) if isinstance(out, np.ndarray) else host(out), want, f"Renderer(on_device={on_device!r})")
     s.check_planes(f, "after Renderer")
 
 
@@ -364,25 +305,25 @@ def test_renderer_feature_angle_is_the_feature_mask(soup256, trex256):
     from cython3dmodelrenderer_amd.renderer import Renderer
     from cython3dmodelrenderer_amd.wireframe import feature_edges
     tri = trex256.tri
-    m = _Soup.__new__(_Soup)
+    m = Soup.__new__(Soup)
     m._vertices_by_triangles, m._colors_by_triangles, m._normals_by_triangles = tri, trex256.col, trex256.nrm
-    f = _filler(256, 256)
+    f = filler(256, 256)
     r = Renderer(f, GuroIllumination(GURO), on_device=True, wireframe=dict(WIRE, feature_angle=30))
-    got = _host(r.render(m))
+    got = host(r.render(m))
     kept = r._wired[1]
-    assert_bit_equal(_host(r.render(m)), got, "the second frame")
+    assert_bit_equal(host(r.render(m)), got, "the second frame")
     assert r._wired[1] is kept                     # once per model
-    a = _filler(256, 256)
+    a = filler(256, 256)
     a.render_model(m, clear=True)
     GuroIllumination(GURO).draw_illumination_device(a)
-    lit = _host(a.get_color_tensor()).copy()
+    lit = host(a.get_color_tensor()).copy()
     a.wire_pass(edges=feature_edges(tri, 30.0), **WIRE)
-    assert_bit_equal(got, _host(a.get_color_tensor()), "feature_angle=30")
+    assert_bit_equal(got, host(a.get_color_tensor()), "feature_angle=30")
     assert_bit_equal(got, trex256.want(base=lit, edges=feature_edges(tri, 30.0), **WIRE), "the model")
     assert (got != trex256.want(base=lit, **WIRE)).any()
     # another model: another mask
     s = soup256
-    got = _host(r.render(s.model))
+    got = host(r.render(s.model))
     assert len(r._wired[1]) == len(s.tri)
     assert_bit_equal(got, _by_hand(s, True, edges=feature_edges(s.tri, 30.0), **WIRE)[0], "the next model")
 
@@ -409,10 +350,10 @@ def test_renderer_draws_the_lines_after_the_shadow(oracle, soup256):
     want = s.want(base=shadowed(lit), **WIRE)
     other = shadowed(s.want(base=lit, **WIRE))
     assert (want != other).any()                   # lines inside a shadow: the two orders differ on this scene
-    f, g = _filler(256, 256), _filler(128, 160)
+    f, g = filler(256, 256), filler(128, 160)
     r = Renderer(f, PhongIllumination(lights=SOUP_LIGHTS, **PHONG_KW), on_device=True,
                  shadow=dict(filler=g, R=R, t=t, bias=2e-3, pcf=3, ambient=0.125), wireframe=WIRE)
-    assert_bit_equal(_host(r.render(s.model)), want, "Renderer(PhongIllumination, shadow=..., wireframe=...)")
+    assert_bit_equal(host(r.render(s.model)), want, "Renderer(PhongIllumination, shadow=..., wireframe=...)")
 
 
 @pytest.mark.parametrize("on_device", [None, True])
@@ -421,31 +362,31 @@ def test_renderer_with_supersampling(soup256, on_device):
     from cython3dmodelrenderer_amd.renderer import Renderer
     s = soup256
     ill = GuroIllumination(GURO)
-    out = Renderer(_filler(256, 256), ill, None, 128, 128, on_device=on_device, wireframe=WIRE, supersample=2).render(s.model)
+    out = Renderer(filler(256, 256), ill, None, 128, 128, on_device=on_device, wireframe=WIRE, supersample=2).render(s.model)
     assert isinstance(out, np.ndarray) == (on_device is None)
-    got = out if on_device is None else _host(out)
+    got = out if on_device is None else host(out)
     assert got.shape == (128, 128, 3)
-    a = _filler(256, 256)
+    a = filler(256, 256)
     a.render_model(s.model, clear=True)
     ill.draw_illumination_device(a)
     a.wire_pass(**WIRE)
-    assert_bit_equal(got, _host(a.resolve(2)), "the illumination pass, wire_pass, resolve(2)")
+    assert_bit_equal(got, host(a.resolve(2)), "the illumination pass, wire_pass, resolve(2)")
     # the light in the resolve would shade the lines
-    b = _filler(256, 256)
+    b = filler(256, 256)
     b.render_model(s.model, clear=True)
     b.wire_pass(**WIRE)
-    assert (got != _host(b.resolve(2, light_direction=ill.light_direction))).any()
+    assert (got != host(b.resolve(2, light_direction=ill.light_direction))).any()
 
 
 # ---- 6. errors -----------------------------------------------------------------------------------------------------
 
 def test_errors_name_their_cause(soup256):
     s = soup256
-    f = _filler(256, 256, track_winner=False)
+    f = filler(256, 256, track_winner=False)
     s.draw(f)
     with pytest.raises(ValueError, match="winner plane"):
         f.wire_pass()
-    f = _filler(256, 256)
+    f = filler(256, 256)
     with pytest.raises(ValueError, match="no frame has been rendered"):
         f.wire_pass()
     s.draw(f)
@@ -453,7 +394,7 @@ def test_errors_name_their_cause(soup256):
     with pytest.raises(ValueError, match="did not start from cleared buffers"):
         f.wire_pass()
     with pytest.raises(ValueError, match="swap chain"):
-        _filler(64, 64, pipeline=True).wire_pass()
+        filler(64, 64, pipeline=True).wire_pass()
     s.draw(f)
     T = len(s.tri)
     for kw, word in ((dict(width=0.0), "width"), (dict(width=65), "width"), (dict(width=float("nan")), "width"),
@@ -465,9 +406,9 @@ def test_errors_name_their_cause(soup256):
         f.wire_pass(edges=np.zeros(T - 1, np.uint8))
     with pytest.raises(ValueError, match=rf"T = {T}.*int32"):
         f.wire_pass(edges=np.zeros(T, np.int32))
-    assert_bit_equal(_host(f.get_color_tensor()), s.cam.color_buffer, "nothing was written")
+    assert_bit_equal(host(f.get_color_tensor()), s.cam.color_buffer, "nothing was written")
     f.wire_pass(**WIRE)                            # and works again
-    assert_bit_equal(_host(f.get_color_tensor()), s.want(**WIRE), "after the errors")
+    assert_bit_equal(host(f.get_color_tensor()), s.want(**WIRE), "after the errors")
 
 
 # ---- 7. bin overflow -----------------------------------------------------------------------------------------------
@@ -478,11 +419,11 @@ def test_a_frame_redrawn_after_a_bin_overflow_ends_wired(oracle):
     s = _Scene(oracle, random_soup(np.random.default_rng(21), 400, 512, size_px=(150, 400), frac_backface=0.0), 512, 512)
     want = s.want(width=3.0, color=LINE)
     for kw in (dict(), dict(presort=True)):
-        f = _filler(512, 512, tile=32, bin_capacity=500, direct_bins=False, **kw)
+        f = filler(512, 512, tile=32, bin_capacity=500, direct_bins=False, **kw)
         s.draw(f)
         need, cap = f.bin_usage()
         assert cap == 500 and need > cap and len(f._pending) == 1     # dropped fragments, nobody has looked yet
         f.wire_pass(width=3.0, color=LINE)
         assert not f._pending                                          # grown and redone before the pass
-        assert_bit_equal(_host(f.get_color_tensor()), want, f"a redone frame, {kw}")
+        assert_bit_equal(host(f.get_color_tensor()), want, f"a redone frame, {kw}")
         s.check_planes(f, "a redone frame")

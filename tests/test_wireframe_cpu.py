@@ -3,7 +3,6 @@ made by the reference's own code (scripts/make_wire_golden.py), the C ABI's argu
 host model the GPU tests compare with (tests/wire_ref.py)."""
 import ctypes as C
 import hashlib
-import json
 import os
 import re
 import subprocess
@@ -11,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from pass_scenes import capi, wire_golden  # noqa: F401 (fixtures)
 from util import other_symbols, sha
 from wire_ref import HostImage, line_pixels, wire_plane
 
@@ -19,22 +19,9 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
 @pytest.fixture(scope="module")
-def capi():
-    from cython3dmodelrenderer_amd import _build, _capi
-    _build.build()           # hipcc cross-compiles for gfx950 without a GPU
-    return _capi
-
-
-@pytest.fixture(scope="module")
 def lines():
     with np.load(os.path.join(GOLDEN, "wire_lines.npz")) as z:
         return {k: z[k] for k in z.files}
-
-
-@pytest.fixture(scope="module")
-def wire_golden():
-    with open(os.path.join(GOLDEN, "wire_golden.json")) as fh:
-        return json.load(fh)
 
 
 class _Log:

@@ -2,25 +2,17 @@
 reference's planes (tests/golden/wire_golden.json) and the host model of tests/wire_ref.py (itself
 pinned on the reference's lines and the host loop in tests/test_wireframe_cpu.py)."""
 import hashlib
-import json
-import os
 
 import numpy as np
 import pytest
 
+from pass_scenes import wire_golden  # noqa: F401 (fixtures)
 from util import assert_bit_equal, sha
 from wire_ref import wire_plane
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LINE = (255.0, 64.5, 3.0)
-
-
-@pytest.fixture(scope="module")
-def wire_golden():
-    with open(os.path.join(ROOT, "tests", "golden", "wire_golden.json")) as fh:
-        return json.load(fh)
 
 
 def _filler(h, w, edges=True, forced=False, line=LINE):
