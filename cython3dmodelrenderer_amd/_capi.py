@@ -86,6 +86,7 @@ UNIT_SIGNATURES = {}
 WIRE_DOTS, WIRE_FORCE_COLORS, WIRE_CLEAR = 1, 2, 4
 WIRE_MAX_WIDTH = 64
 WIRE_OUTLINE_MAX_RADIUS = 8
+WIRE_CONTOUR_BORDERS = 1
 UNIT_SIGNATURES["wire"] = {
     "crender_wire_key_bytes": (_sz, [_i32, _i32]),
     "crender_wire_draw": (_i32, [_vp, _vp, _i64, _f32p, _vp, _vp, _vp, _vp, _i32, _i32, _u32, _vp, _vp]),
@@ -96,6 +97,8 @@ UNIT_SIGNATURES["wire"] = {
     # the overlay's arguments with d_z after d_winner, and depth_bias and radius_px after the opacity
     "crender_wire_outline": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, _f32p, _f32p, C.c_float, C.c_float, C.c_float,
                                     C.c_float, _i32, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
+    # the edge mask of a view for the two: contour edges from the model's partner table (DeferredPasses.contour_edges)
+    "crender_wire_contours": (_i32, [_vp, _i64, _vp, _f32p, _vp, _vp, _vp, _vp, _i32, _i32, _u32, _vp]),
 }
 
 # the numpy filler's entry points (include/crender_py.h), bound from a table of their own

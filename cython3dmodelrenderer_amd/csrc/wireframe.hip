@@ -10,7 +10,8 @@
 //
 // Also here: the hidden-line overlay over the winner plane of AdvancedPixelBufferFiller (k_wire_overlay, at the end
 // of the file), a deferred pass of the shape of k_phong_shade, and after it the outline (k_wire_outline): the same
-// lines at full width from a neighbourhood pass over the winner plane staged in LDS, of the shape of k_ao_shade.
+// lines at full width from a neighbourhood pass over the winner plane staged in LDS, of the shape of k_ao_shade.  And
+// what the two draw for a view: the contour edges (k_wire_facing, k_wire_contour_mask), classified per frame.
 //
 // Order.  With one constant colour every writer of a pixel stores the same 12 bytes.  With
 // per-triangle colours the last write of the reference's sequence (triangle i, edge e) wins; a line
@@ -408,6 +409,64 @@ __global__ __launch_bounds__(kThreads) void k_wire_outline(const int32_t *__rest
     }
 }
 
+// ---- the contour edges (crender_wire_contours) ------------------------------------------------------------------
+// Which edges the overlay and the outline should draw for THIS view: the edges between a triangle that faces the
+// camera and one that faces away, which no classification made once per model can hold.  Two launches over the
+// triangles, in the caller's order, a triangle per work item in a grid-stride loop: the first leaves the sign of every
+// triangle's projected area in a byte, the second reads the three partners of a triangle from the model's table and
+// compares signs.  A sign is computed once and both sides of an edge read the same two bytes, so the two half-edges of
+// a contour always agree.  No LDS: a wavefront's 64 triangles, partner rows and mask bytes are contiguous as they are;
+// only the three partner signs are gathered, and in a mesh that keeps neighbours near each other they share cache lines.
+
+// The sign of the projected area of the triangle at d_tri[q]: "Phase 1" of crender_wire.h.
+__global__ __launch_bounds__(kThreads) void k_wire_facing(const float *__restrict__ tri, int64_t T,
+                                                           const uint32_t *__restrict__ pos_of, ProjConst P,
+                                                           int8_t *__restrict__ facing)
+{
+    const int64_t stride = (int64_t)gridDim.x * kThreads;
+    for (int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x; t < T; t += stride) {
+        const int64_t q = pos_of ? (int64_t)pos_of[t] : t;
+        int f = 0;
+        if (q < T) {
+            float c[3][3];
+            gather_corners(tri, q, c[0], c[1], c[2]);
+            project_vertex(P, c[0]);            // (the projected z is not used: its divisions are dropped)
+            project_vertex(P, c[1]);
+            project_vertex(P, c[2]);
+            // l03 of raster_math.h's barycentric, in its operations and their order
+            const float l01 = c[1][0] - c[2][0], l02 = c[1][1] - c[2][1];
+            const float A = l01 * (c[0][1] - c[2][1]) - l02 * (c[0][0] - c[2][0]);
+            f = A > 0.0f ? 1 : (A < 0.0f ? -1 : 0);        // (a NaN is neither)
+        }
+        facing[t] = (int8_t)f;
+    }
+}
+
+// The mask of a triangle from its partners' signs: "Phase 2" of crender_wire.h.
+__global__ __launch_bounds__(kThreads) void k_wire_contour_mask(const int32_t *__restrict__ partners,
+                                                                 const uint8_t *__restrict__ fixed,
+                                                                 const int8_t *__restrict__ facing, int64_t T, int borders,
+                                                                 uint8_t *__restrict__ edges)
+{
+    const int64_t stride = (int64_t)gridDim.x * kThreads;
+    for (int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x; t < T; t += stride) {
+        unsigned bits = fixed ? (fixed[t] & 7u) : 0u;
+        const int mine = facing[t];
+        const int32_t *row = partners + t * 3;
+        const int32_t v0 = row[0], v1 = row[1], v2 = row[2];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            const int32_t v = e == 0 ? v0 : e == 1 ? v1 : v2;
+            bool on = borders && (v == -1 || v == -2);
+            const int64_t p = (int64_t)(v >> 1);
+            if (v >= 0 && p < T)                       // anything else is "no partner": never an index
+                on = mine * (int)facing[p] == ((v & 1) ? 1 : -1);
+            bits |= on ? (1u << e) : 0u;
+        }
+        edges[t] = (uint8_t)bits;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -537,6 +596,27 @@ int crender_wire_outline(const int32_t *d_winner, const float *d_z, const float 
                        d_tri, T, d_pos_of, make_proj(P16, W, H), d_edges, S, depth_bias, radius_px, d_color, W, y0, y1,
                        tiles_x);
     CR_LAUNCH_CHECK("k_wire_outline");
+    return CRENDER_OK;
+}
+
+int crender_wire_contours(const float *d_tri, int64_t T, const uint32_t *d_pos_of, const float *P16,
+                          const int32_t *d_partners, const uint8_t *d_static, int8_t *d_facing, uint8_t *d_edges, int H,
+                          int W, unsigned flags, void *stream)
+{
+    if (!P16 || !d_partners || !d_facing || !d_edges)
+        return fail(CRENDER_EINVAL, "crender_wire_contours: P16, d_partners, d_facing or d_edges is NULL");
+    if (T < 0) return fail(CRENDER_EINVAL, "crender_wire_contours: T is negative");
+    if (T > 0 && !d_tri) return fail(CRENDER_EINVAL, "crender_wire_contours: d_tri is NULL with T > 0");
+    if (H < 1 || W < 1) return fail(CRENDER_EINVAL, "crender_wire_contours: H or W is below 1");
+    if (flags & ~CRENDER_WIRE_CONTOUR_BORDERS) return fail(CRENDER_EINVAL, "crender_wire_contours: unknown flag bits");
+    if (T == 0) return CRENDER_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(grid_for((size_t)T, 16384));
+    hipLaunchKernelGGL(k_wire_facing, grid, dim3(kThreads), 0, st, d_tri, T, d_pos_of, make_proj(P16, W, H), d_facing);
+    CR_LAUNCH_CHECK("k_wire_facing");
+    hipLaunchKernelGGL(k_wire_contour_mask, grid, dim3(kThreads), 0, st, d_partners, d_static, d_facing, T,
+                       (flags & CRENDER_WIRE_CONTOUR_BORDERS) ? 1 : 0, d_edges);
+    CR_LAUNCH_CHECK("k_wire_contour_mask");
     return CRENDER_OK;
 }
 

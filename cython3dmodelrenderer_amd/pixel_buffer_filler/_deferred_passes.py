@@ -1,7 +1,7 @@
 """The deferred passes of ``AdvancedPixelBufferFiller`` over the winner plane of its last frame: texture (nearest,
 bilinear, trilinear, anisotropic), shadow, Phong, ambient occlusion and the wireframe overlay, with the texture and shadow-map bindings they
-read.  A mixin beside ``_device_planes.DevicePlanes``: the filler supplies ``device, h, w, y0, y1, _lib, _P`` and
-its frame state (``_pipeline, _inputs, _order, _last_flags, _check_bins``).  What every pass has in common is here
+read, and the classification of a view's contour edges for the overlay (``contour_edges``: it reads no plane).  A mixin
+beside ``_device_planes.DevicePlanes``: the filler supplies ``device, h, w, y0, y1, _lib, _P`` and its frame state (``_pipeline, _inputs, _order, _last_flags, _check_bins``).  What every pass has in common is here
 once: whom it refuses (``_pass_target``), which frame it accepts (``_pass_frame``), and how it is launched
 (``_run_pass``).  A ``*_pass`` method holds its own argument checks and operands.  Also here, because the shadow
 binding converts its vertices as the filler's upload does: the model arrays' way to float32."""
@@ -360,3 +360,45 @@ class DeferredPasses:
             return
         self._run_pass("crender_wire_overlay", tri, T,
                        (edges if T else None, line3, fill3, float(width), float(feather), float(opacity)))
+
+    def contour_edges(self, partners, static=None, borders=False):
+        """uint8 [T] on the device: the edge mask of the LAST frame's view, ready for ``wire_pass(edges=...)``
+        (``crender_wire_contours``, include/crender_wire.h).  Bit e of entry t is set if the edge of triangle t from
+        corner e to corner (e + 1) % 3 is a contour — it lies between a triangle whose projection is wound one way and
+        one wound the other: the line that bounds a smooth body, which changes with every pose — or is set in `static`,
+        or, with `borders`, has no partner or more than one.  `partners` is the mesh's partner table, int32 [T, 3]
+        (``wireframe.edge_partners``, made once per model), and `static` None or a uint8 [T] mask of edges drawn in
+        every view (``wireframe.feature_edges``); both numpy arrays or device tensors in the caller's triangle order,
+        with T that of the last frame, which, as for ``wire_pass``, started from cleared buffers and is not a swap
+        chain's.  Two launches over the triangles on torch's current stream.
+
+        The pass reads the last frame's triangles and the camera's projection, never a plane: it needs no winner plane,
+        does not settle the frame (a frame rendered again after a bin overflow is drawn from the same triangles) and
+        does not synchronise."""
+        if self._pipeline:
+            raise ValueError("contour_edges is not available on a swap chain (pipeline=True): per-slot passes are not implemented")
+        tri, T = self._pass_frame("contour_edges")
+        p = partners if isinstance(partners, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(partners))
+        if p.dtype != torch.int32 or p.dim() != 2 or p.shape[1] != 3:
+            raise ValueError(f"partners must be int32 [T, 3] (wireframe.edge_partners), got {p.dtype} {tuple(p.shape)}")
+        if p.shape[0] != T:
+            raise ValueError(f"contour_edges: the partner table holds {p.shape[0]} triangles, the last frame drew {T}")
+        if static is not None:
+            s = static if isinstance(static, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(static))
+            if s.dtype != torch.uint8 or s.dim() != 1:
+                raise ValueError(f"static must be uint8 [T], got {s.dtype} {tuple(s.shape)}")
+            if s.shape[0] != T:
+                raise ValueError(f"contour_edges: the static mask holds {s.shape[0]} triangles, the last frame drew {T}")
+            static = s.to(self.device).contiguous()
+        p = p.to(self.device).contiguous()
+        facing = torch.empty(T, dtype=torch.int8, device=self.device)
+        edges = torch.empty(T, dtype=torch.uint8, device=self.device)
+        if T == 0:
+            return edges
+        pos_of = None if self._order is None else self._order[1]
+        args = (tri if T else None, T, pos_of, self._P, p, static, facing, edges, self.h, self.w,
+                _capi.WIRE_CONTOUR_BORDERS if borders else 0)
+        with torch.cuda.device(self.device):
+            _capi.check(self._lib.crender_wire_contours(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args],
+                                                        self._stream()), "crender_wire_contours")
+        return edges

@@ -105,6 +105,13 @@ class Renderer:
             if not hasattr(pixel_buffer_filler, "wire_pass"):
                 raise ValueError("Renderer(wireframe=...) needs a filler with a wireframe pass "
                                  f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no wire_pass()")
+            # ``contours`` (True): the edge mask is rebuilt for every frame's view on the device
+            # (``AdvancedPixelBufferFiller.contour_edges``) from the model's partner table (``wireframe.edge_partners``,
+            # once per model, on the device for a device model): the contour edges, over the ``feature_angle`` mask or
+            # an explicit ``edges`` if there is one, and with ``borders`` (default True) the rim of an open mesh.
+            if wireframe.get("contours") and not hasattr(pixel_buffer_filler, "contour_edges"):
+                raise ValueError("Renderer(wireframe={'contours': True}) needs a filler that classifies contour edges "
+                                 f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no contour_edges()")
             self.wireframe = dict(wireframe)
         # A PhongIllumination is a deferred pass of the filler over its winner plane (``phong_pass``): every frame
         # starts from cleared buffers (one model per frame, as "fused"); the draw, then the texture pass (unlit) if
@@ -177,17 +184,29 @@ class Renderer:
             return
         opts = dict(self.wireframe)
         angle = opts.pop("feature_angle", None)
-        if angle is not None:
+        contours, borders = opts.pop("contours", False), opts.pop("borders", True)
+        if angle is not None or contours:
             if self._wired is None or self._wired[0]() is not model:     # once per model, not per frame
-                from .wireframe import feature_edges
+                from .wireframe import edge_partners, feature_edges
                 tri = model._vertices_by_triangles
-                mask = feature_edges(tri.cpu().numpy() if hasattr(tri, "cpu") else tri, angle)
                 device = getattr(self.pixel_buffer_filler, "device", None)
-                if device is not None:
-                    import torch
-                    mask = torch.from_numpy(mask).to(device)
-                self._wired = (weakref.ref(model), mask)
-            opts["edges"] = self._wired[1]
+                mask = partners = None
+                if angle is not None:
+                    mask = feature_edges(tri.cpu().numpy() if hasattr(tri, "cpu") else tri, angle)
+                    if device is not None:
+                        import torch
+                        mask = torch.from_numpy(mask).to(device)
+                if contours:
+                    partners = edge_partners(tri)      # (a device model's table is made on the device)
+                    if device is not None and not hasattr(partners, "data_ptr"):
+                        import torch
+                        partners = torch.from_numpy(partners).to(device)
+                self._wired = (weakref.ref(model), mask, partners)
+            if angle is not None:
+                opts["edges"] = self._wired[1]
+        if contours:
+            # the mask of this frame's view: the contours, over the static mask if there is one
+            opts["edges"] = self.pixel_buffer_filler.contour_edges(self._wired[2], static=opts.get("edges"), borders=bool(borders))
         self.pixel_buffer_filler.wire_pass(**opts)
 
     def render(self, model, normalize_model=False, random_colors=True):

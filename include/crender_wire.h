@@ -1,7 +1,8 @@
 /*
  * crender_wire.h — C ABI of the wireframe filler (EdgeOnlyPixelBufferFiller) of
  * libcrender_hip.so, and of the hidden-line overlay over AdvancedPixelBufferFiller's winner plane
- * (crender_wire_overlay, and crender_wire_outline for lines at full width, at the end).  Same conventions as crender_hip.h: raw device pointers, an int
+ * (crender_wire_overlay, and crender_wire_outline for lines at full width, at the end; crender_wire_contours picks the edges
+ * of a view for both).  Same conventions as crender_hip.h: raw device pointers, an int
  * status (CRENDER_OK or a CRENDER_E* code, text in crender_last_error()), work enqueued
  * on `stream` and nothing synchronised.  Reference files cited below are in the
  * reference's crender/py/ (the crender/cy/ copies are identical but for one import).
@@ -193,6 +194,69 @@ CRENDER_API int crender_wire_outline(const int32_t *d_winner, const float *d_z, 
                                      const float *line3, const float *fill3, float width, float feather, float opacity,
                                      float depth_bias, int radius_px, float *d_color,
                                      int H, int W, int y0, int y1, unsigned flags, void *stream);
+
+/*
+ * The contour edges: the edge mask of ONE view, for crender_wire_overlay / crender_wire_outline to draw.  A contour
+ * edge lies between a triangle that faces the camera and one that faces away; it bounds a smooth body, moves with every
+ * pose, and is not among the creases and borders a mask made once per model holds.  The mesh's connectivity does not
+ * move: it comes in as the partner table, made once per model (wireframe.edge_partners).
+ *
+ * The partner table, int32 [T][3] in the caller's triangle order.  Two half-edges are the same edge when their end points
+ * have the same float32 bit patterns, as an unordered pair.  Entry [t][e], for the half-edge from corner e to corner
+ * (e + 1) % 3 of triangle t:
+ *   -1          the edge has no other half-edge (a border);
+ *   -2          it has more than one other half-edge;
+ *   2 * p + s   otherwise: p is the triangle that holds the other half-edge (t itself for a triangle with two equal
+ *               corners), s = 0 if the two half-edges run in opposite directions between the two bit patterns (a
+ *               consistent winding), s = 1 if they run the same way.
+ * Direction.  A corner is the triple of its coordinates' bit patterns as unsigned integers; triples are compared
+ * lexicographically, coordinate 0 first.  A half-edge is SWAPPED if its first corner compares greater than its second,
+ * and unswapped otherwise (so also when the two are equal).  Two half-edges of one edge run the same way iff both are
+ * swapped or neither is.
+ *
+ * Result contract.
+ *
+ *   Arithmetic   every step below is ONE float32 operation, rounded once, with IEEE division (no contraction into fused
+ *                multiply-adds, no reciprocal, denormals kept).
+ *   Phase 1      for every triangle t, in the caller's order: q = d_pos_of ? d_pos_of[t] : t.  If q >= T, facing[t] = 0.
+ *                Otherwise the corners of d_tri[q] are projected as crender_project projects them (.pyx:116-130), with
+ *                xs = (float)(W / 2.0) and ys = (float)(H / 2.0): (x_k, y_k), k = 0, 1, 2.  Nothing is clipped: a corner
+ *                behind the camera projects as the rasterizer projects it.  Then
+ *                  l1 = x1 - x2,   l2 = y1 - y2
+ *                  A  = l1 * (y0 - y2) - l2 * (x0 - x2)       (the denominator l03 of the barycentric b1,
+ *                                                              math_utils.pyx:8-34, in its operations and their order)
+ *                  facing[t] = A > 0 ? 1 : (A < 0 ? -1 : 0)
+ *                A triangle without projected area and every NaN give 0.
+ *   Phase 2      for every triangle t, bit e (e = 0, 1, 2) of d_edges[t] is set iff one of these holds, with
+ *                v = d_partners[t][e]:
+ *                  - d_static is given and bit e of d_static[t] is set (its bits 3 to 7 are ignored);
+ *                  - flags has CRENDER_WIRE_CONTOUR_BORDERS, and v is -1 or -2;
+ *                  - v >= 0, p = v >> 1 is below T, and facing[t] * facing[p] is -1 for s = v & 1 = 0, or +1 for s = 1.
+ *                    A facing of 0 at either side never makes a contour.
+ *                Every other v (below -2, or with p >= T) is "no partner": it sets nothing and is never used as an
+ *                index, so no table makes the pass read outside d_facing.  Bits 3 to 7 of d_edges[t] are written 0.
+ *   Symmetry     a triangle's sign is computed once and both sides of an edge read the same two bytes: if the table
+ *                names the two half-edges of an edge as each other's partners, with one s, both get their bit or neither.
+ *
+ * d_edges is in the caller's order whatever d_pos_of says, as the passes want it.
+ */
+#define CRENDER_WIRE_CONTOUR_BORDERS 1u     /* also draw the edges without a partner, or with more than one */
+
+/* Classify the edges of T triangles for the view P16 of an H x W frame.
+ *   d_tri      float32 [T][3][3], UNPROJECTED camera-frame vertices (may be NULL if T == 0): the last frame's
+ *   d_pos_of   NULL, or uint32 [T]: triangle t sits at d_tri[d_pos_of[t]]; an entry >= T gives t the facing 0
+ *   P16        HOST float[16], the camera's projection matrix (crender_projection_matrix)
+ *   d_partners int32 [T][3], the partner table, in the CALLER's triangle order
+ *   d_static   NULL, or uint8 [T] in the caller's order: edges drawn in every view (creases, an explicit mask)
+ *   d_facing   int8 [T] of scratch, the caller's: holds the signs of phase 1 afterwards.  Nothing is allocated here.
+ *   d_edges    uint8 [T], the result
+ *   flags      0 or CRENDER_WIRE_CONTOUR_BORDERS
+ * CRENDER_EINVAL, before anything is dereferenced or launched, for: a NULL P16, d_partners, d_facing or d_edges, T < 0,
+ * T > 0 without d_tri, H or W < 1, any other flag bit.  T == 0 returns CRENDER_OK without a launch.  Two launches on
+ * `stream`, in order; no synchronisation. */
+CRENDER_API int crender_wire_contours(const float *d_tri, int64_t T, const uint32_t *d_pos_of, const float *P16,
+                                      const int32_t *d_partners, const uint8_t *d_static, int8_t *d_facing,
+                                      uint8_t *d_edges, int H, int W, unsigned flags, void *stream);
 
 #ifdef __cplusplus
 }
