@@ -70,27 +70,34 @@ __global__ __launch_bounds__(kThreads) void k_model_shift(float *__restrict__ v,
     }
 }
 
-// vtx -= mean; vtx *= coef; vtx += mean, three float32 passes in place (model.py:222-228)
+// vtx -= mean; vtx *= coef; vtx += mean, three passes in place (model.py:222-228).  The subtraction and
+// the addition are float32; the multiply is float32 for a float32 (or weak Python) coefficient and, where
+// numpy promotes the product (a float64 scalar or array, an int32 / int64 array), the float64 product
+// rounded once by the in-place store.  One coefficient per component: numpy broadcasts a 3-vector.
 __global__ __launch_bounds__(kThreads) void k_model_scale(float *__restrict__ v, size_t n,
-                                                          const float *__restrict__ mean3, float coef, int keep)
+                                                          const float *__restrict__ mean3, double c0, double c1,
+                                                          double c2, int in_double, int keep)
 {
     const size_t stride = (size_t)gridDim.x * kThreads;
     for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
+        const int c = (int)(i % 3);
+        const double coef = c == 0 ? c0 : c == 1 ? c1 : c2;
         float x = v[i];
         if (keep) {
-            const float m = mean3[i % 3];
+            const float m = mean3[c];
             x = x - m;
-            x = x * coef;
+            x = in_double ? (float)((double)x * coef) : x * (float)coef;
             x = x + m;
         } else {
-            x = x * coef;
+            x = in_double ? (float)((double)x * coef) : x * (float)coef;
         }
         v[i] = x;
     }
 }
 
 // vertices.mean(axis=0): numpy adds the rows one after another into a float32 accumulator per
-// component — the first row is the start value, there is no pairwise summation along a strided
+// component — the accumulator starts from +0 like every add.reduce (a column of -0 sums to +0, not
+// -0: tests/test_model_ops_cpu.py), there is no pairwise summation along a strided
 // axis — and divides by the intp count in float64, stored as float32.  One lane per component; the
 // chain of additions is inherently serial (4 ns each), the LOADS are not: 32 rows are requested
 // together before their 32 additions (one dependent load per row was 0.3 us per vertex: seconds
@@ -100,7 +107,7 @@ __global__ void k_model_mean(const float *__restrict__ v, int64_t V, float *__re
     const int c = threadIdx.x;
     if (c >= 3) return;
     constexpr int kAhead = 32;
-    float acc = v[c];
+    float acc = 0.0f + v[c];
     int64_t i = 1;
     for (; i + kAhead <= V; i += kAhead) {
         float x[kAhead];
@@ -349,16 +356,34 @@ int crender_model_shift(float *d_vertices, int64_t V, const double *shift3, int 
     return CRENDER_OK;
 }
 
+static int model_scale(const char *who, float *d_vertices, int64_t V, const float *d_mean3, double c0, double c1,
+                       double c2, int in_double, int keep_position, void *stream)
+{
+    if (V < 0 || (V > 0 && !d_vertices) || (keep_position && !d_mean3)) {
+        char msg[96];
+        std::snprintf(msg, sizeof msg, "%s: bad argument", who);
+        return fail(CRENDER_EINVAL, msg);
+    }
+    if (V == 0) return CRENDER_OK;
+    hipLaunchKernelGGL(k_model_scale, dim3(grid_for((size_t)V * 3, 4096)), dim3(kThreads), 0,
+                       static_cast<hipStream_t>(stream), d_vertices, (size_t)V * 3, d_mean3, c0, c1, c2, in_double,
+                       keep_position);
+    CR_LAUNCH_CHECK("k_model_scale");
+    return CRENDER_OK;
+}
+
 int crender_model_scale(float *d_vertices, int64_t V, const float *d_mean3, float coef, int keep_position,
                         void *stream)
 {
-    if (V < 0 || (V > 0 && !d_vertices) || (keep_position && !d_mean3))
-        return fail(CRENDER_EINVAL, "crender_model_scale: bad argument");
-    if (V == 0) return CRENDER_OK;
-    hipLaunchKernelGGL(k_model_scale, dim3(grid_for((size_t)V * 3, 4096)), dim3(kThreads), 0,
-                       static_cast<hipStream_t>(stream), d_vertices, (size_t)V * 3, d_mean3, coef, keep_position);
-    CR_LAUNCH_CHECK("k_model_scale");
-    return CRENDER_OK;
+    return model_scale("crender_model_scale", d_vertices, V, d_mean3, coef, coef, coef, 0, keep_position, stream);
+}
+
+int crender_model_scale3(float *d_vertices, int64_t V, const float *d_mean3, const double *coef3,
+                         int coef_is_float32, int keep_position, void *stream)
+{
+    if (!coef3) return fail(CRENDER_EINVAL, "crender_model_scale3: bad argument");
+    return model_scale("crender_model_scale3", d_vertices, V, d_mean3, coef3[0], coef3[1], coef3[2],
+                       coef_is_float32 ? 0 : 1, keep_position, stream);
 }
 
 int crender_model_stats(const float *d_vertices, int64_t V, float *d_mean3, float *d_max_span, void *stream)

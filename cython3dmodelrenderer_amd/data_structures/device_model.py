@@ -7,7 +7,13 @@ and the transforms that are exactly reproducible there running as HIP kernels:
 
 each in numpy's own operation order (float32 elementwise; float64 where numpy promotes; the mean
 as numpy's row-after-row float32 sum), so the arrays handed to the filler are, bit for bit, what
-the host ``Model`` produces.
+the host ``Model`` produces.  Whether numpy promotes ``vertices + shift`` or ``vertices *= coef``
+depends on the argument as the caller passed it, not on its values: a Python number is weak (it is
+rounded to float32 and the arithmetic stays float32), a list or tuple becomes a float64 or int64
+array, a float64 scalar or 0-d array and int32 / int64 arrays promote to float64, float16, float32,
+bool and 8- or 16-bit integer arrays do not.  ``host_arithmetic_is_float64`` asks the installed numpy
+(``np.result_type``) instead of listing these; ``shift`` and ``scale`` follow it, and raise for an
+argument numpy would refuse or take out of float32 / float64.
 
 ``rotate`` — the matrix product and the vertex-normal computation it triggers (model.py:175-208,
 238-256: 1.2 s of Python loops for T-Rex on the host) — runs on the device too
@@ -40,6 +46,27 @@ import torch
 
 from .. import _capi
 from .model import Model
+
+
+def host_arithmetic_is_float64(arg):
+    """Whether the host ``Model`` takes ``float32_vertices + arg`` (``shift``) or ``float32_vertices *= arg``
+    (``scale``) in float64 — numpy's own answer for ``arg`` as the caller passed it, Python scalars weak or
+    not as the installed numpy has them.  TypeError for what is neither float32 nor float64 arithmetic
+    (complex, long double, strings, objects: numpy refuses them or leaves the Model's float32)."""
+    if not isinstance(arg, (bool, int, float, complex, np.generic, np.ndarray)):
+        arg = np.asarray(arg)                    # a list or a tuple is an array to numpy's operators
+    dtype = np.result_type(np.float32, arg)
+    if dtype == np.float32:
+        return False
+    if dtype == np.float64:
+        return True
+    raise TypeError(f"the host Model's arithmetic with {type(arg).__name__} is {dtype}, not float32 or float64")
+
+
+def _three_as_the_host_casts(arg, in_double):
+    """`arg` cast as numpy casts it for the operation (float32 or float64) and broadcast to one per component."""
+    arr = np.asarray(arg).astype(np.float64 if in_double else np.float32)
+    return (C.c_double * 3)(*[float(v) for v in np.broadcast_to(arr, (3,))])
 
 
 class DeviceModel:
@@ -156,25 +183,23 @@ class DeviceModel:
 
     # ----------------------------------------------------------- reference API --
     def shift(self, shift):
-        arr = np.asarray(shift)
-        if arr.shape != (3,):
-            arr = np.broadcast_to(arr, (3,))
-        is_f32 = arr.dtype == np.float32 or arr.dtype == np.float16
-        s3 = (C.c_double * 3)(*[float(v) for v in arr])
+        in_double = host_arithmetic_is_float64(shift)
+        s3 = _three_as_the_host_casts(shift, in_double)
         with torch.cuda.device(self.device):
             _capi.check(self._lib.crender_model_shift(self._vertices.data_ptr(), self._vertices.shape[0], s3,
-                                                      1 if is_f32 else 0, self._stream()), "crender_model_shift")
+                                                      0 if in_double else 1, self._stream()), "crender_model_shift")
         self._update()
 
     def scale(self, scale_coef, keep_position=True):
-        coef = np.float32(scale_coef)            # vtx *= coef is a float32 in-place multiply
+        in_double = host_arithmetic_is_float64(scale_coef)     # vtx *= coef: in place, float64 where numpy promotes
+        c3 = _three_as_the_host_casts(scale_coef, in_double)
         if keep_position:
             self._ensure_stats()                 # (the mean the reference subtracts: of the vertices as they are)
         with torch.cuda.device(self.device):
-            _capi.check(self._lib.crender_model_scale(self._vertices.data_ptr(), self._vertices.shape[0],
-                                                      self._stats.data_ptr(), C.c_float(float(coef)),
-                                                      1 if keep_position else 0, self._stream()),
-                        "crender_model_scale")
+            _capi.check(self._lib.crender_model_scale3(self._vertices.data_ptr(), self._vertices.shape[0],
+                                                       self._stats.data_ptr(), c3, 0 if in_double else 1,
+                                                       1 if keep_position else 0, self._stream()),
+                        "crender_model_scale3")
         self._update()
 
     def rotate(self, angles, on_host=False):

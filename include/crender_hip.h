@@ -356,10 +356,21 @@ CRENDER_API int crender_present_u8(const float *d_color, unsigned char *d_out, i
 /* next row f2: the Model's reproducible transforms on a device-resident
  * vertex buffer d_vertices = float32 [V][3] — crender/cy/data_structures/model.py:153-236.
  *   crender_model_shift   Model.shift (:213-216): vertices + shift.  shift_is_float32 = 1: the
- *                         caller's shift was a float32 array (float32 sum); 0: a Python list / a
- *                         float64 array (numpy promotes the sum to float64, stored as float32).
+ *                         caller's shift leaves the sum float32 (a float32 / float16 / small-integer
+ *                         array, a Python number: the shift is rounded to float32 first); 0: a Python
+ *                         list, a float64 scalar or array, an int32 / int64 array (numpy promotes the sum
+ *                         to float64, stored as float32).
  *   crender_model_scale   Model.scale (:218-236): vtx -= mean; vtx *= coef; vtx += mean in float32
  *                         (keep_position), or vtx *= coef.  d_mean3: DEVICE pointer to 3 floats.
+ *   crender_model_scale3  the same with one coefficient per component (numpy broadcasts a 3-vector) and
+ *                         numpy's promotion of the multiply.  coef_is_float32 = 1: x * (float)coef3[c], what
+ *                         crender_model_scale computes (a float32 / float16 / small-integer array or scalar,
+ *                         a Python number); 0: (float)((double)x * coef3[c]) — a float64 scalar or array or
+ *                         an int32 / int64 array promotes the in-place product to float64, which the store
+ *                         rounds once.  Only the multiply: the mean is subtracted and added in float32
+ *                         either way.  The caller asks numpy which it is (np.result_type of float32 and the
+ *                         argument: DeviceModel's host_arithmetic_is_float64); crender_model_shift's
+ *                         shift_is_float32 is the same rule for the sum.
  *   crender_model_stats   _update_vertices_and_normals (:153-160): mean vertex (numpy's float32
  *                         row-after-row sum, float64 division) and max span (max float32 norm of
  *                         vertices - mean) into DEVICE memory d_mean3 [3], d_max_span [1].
@@ -400,6 +411,8 @@ CRENDER_API int crender_model_shift(float *d_vertices, int64_t V, const double *
                                     int shift_is_float32, void *stream);
 CRENDER_API int crender_model_scale(float *d_vertices, int64_t V, const float *d_mean3, float coef,
                                     int keep_position, void *stream);
+CRENDER_API int crender_model_scale3(float *d_vertices, int64_t V, const float *d_mean3, const double *coef3,
+                                     int coef_is_float32, int keep_position, void *stream);
 CRENDER_API int crender_model_stats(const float *d_vertices, int64_t V, float *d_mean3,
                                     float *d_max_span, void *stream);
 CRENDER_API int crender_model_gather(const float *d_attr, const int32_t *d_index, float *d_out,

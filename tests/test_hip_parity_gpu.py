@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+from model_ref import plain_f32_vertex_normals as _plain_f32_vertex_normals
 from util import assert_bit_equal, numpy_dot3_is_double_accumulated, random_soup, sha
 
 pytestmark = pytest.mark.gpu
@@ -2162,42 +2163,6 @@ def test_usage_records_through_recycled_plans(hip, oracle):
     z, cb, nb, _ = fb.numpy()
     assert_bit_equal(z, ref.z_buffer, "after 1 100 recycled plans: z")
     assert_bit_equal(cb, ref.color_buffer, "after 1 100 recycled plans: colour")
-
-
-def _plain_f32_vertex_normals(vertices, faces):
-    """model.py:175-208 with every operation spelled out (no BLAS call): what the device kernels
-    compute, on the host.  A dot of two float32 3-vectors = float32 products summed in float64 and
-    rounded once (what numpy's OpenBLAS sdot does, tests/test_host_cpu.py)."""
-    f32 = np.float32
-
-    def dot3(a, b):
-        return f32(np.float64(f32(a[0] * b[0])) + np.float64(f32(a[1] * b[1])) + np.float64(f32(a[2] * b[2])))
-    tri = vertices[faces]
-    a = tri[:, 1] - tri[:, 0]
-    b = tri[:, 1] - tri[:, 2]
-    n = np.stack([-(a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1]), -(a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2]),
-                  -(a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0])], axis=1).astype(f32)
-    sq = n * n
-    ln = np.sqrt((sq[:, 0].astype(np.float64) + sq[:, 1].astype(np.float64) + sq[:, 2].astype(np.float64)).astype(f32))
-    with np.errstate(invalid="ignore", divide="ignore"):
-        fn = np.where(ln[:, None] == 0, n, n / ln[:, None]).astype(f32)
-    out = np.zeros((len(vertices), 3), f32)
-    buckets = [[] for _ in range(len(vertices))]
-    for t in range(len(faces)):
-        for v in faces[t]:
-            bk = buckets[v]
-            nn = fn[t]
-            if not any(dot3(e, nn) >= 1 for e in bk):
-                bk.append(nn)
-    for v, bk in enumerate(buckets):
-        if bk:
-            acc = np.zeros(3, f32)
-            for e in bk:
-                acc = (acc + e).astype(f32)
-            r = (acc.astype(np.float64) / len(bk)).astype(f32)
-            l = np.sqrt(dot3(r, r))
-            out[v] = r if l == 0 else (r / l).astype(f32)
-    return out
 
 
 def test_device_model_rotate_and_normals():

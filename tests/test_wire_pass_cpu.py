@@ -44,7 +44,7 @@ def test_overlay_symbol_is_declared_exported_and_bound(capi):
 
 def test_the_build_lists_are_unchanged():
     from cython3dmodelrenderer_amd import _build
-    assert _build.source_sha16() == "f3a47bfc1afb1a02"
+    assert _build.source_sha16() == "35a9bf480abfca1e"
     assert _build.library_sources() == ["abi.hip", "binning.hip", "raster.hip", "model_ops.hip", "wireframe.hip", "pyfill.hip",
                                         "texture.hip", "texmip.hip", "texaniso.hip", "resolve.hip", "shadow.hip", "phong.hip",
                                         "ao.hip", "chain.hip"]
