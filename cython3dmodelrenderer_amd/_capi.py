@@ -100,6 +100,9 @@ UNIT_SIGNATURES["wire"] = {
                                     C.c_float, _i32, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
     # the edge mask of a view for the two: contour edges from the model's partner table (DeferredPasses.contour_edges)
     "crender_wire_contours": (_i32, [_vp, _i64, _vp, _f32p, _vp, _vp, _vp, _vp, _i32, _i32, _u32, _vp]),
+    # geometric edge anti-aliasing over the winner plane (DeferredPasses.edge_aa): the outline's planes and mask, the
+    # result plane in front of the colour plane, which is only read
+    "crender_wire_edge_aa": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
 }
 
 # the numpy filler's entry points (include/crender_py.h), bound from a table of their own

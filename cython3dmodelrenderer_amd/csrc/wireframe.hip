@@ -11,7 +11,8 @@
 // Also here: the hidden-line overlay over the winner plane of AdvancedPixelBufferFiller (k_wire_overlay, at the end
 // of the file), a deferred pass of the shape of k_phong_shade, and after it the outline (k_wire_outline): the same
 // lines at full width from a neighbourhood pass over the winner plane staged in LDS, of the shape of k_ao_shade.  And
-// what the two draw for a view: the contour edges (k_wire_facing, k_wire_contour_mask), classified per frame.
+// what the two draw for a view: the contour edges (k_wire_facing, k_wire_contour_mask), classified per frame.  And the
+// coverage of boundary pixels from the same staged winners (k_wire_edge_aa, after the outline): geometric anti-aliasing.
 //
 // Order.  With one constant colour every writer of a pixel stores the same 12 bytes.  With
 // per-triangle colours the last write of the reference's sequence (triangle i, edge e) wins; a line
@@ -409,6 +410,158 @@ __global__ __launch_bounds__(kThreads) void k_wire_outline(const int32_t *__rest
     }
 }
 
+// ---- geometric edge anti-aliasing (crender_wire_edge_aa) --------------------------------------------------------
+// The coverage of a boundary pixel from the winner plane: where a pixel's left, right, upper or lower neighbour names
+// another triangle, the nearer of the two triangles (by the z plane) has an edge that crosses the line between the two
+// pixel centres, the rasterizer's own barycentrics at the two centres say where, and the pixel is blended with the one
+// neighbour that reaches farthest into its cell.  The outline's shape at R = 1: a workgroup per tile of 32 x 32 pixels,
+// the validated winners of the tile and a halo of one pixel staged in LDS with unit-stride loads (34^2 words), a
+// wavefront two rows of 32, so that each of the four taps is a ds_read_b32 without bank conflicts.  The colour plane is
+// only read and the result goes to a plane of its own (a pixel reads its neighbours' colours).
+//
+// Work.  A wavefront none of whose lanes has a differing neighbour copies its 64 colours, 12 bytes a lane at unit
+// stride, and that is nearly every wavefront of a frame: a scalar branch.  A lane with a differing neighbour reads z,
+// and for each such neighbour gathers and projects the near triangle (nine divisions), takes its barycentrics at both
+// centres (six) and up to three exits.  The pixel's own winner is the near triangle in most directions: it is
+// projected once per pixel; the neighbour's triangle is kept while the next direction names the same one.
+
+// The projected corners of the triangle at d_tri[pos].
+CR_DEV TriXYZ near_triangle(const float *__restrict__ tri, int64_t pos, const ProjConst &P)
+{
+    float c[3][3];
+    gather_corners(tri, pos, c[0], c[1], c[2]);
+    project_vertex(P, c[0]);
+    project_vertex(P, c[1]);
+    project_vertex(P, c[2]);
+    return TriXYZ{c[0][0], c[0][1], c[0][2], c[1][0], c[1][1], c[1][2], c[2][0], c[2][1], c[2][2]};
+}
+
+__global__ __launch_bounds__(kThreads) void k_wire_edge_aa(const int32_t *__restrict__ win, const float *__restrict__ zb,
+                                                            const float *__restrict__ tri, int64_t T,
+                                                            const uint32_t *__restrict__ pos_of, ProjConst P,
+                                                            const uint8_t *__restrict__ edges, float *__restrict__ ob,
+                                                            const float *__restrict__ cb, int W, int y0, int y1,
+                                                            int tiles_x)
+{
+    extern __shared__ int32_t s_win[];          // [kTile + 2][kTile + 2]
+    constexpr int pitch = kTile + 2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lx = threadIdx.x & (kTile - 1), ly = threadIdx.x >> 5;
+    const int tile = blockIdx.x, ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int x0 = tx * kTile, ty0 = y0 + ty * kTile;
+    // ---- stage the validated winners of the tile and its halo: a wavefront per row
+    for (int sy = wave; sy < pitch; sy += kThreads / 64) {
+        const int gy = ty0 - 1 + sy;
+        const bool row_in = gy >= y0 && gy < y1;
+        if (lane < pitch) {
+            const int gx = x0 - 1 + lane;
+            int32_t v = -1;
+            if (row_in && gx >= 0 && gx < W) {
+                const int32_t w = win[(size_t)gy * (size_t)W + (size_t)gx];
+                if (w >= 0 && w < T && (!pos_of || pos_of[w] < T)) v = w;
+            }
+            s_win[sy * pitch + lane] = v;
+        }
+    }
+    __syncthreads();
+    // ---- the tile's pixels, 32 x 8 at a time
+#pragma unroll 1
+    for (int k = 0; k < kTile / kTileRows; ++k) {
+        const int row = ly + k * kTileRows;
+        const int x = x0 + lx, y = ty0 + row;
+        const bool inside = x < W && y < y1;
+        const int base = (row + 1) * pitch + lx + 1;
+        const int32_t own = s_win[base];
+        // a neighbour off the frame or outside the strip is not looked at (its staged word is -1, which is not `own`
+        // for a covered pixel)
+        // (the four taps are read whatever the pixel is, one ds_read_b32 each, and combined without a branch)
+        const int32_t wl = s_win[base - 1], wr = s_win[base + 1], wu = s_win[base - pitch], wd = s_win[base + pitch];
+        const bool differs = inside & (((x > 0) & (wl != own)) | ((x + 1 < W) & (wr != own)) | ((y > y0) & (wu != own)) |
+                                       ((y + 1 < y1) & (wd != own)));
+        const size_t pix = (size_t)y * (size_t)W + (size_t)x;
+        float c[3] = {0.0f, 0.0f, 0.0f};
+        if (inside) {
+            const float *cp = cb + pix * 3;
+            c[0] = cp[0]; c[1] = cp[1]; c[2] = cp[2];
+        }
+        if (!wave_any(differs)) {                   // a scalar branch: the whole wavefront only copies
+            if (inside) {
+                float *op = ob + pix * 3;
+                op[0] = c[0]; op[1] = c[1]; op[2] = c[2];
+            }
+            continue;
+        }
+        if (!inside) continue;
+        float a = 0.0f;
+        size_t qpix = pix;                          // the neighbour the pixel is blended with
+        if (differs) {
+            const float zp = zb[pix];
+            TriXYZ mine = {}, theirs = {};          // the own winner projected, and the neighbour's handled last
+            bool have_mine = false;
+            int32_t held = -1;
+#pragma unroll 1
+            for (int d = 0; d < 4; ++d) {           // (-1, 0), (+1, 0), (0, -1), (0, +1)
+                const int dx = d == 0 ? -1 : (d == 1 ? 1 : 0), dy = d == 2 ? -1 : (d == 3 ? 1 : 0);
+                const int qx = x + dx, qy = y + dy;
+                if (qx < 0 || qx >= W || qy < y0 || qy >= y1) continue;
+                const int32_t wq = s_win[base + dy * pitch + dx];
+                if (wq == own) continue;
+                const size_t at = (size_t)qy * (size_t)W + (size_t)qx;
+                bool near_is_q = wq >= 0;
+                if (near_is_q && own >= 0) near_is_q = zb[at] < zp;         // (a NaN makes p the near one)
+                const int32_t w = near_is_q ? wq : own;
+                const bool is_mine = w == own;
+                if (is_mine ? !have_mine : w != held) {
+                    const TriXYZ t = near_triangle(tri, pos_of ? (int64_t)pos_of[w] : (int64_t)w, P);
+                    if (is_mine) {
+                        mine = t;
+                        have_mine = true;
+                    } else {
+                        theirs = t;
+                        held = w;
+                    }
+                }
+                const TriXYZ &t = is_mine ? mine : theirs;
+                float bn1, bn2, bn3, bf1, bf2, bf3;
+                barycentric(t, near_is_q ? qx : x, near_is_q ? qy : y, bn1, bn2, bn3);
+                barycentric(t, near_is_q ? x : qx, near_is_q ? y : qy, bf1, bf2, bf3);
+                float tmin = INFINITY;
+                int ks = 0;
+                if (bf1 < 0.0f) {
+                    const float tk = bn1 / (bn1 - bf1);
+                    if (tk < tmin) { tmin = tk; ks = 1; }                   // (a NaN is never taken)
+                }
+                if (bf2 < 0.0f) {
+                    const float tk = bn2 / (bn2 - bf2);
+                    if (tk < tmin) { tmin = tk; ks = 2; }
+                }
+                if (bf3 < 0.0f) {
+                    const float tk = bn3 / (bn3 - bf3);
+                    if (tk < tmin) { tmin = tk; ks = 3; }
+                }
+                if (ks == 0) continue;              // the far pixel lies inside the near triangle
+                const int e = ks == 3 ? 0 : ks;     // b1 vanishes on edge 1, b2 on edge 2, b3 on edge 0
+                if (edges && !((edges[w] >> e) & 1u)) continue;
+                float s = near_is_q ? tmin - 0.5f : 0.5f - tmin;
+                s = s > 0.5f ? 0.5f : s;
+                if (s > a) {                        // (the first direction wins a tie; a NaN is never taken)
+                    a = s;
+                    qpix = at;
+                }
+            }
+        }
+        float *op = ob + pix * 3;
+        if (a == 0.0f) {
+            op[0] = c[0]; op[1] = c[1]; op[2] = c[2];
+        } else {
+            const float *cq = cb + qpix * 3;
+            const float kk = 1.0f - a;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) op[j] = c[j] * kk + cq[j] * a;
+        }
+    }
+}
+
 // ---- the contour edges (crender_wire_contours) ------------------------------------------------------------------
 // Which edges the overlay and the outline should draw for THIS view: the edges between a triangle that faces the
 // camera and one that faces away, which no classification made once per model can hold.  Two launches over the
@@ -596,6 +749,31 @@ int crender_wire_outline(const int32_t *d_winner, const float *d_z, const float 
                        d_tri, T, d_pos_of, make_proj(P16, W, H), d_edges, S, depth_bias, radius_px, d_color, W, y0, y1,
                        tiles_x);
     CR_LAUNCH_CHECK("k_wire_outline");
+    return CRENDER_OK;
+}
+
+int crender_wire_edge_aa(const int32_t *d_winner, const float *d_z, const float *d_tri, int64_t T, const uint32_t *d_pos_of,
+                         const float *P16, const uint8_t *d_edges, float *d_out, const float *d_color, int H, int W,
+                         int y0, int y1, unsigned flags, void *stream)
+{
+    if (!d_winner || !d_z || !P16 || !d_out || !d_color)
+        return fail(CRENDER_EINVAL, "crender_wire_edge_aa: d_winner, d_z, P16, d_out or d_color is NULL");
+    if (T < 0) return fail(CRENDER_EINVAL, "crender_wire_edge_aa: T is negative");
+    if (T > 0 && !d_tri) return fail(CRENDER_EINVAL, "crender_wire_edge_aa: d_tri is NULL with T > 0");
+    if (H < 1 || W < 1) return fail(CRENDER_EINVAL, "crender_wire_edge_aa: H or W is below 1");
+    if (y0 < 0 || y1 > H || y0 >= y1) return fail(CRENDER_EINVAL, "crender_wire_edge_aa: rows outside the frame");
+    if (flags) return fail(CRENDER_EINVAL, "crender_wire_edge_aa: unknown flag bits");
+    if (d_out == d_color)
+        return fail(CRENDER_EINVAL, "crender_wire_edge_aa: d_out is d_color (the pass cannot run in place)");
+    const int tiles_x = (W + kTile - 1) / kTile;
+    const int64_t tiles = (int64_t)tiles_x * (int64_t)((y1 - y0 + kTile - 1) / kTile);
+    if (tiles > 0x7FFFFFFF) return fail(CRENDER_EINVAL, "crender_wire_edge_aa: H or W is too large");
+    // (T == 0: every winner is invalid and every wavefront copies)
+    constexpr int side = kTile + 2;
+    hipLaunchKernelGGL(k_wire_edge_aa, dim3((unsigned)tiles), dim3(kThreads), (size_t)(side * side) * sizeof(int32_t),
+                       static_cast<hipStream_t>(stream), d_winner, d_z, d_tri, T, d_pos_of, make_proj(P16, W, H), d_edges,
+                       d_out, d_color, W, y0, y1, tiles_x);
+    CR_LAUNCH_CHECK("k_wire_edge_aa");
     return CRENDER_OK;
 }
 

@@ -1,9 +1,10 @@
 """The deferred passes of ``AdvancedPixelBufferFiller`` over the winner plane of its last frame: texture (nearest,
 bilinear, trilinear, anisotropic), shadow, Phong, ambient occlusion and the wireframe overlay, with the texture and shadow-map bindings they
-read, and the classification of a view's contour edges for the overlay (``contour_edges``: it reads no plane).  A mixin
+read, the classification of a view's contour edges for the overlay (``contour_edges``: it reads no plane) and geometric
+edge anti-aliasing (``edge_aa``: it reads the planes and returns a plane of its own).  A mixin
 beside ``_device_planes.DevicePlanes``: the filler supplies ``device, h, w, y0, y1, _lib, _P`` and its frame state (``_pipeline, _inputs, _order, _last_flags, _check_bins``).  What every pass has in common is here
 once: whom it refuses (``_pass_target``), which frame it accepts (``_pass_frame``), and how it is launched
-(``_run_pass``).  A ``*_pass`` method holds its own argument checks and operands.  Also here, because the shadow
+(``_run_pass``, whose leaf ``_launch_pass`` alone needs the GPU and the library).  A ``*_pass`` method holds its own argument checks and operands.  Also here, because the shadow
 binding converts its vertices as the filler's upload does: the model arrays' way to float32."""
 import ctypes as C
 import operator
@@ -47,6 +48,17 @@ def _as_device_f32(a, name, device):
     return t
 
 
+def _edge_mask(filler, edges, T):
+    """None, or the uint8 [T] edge mask of ``wire_pass`` and ``edge_aa`` on the filler's device, from numpy or a tensor."""
+    if edges is None:
+        return None
+    e = edges if isinstance(edges, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(edges))
+    if e.dtype != torch.uint8 or e.dim() != 1 or e.shape[0] != T:
+        raise ValueError(f"edges must be uint8 [T] with T = {T}, the triangles of the last frame, "
+                         f"got {e.dtype} {tuple(e.shape)}")
+    return e.to(filler.device).contiguous()
+
+
 class DeferredPasses:
     _texture = None    # (uv [T, 3, 2] float32, image [th, tw, 3] uint8) device tensors: bind_texture
     _mip = None        # (chain, [(h_k, w_k)], [byte offsets]) of that image: bind_texture(mipmaps=True)
@@ -72,11 +84,12 @@ class DeferredPasses:
         tri = self._inputs[0]
         return tri, tri.shape[0]
 
-    def _run_pass(self, entry, tri, T, operands, flags=0, more=(), z=False, light=None):
+    def _run_pass(self, entry, tri, T, operands, flags=0, more=(), z=False, light=None, reads_only=False):
         """Settle the frame and call the library's `entry` on torch's current stream:
         ``entry(winner, [z,] tri or NULL, T, pos_of, P, *operands, color, h, w, y0, y1, flags, *more, stream)``.
         Tensors among `operands` are passed by address, taken after the settle.  `light`: a second filler whose
-        planes the pass reads, settled first."""
+        planes the pass reads, settled first.  `reads_only`: the pass writes none of the filler's planes, so the host
+        views stay as fresh or as stale as they were."""
         self._push_host_edits()
         if light is not None:
             light._push_host_edits()
@@ -85,10 +98,16 @@ class DeferredPasses:
         pos_of = None if self._order is None else self._order[1]
         args = (self.winner_buffer,) + ((self.z_buffer,) if z else ()) + (tri if T else None, T, pos_of, self._P) + \
             tuple(operands) + (self.color_buffer, self.h, self.w, self.y0, self.y1, flags) + tuple(more)
+        self._launch_pass(entry, args)
+        if not reads_only:
+            self._host_fresh = False   # views handed out earlier show the pass's colours at the next getter call
+
+    def _launch_pass(self, entry, args):
+        """The leaf of ``_run_pass`` that needs the GPU and the library: `entry` on torch's current stream, the tensors
+        among `args` by address."""
         with torch.cuda.device(self.device):
             _capi.check(getattr(self._lib, entry)(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args],
                                                   self._stream()), entry)
-        self._host_fresh = False       # views handed out earlier show the pass's colours at the next getter call
 
     # ------------------------------------------------- bindings and the passes --
     def bind_texture(self, uv_by_triangles, texture, mipmaps=False):
@@ -345,12 +364,7 @@ class DeferredPasses:
             elif isinstance(radius_px, bool) or not isinstance(radius_px, (int, np.integer)) or not 0 <= radius_px <= top:
                 raise ValueError(f"radius_px must be None or an int from 0 to {top}, got {radius_px!r}")
         tri, T = self._pass_frame("wire_pass")
-        if edges is not None:
-            e = edges if isinstance(edges, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(edges))
-            if e.dtype != torch.uint8 or e.dim() != 1 or e.shape[0] != T:
-                raise ValueError(f"edges must be uint8 [T] with T = {T}, the triangles of the last frame, "
-                                 f"got {e.dtype} {tuple(e.shape)}")
-            edges = e.to(self.device).contiguous()
+        edges = _edge_mask(self, edges, T)
         line3 = (C.c_float * 3)(*[float(v) for v in color])
         fill3 = None if fill is None else (C.c_float * 3)(*[float(v) for v in fill])
         if outline:
@@ -360,6 +374,30 @@ class DeferredPasses:
             return
         self._run_pass("crender_wire_overlay", tri, T,
                        (edges if T else None, line3, fill3, float(width), float(feather), float(opacity)))
+
+    def edge_aa(self, edges=None):
+        """Geometric edge anti-aliasing of the LAST frame (``crender_wire_edge_aa``, include/crender_wire.h): a NEW
+        device tensor [h, w, 3] float32, as ``resolve`` returns one, in which every pixel whose left, right, upper or
+        lower neighbour shows another triangle is blended with ONE of those neighbours by the share of its cell that
+        lies beyond the edge between them.  The edge is the nearer triangle's (by the z plane), and where it crosses
+        the line between the two pixel centres comes from the rasterizer's own barycentrics: coverage computed, not
+        sampled, at the frame's own resolution.  Every other pixel is copied bit for bit.  `edges` is ``wire_pass``'s:
+        None (every edge smooths) or a uint8 array [T], numpy or a device tensor, in the caller's triangle order —
+        ``contour_edges(partners, static=feature_edges(...), borders=True)`` names the contours, creases and borders
+        of a view and leaves the Gouraud-shaded interior of a smooth surface alone.  Rows of the filler's
+        ``row_strip`` (the others of the result are zero; the strip does not see across its edge), on torch's current
+        stream.
+
+        Edits made in the numpy views handed out so far are carried to the device and the frame is settled first (one
+        stream synchronisation, as every getter does).  The planes are only read: the views stay as fresh or as stale
+        as they were."""
+        self._pass_target("edge_aa")
+        tri, T = self._pass_frame("edge_aa")
+        edges = _edge_mask(self, edges, T)
+        new = torch.empty if (self.y0, self.y1) == (0, self.h) else torch.zeros
+        out = new((self.h, self.w, 3), dtype=torch.float32, device=self.color_buffer.device)
+        self._run_pass("crender_wire_edge_aa", tri, T, (edges if T else None, out), z=True, reads_only=True)
+        return out
 
     def contour_edges(self, partners, static=None, borders=False):
         """uint8 [T] on the device: the edge mask of the LAST frame's view, ready for ``wire_pass(edges=...)``

@@ -22,7 +22,7 @@ def _device_form_is_the_same_shading(illumination):
 class Renderer:
     def __init__(self, pixel_buffer_filler, illumination, triangle_iterator_type=None,
                  image_height=512, image_width=512, use_tqdm=True, on_device=None, texture_pass=None,
-                 shadow=None, ambient_occlusion=None, wireframe=None, supersample=None):
+                 shadow=None, ambient_occlusion=None, antialias=None, wireframe=None, supersample=None):
         self.pixel_buffer_filler = pixel_buffer_filler
         self.illumination = illumination
         self.triangle_iterator_type = triangle_iterator_type   # stored, unused (as in Version C)
@@ -113,6 +113,31 @@ class Renderer:
                 raise ValueError("Renderer(wireframe={'contours': True}) needs a filler that classifies contour edges "
                                  f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no contour_edges()")
             self.wireframe = dict(wireframe)
+        # antialias=None (default): every pixel is its one sample.  A dict: geometric edge anti-aliasing
+        # (``AdvancedPixelBufferFiller.edge_aa``) of the finished frame — {} smooths every edge, ``edges`` is an explicit
+        # mask, and ``feature_angle`` / ``contours`` / ``borders`` pick the edges as ``wireframe`` picks them (the mask
+        # and the partner table once per model, the contours of the view every frame).  Every frame starts from cleared
+        # buffers (one model per frame, as "fused").  The pass runs LAST, after everything that shades and after the wire
+        # pass, reads the filler's planes and writes a tensor of its own, which ``render`` returns: the tensor for
+        # on_device=True / "fused", a fresh numpy copy for None / False (as under ``supersample``, with which it does
+        # not combine).
+        self.antialias = None
+        self._smoothed = None          # as _wired, for the edges of ``antialias``
+        if antialias is not None:
+            if supersample is not None:
+                raise ValueError("Renderer(antialias=...) together with supersample=...: the pass smooths the frame's own "
+                                 "pixels and does not combine with the resolve; use one of the two")
+            if not hasattr(pixel_buffer_filler, "edge_aa"):
+                raise ValueError("Renderer(antialias=...) needs a filler with an edge anti-aliasing pass "
+                                 f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no edge_aa()")
+            if antialias.get("contours") and not hasattr(pixel_buffer_filler, "contour_edges"):
+                raise ValueError("Renderer(antialias={'contours': True}) needs a filler that classifies contour edges "
+                                 f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no contour_edges()")
+            unknown = sorted(set(antialias) - {"edges", "feature_angle", "contours", "borders"})
+            if unknown:
+                raise ValueError(f"Renderer(antialias=...) takes the keys 'edges', 'feature_angle', 'contours' and "
+                                 f"'borders': {unknown} unknown")
+            self.antialias = dict(antialias)
         # A PhongIllumination is a deferred pass of the filler over its winner plane (``phong_pass``): every frame
         # starts from cleared buffers (one model per frame, as "fused"); the draw, then the texture pass (unlit) if
         # asked for, then the Phong pass, then the shadow pass — AFTER the light here, since the specular term is
@@ -135,7 +160,7 @@ class Renderer:
         the passes on top of it (but the wireframe's, which follows the light: ``_draw_wire``)."""
         filler = self.pixel_buffer_filler
         if self.texture_pass is None:
-            if self.shadow is None and self.ambient_occlusion is None and self.wireframe is None:
+            if self.shadow is None and self.ambient_occlusion is None and self.wireframe is None and self.antialias is None:
                 return filler.render_model(model, **kw)
             if not kw.get("clear"):        # (the "fused" caller asks for the cleared frame itself: its raster kernel shades)
                 filler.set_fused_illumination(None)
@@ -182,32 +207,49 @@ class Renderer:
         """The wire pass over the frame as it stands (host edits included), if a wireframe was asked for."""
         if self.wireframe is None:
             return
-        opts = dict(self.wireframe)
+        self.pixel_buffer_filler.wire_pass(**self._view_edges(model, self.wireframe, "_wired"))
+
+    def _view_edges(self, model, options, slot):
+        """`options` (``wireframe``'s or ``antialias``'s) with ``feature_angle`` / ``contours`` / ``borders`` turned into
+        the ``edges`` of this frame's view.  `slot` names the once-per-model cache, (weak reference to the model, mask,
+        partner table, angle); what the other option's cache holds for the same model is taken from there."""
+        opts = dict(options)
         angle = opts.pop("feature_angle", None)
         contours, borders = opts.pop("contours", False), opts.pop("borders", True)
         if angle is not None or contours:
-            if self._wired is None or self._wired[0]() is not model:     # once per model, not per frame
+            cache = getattr(self, slot)
+            if cache is None or cache[0]() is not model:     # once per model, not per frame
                 from .wireframe import edge_partners, feature_edges
+                other = self._smoothed if slot == "_wired" else self._wired
+                if other is not None and other[0]() is not model:
+                    other = None
                 tri = model._vertices_by_triangles
                 device = getattr(self.pixel_buffer_filler, "device", None)
                 mask = partners = None
                 if angle is not None:
-                    mask = feature_edges(tri.cpu().numpy() if hasattr(tri, "cpu") else tri, angle)
-                    if device is not None:
-                        import torch
-                        mask = torch.from_numpy(mask).to(device)
+                    if other is not None and other[1] is not None and other[3] == angle:
+                        mask = other[1]
+                    else:
+                        mask = feature_edges(tri.cpu().numpy() if hasattr(tri, "cpu") else tri, angle)
+                        if device is not None:
+                            import torch
+                            mask = torch.from_numpy(mask).to(device)
                 if contours:
-                    partners = edge_partners(tri)      # (a device model's table is made on the device)
-                    if device is not None and not hasattr(partners, "data_ptr"):
-                        import torch
-                        partners = torch.from_numpy(partners).to(device)
-                self._wired = (weakref.ref(model), mask, partners)
+                    if other is not None and other[2] is not None:
+                        partners = other[2]
+                    else:
+                        partners = edge_partners(tri)      # (a device model's table is made on the device)
+                        if device is not None and not hasattr(partners, "data_ptr"):
+                            import torch
+                            partners = torch.from_numpy(partners).to(device)
+                cache = (weakref.ref(model), mask, partners, angle)
+                setattr(self, slot, cache)
             if angle is not None:
-                opts["edges"] = self._wired[1]
+                opts["edges"] = cache[1]
         if contours:
             # the mask of this frame's view: the contours, over the static mask if there is one
-            opts["edges"] = self.pixel_buffer_filler.contour_edges(self._wired[2], static=opts.get("edges"), borders=bool(borders))
-        self.pixel_buffer_filler.wire_pass(**opts)
+            opts["edges"] = self.pixel_buffer_filler.contour_edges(cache[2], static=opts.get("edges"), borders=bool(borders))
+        return opts
 
     def render(self, model, normalize_model=False, random_colors=True):
         if normalize_model:
@@ -216,6 +258,15 @@ class Renderer:
             span = min(centre)
             model.scale(span / model.get_max_span())
             model.shift(-model.get_mean_vertex() + [centre[0], centre[1], -span])
+        if self.antialias is None:
+            return self._render(model)
+        # the frame as ever, then the edges smoothed, last of all: the pass's own tensor is the image
+        self._render(model)
+        image = self.pixel_buffer_filler.edge_aa(**self._view_edges(model, self.antialias, "_smoothed"))
+        return image if self.on_device is True or self.on_device == "fused" else image.cpu().numpy()
+
+    def _render(self, model):
+        """``render`` after the model fit: the draws, the light and the passes, in the constructor's order."""
         filler = self.pixel_buffer_filler
         if self._phong:
             return self._render_phong(model)

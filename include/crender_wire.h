@@ -196,6 +196,63 @@ CRENDER_API int crender_wire_outline(const int32_t *d_winner, const float *d_z, 
                                      int H, int W, int y0, int y1, unsigned flags, void *stream);
 
 /*
+ * Geometric edge anti-aliasing: the coverage of a boundary pixel, computed from the winner plane.  Where a pixel and
+ * its left, right, upper or lower neighbour name different triangles, an edge of the nearer of the two crosses the line
+ * between the two pixel centres; the rasterizer's own barycentrics at the two centres say where, and so how much of the
+ * pixel's cell lies beyond the edge.  The pixel is blended with the ONE neighbour that reaches farthest into its cell.
+ * A neighbourhood pass over the winner plane, as crender_wire_outline is; it needs the z plane of the same frame, reads
+ * the colour plane and writes a second one.
+ *
+ * Result contract.  For every pixel p = (x, y) with y0 <= y < y1:
+ *
+ *   Arithmetic   every step below is ONE float32 operation, rounded once, with IEEE division (no contraction into fused
+ *                multiply-adds, no reciprocal, denormals kept).
+ *   Winners      v(q), the VALIDATED winner of a pixel q, is crender_wire_outline's: t = d_winner[q] if 0 <= t < T and,
+ *                with a d_pos_of, d_pos_of[t] < T; else -1.  Nothing is ever read out of bounds, whatever the planes hold.
+ *   Directions   a = 0; for (dx, dy) = (-1, 0), (+1, 0), (0, -1), (0, +1), in this order, with q = (x + dx, y + dy):
+ *                  - q off the frame or outside rows y0 <= qy < y1 is passed over: a strip does not see across its edge;
+ *                  - wp = v(p), wq = v(q); wp == wq is passed over;
+ *                  - near_is_q = wq >= 0 and (wp < 0 or d_z[q] < d_z[p])   (smaller z is nearer; false for a NaN: p is
+ *                    then the near one, as it is at equal depths);
+ *                  - (n, f, w) = (q, p, wq) if near_is_q, else (p, q, wp): the near pixel, the far one, the near winner.
+ *   Corners      of triangle w: d_tri[w], or d_tri[d_pos_of[w]] with a d_pos_of, projected as crender_project projects
+ *                them (.pyx:116-130): (x_k, y_k), k = 0, 1, 2.
+ *   Barycentrics (bn1, bn2, bn3) at the integer pixel n and (bf1, bf2, bf3) at f: math_utils.pyx:8-34, in its operations
+ *                and their order (l01 = x1 - x2, l02 = y1 - y2, l03 = l01 * (y0 - y2) - l02 * (x0 - x2),
+ *                b1 = (l01 * (fy - y2) - l02 * (fx - x2)) / l03, and b2, b3 alike: the rasterizer's own).
+ *   Exit         t = +inf, k* = none; for k = 1, 2, 3 in order, if bf_k < 0:
+ *                  tk = bn_k / (bn_k - bf_k);   if (tk < t) t = tk, k* = k          (a NaN is never taken)
+ *                t is where the segment from the near centre to the far one leaves the near triangle: the smallest exit
+ *                over the three edge lines, which for a convex triangle is the exit.  Without a k* the far pixel lies
+ *                inside the near triangle, no edge lies between the two, and the direction is passed over.
+ *   Edge mask    e = k* % 3: b1 vanishes on edge 1 (corner 1 -> 2), b2 on edge 2, b3 on edge 0, in the overlay's
+ *                numbering.  With a d_edges the direction is passed over if bit e of d_edges[w] is clear (indexed by w
+ *                itself, the caller's order, whatever d_pos_of says).
+ *   Share        s = near_is_q ? t - 0.5f : 0.5f - t      (how much of p's cell lies on q's side of the edge)
+ *                s = s > 0.5f ? 0.5f : s
+ *                if (s > a) a = s, q* = q                  (the first direction wins a tie; a NaN is never taken)
+ *   Colour       a == 0: d_out[p] = d_color[p], the bits copied.  Otherwise k = 1.0f - a and, per channel j,
+ *                  d_out[p]_j = d_color[p]_j * k + d_color[q*]_j * a
+ *   Other planes z, winners, colours and triangles are only read.  Rows outside y0 <= y < y1 of d_out are not touched.
+ *
+ * The near triangle is taken by depth: the one edge that bounds what is visible decides, from both sides.  Only the
+ * single direction with the largest share is blended.  Not covered: the lines where triangles interpenetrate (no edge
+ * lies there), neighbours on diagonals, and triangles so small that they won no pixel.
+ */
+
+/* Anti-alias rows y0 <= y < y1 of d_color float32 [H][W][3] into d_out float32 [H][W][3].
+ *   d_winner, d_z, d_tri, T, d_pos_of, P16, d_edges   as crender_wire_outline takes them
+ *   d_out      the result; another plane than d_color (a pixel reads its neighbours' colours)
+ *   d_color    only read
+ *   flags      0
+ * CRENDER_EINVAL, before anything is dereferenced or launched, for: a NULL d_winner, d_z, P16, d_out or d_color, T < 0,
+ * T > 0 without d_tri, H or W < 1, rows outside the frame (y0 < 0, y1 > H, y0 >= y1), any flag bit, d_out == d_color.
+ * T == 0 makes every winner invalid: the rows are copied.  One launch with 34^2 words of LDS; no synchronisation. */
+CRENDER_API int crender_wire_edge_aa(const int32_t *d_winner, const float *d_z, const float *d_tri, int64_t T,
+                                     const uint32_t *d_pos_of, const float *P16, const uint8_t *d_edges, float *d_out,
+                                     const float *d_color, int H, int W, int y0, int y1, unsigned flags, void *stream);
+
+/*
  * The contour edges: the edge mask of ONE view, for crender_wire_overlay / crender_wire_outline to draw.  A contour
  * edge lies between a triangle that faces the camera and one that faces away; it bounds a smooth body, moves with every
  * pose, and is not among the creases and borders a mask made once per model holds.  The mesh's connectivity does not
