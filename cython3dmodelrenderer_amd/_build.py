@@ -42,8 +42,9 @@ UNITS = {
     # ao.hip  the deferred ambient-occlusion pass over the z, winner and normal planes (include/crender_ao.h)
     "ao": (["ao.hip"], [os.path.join(_INCLUDE, "crender_ao.h")]),
     # winner_pass.h  what the deferred passes over the winner plane share (texture.hip, texmip.hip, texaniso.hip,
-    # shadow.hip, phong.hip, wireframe.hip): the pixel frame, the corner gather, the store with the fused light, the texel fetches and
-    # the launch geometry; a unit of its own, without a source, so that each pass's header list stays its own.
+    # shadow.hip, phong.hip, ao.hip, wireframe.hip): the winner's triangle projected and the host's frame checks; the
+    # per-pixel frame, the store with the fused light, the texel fetches and the launch geometry; the tile frame and the
+    # tile grid; a unit of its own, without a source, so that each pass's header list stays its own.
     "pass": ([], ["winner_pass.h"]),
     # chain.hip  the swap chain's shared slot: one slot on the caller's stream (include/crender_chain.h; host code
     # only, over the pipeline handle of plan.h): it launches nothing.

@@ -25,12 +25,10 @@
 
 using namespace crender_detail;
 
-#include "winner_pass.h"     // gather_corners
+#include "winner_pass.h"     // gather_corners, the tile frame (kTile, TileLane, tile_origin), tile_grid, frame_checks
 
 namespace {
 
-constexpr int kTile = 32;                 // pixels along each side of a workgroup's tile
-constexpr int kTileRows = kThreads / kTile;   // rows of it the 256 work items cover at a time
 constexpr int kMaxGrid = 2048;            // workgroups of a launch: 8 per CU; the kernel loops over the other tiles
 
 // The taps and the constants of a call.
@@ -51,11 +49,9 @@ __global__ __launch_bounds__(kThreads) void k_ao_shade(const int32_t *__restrict
 {
     extern __shared__ float s_zv[];       // [kTile + 2R][kTile + 2R]
     const int R = A.R, pitch = kTile + 2 * R;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lx = threadIdx.x & (kTile - 1), ly = threadIdx.x >> 5;
+    const auto [lane, wave, lx, ly] = tile_lane();
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-        const int x0 = tx * kTile, ty0 = y0 + ty * kTile;
+        const auto [x0, ty0] = tile_origin(tile, tiles_x, y0);
         // ---- stage zv of the tile and its halo: a wavefront per row, 64 columns at a time
         for (int sy = wave; sy < pitch; sy += kThreads / 64) {
             const int gy = ty0 - R + sy;
@@ -155,37 +151,32 @@ int crender_ao_shade(const int32_t *d_winner, const float *d_z, const float *d_t
                      float radius, float min_cos, float strength, float floor, float *d_color, int H, int W, int y0,
                      int y1, unsigned flags, void *stream)
 {
-    if (!d_winner || !d_z || !P16 || !taps2 || !d_color)
-        return fail(CRENDER_EINVAL, "crender_ao_shade: d_winner, d_z, P16, taps2 or d_color is NULL");
-    if (flags & ~(CRENDER_AO_ROTATE | CRENDER_AO_FACE_NORMALS))
-        return fail(CRENDER_EINVAL, "crender_ao_shade: unknown flag bits");
+    const char *const E = "crender_ao_shade";
+    if (!d_winner || !d_z || !P16 || !taps2 || !d_color) return arg_error(E, "d_winner, d_z, P16, taps2 or d_color is NULL");
+    if (flags & ~(CRENDER_AO_ROTATE | CRENDER_AO_FACE_NORMALS)) return arg_error(E, "unknown flag bits");
     const bool face = (flags & CRENDER_AO_FACE_NORMALS) != 0, rotate = (flags & CRENDER_AO_ROTATE) != 0;
-    if (!face && !d_normal) return fail(CRENDER_EINVAL, "crender_ao_shade: d_normal is NULL without CRENDER_AO_FACE_NORMALS");
-    if (T < 0) return fail(CRENDER_EINVAL, "crender_ao_shade: T is negative");
-    if (face && T > 0 && !d_tri)
-        return fail(CRENDER_EINVAL, "crender_ao_shade: d_tri is NULL with CRENDER_AO_FACE_NORMALS and T > 0");
-    if (H < 1 || W < 1) return fail(CRENDER_EINVAL, "crender_ao_shade: H or W is below 1");
-    if (y0 < 0 || y1 > H || y0 >= y1) return fail(CRENDER_EINVAL, "crender_ao_shade: rows outside the frame");
-    if (n_taps < 1 || n_taps > CRENDER_AO_MAX_TAPS) return fail(CRENDER_EINVAL, "crender_ao_shade: n_taps is not 1 .. 64");
-    if (radius_px < 1 || radius_px > CRENDER_AO_MAX_RADIUS_PX)
-        return fail(CRENDER_EINVAL, "crender_ao_shade: radius_px is not 1 .. 32");
+    if (!face && !d_normal) return arg_error(E, "d_normal is NULL without CRENDER_AO_FACE_NORMALS");
+    if (int rc = frame_checks(E, T, !face || d_tri, H, W, "d_tri is NULL with CRENDER_AO_FACE_NORMALS and T > 0")) return rc;
+    if (int rc = rows_check(E, H, y0, y1)) return rc;
+    if (n_taps < 1 || n_taps > CRENDER_AO_MAX_TAPS) return arg_error(E, "n_taps is not 1 .. 64");
+    if (radius_px < 1 || radius_px > CRENDER_AO_MAX_RADIUS_PX) return arg_error(E, "radius_px is not 1 .. 32");
     for (int i = 0; i < n_taps; ++i) {
         const int dx = taps2[2 * i], dy = taps2[2 * i + 1];
         if (dx > radius_px || dx < -radius_px || dy > radius_px || dy < -radius_px)
-            return fail(CRENDER_EINVAL, "crender_ao_shade: a tap reaches beyond radius_px");
-        if (dx == 0 && dy == 0) return fail(CRENDER_EINVAL, "crender_ao_shade: a tap is (0, 0)");
+            return arg_error(E, "a tap reaches beyond radius_px");
+        if (dx == 0 && dy == 0) return arg_error(E, "a tap is (0, 0)");
     }
-    if (!isfinite(radius) || radius <= 0.0f) return fail(CRENDER_EINVAL, "crender_ao_shade: radius is not finite and positive");
+    if (!isfinite(radius) || radius <= 0.0f) return arg_error(E, "radius is not finite and positive");
     if (!isfinite(min_cos) || !isfinite(strength) || !isfinite(floor))
-        return fail(CRENDER_EINVAL, "crender_ao_shade: min_cos, strength or floor is not finite");
-    if (strength < 0.0f) return fail(CRENDER_EINVAL, "crender_ao_shade: strength is negative");
-    if (floor < 0.0f || floor > 1.0f) return fail(CRENDER_EINVAL, "crender_ao_shade: floor is not 0 .. 1");
+        return arg_error(E, "min_cos, strength or floor is not finite");
+    if (strength < 0.0f) return arg_error(E, "strength is negative");
+    if (floor < 0.0f || floor > 1.0f) return arg_error(E, "floor is not 0 .. 1");
     for (int i : {1, 2, 4, 6, 8, 9, 12, 13})
         if (!(P16[i] == 0.0f))
-            return fail(CRENDER_EINVAL, "crender_ao_shade: P16 is not of crender_projection_matrix's shape (an entry that must be 0 is not)");
+            return arg_error(E, "P16 is not of crender_projection_matrix's shape (an entry that must be 0 is not)");
     for (int i : {0, 5, 14})
         if (!isfinite(P16[i]) || P16[i] == 0.0f)
-            return fail(CRENDER_EINVAL, "crender_ao_shade: P16 is not of crender_projection_matrix's shape (entry 0, 5 or 14 is 0 or not finite)");
+            return arg_error(E, "P16 is not of crender_projection_matrix's shape (entry 0, 5 or 14 is 0 or not finite)");
     if (T == 0) return CRENDER_OK;
     const ProjConst P = make_proj(P16, W, H);
     AoParams A{};
@@ -205,15 +196,13 @@ int crender_ao_shade(const int32_t *d_winner, const float *d_z, const float *d_t
     A.min_cos = min_cos;
     A.strength = strength;
     A.floor_ = floor;
-    const int tiles_x = (W + kTile - 1) / kTile;
-    const int64_t tiles = (int64_t)tiles_x * (int64_t)((y1 - y0 + kTile - 1) / kTile);
-    if (tiles > 0x7FFFFFFF) return fail(CRENDER_EINVAL, "crender_ao_shade: H or W is too large");
-    const int side = kTile + 2 * radius_px;
+    int tiles_x, tiles;
+    if (int rc = tile_grid(E, W, y0, y1, tiles_x, tiles)) return rc;
     static constexpr decltype(&k_ao_shade<false, false>) kernels[4] = {k_ao_shade<false, false>, k_ao_shade<false, true>,
                                                                         k_ao_shade<true, false>, k_ao_shade<true, true>};
     hipLaunchKernelGGL(kernels[(face ? 2 : 0) | (rotate ? 1 : 0)], dim3((unsigned)(tiles < kMaxGrid ? tiles : kMaxGrid)),
-                       dim3(kThreads), (size_t)side * (size_t)side * sizeof(float), static_cast<hipStream_t>(stream),
-                       d_winner, d_z, d_tri, T, d_pos_of, d_normal, A, d_color, W, y0, y1, tiles_x, (int)tiles);
+                       dim3(kThreads), tile_lds_bytes(radius_px), static_cast<hipStream_t>(stream), d_winner, d_z, d_tri, T,
+                       d_pos_of, d_normal, A, d_color, W, y0, y1, tiles_x, tiles);
     CR_LAUNCH_CHECK("k_ao_shade");
     return CRENDER_OK;
 }

@@ -112,18 +112,16 @@ template <bool PERSPECTIVE>
 CR_DEV PixelUV pixel_uv(const ProjConst &P, const float *__restrict__ tri, const float *__restrict__ uv,
                         const WinnerPixel &p)
 {
-    float a[3], b[3], c[3];
-    gather_corners(tri, p.t, a, b, c);
     const float *w = uv + p.orig * 6;
-    CornerUV K{w[0], w[1], w[2], w[3], w[4], w[5], a[2], b[2], c[2], 0.0f, 0.0f, 0.0f, false};
+    CornerUV K{w[0], w[1], w[2], w[3], w[4], w[5], 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, false};
+    float raw[3][3];
+    const TriXYZ X = winner_triangle(tri, p.t, P, raw);
+    K.za = raw[0][2]; K.zb = raw[1][2]; K.zc = raw[2][2];
     if (PERSPECTIVE && in_div_window(K.za) && in_div_window(K.zb) && in_div_window(K.zc)) {
         K.ra = refined_rcp(K.za); K.rb = refined_rcp(K.zb); K.rc = refined_rcp(K.zc);
         K.z_fast = true;
     }
-    project_vertex(P, a);
-    project_vertex(P, b);
-    project_vertex(P, c);
-    const TriSetup S = make_setup(TriXYZ{a[0], a[1], a[2], b[0], b[1], b[2], c[0], c[1], c[2]}, true);
+    const TriSetup S = make_setup(X, true);
     PixelUV r;
     uv_at<PERSPECTIVE>(S, K, p.x, p.y, r.tu, r.tv);
     uv_at<PERSPECTIVE>(S, K, p.x + 1, p.y, r.ux, r.vx);

@@ -17,7 +17,7 @@
 
 using namespace crender_detail;
 
-#include "winner_pass.h"     // WinnerPixel, gather_corners, pass_grid
+#include "winner_pass.h"     // WinnerPixel, winner_triangle, pass_grid, frame_checks
 
 namespace {
 
@@ -70,13 +70,9 @@ __global__ __launch_bounds__(kThreads) void k_phong_shade(const int32_t *__restr
         const WinnerPixel px = winner_pixel(win, T, pos_of, W, y0, y1, rb);
         if (!wave_any(px.covered)) continue;        // a scalar branch: the whole wavefront leaves
         if (!px.covered) continue;
-        float a[3], b[3], c[3];
-        gather_corners(tri, px.t, a, b, c);
-        const float A[3] = {a[0], a[1], a[2]}, B[3] = {b[0], b[1], b[2]}, Cc[3] = {c[0], c[1], c[2]};
-        project_vertex(P, a);
-        project_vertex(P, b);
-        project_vertex(P, c);
-        const TriXYZ X{a[0], a[1], a[2], b[0], b[1], b[2], c[0], c[1], c[2]};
+        float raw[3][3];
+        const TriXYZ X = winner_triangle(tri, px.t, P, raw);
+        const float *A = raw[0], *B = raw[1], *Cc = raw[2];
         float b1, b2, b3;
         barycentric(X, px.x, px.y, b1, b2, b3);
         const float q1 = b1 / A[2], q2 = b2 / B[2], q3 = b3 / Cc[2];
@@ -125,18 +121,15 @@ int crender_phong_shade(const int32_t *d_winner, const float *d_tri, int64_t T, 
                         unsigned directional_mask, float ambient, int shininess_log2, const float *spec_color3,
                         float clamp, float *d_color, int H, int W, int y0, int y1, unsigned flags, void *stream)
 {
+    const char *const E = "crender_phong_shade";
     if (!d_winner || !P16 || !d_normal || !lights5 || !spec_color3 || !d_color)
-        return fail(CRENDER_EINVAL, "crender_phong_shade: d_winner, P16, d_normal, lights5, spec_color3 or d_color is NULL");
-    if (T < 0) return fail(CRENDER_EINVAL, "crender_phong_shade: T is negative");
-    if (T > 0 && !d_tri) return fail(CRENDER_EINVAL, "crender_phong_shade: d_tri is NULL with T > 0");
-    if (H < 1 || W < 1) return fail(CRENDER_EINVAL, "crender_phong_shade: H or W is below 1");
-    if (y0 < 0 || y1 > H || y0 >= y1) return fail(CRENDER_EINVAL, "crender_phong_shade: rows outside the frame");
-    if (n_lights < 1 || n_lights > CRENDER_PHONG_MAX_LIGHTS)
-        return fail(CRENDER_EINVAL, "crender_phong_shade: n_lights is not 1 .. 4");
-    if (directional_mask >> n_lights)
-        return fail(CRENDER_EINVAL, "crender_phong_shade: directional_mask has bits at or above n_lights");
+        return arg_error(E, "d_winner, P16, d_normal, lights5, spec_color3 or d_color is NULL");
+    if (int rc = frame_checks(E, T, d_tri, H, W)) return rc;
+    if (int rc = rows_check(E, H, y0, y1)) return rc;
+    if (n_lights < 1 || n_lights > CRENDER_PHONG_MAX_LIGHTS) return arg_error(E, "n_lights is not 1 .. 4");
+    if (directional_mask >> n_lights) return arg_error(E, "directional_mask has bits at or above n_lights");
     if (shininess_log2 < 0 || shininess_log2 > CRENDER_PHONG_MAX_SHININESS_LOG2)
-        return fail(CRENDER_EINVAL, "crender_phong_shade: shininess_log2 is not 0 .. 12");
+        return arg_error(E, "shininess_log2 is not 0 .. 12");
     bool finite = isfinite(ambient) && isfinite(spec_color3[0]) && isfinite(spec_color3[1]) && isfinite(spec_color3[2]);
     bool negative = ambient < 0.0f;
     for (int j = 0; j < n_lights; ++j)
@@ -144,11 +137,10 @@ int crender_phong_shade(const int32_t *d_winner, const float *d_tri, int64_t T, 
             finite = finite && isfinite(lights5[j * 5 + i]);
             negative = negative || (i >= 3 && lights5[j * 5 + i] < 0.0f);
         }
-    if (!finite)
-        return fail(CRENDER_EINVAL, "crender_phong_shade: ambient, a light or spec_color3 is not finite");
-    if (negative) return fail(CRENDER_EINVAL, "crender_phong_shade: ambient, kd or ks is negative");
-    if (clamp != clamp) return fail(CRENDER_EINVAL, "crender_phong_shade: clamp is NaN");
-    if (flags) return fail(CRENDER_EINVAL, "crender_phong_shade: unknown flag bits");
+    if (!finite) return arg_error(E, "ambient, a light or spec_color3 is not finite");
+    if (negative) return arg_error(E, "ambient, kd or ks is negative");
+    if (clamp != clamp) return arg_error(E, "clamp is NaN");
+    if (flags) return arg_error(E, "unknown flag bits");
     if (T == 0) return CRENDER_OK;
     PhongLights L{};
     for (int j = 0; j < n_lights; ++j)

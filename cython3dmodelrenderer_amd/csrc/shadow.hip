@@ -17,7 +17,7 @@
 
 using namespace crender_detail;
 
-#include "winner_pass.h"     // WinnerPixel, gather_corners, host_f32_to_i32, pass_grid
+#include "winner_pass.h"     // WinnerPixel, winner_triangle, host_f32_to_i32, pass_grid, frame_checks
 
 namespace {
 
@@ -42,16 +42,11 @@ __global__ __launch_bounds__(kThreads) void k_shadow_shade(const int32_t *__rest
         if (!wave_any(px.covered)) continue;        // a scalar branch: the whole wavefront leaves
         if (!px.covered) continue;
         const int64_t orig = px.orig;               // the winner in the caller's order: ltri, the light's winners
-        float a[3], b[3], c[3];
-        gather_corners(tri, px.t, a, b, c);
-        const float za = a[2], zb = b[2], zc = c[2];
-        project_vertex(P, a);
-        project_vertex(P, b);
-        project_vertex(P, c);
-        const TriXYZ X{a[0], a[1], a[2], b[0], b[1], b[2], c[0], c[1], c[2]};
+        float raw[3][3];
+        const TriXYZ X = winner_triangle(tri, px.t, P, raw);
         float b1, b2, b3;
         barycentric(X, px.x, px.y, b1, b2, b3);
-        const float q1 = b1 / za, q2 = b2 / zb, q3 = b3 / zc;
+        const float q1 = b1 / raw[0][2], q2 = b2 / raw[1][2], q3 = b3 / raw[2][2];
         const float s = (q1 + q2) + q3;
         const float *l = ltri + orig * 9;
         float p[3];
@@ -104,18 +99,15 @@ int crender_shadow_shade(const int32_t *d_winner, const float *d_tri, int64_t T,
                          const int32_t *d_lwinner, int Hl, int Wl, float bias, float ambient, int pcf, float *d_color,
                          int H, int W, int y0, int y1, unsigned flags, void *stream)
 {
-    if (!d_winner || !P16 || !PL16 || !d_lz || !d_color)
-        return fail(CRENDER_EINVAL, "crender_shadow_shade: d_winner, P16, PL16, d_lz or d_color is NULL");
-    if (T < 0) return fail(CRENDER_EINVAL, "crender_shadow_shade: T is negative");
-    if (T > 0 && (!d_tri || !d_ltri)) return fail(CRENDER_EINVAL, "crender_shadow_shade: d_tri or d_ltri is NULL with T > 0");
-    if (H < 1 || W < 1) return fail(CRENDER_EINVAL, "crender_shadow_shade: H or W is below 1");
-    if (Hl < 1 || Wl < 1) return fail(CRENDER_EINVAL, "crender_shadow_shade: Hl or Wl is below 1");
-    if (y0 < 0 || y1 > H || y0 >= y1) return fail(CRENDER_EINVAL, "crender_shadow_shade: rows outside the frame");
-    if (pcf != 1 && pcf != 3 && pcf != 5) return fail(CRENDER_EINVAL, "crender_shadow_shade: pcf is not 1, 3 or 5");
-    if (!(ambient >= 0.0f && ambient <= 1.0f))
-        return fail(CRENDER_EINVAL, "crender_shadow_shade: ambient outside [0, 1] or NaN");
-    if (!isfinite(bias)) return fail(CRENDER_EINVAL, "crender_shadow_shade: bias is not finite");
-    if (flags) return fail(CRENDER_EINVAL, "crender_shadow_shade: unknown flag bits");
+    const char *const E = "crender_shadow_shade";
+    if (!d_winner || !P16 || !PL16 || !d_lz || !d_color) return arg_error(E, "d_winner, P16, PL16, d_lz or d_color is NULL");
+    if (int rc = frame_checks(E, T, d_tri && d_ltri, H, W, "d_tri or d_ltri is NULL with T > 0")) return rc;
+    if (Hl < 1 || Wl < 1) return arg_error(E, "Hl or Wl is below 1");
+    if (int rc = rows_check(E, H, y0, y1)) return rc;
+    if (pcf != 1 && pcf != 3 && pcf != 5) return arg_error(E, "pcf is not 1, 3 or 5");
+    if (!(ambient >= 0.0f && ambient <= 1.0f)) return arg_error(E, "ambient outside [0, 1] or NaN");
+    if (!isfinite(bias)) return arg_error(E, "bias is not finite");
+    if (flags) return arg_error(E, "unknown flag bits");
     if (T == 0) return CRENDER_OK;
     const ShadowMap M{make_proj(PL16, Wl, Hl), d_lz, d_lwinner, Hl, Wl, bias, ambient};
     // [pcf / 2][the light's winner plane given]

@@ -19,7 +19,7 @@
 
 using namespace crender_detail;
 
-#include "winner_pass.h"     // WinnerPixel, gather_corners, bilinear, store_shaded, pass_grid
+#include "winner_pass.h"     // WinnerPixel, winner_triangle, bilinear, store_shaded, pass_grid
 
 namespace {
 
@@ -36,20 +36,15 @@ __global__ __launch_bounds__(kThreads) void k_tex_shade(const int32_t *__restric
         if (!LIGHT && !wave_any(px.covered)) continue;
         float col[3] = {0.0f, 0.0f, 0.0f};
         if (px.covered) {
-            float a[3], b[3], c[3];
-            gather_corners(tri, px.t, a, b, c);
-            const float za = a[2], zb = b[2], zc = c[2];
-            project_vertex(P, a);
-            project_vertex(P, b);
-            project_vertex(P, c);
-            const TriXYZ X{a[0], a[1], a[2], b[0], b[1], b[2], c[0], c[1], c[2]};
+            float raw[3][3];
+            const TriXYZ X = winner_triangle(tri, px.t, P, raw);
             float b1, b2, b3;
             barycentric(X, px.x, px.y, b1, b2, b3);
             const float *w = uv + px.orig * 6;
             const float u0 = w[0], v0 = w[1], u1 = w[2], v1 = w[3], u2 = w[4], v2 = w[5];
             float tu, tv;
             if (PERSPECTIVE) {
-                const float q1 = b1 / za, q2 = b2 / zb, q3 = b3 / zc;
+                const float q1 = b1 / raw[0][2], q2 = b2 / raw[1][2], q3 = b3 / raw[2][2];
                 const float s = (q1 + q2) + q3;
                 tu = ((u0 * q1 + u1 * q2) + u2 * q3) / s;
                 tv = ((v0 * q1 + v1 * q2) + v2 * q3) / s;

@@ -1,11 +1,60 @@
-// winner_pass.h — what every deferred pass over the winner plane shares (texture.hip, texmip.hip, texaniso.hip,
-// shadow.hip): a lane's pixel of an 8 x 8 block and its winner, the gather of the winner's corners, the store with
-// the fused light, the texel fetches, and on the host the launch geometry, the light and the common argument
-// checks.  Each translation unit gets its own copy (anonymous namespace); include after common.h and
-// `using namespace crender_detail;`.
+// winner_pass.h — what the deferred passes over the winner plane share (texture.hip, texmip.hip and texaniso.hip, the
+// last two also through mip_sample.h; shadow.hip, phong.hip, ao.hip, wireframe.hip): the winner's triangle projected and
+// the host's frame checks, then what the per-pixel passes share, then what the neighbourhood passes share.  Each
+// translation unit gets its own copy (anonymous namespace); include after common.h and `using namespace crender_detail;`.
 #pragma once
 
 namespace {
+
+// The three corners of triangle t, unprojected.
+CR_DEV void gather_corners(const float *__restrict__ tri, int64_t t, float a[3], float b[3], float c[3])
+{
+    const float *v = tri + t * 9;
+    a[0] = v[0]; a[1] = v[1]; a[2] = v[2];
+    b[0] = v[3]; b[1] = v[4]; b[2] = v[5];
+    c[0] = v[6]; c[1] = v[7]; c[2] = v[8];
+}
+
+// Triangle t on the screen: its corners gathered and projected.  `raw` keeps them unprojected, for what a pass blends.
+CR_DEV TriXYZ winner_triangle(const float *__restrict__ tri, int64_t t, const ProjConst &P, float raw[3][3])
+{
+    gather_corners(tri, t, raw[0], raw[1], raw[2]);
+    float a[3] = {raw[0][0], raw[0][1], raw[0][2]}, b[3] = {raw[1][0], raw[1][1], raw[1][2]},
+          c[3] = {raw[2][0], raw[2][1], raw[2][2]};
+    project_vertex(P, a);
+    project_vertex(P, b);
+    project_vertex(P, c);
+    return TriXYZ{a[0], a[1], a[2], b[0], b[1], b[2], c[0], c[1], c[2]};
+}
+
+CR_DEV TriXYZ winner_triangle(const float *__restrict__ tri, int64_t t, const ProjConst &P)
+{
+    float raw[3][3];
+    return winner_triangle(tri, t, P, raw);
+}
+
+// fail() for a bad argument of `entry`: "<entry>: <what>".
+inline int arg_error(const char *entry, const char *what)
+{
+    return fail(CRENDER_EINVAL, (std::string(entry) + ": " + what).c_str());
+}
+
+// The frame checks the passes make in these words and in this order; CRENDER_OK or the failure.  `have_tri`: the
+// triangle arrays the entry needs with T > 0 are given.  The rows are apart: an entry may check more before them, or take none.
+inline int frame_checks(const char *entry, int64_t T, bool have_tri, int H, int W, const char *no_tri = "d_tri is NULL with T > 0")
+{
+    if (T < 0) return arg_error(entry, "T is negative");
+    if (T > 0 && !have_tri) return arg_error(entry, no_tri);
+    if (H < 1 || W < 1) return arg_error(entry, "H or W is below 1");
+    return CRENDER_OK;
+}
+
+inline int rows_check(const char *entry, int H, int y0, int y1)
+{
+    return (y0 < 0 || y1 > H || y0 >= y1) ? arg_error(entry, "rows outside the frame") : CRENDER_OK;
+}
+
+// ---- per-pixel passes ---------------------------------------------------------------------------------------------
 
 constexpr int kPassBlock = 8;        // pixels along each side of a wavefront's block
 
@@ -37,15 +86,6 @@ CR_DEV WinnerPixel winner_pixel(const int32_t *__restrict__ win, int64_t T, cons
         p.covered = p.t < T;
     }
     return p;
-}
-
-// The three corners of triangle t, unprojected.
-CR_DEV void gather_corners(const float *__restrict__ tri, int64_t t, float a[3], float b[3], float c[3])
-{
-    const float *v = tri + t * 9;
-    a[0] = v[0]; a[1] = v[1]; a[2] = v[2];
-    b[0] = v[3]; b[1] = v[4]; b[2] = v[5];
-    c[0] = v[6]; c[1] = v[7]; c[2] = v[8];
 }
 
 // The end of a texture pass: `col` is the texture's colour of a covered pixel.  With the light every pixel of the
@@ -114,7 +154,7 @@ inline Light pass_light(const float *light3)
     return light3 ? Light{light3[0], light3[1], light3[2], 1} : Light{0.0f, 0.0f, 0.0f, 0};
 }
 
-// The argument checks every pass makes in these words; what else a pass takes it checks itself.
+// The argument checks of the texture passes, which report them all in one message; what else a pass takes it checks itself.
 inline bool frame_args_ok(const int32_t *d_winner, const float *P16, const float *d_color, int64_t T, const float *d_tri,
                           int H, int W, int y0, int y1)
 {
@@ -125,6 +165,46 @@ inline bool frame_args_ok(const int32_t *d_winner, const float *P16, const float
 inline bool light_args_ok(const float *light3, const float *d_normal)
 {
     return (light3 != nullptr) == (d_normal != nullptr);
+}
+
+// ---- neighbourhood passes -----------------------------------------------------------------------------------------
+// A workgroup owns a tile of kTile x kTile pixels and stages what its taps read of the tile plus a halo of R pixels on
+// every side into LDS, [kTile + 2R][kTile + 2R] words.  256 work items are 32 x 8 pixels, a wavefront two rows of 32.
+
+constexpr int kTile = 32;                       // pixels along each side of a workgroup's tile
+constexpr int kTileRows = kThreads / kTile;     // rows of it the 256 work items cover at a time
+
+// A work item's place: in its wavefront, which stages a row at a time, and in the 32 x 8 pixels.
+struct TileLane { int lane, wave, lx, ly; };
+
+CR_DEV TileLane tile_lane()
+{
+    return {(int)(threadIdx.x & 63), (int)(threadIdx.x >> 6), (int)(threadIdx.x & (kTile - 1)), (int)(threadIdx.x >> 5)};
+}
+
+// The first pixel (x0, ty0) of tile `tile` of a strip that starts at row y0, tiles_x tiles across.
+struct TileOrigin { int x0, ty0; };
+
+CR_DEV TileOrigin tile_origin(int tile, int tiles_x, int y0)
+{
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    return {tx * kTile, y0 + ty * kTile};
+}
+
+// The tiles of rows [y0, y1) of a frame W wide: tiles_x across and `tiles` in all; the failure if a grid cannot count them.
+inline int tile_grid(const char *entry, int W, int y0, int y1, int &tiles_x, int &tiles)
+{
+    tiles_x = (W + kTile - 1) / kTile;
+    const int64_t n = (int64_t)tiles_x * (int64_t)((y1 - y0 + kTile - 1) / kTile);
+    if (n > 0x7FFFFFFF) return arg_error(entry, "H or W is too large");
+    tiles = (int)n;
+    return CRENDER_OK;
+}
+
+// The bytes of LDS of a tile staged with a halo of R, and `more` words after it.
+inline size_t tile_lds_bytes(int R, int more = 0)
+{
+    return (size_t)((kTile + 2 * R) * (kTile + 2 * R) + more) * 4;
 }
 
 }  // namespace

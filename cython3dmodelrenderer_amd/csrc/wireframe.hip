@@ -27,7 +27,7 @@
 
 using namespace crender_detail;
 
-#include "winner_pass.h"     // WinnerPixel, gather_corners, pass_grid (k_wire_overlay)
+#include "winner_pass.h"     // WinnerPixel, winner_triangle, pass_grid; the tile frame, tile_grid; frame_checks
 
 namespace {
 
@@ -232,11 +232,8 @@ __global__ __launch_bounds__(kThreads) void k_wire_overlay(const int32_t *__rest
         if (!px.covered) continue;
         unsigned mask = 7u;
         if (edges) mask = edges[px.orig];           // a scalar branch; the caller's order, as uv
-        float c[3][3];
-        gather_corners(tri, px.t, c[0], c[1], c[2]);
-        project_vertex(P, c[0]);
-        project_vertex(P, c[1]);
-        project_vertex(P, c[2]);
+        const TriXYZ X = winner_triangle(tri, px.t, P);
+        const float c[3][3] = {{X.x0, X.y0, X.z0}, {X.x1, X.y1, X.z1}, {X.x2, X.y2, X.z2}};
         const float fx = (float)px.x, fy = (float)px.y;
         float m = INFINITY;
 #pragma unroll
@@ -285,19 +282,14 @@ __global__ __launch_bounds__(kThreads) void k_wire_overlay(const int32_t *__rest
 // and a square root per drawn edge.  The minimum is exact, so the order of the taps does not matter.  A wavefront
 // whose two rows' window holds no winner leaves after one read per staged row of it; a workgroup over background alone
 // is four such wavefronts.
-constexpr int kTile = 32;                       // pixels along each side of a workgroup's tile
-constexpr int kTileRows = kThreads / kTile;     // rows of it the 256 work items cover at a time
 
 // The statements "Per candidate" of crender_wire_outline: the distances of (fx, fy) to the drawn edge SEGMENTS of the
 // triangle at d_tri[pos], each taken into m if it counts there (`always`, or nearer than zp by the bias).
 CR_DEV void outline_candidate(const float *__restrict__ tri, int64_t pos, const ProjConst &P, unsigned mask, float fx,
                               float fy, bool always, float bias, float zp, float &m)
 {
-    float c[3][3];
-    gather_corners(tri, pos, c[0], c[1], c[2]);
-    project_vertex(P, c[0]);
-    project_vertex(P, c[1]);
-    project_vertex(P, c[2]);
+    const TriXYZ X = winner_triangle(tri, pos, P);
+    const float c[3][3] = {{X.x0, X.y0, X.z0}, {X.x1, X.y1, X.z1}, {X.x2, X.y2, X.z2}};
 #pragma unroll
     for (int e = 0; e < 3; ++e) {
         if (!((mask >> e) & 1u)) continue;
@@ -329,10 +321,8 @@ __global__ __launch_bounds__(kThreads) void k_wire_outline(const int32_t *__rest
     extern __shared__ int32_t s_win[];          // [kTile + 2R][kTile + 2R], then s_row[kTile + 2R]
     const int side = 2 * R + 1, pitch = kTile + 2 * R;
     int32_t *s_row = s_win + pitch * pitch;     // 1 if the staged row holds a winner
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lx = threadIdx.x & (kTile - 1), ly = threadIdx.x >> 5;
-    const int tile = blockIdx.x, ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int x0 = tx * kTile, ty0 = y0 + ty * kTile;
+    const auto [lane, wave, lx, ly] = tile_lane();
+    const auto [x0, ty0] = tile_origin(blockIdx.x, tiles_x, y0);
     // ---- stage the validated winners of the tile and its halo: a wavefront per row, 64 columns at a time
     for (int sy = wave; sy < pitch; sy += kThreads / 64) {
         const int gy = ty0 - R + sy;
@@ -393,7 +383,7 @@ __global__ __launch_bounds__(kThreads) void k_wire_outline(const int32_t *__rest
                 }
             }
         }
-        float a = (S.hi - m) / S.feather;
+        float a = (S.hi - m) / S.feather;       // (the overlay's ending, with `own >= 0` beside FILL)
         const bool on = a > 0.0f;
         a = a > 1.0f ? 1.0f : a;
         a = a * S.opacity;
@@ -425,17 +415,6 @@ __global__ __launch_bounds__(kThreads) void k_wire_outline(const int32_t *__rest
 // centres (six) and up to three exits.  The pixel's own winner is the near triangle in most directions: it is
 // projected once per pixel; the neighbour's triangle is kept while the next direction names the same one.
 
-// The projected corners of the triangle at d_tri[pos].
-CR_DEV TriXYZ near_triangle(const float *__restrict__ tri, int64_t pos, const ProjConst &P)
-{
-    float c[3][3];
-    gather_corners(tri, pos, c[0], c[1], c[2]);
-    project_vertex(P, c[0]);
-    project_vertex(P, c[1]);
-    project_vertex(P, c[2]);
-    return TriXYZ{c[0][0], c[0][1], c[0][2], c[1][0], c[1][1], c[1][2], c[2][0], c[2][1], c[2][2]};
-}
-
 __global__ __launch_bounds__(kThreads) void k_wire_edge_aa(const int32_t *__restrict__ win, const float *__restrict__ zb,
                                                             const float *__restrict__ tri, int64_t T,
                                                             const uint32_t *__restrict__ pos_of, ProjConst P,
@@ -445,11 +424,9 @@ __global__ __launch_bounds__(kThreads) void k_wire_edge_aa(const int32_t *__rest
 {
     extern __shared__ int32_t s_win[];          // [kTile + 2][kTile + 2]
     constexpr int pitch = kTile + 2;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lx = threadIdx.x & (kTile - 1), ly = threadIdx.x >> 5;
-    const int tile = blockIdx.x, ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int x0 = tx * kTile, ty0 = y0 + ty * kTile;
-    // ---- stage the validated winners of the tile and its halo: a wavefront per row
+    const auto [lane, wave, lx, ly] = tile_lane();
+    const auto [x0, ty0] = tile_origin(blockIdx.x, tiles_x, y0);
+    // ---- stage the validated winners of the tile and its halo (the outline's rule): a wavefront per row
     for (int sy = wave; sy < pitch; sy += kThreads / 64) {
         const int gy = ty0 - 1 + sy;
         const bool row_in = gy >= y0 && gy < y1;
@@ -512,7 +489,7 @@ __global__ __launch_bounds__(kThreads) void k_wire_edge_aa(const int32_t *__rest
                 const int32_t w = near_is_q ? wq : own;
                 const bool is_mine = w == own;
                 if (is_mine ? !have_mine : w != held) {
-                    const TriXYZ t = near_triangle(tri, pos_of ? (int64_t)pos_of[w] : (int64_t)w, P);
+                    const TriXYZ t = winner_triangle(tri, pos_of ? (int64_t)pos_of[w] : (int64_t)w, P);
                     if (is_mine) {
                         mine = t;
                         have_mine = true;
@@ -581,14 +558,10 @@ __global__ __launch_bounds__(kThreads) void k_wire_facing(const float *__restric
         const int64_t q = pos_of ? (int64_t)pos_of[t] : t;
         int f = 0;
         if (q < T) {
-            float c[3][3];
-            gather_corners(tri, q, c[0], c[1], c[2]);
-            project_vertex(P, c[0]);            // (the projected z is not used: its divisions are dropped)
-            project_vertex(P, c[1]);
-            project_vertex(P, c[2]);
+            const TriXYZ X = winner_triangle(tri, q, P);    // (the projected z is not used: its divisions are dropped)
             // l03 of raster_math.h's barycentric, in its operations and their order
-            const float l01 = c[1][0] - c[2][0], l02 = c[1][1] - c[2][1];
-            const float A = l01 * (c[0][1] - c[2][1]) - l02 * (c[0][0] - c[2][0]);
+            const float l01 = X.x1 - X.x2, l02 = X.y1 - X.y2;
+            const float A = l01 * (X.y0 - X.y2) - l02 * (X.x0 - X.x2);
             f = A > 0.0f ? 1 : (A < 0.0f ? -1 : 0);        // (a NaN is neither)
         }
         facing[t] = (int8_t)f;
@@ -618,6 +591,31 @@ __global__ __launch_bounds__(kThreads) void k_wire_contour_mask(const int32_t *_
         }
         edges[t] = (uint8_t)bits;
     }
+}
+
+// The line of an overlay or outline call: its window, then (after what only the outline checks) its colours and the WireStyle.
+int wire_window(const char *entry, float width, float feather, float opacity)
+{
+    if (!isfinite(width) || !(width > 0.0f && width <= (float)CRENDER_WIRE_MAX_WIDTH))
+        return arg_error(entry, "width is not in (0, 64]");
+    if (!isfinite(feather) || !(feather > 0.0f && feather <= (float)CRENDER_WIRE_MAX_WIDTH))
+        return arg_error(entry, "feather is not in (0, 64]");
+    return (opacity >= 0.0f && opacity <= 1.0f) ? CRENDER_OK : arg_error(entry, "opacity is not in [0, 1]");
+}
+
+int wire_style(const char *entry, const float *line3, const float *fill3, float width, float feather, float opacity, WireStyle &S)
+{
+    bool finite = isfinite(line3[0]) && isfinite(line3[1]) && isfinite(line3[2]);
+    if (fill3) finite = finite && isfinite(fill3[0]) && isfinite(fill3[1]) && isfinite(fill3[2]);
+    if (!finite) return arg_error(entry, "line3 or fill3 is not finite");
+    for (int j = 0; j < 3; ++j) {
+        S.line[j] = line3[j];
+        S.fill[j] = fill3 ? fill3[j] : 0.0f;
+    }
+    S.hi = width * 0.5f + feather * 0.5f;
+    S.feather = feather;
+    S.opacity = opacity;
+    return CRENDER_OK;
 }
 
 }  // namespace
@@ -675,30 +673,15 @@ int crender_wire_overlay(const int32_t *d_winner, const float *d_tri, int64_t T,
                          float feather, float opacity, float *d_color, int H, int W, int y0, int y1, unsigned flags,
                          void *stream)
 {
-    if (!d_winner || !P16 || !line3 || !d_color)
-        return fail(CRENDER_EINVAL, "crender_wire_overlay: d_winner, P16, line3 or d_color is NULL");
-    if (T < 0) return fail(CRENDER_EINVAL, "crender_wire_overlay: T is negative");
-    if (T > 0 && !d_tri) return fail(CRENDER_EINVAL, "crender_wire_overlay: d_tri is NULL with T > 0");
-    if (H < 1 || W < 1) return fail(CRENDER_EINVAL, "crender_wire_overlay: H or W is below 1");
-    if (y0 < 0 || y1 > H || y0 >= y1) return fail(CRENDER_EINVAL, "crender_wire_overlay: rows outside the frame");
-    if (!isfinite(width) || !(width > 0.0f && width <= (float)CRENDER_WIRE_MAX_WIDTH))
-        return fail(CRENDER_EINVAL, "crender_wire_overlay: width is not in (0, 64]");
-    if (!isfinite(feather) || !(feather > 0.0f && feather <= (float)CRENDER_WIRE_MAX_WIDTH))
-        return fail(CRENDER_EINVAL, "crender_wire_overlay: feather is not in (0, 64]");
-    if (!(opacity >= 0.0f && opacity <= 1.0f)) return fail(CRENDER_EINVAL, "crender_wire_overlay: opacity is not in [0, 1]");
-    bool finite = isfinite(line3[0]) && isfinite(line3[1]) && isfinite(line3[2]);
-    if (fill3) finite = finite && isfinite(fill3[0]) && isfinite(fill3[1]) && isfinite(fill3[2]);
-    if (!finite) return fail(CRENDER_EINVAL, "crender_wire_overlay: line3 or fill3 is not finite");
-    if (flags) return fail(CRENDER_EINVAL, "crender_wire_overlay: unknown flag bits");
-    if (T == 0) return CRENDER_OK;
+    const char *const E = "crender_wire_overlay";
+    if (!d_winner || !P16 || !line3 || !d_color) return arg_error(E, "d_winner, P16, line3 or d_color is NULL");
+    if (int rc = frame_checks(E, T, d_tri, H, W)) return rc;
+    if (int rc = rows_check(E, H, y0, y1)) return rc;
     WireStyle S{};
-    for (int j = 0; j < 3; ++j) {
-        S.line[j] = line3[j];
-        S.fill[j] = fill3 ? fill3[j] : 0.0f;
-    }
-    S.hi = width * 0.5f + feather * 0.5f;
-    S.feather = feather;
-    S.opacity = opacity;
+    if (int rc = wire_window(E, width, feather, opacity)) return rc;
+    if (int rc = wire_style(E, line3, fill3, width, feather, opacity, S)) return rc;
+    if (flags) return arg_error(E, "unknown flag bits");
+    if (T == 0) return CRENDER_OK;
     static constexpr decltype(&k_wire_overlay<false>) kernels[2] = {k_wire_overlay<false>, k_wire_overlay<true>};
     const PassGrid G = pass_grid(W, y0, y1);
     hipLaunchKernelGGL(kernels[fill3 != nullptr], G.grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), d_winner,
@@ -712,40 +695,22 @@ int crender_wire_outline(const int32_t *d_winner, const float *d_z, const float 
                          const float *fill3, float width, float feather, float opacity, float depth_bias, int radius_px,
                          float *d_color, int H, int W, int y0, int y1, unsigned flags, void *stream)
 {
-    if (!d_winner || !d_z || !P16 || !line3 || !d_color)
-        return fail(CRENDER_EINVAL, "crender_wire_outline: d_winner, d_z, P16, line3 or d_color is NULL");
-    if (T < 0) return fail(CRENDER_EINVAL, "crender_wire_outline: T is negative");
-    if (T > 0 && !d_tri) return fail(CRENDER_EINVAL, "crender_wire_outline: d_tri is NULL with T > 0");
-    if (H < 1 || W < 1) return fail(CRENDER_EINVAL, "crender_wire_outline: H or W is below 1");
-    if (y0 < 0 || y1 > H || y0 >= y1) return fail(CRENDER_EINVAL, "crender_wire_outline: rows outside the frame");
-    if (!isfinite(width) || !(width > 0.0f && width <= (float)CRENDER_WIRE_MAX_WIDTH))
-        return fail(CRENDER_EINVAL, "crender_wire_outline: width is not in (0, 64]");
-    if (!isfinite(feather) || !(feather > 0.0f && feather <= (float)CRENDER_WIRE_MAX_WIDTH))
-        return fail(CRENDER_EINVAL, "crender_wire_outline: feather is not in (0, 64]");
-    if (!(opacity >= 0.0f && opacity <= 1.0f)) return fail(CRENDER_EINVAL, "crender_wire_outline: opacity is not in [0, 1]");
-    if (!isfinite(depth_bias)) return fail(CRENDER_EINVAL, "crender_wire_outline: depth_bias is not finite");
-    if (radius_px < 0 || radius_px > CRENDER_WIRE_OUTLINE_MAX_RADIUS)
-        return fail(CRENDER_EINVAL, "crender_wire_outline: radius_px is not 0 .. 8");
-    bool finite = isfinite(line3[0]) && isfinite(line3[1]) && isfinite(line3[2]);
-    if (fill3) finite = finite && isfinite(fill3[0]) && isfinite(fill3[1]) && isfinite(fill3[2]);
-    if (!finite) return fail(CRENDER_EINVAL, "crender_wire_outline: line3 or fill3 is not finite");
-    if (flags) return fail(CRENDER_EINVAL, "crender_wire_outline: unknown flag bits");
-    if (T == 0) return CRENDER_OK;
-    const int tiles_x = (W + kTile - 1) / kTile;
-    const int64_t tiles = (int64_t)tiles_x * (int64_t)((y1 - y0 + kTile - 1) / kTile);
-    if (tiles > 0x7FFFFFFF) return fail(CRENDER_EINVAL, "crender_wire_outline: H or W is too large");
+    const char *const E = "crender_wire_outline";
+    if (!d_winner || !d_z || !P16 || !line3 || !d_color) return arg_error(E, "d_winner, d_z, P16, line3 or d_color is NULL");
+    if (int rc = frame_checks(E, T, d_tri, H, W)) return rc;
+    if (int rc = rows_check(E, H, y0, y1)) return rc;
     WireStyle S{};
-    for (int j = 0; j < 3; ++j) {
-        S.line[j] = line3[j];
-        S.fill[j] = fill3 ? fill3[j] : 0.0f;
-    }
-    S.hi = width * 0.5f + feather * 0.5f;
-    S.feather = feather;
-    S.opacity = opacity;
-    const int side = kTile + 2 * radius_px;
+    if (int rc = wire_window(E, width, feather, opacity)) return rc;
+    if (!isfinite(depth_bias)) return arg_error(E, "depth_bias is not finite");
+    if (radius_px < 0 || radius_px > CRENDER_WIRE_OUTLINE_MAX_RADIUS) return arg_error(E, "radius_px is not 0 .. 8");
+    if (int rc = wire_style(E, line3, fill3, width, feather, opacity, S)) return rc;
+    if (flags) return arg_error(E, "unknown flag bits");
+    if (T == 0) return CRENDER_OK;
+    int tiles_x, tiles;
+    if (int rc = tile_grid(E, W, y0, y1, tiles_x, tiles)) return rc;
     static constexpr decltype(&k_wire_outline<false>) kernels[2] = {k_wire_outline<false>, k_wire_outline<true>};
     hipLaunchKernelGGL(kernels[fill3 != nullptr], dim3((unsigned)tiles), dim3(kThreads),
-                       (size_t)(side * side + side) * sizeof(int32_t), static_cast<hipStream_t>(stream), d_winner, d_z,
+                       tile_lds_bytes(radius_px, kTile + 2 * radius_px), static_cast<hipStream_t>(stream), d_winner, d_z,
                        d_tri, T, d_pos_of, make_proj(P16, W, H), d_edges, S, depth_bias, radius_px, d_color, W, y0, y1,
                        tiles_x);
     CR_LAUNCH_CHECK("k_wire_outline");
@@ -756,21 +721,16 @@ int crender_wire_edge_aa(const int32_t *d_winner, const float *d_z, const float 
                          const float *P16, const uint8_t *d_edges, float *d_out, const float *d_color, int H, int W,
                          int y0, int y1, unsigned flags, void *stream)
 {
-    if (!d_winner || !d_z || !P16 || !d_out || !d_color)
-        return fail(CRENDER_EINVAL, "crender_wire_edge_aa: d_winner, d_z, P16, d_out or d_color is NULL");
-    if (T < 0) return fail(CRENDER_EINVAL, "crender_wire_edge_aa: T is negative");
-    if (T > 0 && !d_tri) return fail(CRENDER_EINVAL, "crender_wire_edge_aa: d_tri is NULL with T > 0");
-    if (H < 1 || W < 1) return fail(CRENDER_EINVAL, "crender_wire_edge_aa: H or W is below 1");
-    if (y0 < 0 || y1 > H || y0 >= y1) return fail(CRENDER_EINVAL, "crender_wire_edge_aa: rows outside the frame");
-    if (flags) return fail(CRENDER_EINVAL, "crender_wire_edge_aa: unknown flag bits");
-    if (d_out == d_color)
-        return fail(CRENDER_EINVAL, "crender_wire_edge_aa: d_out is d_color (the pass cannot run in place)");
-    const int tiles_x = (W + kTile - 1) / kTile;
-    const int64_t tiles = (int64_t)tiles_x * (int64_t)((y1 - y0 + kTile - 1) / kTile);
-    if (tiles > 0x7FFFFFFF) return fail(CRENDER_EINVAL, "crender_wire_edge_aa: H or W is too large");
+    const char *const E = "crender_wire_edge_aa";
+    if (!d_winner || !d_z || !P16 || !d_out || !d_color) return arg_error(E, "d_winner, d_z, P16, d_out or d_color is NULL");
+    if (int rc = frame_checks(E, T, d_tri, H, W)) return rc;
+    if (int rc = rows_check(E, H, y0, y1)) return rc;
+    if (flags) return arg_error(E, "unknown flag bits");
+    if (d_out == d_color) return arg_error(E, "d_out is d_color (the pass cannot run in place)");
+    int tiles_x, tiles;
+    if (int rc = tile_grid(E, W, y0, y1, tiles_x, tiles)) return rc;
     // (T == 0: every winner is invalid and every wavefront copies)
-    constexpr int side = kTile + 2;
-    hipLaunchKernelGGL(k_wire_edge_aa, dim3((unsigned)tiles), dim3(kThreads), (size_t)(side * side) * sizeof(int32_t),
+    hipLaunchKernelGGL(k_wire_edge_aa, dim3((unsigned)tiles), dim3(kThreads), tile_lds_bytes(1),
                        static_cast<hipStream_t>(stream), d_winner, d_z, d_tri, T, d_pos_of, make_proj(P16, W, H), d_edges,
                        d_out, d_color, W, y0, y1, tiles_x);
     CR_LAUNCH_CHECK("k_wire_edge_aa");
@@ -781,12 +741,10 @@ int crender_wire_contours(const float *d_tri, int64_t T, const uint32_t *d_pos_o
                           const int32_t *d_partners, const uint8_t *d_static, int8_t *d_facing, uint8_t *d_edges, int H,
                           int W, unsigned flags, void *stream)
 {
-    if (!P16 || !d_partners || !d_facing || !d_edges)
-        return fail(CRENDER_EINVAL, "crender_wire_contours: P16, d_partners, d_facing or d_edges is NULL");
-    if (T < 0) return fail(CRENDER_EINVAL, "crender_wire_contours: T is negative");
-    if (T > 0 && !d_tri) return fail(CRENDER_EINVAL, "crender_wire_contours: d_tri is NULL with T > 0");
-    if (H < 1 || W < 1) return fail(CRENDER_EINVAL, "crender_wire_contours: H or W is below 1");
-    if (flags & ~CRENDER_WIRE_CONTOUR_BORDERS) return fail(CRENDER_EINVAL, "crender_wire_contours: unknown flag bits");
+    const char *const E = "crender_wire_contours";
+    if (!P16 || !d_partners || !d_facing || !d_edges) return arg_error(E, "P16, d_partners, d_facing or d_edges is NULL");
+    if (int rc = frame_checks(E, T, d_tri, H, W)) return rc;
+    if (flags & ~CRENDER_WIRE_CONTOUR_BORDERS) return arg_error(E, "unknown flag bits");
     if (T == 0) return CRENDER_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(grid_for((size_t)T, 16384));

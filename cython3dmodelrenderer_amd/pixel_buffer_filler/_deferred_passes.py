@@ -48,15 +48,21 @@ def _as_device_f32(a, name, device):
     return t
 
 
+def _device_array(filler, a, dtype, shape_ok, what, part=slice(None)):
+    """`a`, a numpy array or a tensor, as a contiguous tensor on the filler's device, which is looked at only after the
+    check ("`what`, got <dtype> <shape>" unless its dtype is `dtype` and `shape_ok(its shape)`); `part` of it is moved."""
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    if t.dtype != dtype or not shape_ok(tuple(t.shape)):
+        raise ValueError(f"{what}, got {t.dtype} {tuple(t.shape)}")
+    return t[part].to(filler.device).contiguous()
+
+
 def _edge_mask(filler, edges, T):
     """None, or the uint8 [T] edge mask of ``wire_pass`` and ``edge_aa`` on the filler's device, from numpy or a tensor."""
     if edges is None:
         return None
-    e = edges if isinstance(edges, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(edges))
-    if e.dtype != torch.uint8 or e.dim() != 1 or e.shape[0] != T:
-        raise ValueError(f"edges must be uint8 [T] with T = {T}, the triangles of the last frame, "
-                         f"got {e.dtype} {tuple(e.shape)}")
-    return e.to(filler.device).contiguous()
+    return _device_array(filler, edges, torch.uint8, lambda s: s == (T,),
+                         f"edges must be uint8 [T] with T = {T}, the triangles of the last frame")
 
 
 class DeferredPasses:
@@ -121,15 +127,12 @@ class DeferredPasses:
             return
         if uv_by_triangles is None or texture is None:
             raise ValueError("bind_texture needs both the texture coordinates and the texture (or None, None)")
-        uv = uv_by_triangles if isinstance(uv_by_triangles, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(uv_by_triangles))
-        tex = texture if isinstance(texture, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(texture))
-        if uv.dtype != torch.float32 or uv.dim() != 3 or uv.shape[1] != 3 or uv.shape[2] != 2:
-            raise ValueError(f"uv_by_triangles must be float32 [T, 3, 2], got {uv.dtype} {tuple(uv.shape)}")
-        if tex.dtype != torch.uint8 or tex.dim() != 3 or tex.shape[2] < 3 or tex.shape[0] < 1 or tex.shape[1] < 1:
-            raise ValueError(f"texture must be uint8 [th, tw, 3], got {tex.dtype} {tuple(tex.shape)}")
-        bound = (uv.to(self.device).contiguous(), tex[:, :, :3].to(self.device).contiguous())
-        self._mip = self._build_mip_chain(bound[1]) if mipmaps else None
-        self._texture = bound
+        uv = _device_array(self, uv_by_triangles, torch.float32, lambda s: len(s) == 3 and s[1:] == (3, 2),
+                           "uv_by_triangles must be float32 [T, 3, 2]")
+        tex = _device_array(self, texture, torch.uint8, lambda s: len(s) == 3 and s[2] >= 3 and s[0] >= 1 and s[1] >= 1,
+                            "texture must be uint8 [th, tw, 3]", part=(..., slice(3)))
+        self._mip = self._build_mip_chain(tex) if mipmaps else None
+        self._texture = (uv, tex)
 
     def _build_mip_chain(self, tex):
         """(chain uint8 [total bytes], [(h_k, w_k)], [byte offset of level k]) of a device texture."""
@@ -416,27 +419,18 @@ class DeferredPasses:
         if self._pipeline:
             raise ValueError("contour_edges is not available on a swap chain (pipeline=True): per-slot passes are not implemented")
         tri, T = self._pass_frame("contour_edges")
-        p = partners if isinstance(partners, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(partners))
-        if p.dtype != torch.int32 or p.dim() != 2 or p.shape[1] != 3:
-            raise ValueError(f"partners must be int32 [T, 3] (wireframe.edge_partners), got {p.dtype} {tuple(p.shape)}")
+        p = _device_array(self, partners, torch.int32, lambda s: len(s) == 2 and s[1] == 3,
+                          "partners must be int32 [T, 3] (wireframe.edge_partners)")
         if p.shape[0] != T:
             raise ValueError(f"contour_edges: the partner table holds {p.shape[0]} triangles, the last frame drew {T}")
         if static is not None:
-            s = static if isinstance(static, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(static))
-            if s.dtype != torch.uint8 or s.dim() != 1:
-                raise ValueError(f"static must be uint8 [T], got {s.dtype} {tuple(s.shape)}")
-            if s.shape[0] != T:
-                raise ValueError(f"contour_edges: the static mask holds {s.shape[0]} triangles, the last frame drew {T}")
-            static = s.to(self.device).contiguous()
-        p = p.to(self.device).contiguous()
+            static = _device_array(self, static, torch.uint8, lambda s: len(s) == 1, "static must be uint8 [T]")
+            if static.shape[0] != T:
+                raise ValueError(f"contour_edges: the static mask holds {static.shape[0]} triangles, the last frame drew {T}")
         facing = torch.empty(T, dtype=torch.int8, device=self.device)
         edges = torch.empty(T, dtype=torch.uint8, device=self.device)
-        if T == 0:
-            return edges
-        pos_of = None if self._order is None else self._order[1]
-        args = (tri if T else None, T, pos_of, self._P, p, static, facing, edges, self.h, self.w,
-                _capi.WIRE_CONTOUR_BORDERS if borders else 0)
-        with torch.cuda.device(self.device):
-            _capi.check(self._lib.crender_wire_contours(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args],
-                                                        self._stream()), "crender_wire_contours")
+        if T:
+            pos_of = None if self._order is None else self._order[1]
+            self._launch_pass("crender_wire_contours", (tri, T, pos_of, self._P, p, static, facing, edges, self.h, self.w,
+                                                        _capi.WIRE_CONTOUR_BORDERS if borders else 0))
         return edges

@@ -55,7 +55,8 @@ def test_edge_aa_symbol_is_declared_exported_and_bound(capi):
     # after the outline, before the contour kernels; the projection and the barycentrics are the rasterizer's, called
     assert unit.index("void k_wire_outline") < unit.index("void k_wire_edge_aa") < unit.index("void k_wire_facing")
     body = unit[unit.index("void k_wire_edge_aa"):unit.index("void k_wire_facing")]
-    assert body.count("barycentric(t, ") == 2 and "near_triangle(" in body and "asm" not in body
+    assert body.count("barycentric(t, ") == 2 and "winner_triangle(" in body and "asm" not in body
+    assert not re.search(r"CR_DEV[^\n]*\bwinner_triangle\(", unit) and "project_vertex(" not in unit
     assert "extern __shared__" in body and "wave_any(" in body
 
 

@@ -60,8 +60,8 @@ def test_phong_sources_are_built_and_stay_out_of_the_profile_fingerprint():
     assert unit_inputs(_build, "phong") <= set(_build.build_inputs())
     # the kernel takes the rasterizer's arithmetic and the passes' frame from the shared headers by inclusion
     unit = open(os.path.join(_build.SRC_DIR, "phong.hip")).read()
-    for name in ("project_vertex(", "barycentric(", "guro_factor(", "make_proj(", "wave_any(", "winner_pixel(",
-                 "gather_corners(", "pass_grid("):
+    # (the gather and the projection of the winner's corners are the header's winner_triangle)
+    for name in ("winner_triangle(", "barycentric(", "guro_factor(", "make_proj(", "wave_any(", "winner_pixel(", "pass_grid("):
         assert name in unit and not re.search(r"CR_DEV[^\n]*\b" + re.escape(name), unit), name
 
 

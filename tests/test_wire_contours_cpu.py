@@ -55,7 +55,9 @@ def test_contours_symbol_is_declared_exported_and_bound(capi):
     assert "k_wire_facing" in unit and "k_wire_contour_mask" in unit
     # the projection is the rasterizer's, called: the kernel restates neither it nor the gather
     body = unit[unit.index("void k_wire_facing"):unit.index("void k_wire_contour_mask")]
-    assert body.count("project_vertex(P, ") == 3 and "gather_corners(" in body and "asm" not in body
+    # (both through winner_pass.h's winner_triangle, once per triangle)
+    assert body.count("winner_triangle(tri, q, P)") == 1 and "asm" not in body
+    assert "project_vertex(" not in unit and "gather_corners(" not in unit
 
 
 def test_contours_argument_errors_without_a_gpu(capi):

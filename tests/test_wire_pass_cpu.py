@@ -55,8 +55,11 @@ def test_the_build_lists_are_unchanged():
     assert unit_inputs(_build, "wire") | unit_inputs(_build, "pass") <= set(inputs) and len(inputs) == len(set(inputs))
     unit = open(os.path.join(_build.SRC_DIR, "wireframe.hip")).read()
     assert '#include "winner_pass.h"' in unit
-    for name in ("project_vertex(", "make_proj(", "wave_any(", "winner_pixel(", "gather_corners(", "pass_grid("):
+    # (the gather and the projection of a winner's corners are the header's winner_triangle)
+    for name in ("winner_triangle(", "make_proj(", "wave_any(", "winner_pixel(", "tile_origin(", "pass_grid("):
         assert name in unit and not re.search(r"CR_DEV[^\n]*\b" + re.escape(name), unit), name
+    for name in ("project_vertex(", "gather_corners("):
+        assert name not in unit, name
 
 
 def test_overlay_argument_errors_without_a_gpu(capi):
