@@ -88,6 +88,8 @@ WIRE_DOTS, WIRE_FORCE_COLORS, WIRE_CLEAR = 1, 2, 4
 WIRE_MAX_WIDTH = 64
 WIRE_OUTLINE_MAX_RADIUS = 8
 WIRE_CONTOUR_BORDERS = 1
+WIRE_HIDDEN_USE_WINNER = 1
+WIRE_MAX_DASH = 64
 UNIT_SIGNATURES["wire"] = {
     "crender_wire_key_bytes": (_sz, [_i32, _i32]),
     "crender_wire_draw": (_i32, [_vp, _vp, _i64, _f32p, _vp, _vp, _vp, _vp, _i32, _i32, _u32, _vp, _vp]),
@@ -103,6 +105,10 @@ UNIT_SIGNATURES["wire"] = {
     # geometric edge anti-aliasing over the winner plane (DeferredPasses.edge_aa): the outline's planes and mask, the
     # result plane in front of the colour plane, which is only read
     "crender_wire_edge_aa": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
+    # the edges behind the surface, dashed (DeferredPasses.hidden_line_pass): the outline's planes and mask, the line's
+    # colour, opacity, dash and depth bias, the key plane in front of the colour plane
+    "crender_wire_hidden": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, _f32p, C.c_float, _i32, _i32, C.c_float, _vp, _vp,
+                                   _i32, _i32, _i32, _i32, _u32, _vp]),
 }
 
 # the numpy filler's entry points (include/crender_py.h), bound from a table of their own

@@ -13,6 +13,7 @@
 // lines at full width from a neighbourhood pass over the winner plane staged in LDS, of the shape of k_ao_shade.  And
 // what the two draw for a view: the contour edges (k_wire_facing, k_wire_contour_mask), classified per frame.  And the
 // coverage of boundary pixels from the same staged winners (k_wire_edge_aa, after the outline): geometric anti-aliasing.
+// And the edges BEHIND the surface, dashed (k_wire_hidden, after the contour kernels): k_wire's walker over the z plane.
 //
 // Order.  With one constant colour every writer of a pixel stores the same 12 bytes.  With
 // per-triangle colours the last write of the reference's sequence (triangle i, edge e) wins; a line
@@ -593,6 +594,124 @@ __global__ __launch_bounds__(kThreads) void k_wire_contour_mask(const int32_t *_
     }
 }
 
+// ---- the hidden lines (crender_wire_hidden) ---------------------------------------------------------------------
+// The edges BEHIND the surface, dashed: what no pass over the winner plane can draw, since a hidden edge belongs to
+// triangles that won nothing where it runs.  The shape of k_wire: one workgroup per 256 half-edges (segment s = 3 i + e,
+// i in the caller's order), each work item projects, rounds and clips its own segment with seg_setup, the workgroup
+// scans the counts and deals the candidate pixels one per work item.  A step compares the edge's depth, interpolated
+// along the major axis (projected z is affine on the screen), with the z plane.  Two launches over a uint32 key plane,
+// zero before and after: the first marks a visible step with 2 and a drawn hidden step with 1 by atomicMax, the second
+// walks the same candidates again and the one walker that takes a 1 out of a pixel blends the line's colour into it.
+// The result is a function of the set of marked pixels.  Per-segment LDS: the Seg's six words, the offset, za and
+// zb - za: 9.2 KB per workgroup, static.
+
+enum { kHiddenMark = 0, kHiddenResolve = 1 };
+
+// The line and the test of a call.
+struct HiddenStyle {
+    float line[3];
+    float opacity, bias;
+    int on, period;                          // dash_on, dash_on + dash_off
+    int use_winner;
+};
+
+template <int MODE>
+__global__ __launch_bounds__(kThreads) void k_wire_hidden(const int32_t *__restrict__ win, const float *__restrict__ zb,
+                                                           const float *__restrict__ tri, int64_t T,
+                                                           const uint32_t *__restrict__ pos_of, ProjConst P,
+                                                           const uint8_t *__restrict__ edges, int64_t nseg, HiddenStyle S,
+                                                           uint32_t *__restrict__ key, float *__restrict__ cb, int H, int W,
+                                                           int y0, int y1)
+{
+    __shared__ int s_a1[kThreads], s_b1[kThreads], s_el[kThreads], s_es[kThreads], s_t0[kThreads],
+        s_sg[kThreads];
+    __shared__ float s_za[kThreads], s_dz[kThreads];
+    __shared__ uint32_t s_off[kThreads];
+    __shared__ uint32_t s_wave[kThreads / 64];
+    const int tid = threadIdx.x;
+    const int64_t first = (int64_t)blockIdx.x * kThreads;
+    const int64_t seg = first + tid;
+    uint32_t cnt = 0;
+    Seg s = {0, 0, 0, 0, 0, 0};
+    float za = 0.0f, dz = 0.0f;
+    if (seg < nseg) {
+        const int64_t i = seg / 3;
+        const int e = (int)(seg - 3 * i);
+        const unsigned mask = edges ? edges[i] : 7u;            // the caller's order, whatever pos_of says
+        const int64_t pos = pos_of ? (int64_t)pos_of[i] : i;
+        if (((mask >> e) & 1u) && pos < T) {
+            float raw[3][3];
+            const TriXYZ X = winner_triangle(tri, pos, P, raw);
+            // corner e and corner (e + 1) % 3, by selects (an index would put the corners into scratch)
+            float xa = e == 0 ? X.x0 : e == 1 ? X.x1 : X.x2, ya = e == 0 ? X.y0 : e == 1 ? X.y1 : X.y2;
+            float pza = e == 0 ? X.z0 : e == 1 ? X.z1 : X.z2;
+            float xb = e == 0 ? X.x1 : e == 1 ? X.x2 : X.x0, yb = e == 0 ? X.y1 : e == 1 ? X.y2 : X.y0;
+            float pzb = e == 0 ? X.z1 : e == 1 ? X.z2 : X.z0;
+            const float rza = e == 0 ? raw[0][2] : e == 1 ? raw[1][2] : raw[2][2];
+            const float rzb = e == 0 ? raw[1][2] : e == 1 ? raw[2][2] : raw[0][2];
+            // in front of the camera (a NaN fails), and in k_wire_check's domain
+            if (rza > 0.0f && rzb > 0.0f && fabsf(xa) < kDomain && fabsf(ya) < kDomain && fabsf(xb) < kDomain &&
+                fabsf(yb) < kDomain) {
+                int ax = (int)rintf(xa), ay = (int)rintf(ya), bx = (int)rintf(xb), by = (int)rintf(yb);
+                // from the end whose (y, x) is smaller: both half-edges of an edge then walk the same pixels
+                if (by < ay || (by == ay && bx < ax)) {
+                    int ti = ax; ax = bx; bx = ti;
+                    ti = ay; ay = by; by = ti;
+                    const float tf = pza; pza = pzb; pzb = tf;
+                }
+                cnt = seg_setup(ax, ay, bx, by, W, H, s);
+                za = pza;
+                dz = pzb - pza;
+            }
+        }
+    }
+    s_a1[tid] = s.a1; s_b1[tid] = s.b1; s_el[tid] = s.el; s_es[tid] = s.es; s_t0[tid] = s.t0; s_sg[tid] = s.sg;
+    s_za[tid] = za; s_dz[tid] = dz;
+    // exclusive scan of the counts over the workgroup
+    const uint32_t incl = wave_incl_sum(cnt);
+    if ((tid & 63) == 63) s_wave[tid >> 6] = incl;
+    __syncthreads();
+    uint32_t base = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kThreads / 64; ++w) {
+        base += w < (tid >> 6) ? s_wave[w] : 0u;
+        total += s_wave[w];
+    }
+    s_off[tid] = base + incl - cnt;
+    __syncthreads();
+    for (uint32_t p = tid; p < total; p += kThreads) {
+        // the last segment whose first candidate is at or before p holds p (empty ones share the next offset)
+        int j = 0;
+#pragma unroll
+        for (int step = kThreads / 2; step; step >>= 1)
+            if (s_off[j + step] <= p) j += step;
+        const Seg g = {s_a1[j], s_b1[j], s_el[j], s_es[j], s_t0[j], s_sg[j]};
+        const int64_t t = (int64_t)g.t0 + (p - s_off[j]);
+        int x, y;
+        seg_pixel(g, t, x, y);
+        if ((unsigned)x >= (unsigned)W || (unsigned)y >= (unsigned)H) continue;   // (clipped above; kept as a guard)
+        if (y < y0 || y >= y1) continue;
+        const size_t pix = (size_t)y * W + x;
+        if (MODE == kHiddenMark) {
+            const float lam = g.el ? (float)t / (float)g.el : 0.0f;
+            const float ze = s_za[j] + s_dz[j] * lam;
+            bool hidden = zb[pix] < ze - S.bias;                // (false for every NaN; the background's 1e6 never hides)
+            if (hidden && S.use_winner && (int64_t)win[pix] == (first + j) / 3) hidden = false;
+            if (!hidden) {
+                atomicMax(key + pix, 2u);
+            } else {
+                const int c = (g.sg & 1) ? x : y;               // on the frame: never negative
+                if (c % S.period < S.on) atomicMax(key + pix, 1u);
+            }
+        } else if (atomicExch(key + pix, 0u) == 1u) {              // (one walker per pixel gets the 1)
+            float *cp = cb + pix * 3;
+            const float k = 1.0f - S.opacity;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) cp[c] = cp[c] * k + S.line[c] * S.opacity;
+        }
+    }
+}
+
 // The line of an overlay or outline call: its window, then (after what only the outline checks) its colours and the WireStyle.
 int wire_window(const char *entry, float width, float feather, float opacity)
 {
@@ -753,6 +872,40 @@ int crender_wire_contours(const float *d_tri, int64_t T, const uint32_t *d_pos_o
     hipLaunchKernelGGL(k_wire_contour_mask, grid, dim3(kThreads), 0, st, d_partners, d_static, d_facing, T,
                        (flags & CRENDER_WIRE_CONTOUR_BORDERS) ? 1 : 0, d_edges);
     CR_LAUNCH_CHECK("k_wire_contour_mask");
+    return CRENDER_OK;
+}
+
+int crender_wire_hidden(const int32_t *d_winner, const float *d_z, const float *d_tri, int64_t T, const uint32_t *d_pos_of,
+                        const float *P16, const uint8_t *d_edges, const float *line3, float opacity, int dash_on,
+                        int dash_off, float depth_bias, uint32_t *d_key, float *d_color, int H, int W, int y0, int y1,
+                        unsigned flags, void *stream)
+{
+    const char *const E = "crender_wire_hidden";
+    if (!d_winner || !d_z || !P16 || !line3 || !d_key || !d_color)
+        return arg_error(E, "d_winner, d_z, P16, line3, d_key or d_color is NULL");
+    if (int rc = frame_checks(E, T, d_tri, H, W)) return rc;
+    if (int rc = rows_check(E, H, y0, y1)) return rc;
+    if (H > kMaxSide || W > kMaxSide) return arg_error(E, "H or W is above 2^20");      // (crender_wire_key_bytes' bound)
+    if (!(opacity >= 0.0f && opacity <= 1.0f)) return arg_error(E, "opacity is not in [0, 1]");
+    if (!(isfinite(line3[0]) && isfinite(line3[1]) && isfinite(line3[2]))) return arg_error(E, "line3 is not finite");
+    if (dash_on < 1 || dash_on > CRENDER_WIRE_MAX_DASH || dash_off < 0 || dash_off > CRENDER_WIRE_MAX_DASH)
+        return arg_error(E, "dash_on is not 1 .. 64 or dash_off is not 0 .. 64");
+    if (!isfinite(depth_bias)) return arg_error(E, "depth_bias is not finite");
+    if (flags & ~CRENDER_WIRE_HIDDEN_USE_WINNER) return arg_error(E, "unknown flag bits");
+    if (T > ((int64_t)0x7FFFFFFF * kThreads) / 3) return arg_error(E, "T is too large");   // 3 T segments, 256 to a workgroup
+    if (T == 0) return CRENDER_OK;
+    const HiddenStyle S = {{line3[0], line3[1], line3[2]}, opacity, depth_bias, dash_on, dash_on + dash_off,
+                           (flags & CRENDER_WIRE_HIDDEN_USE_WINNER) ? 1 : 0};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t nseg = T * 3;
+    const dim3 grid((unsigned)((nseg + kThreads - 1) / kThreads));
+    const ProjConst P = make_proj(P16, W, H);
+    hipLaunchKernelGGL(k_wire_hidden<kHiddenMark>, grid, dim3(kThreads), 0, st, d_winner, d_z, d_tri, T, d_pos_of, P, d_edges,
+                       nseg, S, d_key, d_color, H, W, y0, y1);
+    CR_LAUNCH_CHECK("k_wire_hidden<mark>");
+    hipLaunchKernelGGL(k_wire_hidden<kHiddenResolve>, grid, dim3(kThreads), 0, st, d_winner, d_z, d_tri, T, d_pos_of, P,
+                       d_edges, nseg, S, d_key, d_color, H, W, y0, y1);
+    CR_LAUNCH_CHECK("k_wire_hidden<resolve>");
     return CRENDER_OK;
 }
 

@@ -1,6 +1,7 @@
 """The deferred passes of ``AdvancedPixelBufferFiller`` over the winner plane of its last frame: texture (nearest,
 bilinear, trilinear, anisotropic), shadow, Phong, ambient occlusion and the wireframe overlay, with the texture and shadow-map bindings they
-read, the classification of a view's contour edges for the overlay (``contour_edges``: it reads no plane) and geometric
+read, the classification of a view's contour edges for the overlay (``contour_edges``: it reads no plane), the edges behind
+the surface, dashed (``hidden_line_pass``: it walks the edges, not the winner plane's pixels, and keeps a key plane) and geometric
 edge anti-aliasing (``edge_aa``: it reads the planes and returns a plane of its own).  A mixin
 beside ``_device_planes.DevicePlanes``: the filler supplies ``device, h, w, y0, y1, _lib, _P`` and its frame state (``_pipeline, _inputs, _order, _last_flags, _check_bins``).  What every pass has in common is here
 once: whom it refuses (``_pass_target``), which frame it accepts (``_pass_frame``), and how it is launched
@@ -69,6 +70,7 @@ class DeferredPasses:
     _texture = None    # (uv [T, 3, 2] float32, image [th, tw, 3] uint8) device tensors: bind_texture
     _mip = None        # (chain, [(h_k, w_k)], [byte offsets]) of that image: bind_texture(mipmaps=True)
     _shadow = None     # (the light's filler, its vertices [T, 3, 3] float32 on the device): bind_shadow_map
+    _hidden_key = None  # the zeroed int32 [h, w] key plane of hidden_line_pass, which every call leaves zero
 
     # --------------------------------------------------- what every pass shares --
     def _pass_target(self, name):
@@ -377,6 +379,50 @@ class DeferredPasses:
             return
         self._run_pass("crender_wire_overlay", tri, T,
                        (edges if T else None, line3, fill3, float(width), float(feather), float(opacity)))
+
+    def hidden_line_pass(self, color=(0, 0, 0), opacity=0.5, dash=(4, 4), edges=None, depth_bias=1e-3, use_winner=True):
+        """The edges BEHIND the surface, dashed, over the LAST frame's colour plane (``crender_wire_hidden``,
+        include/crender_wire.h): the far side of a technical drawing, which ``wire_pass`` cannot show, since it sees an
+        edge only through pixels the edge's own triangle won.  Every drawn half-edge is projected, rounded to pixel
+        centres and walked with the wireframe filler's Bresenham; a step is hidden where the z plane holds something
+        nearer than the edge's own depth there, less `depth_bias` (in the z plane's units, as ``wire_pass``'s), and —
+        with `use_winner` — the pixel was not won by the edge's own triangle.  A pixel through which a hidden edge runs,
+        and no drawn edge that is visible there, is blended towards `color` by `opacity` (0 to 1) if its coordinate
+        along the edge's major axis falls into the first ``dash[0]`` (1 to 64) pixels of every ``dash[0] + dash[1]``
+        (``dash[1]`` 0 to 64; 0 is a solid line): one pixel wide, the pattern anchored to the screen.  `edges` is
+        ``wire_pass``'s: None or a uint8 array [T] in the caller's triangle order (``wireframe.feature_edges``,
+        ``contour_edges``).  Rows of the filler's ``row_strip``, on torch's current stream.  The pass keeps a zeroed
+        int32 [h, w] key plane on the device, allocated at the first call.
+
+        The frame is settled first (one stream synchronisation, as every getter does): a frame whose bin lists
+        overflowed is rendered again, and the pass must land on the frame that stays."""
+        self._pass_target("hidden_line_pass")
+        number = (int, float, np.integer, np.floating)
+        if isinstance(opacity, bool) or not isinstance(opacity, number) or not 0 <= float(opacity) <= 1:
+            raise ValueError(f"opacity must be a number from 0 to 1, got {opacity!r}")
+        top = _capi.WIRE_MAX_DASH
+        try:
+            on, off = dash
+            bad = any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in (on, off))
+        except (TypeError, ValueError):
+            bad = True
+        if bad or not 1 <= on <= top or not 0 <= off <= top:
+            raise ValueError(f"dash must be a pair of ints (on, off) with on from 1 to {top} and off from 0 to {top}, got {dash!r}")
+        if isinstance(depth_bias, bool) or not isinstance(depth_bias, number) or not np.isfinite(float(depth_bias)):
+            raise ValueError(f"depth_bias must be a finite number, got {depth_bias!r}")
+        try:
+            line = [float(v) for v in color]
+        except (TypeError, ValueError):
+            line = []
+        if len(line) != 3 or not np.isfinite(line).all():
+            raise ValueError(f"color must be three finite numbers, got {color!r}")
+        tri, T = self._pass_frame("hidden_line_pass")
+        edges = _edge_mask(self, edges, T)
+        if self._hidden_key is None:
+            self._hidden_key = torch.zeros((self.h, self.w), dtype=torch.int32, device=self.color_buffer.device)
+        self._run_pass("crender_wire_hidden", tri, T,
+                       (edges if T else None, (C.c_float * 3)(*line), float(opacity), int(on), int(off), float(depth_bias),
+                        self._hidden_key), _capi.WIRE_HIDDEN_USE_WINNER if use_winner else 0, z=True)
 
     def edge_aa(self, edges=None):
         """Geometric edge anti-aliasing of the LAST frame (``crender_wire_edge_aa``, include/crender_wire.h): a NEW

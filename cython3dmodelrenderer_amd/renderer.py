@@ -112,6 +112,18 @@ class Renderer:
             if wireframe.get("contours") and not hasattr(pixel_buffer_filler, "contour_edges"):
                 raise ValueError("Renderer(wireframe={'contours': True}) needs a filler that classifies contour edges "
                                  f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no contour_edges()")
+            # ``hidden`` (True, or a dict of AdvancedPixelBufferFiller.hidden_line_pass's arguments): the edges BEHIND the
+            # surface, dashed, right after the wire pass and with the same mask of the view, so that the contours, creases
+            # and borders of the far side are drawn; with ``supersample=s`` on the supersampled frame, whose pixels
+            # ``dash`` counts.
+            hidden = wireframe.get("hidden")
+            if hidden is not None and hidden is not False:
+                if not hasattr(pixel_buffer_filler, "hidden_line_pass"):
+                    raise ValueError("Renderer(wireframe={'hidden': ...}) needs a filler with a hidden-line pass "
+                                     f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no hidden_line_pass()")
+                if hidden is not True and not isinstance(hidden, dict):
+                    raise ValueError(f"Renderer(wireframe={{'hidden': ...}}) takes True or a dict of hidden_line_pass's "
+                                     f"arguments, got {hidden!r}")
             self.wireframe = dict(wireframe)
         # antialias=None (default): every pixel is its one sample.  A dict: geometric edge anti-aliasing
         # (``AdvancedPixelBufferFiller.edge_aa``) of the finished frame — {} smooths every edge, ``edges`` is an explicit
@@ -207,7 +219,14 @@ class Renderer:
         """The wire pass over the frame as it stands (host edits included), if a wireframe was asked for."""
         if self.wireframe is None:
             return
-        self.pixel_buffer_filler.wire_pass(**self._view_edges(model, self.wireframe, "_wired"))
+        opts = self._view_edges(model, self.wireframe, "_wired")
+        hidden = opts.pop("hidden", None)
+        self.pixel_buffer_filler.wire_pass(**opts)
+        if hidden is not None and hidden is not False:
+            # right after the visible lines (a ``fill`` would paint over dashes drawn first), with the same mask of the view
+            more = {} if hidden is True else dict(hidden)
+            more.setdefault("edges", opts.get("edges"))
+            self.pixel_buffer_filler.hidden_line_pass(**more)
 
     def _view_edges(self, model, options, slot):
         """`options` (``wireframe``'s or ``antialias``'s) with ``feature_angle`` / ``contours`` / ``borders`` turned into

@@ -2,7 +2,7 @@
  * crender_wire.h — C ABI of the wireframe filler (EdgeOnlyPixelBufferFiller) of
  * libcrender_hip.so, and of the hidden-line overlay over AdvancedPixelBufferFiller's winner plane
  * (crender_wire_overlay, and crender_wire_outline for lines at full width, at the end; crender_wire_contours picks the edges
- * of a view for both).  Same conventions as crender_hip.h: raw device pointers, an int
+ * of a view for both, crender_wire_hidden draws the edges behind the surface, dashed).  Same conventions as crender_hip.h: raw device pointers, an int
  * status (CRENDER_OK or a CRENDER_E* code, text in crender_last_error()), work enqueued
  * on `stream` and nothing synchronised.  Reference files cited below are in the
  * reference's crender/py/ (the crender/cy/ copies are identical but for one import).
@@ -314,6 +314,79 @@ CRENDER_API int crender_wire_edge_aa(const int32_t *d_winner, const float *d_z, 
 CRENDER_API int crender_wire_contours(const float *d_tri, int64_t T, const uint32_t *d_pos_of, const float *P16,
                                       const int32_t *d_partners, const uint8_t *d_static, int8_t *d_facing,
                                       uint8_t *d_edges, int H, int W, unsigned flags, void *stream);
+
+/*
+ * The hidden lines: the edges BEHIND the surface, dashed, as a technical drawing shows the far side of a body.  The
+ * overlay, the outline and the contours see an edge only through pixels its own triangle won; a hidden edge belongs to
+ * triangles that won nothing where it runs, so no pass over the pixels of the winner plane can draw it.  This one walks
+ * the EDGES, with crender_wire_draw's Bresenham, and compares each step's depth with the z plane of the frame.
+ *
+ * Result contract.
+ *
+ *   Arithmetic   every float step below is ONE float32 operation, rounded once, with IEEE division (no contraction into
+ *                fused multiply-adds, no reciprocal, denormals kept); every integer step is exact.
+ *   Key plane    d_key, uint32 [H][W] (crender_wire_key_bytes), is ZERO on entry, and the call leaves it zero.
+ *   Segments     segment s = 3 i + e, 0 <= s < 3 T, is the half-edge of triangle i (the caller's order) from corner e to
+ *                corner (e + 1) % 3.  It is walked only if bit e of d_edges[i] is set (indexed by i itself, whatever
+ *                d_pos_of says; without d_edges all three are; bits 3 to 7 are ignored).  The triangle sits at d_tri[q],
+ *                q = d_pos_of ? d_pos_of[i] : i; q >= T skips the segment.  Nothing is ever read out of bounds.
+ *   Projection   the corners of d_tri[q] are projected as crender_project projects them (.pyx:116-130), the rasterizer's
+ *                own projection: (x_k, y_k, z_k), z_k the projected depth, the unit of d_z.  With a = corner e and
+ *                b = corner (e + 1) % 3 the segment is skipped unless both UNPROJECTED z are > 0 (a NaN fails), and
+ *                unless fabsf(c) < 2^30 for c = xa, ya, xb, yb (a NaN or an infinity fails): crender_wire_draw's domain.
+ *   End points   Xa = (int)rintf(xa), Ya = (int)rintf(ya), and b alike: the nearest pixel centre, ties to even (the
+ *                rasterizer samples at integer coordinates).  If (Yb, Xb) is lexicographically smaller than (Ya, Xa),
+ *                a and b change places, z_a and z_b with them: the two half-edges of an edge walk the same pixels with
+ *                the same operands.  Equal integer end points keep the half-edge's own order; it is one pixel.
+ *   Pixels       those of crender_wire_draw's line from (Xa, Ya) to (Xb, Yb) (above: major length el, minor length es,
+ *                step t = 0 .. el at the major coordinate advanced by t and the minor by k(t)), without the pixels
+ *                off the frame and without those outside rows y0 <= y < y1.
+ *   Depth        at step t:  lam = (float)t / (float)el   (0.0f for el = 0)
+ *                            dz  = z_b - z_a               (once per segment)
+ *                            ze  = z_a + dz * lam
+ *                Projected z is affine on the screen: ze is the edge's depth at that step in d_z's units.
+ *   Hidden       hidden = d_z[y][x] < (ze - depth_bias).  False for every NaN; the background's 1e6 never hides.  With
+ *                CRENDER_WIRE_HIDDEN_USE_WINNER a step with d_winner[y][x] == i, the segment's own triangle, is
+ *                visible whatever the depths say.
+ *   Stipple      a hidden step is DRAWN iff c % (dash_on + dash_off) < dash_on, c the pixel's coordinate along the
+ *                segment's major axis (x if |Xb - Xa| > |Yb - Ya|, else y; never negative on the frame).  The pattern
+ *                is anchored to the screen: it continues across chains of short edges and does not depend on the
+ *                walking direction.  dash_off = 0 draws a solid line.
+ *   Combination  a visible step marks its pixel 2, a drawn hidden step 1, a pixel keeps the largest mark (atomicMax on
+ *                d_key).  A pixel is a HIDDEN-LINE pixel iff its mark ends at 1: a hidden edge runs through it and no
+ *                walked edge is visible there.  A second launch walks the same steps; the one walker whose
+ *                atomicExch(key, 0) returns 1 stores, per channel j,
+ *                            k = 1.0f - opacity,   colour_j = colour_j * k + line3_j * opacity
+ *                Every other pixel keeps its bits, and the key plane is zero again.  The result is a function of the
+ *                SET of marked pixels, not of the order of the walkers.
+ *   Other planes z, normals and the winner plane are only read.
+ *
+ * One pixel wide, not anti-aliased; the dash phase is by screen coordinate, not by arc length.  The winner rule knows
+ * the segment's own triangle only: where the partner across the edge won the pixel, the depths decide (depth_bias).
+ */
+#define CRENDER_WIRE_HIDDEN_USE_WINNER 1u
+#define CRENDER_WIRE_MAX_DASH 64
+
+/* Draw the hidden lines of T triangles into d_color float32 [H][W][3] over rows y0 <= y < y1.
+ *   d_winner, d_z, d_tri, T, d_pos_of, P16, d_edges   as crender_wire_outline takes them
+ *   line3      HOST float[3], the colour of the lines
+ *   opacity    of the lines, in [0, 1]
+ *   dash_on    pixels drawn per period, 1 .. CRENDER_WIRE_MAX_DASH
+ *   dash_off   pixels left out per period, 0 .. CRENDER_WIRE_MAX_DASH
+ *   depth_bias finite; in the units of d_z (projected z)
+ *   d_key      uint32 [H][W] of crender_wire_key_bytes, zero on entry and zero afterwards
+ *   flags      0 or CRENDER_WIRE_HIDDEN_USE_WINNER
+ * CRENDER_EINVAL, before anything is dereferenced or launched, checked in THIS order: a NULL d_winner, d_z, P16, line3,
+ * d_key or d_color; T < 0; T > 0 without d_tri; H or W < 1; rows outside the frame (y0 < 0, y1 > H, y0 >= y1); H or W
+ * above 2^20 (crender_wire_key_bytes' bound); an opacity not in [0, 1]; a line3 component that is not finite; dash_on
+ * outside 1 .. CRENDER_WIRE_MAX_DASH or dash_off outside 0 .. CRENDER_WIRE_MAX_DASH; a depth_bias that is not finite;
+ * any other flag bit; 3 T beyond what a grid of workgroups of 256 segments can count (T > (2^31 - 1) * 256 / 3).
+ * T == 0 returns CRENDER_OK without a launch.  Two launches on `stream`, in order, with 9.2 KB of static LDS each; no
+ * synchronisation. */
+CRENDER_API int crender_wire_hidden(const int32_t *d_winner, const float *d_z, const float *d_tri, int64_t T,
+                                    const uint32_t *d_pos_of, const float *P16, const uint8_t *d_edges, const float *line3,
+                                    float opacity, int dash_on, int dash_off, float depth_bias, uint32_t *d_key,
+                                    float *d_color, int H, int W, int y0, int y1, unsigned flags, void *stream);
 
 #ifdef __cplusplus
 }
