@@ -90,6 +90,8 @@ WIRE_OUTLINE_MAX_RADIUS = 8
 WIRE_CONTOUR_BORDERS = 1
 WIRE_HIDDEN_USE_WINNER = 1
 WIRE_MAX_DASH = 64
+WIRE_RUNS_GROUP = 256
+WIRE_RUNS_USE_WINNER = 1
 UNIT_SIGNATURES["wire"] = {
     "crender_wire_key_bytes": (_sz, [_i32, _i32]),
     "crender_wire_draw": (_i32, [_vp, _vp, _i64, _f32p, _vp, _vp, _vp, _vp, _i32, _i32, _u32, _vp, _vp]),
@@ -109,6 +111,13 @@ UNIT_SIGNATURES["wire"] = {
     # colour, opacity, dash and depth bias, the key plane in front of the colour plane
     "crender_wire_hidden": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, _f32p, C.c_float, _i32, _i32, C.c_float, _vp, _vp,
                                    _i32, _i32, _i32, _i32, _u32, _vp]),
+    # the same classification kept as vector segments (DeferredPasses.line_runs): the hidden pass's planes and mask, the
+    # partner table and the bias; the counts per group of 256 segments, then their prefix, the total and the two results
+    "crender_wire_runs_groups": (_i64, [_i64]),
+    "crender_wire_runs_count": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, _vp, C.c_float, _vp, _i32, _i32, _i32, _i32,
+                                       _u32, _vp]),
+    "crender_wire_runs_emit": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, _vp, C.c_float, _vp, _i64, _vp, _vp, _i32, _i32,
+                                      _i32, _i32, _u32, _vp]),
 }
 
 # the numpy filler's entry points (include/crender_py.h), bound from a table of their own

@@ -14,6 +14,7 @@
 // what the two draw for a view: the contour edges (k_wire_facing, k_wire_contour_mask), classified per frame.  And the
 // coverage of boundary pixels from the same staged winners (k_wire_edge_aa, after the outline): geometric anti-aliasing.
 // And the edges BEHIND the surface, dashed (k_wire_hidden, after the contour kernels): k_wire's walker over the z plane.
+// And that classification kept as vector segments (k_wire_runs, last): maximal runs per edge, compacted in order.
 //
 // Order.  With one constant colour every writer of a pixel stores the same 12 bytes.  With
 // per-triangle colours the last write of the reference's sequence (triangle i, edge e) wins; a line
@@ -737,6 +738,228 @@ int wire_style(const char *entry, const float *line3, const float *fill3, float 
     return CRENDER_OK;
 }
 
+// ---- the drawing as vectors (crender_wire_runs_count, crender_wire_runs_emit) -----------------------------------
+// The hidden pass's classification KEPT: k_wire_hidden's shape — a workgroup per 256 half-edges, each work item sets its
+// own segment up, the workgroup scans the counts and deals the candidate steps one per work item, 256 at a time — but a
+// step's class (hidden 1, visible 2, off the rows 0) goes into maximal RUNS per segment instead of a key plane.  The order
+// of the candidates p within a workgroup is the order (segment, step), so a run's rank in its group is the number of run
+// starts at candidates before it, and the k-th start and the k-th end of a group are the same run: the lane that finds a
+// start stores (s, t0, class) and the first point into slot k, the lane that finds an end stores t1 and the second point
+// into slot k, and nobody walks a run.  A lane looks at ONE neighbour, the candidate before its own, whose class and
+// segment it reads from LDS (the last lane's are carried to the next trip): candidate p starts a run if its class is not
+// 0 and the pair (segment, class) before it differs, and it ENDS the run of candidate p - 1 if that one's class is not 0
+// and the pair differs.  One candidate beyond the last closes the group's last run.  The ranks are a ballot and a count
+// of the lanes below per wavefront, the wavefronts' totals through LDS, and two running bases across the trips (a run may
+// start in one trip and end in a later one).  No atomics: a slot is a function of the inputs alone.
+// Per-segment LDS: k_wire_hidden's nine words, the partner's triangle, and for the emit the four unrounded coordinates.
+
+enum { kRunsCount = 0, kRunsEmit = 1 };
+
+// How many lanes below this one have `flag`, and how many of the wavefront: a ballot and its counts.
+CR_DEV uint32_t wave_rank(bool flag, uint32_t &total)
+{
+    const uint64_t b = __builtin_amdgcn_ballot_w64(flag);
+    total = (uint32_t)__popcll(b);
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+}
+
+// A point of a run: x(u) = xa (1 - u) + xb u, which gives the ends back bit for bit at u = 0 and u = 1.
+CR_DEV float run_lerp(float a, float b, float u)
+{
+    return a * (1.0f - u) + b * u;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kThreads) void k_wire_runs(const int32_t *__restrict__ win, const float *__restrict__ zb,
+                                                         const float *__restrict__ tri, int64_t T,
+                                                         const uint32_t *__restrict__ pos_of, ProjConst P,
+                                                         const uint8_t *__restrict__ edges,
+                                                         const int32_t *__restrict__ partners, int64_t nseg, float bias,
+                                                         int use_winner, uint32_t *__restrict__ counts,
+                                                         const int64_t *__restrict__ offsets, int64_t N,
+                                                         int32_t *__restrict__ runs, float *__restrict__ ends, int H, int W,
+                                                         int y0, int y1)
+{
+    constexpr bool EMIT = MODE == kRunsEmit;
+    constexpr int kEnds = EMIT ? kThreads : 1;
+    __shared__ int s_a1[kThreads], s_b1[kThreads], s_el[kThreads], s_es[kThreads], s_t0[kThreads],
+        s_sg[kThreads];
+    __shared__ float s_za[kThreads], s_dz[kThreads];
+    __shared__ int32_t s_partner[kThreads];             // the triangle across the edge, or -1
+    __shared__ float s_xa[kEnds], s_ya[kEnds], s_xb[kEnds], s_yb[kEnds];      // the unrounded ends, in walking order
+    __shared__ uint32_t s_off[kThreads];
+    __shared__ uint32_t s_wave[kThreads / 64];
+    __shared__ uint32_t s_prev[kThreads + 1];           // class | (segment + 1) << 2 of the candidate before each lane's
+    __shared__ uint32_t s_starts[kThreads / 64], s_ends[kThreads / 64];
+    const int tid = threadIdx.x;
+    const int64_t first = (int64_t)blockIdx.x * kThreads;
+    const int64_t seg = first + tid;
+    uint32_t cnt = 0;
+    Seg s = {0, 0, 0, 0, 0, 0};
+    float za = 0.0f, dz = 0.0f;
+    float exa = 0.0f, eya = 0.0f, exb = 0.0f, eyb = 0.0f;
+    int32_t partner = -1;
+    if (seg < nseg) {
+        const int64_t i = seg / 3;
+        const int e = (int)(seg - 3 * i);
+        const unsigned mask = edges ? edges[i] : 7u;            // the caller's order, whatever pos_of says
+        const int64_t pos = pos_of ? (int64_t)pos_of[i] : i;
+        if (((mask >> e) & 1u) && pos < T) {
+            float raw[3][3];
+            const TriXYZ X = winner_triangle(tri, pos, P, raw);
+            // corner e and corner (e + 1) % 3, by selects (k_wire_hidden's statements)
+            float xa = e == 0 ? X.x0 : e == 1 ? X.x1 : X.x2, ya = e == 0 ? X.y0 : e == 1 ? X.y1 : X.y2;
+            float pza = e == 0 ? X.z0 : e == 1 ? X.z1 : X.z2;
+            float xb = e == 0 ? X.x1 : e == 1 ? X.x2 : X.x0, yb = e == 0 ? X.y1 : e == 1 ? X.y2 : X.y0;
+            float pzb = e == 0 ? X.z1 : e == 1 ? X.z2 : X.z0;
+            const float rza = e == 0 ? raw[0][2] : e == 1 ? raw[1][2] : raw[2][2];
+            const float rzb = e == 0 ? raw[1][2] : e == 1 ? raw[2][2] : raw[0][2];
+            if (rza > 0.0f && rzb > 0.0f && fabsf(xa) < kDomain && fabsf(ya) < kDomain && fabsf(xb) < kDomain &&
+                fabsf(yb) < kDomain) {
+                int ax = (int)rintf(xa), ay = (int)rintf(ya), bx = (int)rintf(xb), by = (int)rintf(yb);
+                if (by < ay || (by == ay && bx < ax)) {         // from the end whose (y, x) is smaller
+                    int ti = ax; ax = bx; bx = ti;
+                    ti = ay; ay = by; by = ti;
+                    float tf = pza; pza = pzb; pzb = tf;
+                    tf = xa; xa = xb; xb = tf;
+                    tf = ya; ya = yb; yb = tf;
+                }
+                cnt = seg_setup(ax, ay, bx, by, W, H, s);
+                za = pza;
+                dz = pzb - pza;
+                exa = xa; eya = ya; exb = xb; eyb = yb;
+                if (use_winner && partners) {
+                    const int32_t v = partners[i * 3 + e];
+                    if (v >= 0) partner = v >> 1;
+                }
+            }
+        }
+    }
+    s_a1[tid] = s.a1; s_b1[tid] = s.b1; s_el[tid] = s.el; s_es[tid] = s.es; s_t0[tid] = s.t0; s_sg[tid] = s.sg;
+    s_za[tid] = za; s_dz[tid] = dz;
+    s_partner[tid] = partner;
+    if (EMIT) {
+        s_xa[tid] = exa; s_ya[tid] = eya; s_xb[tid] = exb; s_yb[tid] = eyb;
+    }
+    if (tid == 0) s_prev[0] = 0u;                               // nothing lies before the group's first candidate
+    // exclusive scan of the counts over the workgroup
+    const uint32_t incl = wave_incl_sum(cnt);
+    if ((tid & 63) == 63) s_wave[tid >> 6] = incl;
+    __syncthreads();
+    uint32_t base = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kThreads / 64; ++w) {
+        base += w < (tid >> 6) ? s_wave[w] : 0u;
+        total += s_wave[w];
+    }
+    s_off[tid] = base + incl - cnt;
+    __syncthreads();
+    int64_t slot0 = 0, limit = 0;                               // the group's first slot, and the first that is not its own
+    if (EMIT) {
+        slot0 = offsets[blockIdx.x];
+        limit = blockIdx.x + 1u < gridDim.x ? offsets[blockIdx.x + 1u] : N;
+        limit = limit < N ? limit : N;
+    }
+    uint32_t nstart = 0, nend = 0;                              // the starts and ends of the trips so far (uniform)
+    // candidates 0 .. total - 1, and one beyond them, which ends the last run
+    for (uint32_t c0 = 0; c0 <= total; c0 += kThreads) {
+        const uint32_t p = c0 + tid;
+        uint32_t cls = 0;
+        int j = -1, t = 0;
+        if (p < total) {
+            // the last segment whose first candidate is at or before p holds p (empty ones share the next offset)
+            j = 0;
+#pragma unroll
+            for (int step = kThreads / 2; step; step >>= 1)
+                if (s_off[j + step] <= p) j += step;
+            const Seg g = {s_a1[j], s_b1[j], s_el[j], s_es[j], s_t0[j], s_sg[j]};
+            t = g.t0 + (int)(p - s_off[j]);
+            int x, y;
+            seg_pixel(g, (int64_t)t, x, y);
+            if ((unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H && y >= y0 && y < y1) {
+                const size_t pix = (size_t)y * W + x;
+                const float lam = g.el ? (float)t / (float)g.el : 0.0f;
+                const float ze = s_za[j] + s_dz[j] * lam;
+                bool hidden = zb[pix] < ze - bias;              // (false for every NaN)
+                if (hidden && use_winner) {
+                    const int64_t w = (int64_t)win[pix];
+                    const int32_t q = s_partner[j];
+                    if (w == (first + j) / 3 || (q >= 0 && w == (int64_t)q)) hidden = false;
+                }
+                cls = hidden ? 1u : 2u;
+            }
+        }
+        const uint32_t mine = cls | ((uint32_t)(j + 1) << 2);
+        s_prev[tid + 1] = mine;
+        __syncthreads();
+        const uint32_t prev = s_prev[tid];
+        const bool differs = prev != mine;                      // another segment, or another class
+        const bool start = cls != 0u && differs;
+        const bool end = (prev & 3u) != 0u && differs;          // of the run that holds candidate p - 1
+        uint32_t wave_starts, wave_ends;
+        const uint32_t rs = wave_rank(start, wave_starts), re = wave_rank(end, wave_ends);
+        if ((tid & 63) == 0) {
+            s_starts[tid >> 6] = wave_starts;
+            s_ends[tid >> 6] = wave_ends;
+        }
+        __syncthreads();
+        uint32_t ks = nstart + rs, ke = nend + re;
+#pragma unroll
+        for (int w = 0; w < kThreads / 64; ++w) {
+            ks += w < (tid >> 6) ? s_starts[w] : 0u;
+            ke += w < (tid >> 6) ? s_ends[w] : 0u;
+            nstart += s_starts[w];
+            nend += s_ends[w];
+        }
+        if (EMIT) {
+            if (start) {
+                const int64_t slot = slot0 + (int64_t)ks;
+                if (slot >= 0 && slot < limit) {
+                    const int el = s_el[j];
+                    const float u = el ? fmaxf((float)t - 0.5f, 0.0f) / (float)el : 0.0f;
+                    int32_t *r = runs + slot * 4;
+                    float *q = ends + slot * 4;
+                    r[0] = (int32_t)(first + j);
+                    r[1] = t;
+                    r[3] = (int32_t)cls;
+                    q[0] = run_lerp(s_xa[j], s_xb[j], u);
+                    q[1] = run_lerp(s_ya[j], s_yb[j], u);
+                }
+            }
+            if (end) {
+                const int jp = (int)(prev >> 2) - 1;            // candidate p - 1: its segment, and its step
+                const int tp = s_t0[jp] + (int)(p - 1u - s_off[jp]);
+                const int64_t slot = slot0 + (int64_t)ke;
+                if (slot >= 0 && slot < limit) {
+                    const int el = s_el[jp];
+                    const float u = el ? fminf((float)tp + 0.5f, (float)el) / (float)el : 1.0f;
+                    runs[slot * 4 + 2] = tp;
+                    float *q = ends + slot * 4;
+                    q[2] = run_lerp(s_xa[jp], s_xb[jp], u);
+                    q[3] = run_lerp(s_ya[jp], s_yb[jp], u);
+                }
+            }
+        }
+        if (tid == kThreads - 1) s_prev[0] = mine;              // (every lane has read its word: the barrier above)
+    }
+    if (!EMIT && tid == 0) counts[blockIdx.x] = nstart;
+}
+
+// The checks the two entries share, in the header's order; `nulls` names the pointers that were found NULL.
+int runs_checks(const char *entry, bool null_arg, const char *nulls, int64_t T, const float *d_tri, int H, int W, int y0,
+                int y1, float depth_bias, unsigned flags, int64_t N)
+{
+    if (null_arg) return arg_error(entry, nulls);
+    if (int rc = frame_checks(entry, T, d_tri, H, W)) return rc;
+    if (int rc = rows_check(entry, H, y0, y1)) return rc;
+    if (H > kMaxSide || W > kMaxSide) return arg_error(entry, "H or W is above 2^20");
+    if (!isfinite(depth_bias)) return arg_error(entry, "depth_bias is not finite");
+    if (flags & ~CRENDER_WIRE_RUNS_USE_WINNER) return arg_error(entry, "unknown flag bits");
+    if (N < 0) return arg_error(entry, "N is negative");
+    if (T > (int64_t)0x7FFFFFFF / 3) return arg_error(entry, "T is too large");        // 3 T segments in an int32
+    return CRENDER_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -906,6 +1129,51 @@ int crender_wire_hidden(const int32_t *d_winner, const float *d_z, const float *
     hipLaunchKernelGGL(k_wire_hidden<kHiddenResolve>, grid, dim3(kThreads), 0, st, d_winner, d_z, d_tri, T, d_pos_of, P,
                        d_edges, nseg, S, d_key, d_color, H, W, y0, y1);
     CR_LAUNCH_CHECK("k_wire_hidden<resolve>");
+    return CRENDER_OK;
+}
+
+int64_t crender_wire_runs_groups(int64_t T)
+{
+    if (T < 0 || T > (int64_t)0x7FFFFFFF / 3) return -1;
+    return (T * 3 + CRENDER_WIRE_RUNS_GROUP - 1) / CRENDER_WIRE_RUNS_GROUP;
+}
+
+int crender_wire_runs_count(const int32_t *d_winner, const float *d_z, const float *d_tri, int64_t T, const uint32_t *d_pos_of,
+                            const float *P16, const uint8_t *d_edges, const int32_t *d_partners, float depth_bias,
+                            uint32_t *d_counts, int H, int W, int y0, int y1, unsigned flags, void *stream)
+{
+    const char *const E = "crender_wire_runs_count";
+    if (int rc = runs_checks(E, !d_winner || !d_z || !P16 || !d_counts, "d_winner, d_z, P16 or d_counts is NULL", T, d_tri, H,
+                             W, y0, y1, depth_bias, flags, 0))
+        return rc;
+    if (T == 0) return CRENDER_OK;
+    static_assert(CRENDER_WIRE_RUNS_GROUP == kThreads, "a group is a workgroup's segments");
+    const int64_t nseg = T * 3;
+    hipLaunchKernelGGL(k_wire_runs<kRunsCount>, dim3((unsigned)crender_wire_runs_groups(T)), dim3(kThreads), 0,
+                       static_cast<hipStream_t>(stream), d_winner, d_z, d_tri, T, d_pos_of, make_proj(P16, W, H), d_edges,
+                       d_partners, nseg, depth_bias, (flags & CRENDER_WIRE_RUNS_USE_WINNER) ? 1 : 0, d_counts,
+                       (const int64_t *)nullptr, (int64_t)0, (int32_t *)nullptr, (float *)nullptr, H, W, y0, y1);
+    CR_LAUNCH_CHECK("k_wire_runs<count>");
+    return CRENDER_OK;
+}
+
+int crender_wire_runs_emit(const int32_t *d_winner, const float *d_z, const float *d_tri, int64_t T, const uint32_t *d_pos_of,
+                           const float *P16, const uint8_t *d_edges, const int32_t *d_partners, float depth_bias,
+                           const int64_t *d_offsets, int64_t N, int32_t *d_runs, float *d_ends, int H, int W, int y0, int y1,
+                           unsigned flags, void *stream)
+{
+    const char *const E = "crender_wire_runs_emit";
+    if (int rc = runs_checks(E, !d_winner || !d_z || !P16 || !d_offsets || !d_runs || !d_ends,
+                             "d_winner, d_z, P16, d_offsets, d_runs or d_ends is NULL", T, d_tri, H, W, y0, y1, depth_bias,
+                             flags, N))
+        return rc;
+    if (T == 0 || N == 0) return CRENDER_OK;
+    const int64_t nseg = T * 3;
+    hipLaunchKernelGGL(k_wire_runs<kRunsEmit>, dim3((unsigned)crender_wire_runs_groups(T)), dim3(kThreads), 0,
+                       static_cast<hipStream_t>(stream), d_winner, d_z, d_tri, T, d_pos_of, make_proj(P16, W, H), d_edges,
+                       d_partners, nseg, depth_bias, (flags & CRENDER_WIRE_RUNS_USE_WINNER) ? 1 : 0, (uint32_t *)nullptr,
+                       d_offsets, N, d_runs, d_ends, H, W, y0, y1);
+    CR_LAUNCH_CHECK("k_wire_runs<emit>");
     return CRENDER_OK;
 }
 

@@ -1,7 +1,8 @@
 """The deferred passes of ``AdvancedPixelBufferFiller`` over the winner plane of its last frame: texture (nearest,
 bilinear, trilinear, anisotropic), shadow, Phong, ambient occlusion and the wireframe overlay, with the texture and shadow-map bindings they
 read, the classification of a view's contour edges for the overlay (``contour_edges``: it reads no plane), the edges behind
-the surface, dashed (``hidden_line_pass``: it walks the edges, not the winner plane's pixels, and keeps a key plane) and geometric
+the surface, dashed (``hidden_line_pass``: it walks the edges, not the winner plane's pixels, and keeps a key plane), the same
+classification kept as vector segments (``line_runs``: it only reads the planes and returns a ``LineDrawing``) and geometric
 edge anti-aliasing (``edge_aa``: it reads the planes and returns a plane of its own).  A mixin
 beside ``_device_planes.DevicePlanes``: the filler supplies ``device, h, w, y0, y1, _lib, _P`` and its frame state (``_pipeline, _inputs, _order, _last_flags, _check_bins``).  What every pass has in common is here
 once: whom it refuses (``_pass_target``), which frame it accepts (``_pass_frame``), and how it is launched
@@ -66,8 +67,28 @@ def _edge_mask(filler, edges, T):
                          f"edges must be uint8 [T] with T = {T}, the triangles of the last frame")
 
 
+class LineDrawing:
+    """What ``line_runs`` returns: ``runs`` int32 [N, 4] (segment, first step, last step, class) and ``ends`` float32
+    [N, 4] (x0, y0, x1, y1) in the pixel coordinates of a frame ``height`` x ``width``, row k of both for run k."""
+    HIDDEN, VISIBLE = 1, 2
+
+    def __init__(self, runs, ends, height, width):
+        self.runs, self.ends, self.height, self.width = runs, ends, int(height), int(width)
+
+    def __len__(self):
+        return int(self.runs.shape[0])
+
+    def visible(self):
+        """The ``ends`` rows of the visible runs, in order."""
+        return self.ends[self.runs[:, 3] == self.VISIBLE]
+
+    def hidden(self):
+        """The ``ends`` rows of the hidden runs, in order."""
+        return self.ends[self.runs[:, 3] == self.HIDDEN]
+
+
 class DeferredPasses:
-    _texture = None    # (uv [T, 3, 2] float32, image [th, tw, 3] uint8) device tensors: bind_texture
+    _texture = None   # (uv [T, 3, 2] float32, image [th, tw, 3] uint8) device tensors: bind_texture
     _mip = None        # (chain, [(h_k, w_k)], [byte offsets]) of that image: bind_texture(mipmaps=True)
     _shadow = None     # (the light's filler, its vertices [T, 3, 3] float32 on the device): bind_shadow_map
     _hidden_key = None  # the zeroed int32 [h, w] key plane of hidden_line_pass, which every call leaves zero
@@ -423,6 +444,59 @@ class DeferredPasses:
         self._run_pass("crender_wire_hidden", tri, T,
                        (edges if T else None, (C.c_float * 3)(*line), float(opacity), int(on), int(off), float(depth_bias),
                         self._hidden_key), _capi.WIRE_HIDDEN_USE_WINNER if use_winner else 0, z=True)
+
+    def line_runs(self, edges=None, partners=None, depth_bias=1e-3, use_winner=True):
+        """The hidden-line drawing of the LAST frame as vector segments (``crender_wire_runs_count`` and
+        ``crender_wire_runs_emit``, include/crender_wire.h): a ``LineDrawing``.  Every drawn half-edge is projected, rounded
+        and walked as ``hidden_line_pass`` walks it, and every step is classed hidden or visible by the same test against
+        the z plane; the steps are then joined into maximal runs of one class per edge, and every run comes back as a
+        sub-segment of the edge's unrounded projection, in the frame's pixel coordinates and clipped to the frame:
+        ``drawing.runs`` int32 [N, 4] holds (segment 3 i + e, first step, last step, class: 1 hidden, 2 visible) and
+        ``drawing.ends`` float32 [N, 4] (x0, y0, x1, y1), ordered by (segment, first step), device tensors both.
+        `edges` is ``hidden_line_pass``'s mask; a vector drawing wants every mesh edge ONCE: ``wireframe.half_edges_once``.
+        `partners` (None, or the int32 [T, 3] table of ``wireframe.edge_partners``, numpy or a device tensor) extends the
+        winner rule of `use_winner` to the triangle across the edge: a step is visible where either of the edge's two
+        triangles won the pixel.  ``wireframe.write_svg`` writes the drawing.  Rows of the filler's ``row_strip``, on
+        torch's current stream.
+
+        Edits made in the numpy views handed out so far are carried to the device and the frame is settled first (one
+        stream synchronisation, as every getter does).  The call then counts, reads the total ONCE (``.item()``: its one
+        extra synchronisation; the size of the result is not known before) and stores.  The planes are only read: the
+        views stay as fresh or as stale as they were."""
+        self._pass_target("line_runs")
+        if isinstance(depth_bias, bool) or not isinstance(depth_bias, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(float(depth_bias)):
+            raise ValueError(f"depth_bias must be a finite number, got {depth_bias!r}")
+        tri, T = self._pass_frame("line_runs")
+        edges = _edge_mask(self, edges, T)
+        if partners is not None:
+            partners = _device_array(self, partners, torch.int32, lambda s: len(s) == 2 and s[1] == 3,
+                                     "partners must be int32 [T, 3] (wireframe.edge_partners)")
+            if partners.shape[0] != T:
+                raise ValueError(f"line_runs: the partner table holds {partners.shape[0]} triangles, the last frame drew {T}")
+        if 3 * T > 2 ** 31 - 1:
+            raise ValueError(f"line_runs takes at most {(2 ** 31 - 1) // 3} triangles, the last frame drew {T}")
+        self._push_host_edits()
+        self._check_bins()
+        device = self.color_buffer.device
+        groups = -(-3 * T // _capi.WIRE_RUNS_GROUP)
+        runs = torch.empty((0, 4), dtype=torch.int32, device=device)
+        ends = torch.empty((0, 4), dtype=torch.float32, device=device)
+        if groups == 0:
+            return LineDrawing(runs, ends, self.h, self.w)
+        pos_of = None if self._order is None else self._order[1]
+        flags = _capi.WIRE_RUNS_USE_WINNER if use_winner else 0
+        head = (self.winner_buffer, self.z_buffer, tri, T, pos_of, self._P, edges, partners, float(depth_bias))
+        tail = (self.h, self.w, self.y0, self.y1, flags)
+        counts = torch.empty(groups, dtype=torch.int32, device=device)       # (a uint32 below 2^28: the same bits)
+        self._launch_pass("crender_wire_runs_count", head + (counts,) + tail)
+        after = torch.cumsum(counts, 0, dtype=torch.int64)
+        N = int(after[-1].item())
+        if N:
+            runs = torch.empty((N, 4), dtype=torch.int32, device=device)
+            ends = torch.empty((N, 4), dtype=torch.float32, device=device)
+            self._launch_pass("crender_wire_runs_emit", head + (after - counts, N, runs, ends) + tail)
+        return LineDrawing(runs, ends, self.h, self.w)
 
     def edge_aa(self, edges=None):
         """Geometric edge anti-aliasing of the LAST frame (``crender_wire_edge_aa``, include/crender_wire.h): a NEW

@@ -124,7 +124,22 @@ class Renderer:
                 if hidden is not True and not isinstance(hidden, dict):
                     raise ValueError(f"Renderer(wireframe={{'hidden': ...}}) takes True or a dict of hidden_line_pass's "
                                      f"arguments, got {hidden!r}")
+            # ``vector`` (True, or a dict of AdvancedPixelBufferFiller.line_runs' arguments): after the wire pass and the
+            # hidden pass of a frame the same view's drawing is also taken as vector segments, with the view's mask reduced
+            # to one half-edge per edge (``wireframe.half_edges_once``) and the model's partner table (the contours' own, or
+            # made once per model), and kept as ``renderer.line_drawing`` (``wireframe.write_svg`` writes it).  With
+            # ``supersample=s`` its coordinates are the supersampled frame's.
+            vector = wireframe.get("vector")
+            if vector is not None and vector is not False:
+                if not hasattr(pixel_buffer_filler, "line_runs"):
+                    raise ValueError("Renderer(wireframe={'vector': ...}) needs a filler that returns the drawing as vectors "
+                                     f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no line_runs()")
+                if vector is not True and not isinstance(vector, dict):
+                    raise ValueError(f"Renderer(wireframe={{'vector': ...}}) takes True or a dict of line_runs' "
+                                     f"arguments, got {vector!r}")
             self.wireframe = dict(wireframe)
+        self.line_drawing = None       # the last frame's LineDrawing under wireframe={"vector": ...}
+        self._paired = None            # (weak reference to the model, its partner table) where the contours keep none
         # antialias=None (default): every pixel is its one sample.  A dict: geometric edge anti-aliasing
         # (``AdvancedPixelBufferFiller.edge_aa``) of the finished frame — {} smooths every edge, ``edges`` is an explicit
         # mask, and ``feature_angle`` / ``contours`` / ``borders`` pick the edges as ``wireframe`` picks them (the mask
@@ -221,12 +236,36 @@ class Renderer:
             return
         opts = self._view_edges(model, self.wireframe, "_wired")
         hidden = opts.pop("hidden", None)
+        vector = opts.pop("vector", None)
         self.pixel_buffer_filler.wire_pass(**opts)
         if hidden is not None and hidden is not False:
             # right after the visible lines (a ``fill`` would paint over dashes drawn first), with the same mask of the view
             more = {} if hidden is True else dict(hidden)
             more.setdefault("edges", opts.get("edges"))
             self.pixel_buffer_filler.hidden_line_pass(**more)
+        if vector is not None and vector is not False:
+            # the same view as vectors: every drawn edge once, either of its two triangles makes it visible
+            from .wireframe import half_edges_once
+            more = {} if vector is True else dict(vector)
+            if more.get("partners") is None:
+                more["partners"] = self._partners(model)
+            if "edges" not in more:
+                more["edges"] = half_edges_once(opts.get("edges"), more["partners"])
+            self.line_drawing = self.pixel_buffer_filler.line_runs(**more)
+
+    def _partners(self, model):
+        """The model's partner table: the one the contours of ``wireframe`` hold, or one made once per model."""
+        if self._wired is not None and self._wired[0]() is model and self._wired[2] is not None:
+            return self._wired[2]
+        if self._paired is None or self._paired[0]() is not model:
+            from .wireframe import edge_partners
+            partners = edge_partners(model._vertices_by_triangles)      # (a device model's table is made on the device)
+            device = getattr(self.pixel_buffer_filler, "device", None)
+            if device is not None and not hasattr(partners, "data_ptr"):
+                import torch
+                partners = torch.from_numpy(partners).to(device)
+            self._paired = (weakref.ref(model), partners)
+        return self._paired[1]
 
     def _view_edges(self, model, options, slot):
         """`options` (``wireframe``'s or ``antialias``'s) with ``feature_angle`` / ``contours`` / ``borders`` turned into

@@ -1,7 +1,9 @@
 """Which edges of a mesh a wireframe should show: the per-triangle edge masks ``AdvancedPixelBufferFiller.wire_pass``
 takes as ``edges`` (``feature_edges``: creases and borders), and the mesh's connectivity as the table from which
 ``AdvancedPixelBufferFiller.contour_edges`` classifies the edges of a view on the device (``edge_partners``).  Host numpy
-in float64, or torch ops on the device the triangles are on; once per model: not a hot path."""
+in float64, or torch ops on the device the triangles are on; once per model: not a hot path.  And for the drawing as
+vectors (``AdvancedPixelBufferFiller.line_runs``): ``half_edges_once``, which leaves one half-edge of every drawn edge in
+a mask, and ``write_svg``, which writes the runs out."""
 import numpy as np
 
 
@@ -137,3 +139,108 @@ def _edge_partners_torch(tri):
     table = torch.empty(3 * T, dtype=torch.int32, device=tri.device)
     table[order] = entry.to(torch.int32)
     return table.reshape(T, 3)
+
+
+def half_edges_once(edges, partners):
+    """uint8 [T]: the edge mask `edges` (uint8 [T], or None for every edge) with one of the two half-edges of every drawn
+    mesh edge cleared, so that ``AdvancedPixelBufferFiller.line_runs`` walks every drawn edge exactly once.  `partners` is
+    the mesh's partner table (int32 [T, 3], ``edge_partners``).  numpy arrays give a numpy array; torch tensors give a
+    tensor on the device of `partners`, made there: nothing is downloaded.
+
+    Bit e of triangle i is cleared when it is set, ``partners[i, e] >= 0``, the partner ``p = partners[i, e] >> 1`` is
+    below i, and some half-edge e' of p names i as its partner (``partners[p, e'] >= 0`` and ``partners[p, e'] >> 1 ==
+    i``) and is drawn itself.  Borders, edges of more than two faces, the half-edge of the smaller triangle and every
+    half-edge whose twin is not drawn stay.  Bits 3 to 7 come out 0.  Applying it twice changes nothing more."""
+    if hasattr(partners, "data_ptr"):
+        import torch
+        T = partners.shape[0]
+        if partners.dtype != torch.int32 or partners.dim() != 2 or partners.shape[1] != 3:
+            raise ValueError(f"partners must be int32 [T, 3] (edge_partners), got {partners.dtype} {tuple(partners.shape)}")
+        ids = torch.arange(T, device=partners.device)
+        shifts = torch.arange(3, device=partners.device)
+        weights = torch.tensor([1, 2, 4], device=partners.device)
+        if edges is None:
+            bits = torch.full((T,), 7, dtype=torch.int64, device=partners.device)
+        else:
+            if not hasattr(edges, "data_ptr"):
+                edges = torch.from_numpy(np.ascontiguousarray(edges))
+            if edges.dtype != torch.uint8 or tuple(edges.shape) != (T,):
+                raise ValueError(f"edges must be uint8 [T] with T = {T}, got {edges.dtype} {tuple(edges.shape)}")
+            bits = edges.to(partners.device).to(torch.int64)
+        table = partners.to(torch.int64)
+        clip = lambda a: a.clamp(0, max(T - 1, 0))      # noqa: E731
+        as_u8 = lambda a: a.to(torch.uint8)             # noqa: E731
+    else:
+        table = np.asarray(partners)
+        if table.dtype != np.int32 or table.ndim != 2 or table.shape[1] != 3:
+            raise ValueError(f"partners must be int32 [T, 3] (edge_partners), got {table.dtype} {tuple(table.shape)}")
+        T = table.shape[0]
+        ids, shifts, weights = np.arange(T), np.arange(3), np.array([1, 2, 4])
+        if edges is None:
+            bits = np.full(T, 7, np.int64)
+        else:
+            given = np.asarray(edges)
+            if given.dtype != np.uint8 or given.shape != (T,):
+                raise ValueError(f"edges must be uint8 [T] with T = {T}, got {given.dtype} {tuple(given.shape)}")
+            bits = given.astype(np.int64)
+        table = table.astype(np.int64)
+        clip = lambda a: np.clip(a, 0, max(T - 1, 0))   # noqa: E731
+        as_u8 = lambda a: a.astype(np.uint8)            # noqa: E731
+    if T == 0:
+        return as_u8(bits)
+    drawn = ((bits[:, None] >> shifts[None, :]) & 1) == 1                      # [T, 3]
+    p = table >> 1
+    lower = drawn & (table >= 0) & (p < ids[:, None])
+    back = table[clip(p)]                                                     # [T, 3, 3]: the partner's own row
+    twin = ((back >= 0) & ((back >> 1) == ids[:, None, None]) & drawn[clip(p)]).any(-1)
+    keep = drawn & ~(lower & twin)
+    return as_u8((keep * weights[None, :]).sum(1))
+
+
+def _host(a):
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
+def write_svg(target, drawing, stroke="#000", width=1.0, hidden=True, hidden_dash=(4, 4), hidden_opacity=0.5,
+              background=None, scale=1.0):
+    """Write the ``LineDrawing`` of ``AdvancedPixelBufferFiller.line_runs`` as an SVG to `target`, a path or a text file
+    object.  Host code on the standard library: one download of ``drawing.ends`` and one of the classes.
+
+    The centre of pixel (x, y) maps to ((x + 0.5) * scale, (y + 0.5) * scale), computed in double precision from the float32
+    coordinates, and the picture is ``width * scale`` by ``height * scale`` of the drawing's frame.  Every run is one
+    ``<line>``: the hidden runs in a group ``class="hidden"`` with ``stroke-dasharray`` `hidden_dash` and
+    ``stroke-opacity`` `hidden_opacity` (left out with ``hidden=False``), then the visible runs, solid, in a group
+    ``class="visible"``, which so paints over the hidden one.  `stroke` and `width` (in SVG units, not scaled) are both
+    groups'; `background`, a colour, puts a rectangle under everything.  Coordinates are written with three decimals
+    (``"%.3f"``): equal float32 coordinates give equal text, so chains of edges that share an end point close exactly."""
+    from xml.sax.saxutils import quoteattr
+    ends = _host(drawing.ends).astype(np.float64)
+    cls = _host(drawing.runs[:, 3])
+    scale = float(scale)
+    if not scale > 0 or not np.isfinite(scale):
+        raise ValueError(f"scale must be a positive number, got {scale!r}")
+    on, off = (float(v) for v in hidden_dash)
+    W, H = drawing.width * scale, drawing.height * scale
+    out = ['<?xml version="1.0" encoding="UTF-8"?>\n',
+           f'<svg xmlns="http://www.w3.org/2000/svg" version="1.1" width="{W:.3f}" height="{H:.3f}" '
+           f'viewBox="0 0 {W:.3f} {H:.3f}">\n']
+    if background is not None:
+        out.append(f'<rect x="0" y="0" width="{W:.3f}" height="{H:.3f}" fill={quoteattr(str(background))}/>\n')
+    xy = (ends + 0.5) * scale
+    style = f'fill="none" stroke={quoteattr(str(stroke))} stroke-width="{float(width):g}"'
+    groups = [("visible", 2, ' stroke-linecap="round"')]
+    if hidden:
+        groups.insert(0, ("hidden", 1, f' stroke-linecap="butt" stroke-opacity="{float(hidden_opacity):g}" '
+                                       f'stroke-dasharray="{on:g},{off:g}"'))
+    for name, value, more in groups:
+        out.append(f'<g class="{name}" {style}{more}>\n')
+        for x0, y0, x1, y1 in xy[cls == value].tolist():
+            out.append(f'<line x1="{x0:.3f}" y1="{y0:.3f}" x2="{x1:.3f}" y2="{y1:.3f}"/>\n')
+        out.append("</g>\n")
+    out.append("</svg>\n")
+    text = "".join(out)
+    if hasattr(target, "write"):
+        target.write(text)
+    else:
+        with open(target, "w", encoding="utf-8") as fh:
+            fh.write(text)

@@ -388,6 +388,87 @@ CRENDER_API int crender_wire_hidden(const int32_t *d_winner, const float *d_z, c
                                     float opacity, int dash_on, int dash_off, float depth_bias, uint32_t *d_key,
                                     float *d_color, int H, int W, int y0, int y1, unsigned flags, void *stream);
 
+/*
+ * The drawing as vectors: crender_wire_hidden's classification of every step, kept.  A hidden-line drawing is a vector
+ * object — visible edges solid, hidden edges dashed, at any print size — and the raster pass throws what it knows away
+ * into pixels.  These two entries turn the steps of every walked half-edge into maximal RUNS of one class and hand them
+ * back as sub-segments of the projected edges, compacted on the device in an order that is a function of the inputs alone.
+ *
+ * Result contract.
+ *
+ *   Arithmetic   every float step below is ONE float32 operation, rounded once, with IEEE division (no contraction into
+ *                fused multiply-adds, no reciprocal, denormals kept); every integer step is exact.
+ *   Segments     crender_wire_hidden's, unchanged: segment s = 3 i + e, i in the caller's order; walked iff bit e of
+ *                d_edges[i] is set (all three without d_edges) and q = d_pos_of ? d_pos_of[i] : i is below T; the ends a,
+ *                b projected as crender_project projects them; skipped unless both unprojected z are > 0 and
+ *                fabsf(c) < 2^30 for c = xa, ya, xb, yb; the ends rounded with rintf; walked from the end whose rounded
+ *                (y, x) is smaller (a and b change places, with their depths AND their unrounded coordinates); the
+ *                pixels of crender_wire_draw's line, step t = 0 .. el.
+ *   Class        of step t: 0 if its pixel is off the frame or outside rows y0 <= y < y1.  Otherwise
+ *                  lam = (float)t / (float)el   (0.0f for el = 0),   ze = z_a + (z_b - z_a) * lam
+ *                  hidden = d_z[y][x] < (ze - depth_bias)            (false for every NaN)
+ *                With CRENDER_WIRE_RUNS_USE_WINNER hidden is cancelled if d_winner[y][x] == i, and, with a d_partners,
+ *                also if v = d_partners[i][e] is >= 0 and d_winner[y][x] == v >> 1: a vector drawing draws a mesh edge
+ *                ONCE, the edge belongs to two triangles, and either of them winning the pixel means "visible".
+ *                Without the flag d_partners is not read.  The class is 1 (HIDDEN) if hidden, else 2 (VISIBLE).
+ *   Runs         a run is a maximal interval [t0, t1] of consecutive steps of one segment with the same non-zero class.
+ *                A run ends where the walk leaves the frame or the rows: the drawing is clipped to them.  The runs of a
+ *                call are ordered by (s, t0), ascending; run k is row k of both results.
+ *   d_runs       int32 [N][4]: (s, t0, t1, class).
+ *   d_ends       float32 [N][4]: (x0, y0, x1, y1), on the line through the UNROUNDED projected ends A, B in walking order:
+ *                  el == 0:   u0 = 0.0f,   u1 = 1.0f
+ *                  otherwise  u0 = fmaxf((float)t0 - 0.5f, 0.0f) / (float)el
+ *                             u1 = fminf((float)t1 + 0.5f, (float)el) / (float)el
+ *                  x(u) = xa * (1.0f - u) + xb * u,   y(u) = ya * (1.0f - u) + yb * u      (left to right)
+ *                A run reaches half a step beyond its first and last pixel, but never beyond A or B.  The form gives A
+ *                and B back bit for bit at u = 0 and u = 1: chains of fully visible edges close exactly.
+ *   Groups       the segments are counted in groups of CRENDER_WIRE_RUNS_GROUP: group g holds segments 256 g .. 256 g + 255.
+ *                crender_wire_runs_count writes the number of runs of every group; the caller turns them into the
+ *                exclusive prefix d_offsets (int64) and their sum N, allocates, and calls crender_wire_runs_emit with the
+ *                SAME operands: run r of group g goes to row d_offsets[g] + r.  Emit stores a row only if its index is
+ *                >= 0, below N and below d_offsets[g + 1] (N for the last group): offsets or an N that do not belong to
+ *                the operands lose runs, they never make the call write outside d_runs and d_ends.
+ *   Other planes everything but d_counts, d_runs and d_ends is only read.
+ *
+ * Not covered: chaining the runs into polylines, bridging runs of one step.
+ */
+#define CRENDER_WIRE_RUNS_GROUP 256          /* segments per count */
+#define CRENDER_WIRE_RUNS_USE_WINNER 1u
+
+/* The groups of T triangles: ceil(3 T / CRENDER_WIRE_RUNS_GROUP); -1 for T < 0 or 3 T beyond an int32. */
+CRENDER_API int64_t crender_wire_runs_groups(int64_t T);
+
+/* Count the runs of every group over rows y0 <= y < y1.
+ *   d_winner, d_z, d_tri, T, d_pos_of, P16, d_edges   as crender_wire_hidden takes them
+ *   d_partners NULL, or int32 [T][3], the partner table of crender_wire_contours, in the CALLER's triangle order
+ *   depth_bias finite; in the units of d_z (projected z)
+ *   d_counts   uint32 [crender_wire_runs_groups(T)]: every element is written
+ *   flags      0 or CRENDER_WIRE_RUNS_USE_WINNER
+ * CRENDER_EINVAL, before anything is dereferenced or launched, checked in THIS order: a NULL d_winner, d_z, P16 or
+ * d_counts; T < 0; T > 0 without d_tri; H or W < 1; rows outside the frame (y0 < 0, y1 > H, y0 >= y1); H or W above 2^20
+ * (a group's count is a uint32); a depth_bias that is not finite; any other flag bit; 3 T beyond an int32
+ * (T > (2^31 - 1) / 3).  T == 0 returns CRENDER_OK without a launch.  One launch on `stream` with 11.3 KB of static LDS;
+ * no synchronisation, no atomics. */
+CRENDER_API int crender_wire_runs_count(const int32_t *d_winner, const float *d_z, const float *d_tri, int64_t T,
+                                        const uint32_t *d_pos_of, const float *P16, const uint8_t *d_edges,
+                                        const int32_t *d_partners, float depth_bias, uint32_t *d_counts, int H, int W,
+                                        int y0, int y1, unsigned flags, void *stream);
+
+/* Store the runs.  crender_wire_runs_count's operands, unchanged, and
+ *   d_offsets  int64 [crender_wire_runs_groups(T)]: the exclusive prefix of the counts
+ *   N          the sum of the counts: the rows of d_runs and d_ends
+ *   d_runs     int32 [N][4]
+ *   d_ends     float32 [N][4]
+ * CRENDER_EINVAL, before anything is dereferenced or launched, checked in THIS order: a NULL d_winner, d_z, P16,
+ * d_offsets, d_runs or d_ends; then crender_wire_runs_count's checks, with N < 0 between the flag bits and 3 T beyond an
+ * int32.  T == 0 and N == 0 return CRENDER_OK without a launch.  One launch on `stream` with 15.4 KB of static LDS; no
+ * synchronisation, no atomics. */
+CRENDER_API int crender_wire_runs_emit(const int32_t *d_winner, const float *d_z, const float *d_tri, int64_t T,
+                                       const uint32_t *d_pos_of, const float *P16, const uint8_t *d_edges,
+                                       const int32_t *d_partners, float depth_bias, const int64_t *d_offsets, int64_t N,
+                                       int32_t *d_runs, float *d_ends, int H, int W, int y0, int y1, unsigned flags,
+                                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif
