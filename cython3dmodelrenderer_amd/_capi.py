@@ -92,6 +92,8 @@ WIRE_HIDDEN_USE_WINNER = 1
 WIRE_MAX_DASH = 64
 WIRE_RUNS_GROUP = 256
 WIRE_RUNS_USE_WINNER = 1
+NMAP_WRAP = 1
+NMAP_PERSPECTIVE, NMAP_BILINEAR, NMAP_CHAIN = 1, 2, 4
 UNIT_SIGNATURES["wire"] = {
     "crender_wire_key_bytes": (_sz, [_i32, _i32]),
     "crender_wire_draw": (_i32, [_vp, _vp, _i64, _f32p, _vp, _vp, _vp, _vp, _i32, _i32, _u32, _vp, _vp]),
@@ -118,6 +120,11 @@ UNIT_SIGNATURES["wire"] = {
                                        _u32, _vp]),
     "crender_wire_runs_emit": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, _vp, C.c_float, _vp, _i64, _vp, _vp, _i32, _i32,
                                       _i32, _i32, _u32, _vp]),
+    # normal mapping (DeferredPasses.bind_normal_map, normal_map_pass): a tangent-space map from a height map, and the
+    # pass that perturbs the normal plane: the overlay's frame, then the uv, the map and its size, the strength, the plane
+    "crender_nmap_from_height": (_i32, [_vp, _i32, _i32, C.c_float, _u32, _vp, _vp]),
+    "crender_nmap_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _i32, C.c_float, _vp, _i32, _i32, _i32, _i32,
+                                  _u32, _vp]),
 }
 
 # the numpy filler's entry points (include/crender_py.h), bound from a table of their own

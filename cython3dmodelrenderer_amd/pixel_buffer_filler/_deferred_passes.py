@@ -1,5 +1,6 @@
 """The deferred passes of ``AdvancedPixelBufferFiller`` over the winner plane of its last frame: texture (nearest,
-bilinear, trilinear, anisotropic), shadow, Phong, ambient occlusion and the wireframe overlay, with the texture and shadow-map bindings they
+bilinear, trilinear, anisotropic), shadow, Phong, ambient occlusion and the wireframe overlay, and normal mapping (``normal_map_pass``: the one that writes the
+normal plane the others read), with the texture, normal-map and shadow-map bindings they
 read, the classification of a view's contour edges for the overlay (``contour_edges``: it reads no plane), the edges behind
 the surface, dashed (``hidden_line_pass``: it walks the edges, not the winner plane's pixels, and keeps a key plane), the same
 classification kept as vector segments (``line_runs``: it only reads the planes and returns a ``LineDrawing``) and geometric
@@ -90,6 +91,7 @@ class LineDrawing:
 class DeferredPasses:
     _texture = None   # (uv [T, 3, 2] float32, image [th, tw, 3] uint8) device tensors: bind_texture
     _mip = None        # (chain, [(h_k, w_k)], [byte offsets]) of that image: bind_texture(mipmaps=True)
+    _normal_map = None  # (uv [T, 3, 2] float32 or None, map [mh, mw, 3] uint8, its mip chain or None): bind_normal_map
     _shadow = None     # (the light's filler, its vertices [T, 3, 3] float32 on the device): bind_shadow_map
     _hidden_key = None  # the zeroed int32 [h, w] key plane of hidden_line_pass, which every call leaves zero
 
@@ -113,12 +115,12 @@ class DeferredPasses:
         tri = self._inputs[0]
         return tri, tri.shape[0]
 
-    def _run_pass(self, entry, tri, T, operands, flags=0, more=(), z=False, light=None, reads_only=False):
+    def _run_pass(self, entry, tri, T, operands, flags=0, more=(), z=False, light=None, reads_only=False, target=None):
         """Settle the frame and call the library's `entry` on torch's current stream:
         ``entry(winner, [z,] tri or NULL, T, pos_of, P, *operands, color, h, w, y0, y1, flags, *more, stream)``.
         Tensors among `operands` are passed by address, taken after the settle.  `light`: a second filler whose
         planes the pass reads, settled first.  `reads_only`: the pass writes none of the filler's planes, so the host
-        views stay as fresh or as stale as they were."""
+        views stay as fresh or as stale as they were.  `target`: the plane the pass writes in the colour plane's place."""
         self._push_host_edits()
         if light is not None:
             light._push_host_edits()
@@ -126,7 +128,8 @@ class DeferredPasses:
         self._check_bins()             # nothing pending from here on: no later redo can undo the pass
         pos_of = None if self._order is None else self._order[1]
         args = (self.winner_buffer,) + ((self.z_buffer,) if z else ()) + (tri if T else None, T, pos_of, self._P) + \
-            tuple(operands) + (self.color_buffer, self.h, self.w, self.y0, self.y1, flags) + tuple(more)
+            tuple(operands) + (self.color_buffer if target is None else target, self.h, self.w, self.y0, self.y1, flags) + \
+            tuple(more)
         self._launch_pass(entry, args)
         if not reads_only:
             self._host_fresh = False   # views handed out earlier show the pass's colours at the next getter call
@@ -231,6 +234,93 @@ class DeferredPasses:
             flags = (_capi.TEX_PERSPECTIVE if perspective else 0) | (_capi.TEX_BILINEAR if filter == "bilinear" else 0)
         self._run_pass(entry, tri, T, (uv if T else None, image, int(tex.shape[0]), int(tex.shape[1]),
                                        None if light is None else self.normals_buffer, light), flags, more)
+
+    def bind_normal_map(self, normal_map=None, *, height=None, scale=1.0, wrap=False, uv_by_triangles=None, mipmaps=False):
+        """Keep a tangent-space normal map resident for ``normal_map_pass``: `normal_map` uint8 [mh, mw, 3]
+        (byte = 128 + 127 * component of a unit vector along u, along v and out of the surface; row 0 is the top of the
+        image), or `height` uint8 [mh, mw], from which the map is made on the device (``crender_nmap_from_height``,
+        include/crender_wire.h, on torch's current stream): central differences times ``scale / 255``, the neighbours
+        clamped to the edge or, with `wrap`, wrapped around.  Exactly one of the two, numpy arrays or device tensors; both
+        None drops the binding.  `uv_by_triangles` float32 [T, 3, 2] (``bind_texture``'s) are the map's own coordinates;
+        None means those of ``bind_texture`` at the time the pass runs.  With `mipmaps` the map's mip chain is built as
+        a texture's is (the box average of the bytes), which ``normal_map_pass(filter="trilinear")`` needs."""
+        if normal_map is None and height is None:
+            self._normal_map = None
+            return
+        if normal_map is not None and height is not None:
+            raise ValueError("bind_normal_map takes the normal map or the height map, not both")
+        number = (int, float, np.integer, np.floating)
+        if isinstance(scale, bool) or not isinstance(scale, number) or not np.isfinite(np.float32(scale)):
+            raise ValueError(f"scale must be a finite number, got {scale!r}")
+        side = lambda s: 1 <= s[0] <= 65535 and 1 <= s[1] <= 65535
+        uv = None
+        if uv_by_triangles is not None:
+            uv = _device_array(self, uv_by_triangles, torch.float32, lambda s: len(s) == 3 and s[1:] == (3, 2),
+                               "uv_by_triangles must be float32 [T, 3, 2]")
+        if height is None:
+            nmap = _device_array(self, normal_map, torch.uint8, lambda s: len(s) == 3 and s[2] >= 3 and side(s),
+                                 "normal_map must be uint8 [mh, mw, 3] with sides from 1 to 65535", part=(..., slice(3)))
+        else:
+            hm = _device_array(self, height, torch.uint8, lambda s: len(s) == 2 and side(s),
+                               "height must be uint8 [mh, mw] with sides from 1 to 65535")
+            mh, mw = int(hm.shape[0]), int(hm.shape[1])
+            nmap = torch.empty((mh, mw, 3), dtype=torch.uint8, device=self.device)
+            self._launch_pass("crender_nmap_from_height", (hm, mh, mw, float(scale), _capi.NMAP_WRAP if wrap else 0, nmap))
+        self._normal_map = (uv, nmap, self._build_mip_chain(nmap) if mipmaps else None)
+
+    def bind_normal_map_uv(self, uv_by_triangles):
+        """Replace the coordinates of the bound normal map and keep the map: `uv_by_triangles` float32 [T, 3, 2], or None
+        for those of ``bind_texture``.  (``Renderer(normal_map=...)`` binds the map once and the model's uv per model.)"""
+        if self._normal_map is None:
+            raise ValueError("bind_normal_map_uv: no normal map is bound (bind_normal_map)")
+        uv = None
+        if uv_by_triangles is not None:
+            uv = _device_array(self, uv_by_triangles, torch.float32, lambda s: len(s) == 3 and s[1:] == (3, 2),
+                               "uv_by_triangles must be float32 [T, 3, 2]")
+        self._normal_map = (uv,) + self._normal_map[1:]
+
+    def get_normal_map(self):
+        """The bound normal map, a uint8 [mh, mw, 3] device tensor, or None without a binding."""
+        return None if self._normal_map is None else self._normal_map[1]
+
+    def normal_map_pass(self, strength=1.0, perspective=True, filter="bilinear"):
+        """Normal (bump) mapping of the LAST frame's NORMAL plane (``crender_nmap_shade``, include/crender_wire.h): every
+        covered pixel samples the bound map at its interpolated (u, v) — the nearest texel, four of them, or
+        (``"trilinear"``, which needs ``bind_normal_map(..., mipmaps=True)``) two levels of the map's mip chain picked
+        from the screen-space derivatives of (u, v) —, decodes the tangent-space vector, scales its two tangent
+        components by `strength`, and replaces its stored normal by that vector in the frame made of the normal itself
+        and the winner's tangents (the directions of increasing u and v on the triangle, turned around the normal).  Run
+        it right after the draw: the illumination, the fused light of ``texture_pass`` and ``resolve``, ``phong_pass`` and
+        ``ao_pass(normals="plane")`` all read that plane and show the bumps.  A flat texel (128, 128, 255), ``strength=0``,
+        degenerate uv and the background leave a pixel's bits alone; colour, z and winners are never written.  Rows of
+        the filler's ``row_strip``, on torch's current stream.
+
+        The frame is settled first (one stream synchronisation, as every getter does): a frame whose bin lists
+        overflowed is rendered again, and the pass must land on the frame that stays."""
+        if filter not in ("nearest", "bilinear", "trilinear"):
+            raise ValueError(f"filter must be 'nearest', 'bilinear' or 'trilinear', got {filter!r}")
+        if isinstance(strength, bool) or not isinstance(strength, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(np.float32(strength)):
+            raise ValueError(f"strength must be a finite number, got {strength!r}")
+        self._pass_target("normal_map_pass")
+        if self._normal_map is None:
+            raise ValueError("normal_map_pass: no normal map is bound (bind_normal_map)")
+        uv, nmap, chain = self._normal_map
+        if filter == "trilinear" and chain is None:
+            raise ValueError("filter 'trilinear' needs a mip chain: bind_normal_map(..., mipmaps=True)")
+        if uv is None:
+            if self._texture is None:
+                raise ValueError("normal_map_pass: no texture coordinates are bound (bind_normal_map(..., uv_by_triangles=...) "
+                                 "or bind_texture)")
+            uv = self._texture[0]
+        tri, T = self._pass_frame("normal_map_pass")
+        if uv.shape[0] != T:
+            raise ValueError(f"normal_map_pass: {uv.shape[0]} triangles of texture coordinates are bound, the last frame drew {T}")
+        flags = (_capi.NMAP_PERSPECTIVE if perspective else 0) | (_capi.NMAP_BILINEAR if filter == "bilinear" else 0) | \
+            (_capi.NMAP_CHAIN if filter == "trilinear" else 0)
+        self._run_pass("crender_nmap_shade", tri, T,
+                       (uv if T else None, chain[0] if filter == "trilinear" else nmap, int(nmap.shape[0]), int(nmap.shape[1]),
+                        float(strength)), flags, target=self.normals_buffer)
 
     def bind_shadow_map(self, light_filler, light_vertices):
         """Name the shadow map of ``shadow_pass``: `light_filler`, another ``AdvancedPixelBufferFiller`` on the same

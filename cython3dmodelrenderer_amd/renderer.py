@@ -22,7 +22,7 @@ def _device_form_is_the_same_shading(illumination):
 class Renderer:
     def __init__(self, pixel_buffer_filler, illumination, triangle_iterator_type=None,
                  image_height=512, image_width=512, use_tqdm=True, on_device=None, texture_pass=None,
-                 shadow=None, ambient_occlusion=None, antialias=None, wireframe=None, supersample=None):
+                 shadow=None, ambient_occlusion=None, antialias=None, normal_map=None, wireframe=None, supersample=None):
         self.pixel_buffer_filler = pixel_buffer_filler
         self.illumination = illumination
         self.triangle_iterator_type = triangle_iterator_type   # stored, unused (as in Version C)
@@ -165,6 +165,36 @@ class Renderer:
                 raise ValueError(f"Renderer(antialias=...) takes the keys 'edges', 'feature_angle', 'contours' and "
                                  f"'borders': {unknown} unknown")
             self.antialias = dict(antialias)
+        # normal_map=None (default): the light sees the interpolated vertex normals.  A dict of
+        # AdvancedPixelBufferFiller.bind_normal_map's arguments but the uv (``normal_map`` or ``height``, ``scale``, ``wrap``,
+        # ``mipmaps``) and of normal_map_pass's (``strength``, ``perspective``, ``filter``; "trilinear" binds the map with
+        # its mip chain): the map is bound here, once, and the model's texture coordinates once per model.  Every frame
+        # starts from cleared buffers (one model per frame, as "fused") and the pass runs FIRST, directly after the draw:
+        # it perturbs the normal plane, which the ambient occlusion, the fused light of the texture pass, the Phong
+        # pass, the illumination and the resolve read afterwards.  With ``supersample=s`` it runs on the supersampled
+        # frame.  on_device="fused" needs a ``texture_pass`` (which then carries the light): without one the raster
+        # kernel has shaded from the unperturbed normals before any pass can run.
+        self.normal_map = None
+        self._bumped = None            # weak reference to the model whose uv the normal map is bound with
+        if normal_map is not None:
+            if not hasattr(pixel_buffer_filler, "normal_map_pass"):
+                raise ValueError("Renderer(normal_map=...) needs a filler with a normal-map pass "
+                                 f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no normal_map_pass()")
+            if on_device == "fused" and texture_pass is None:
+                raise ValueError("Renderer(normal_map=..., on_device='fused') without a texture_pass: the raster kernel "
+                                 "shades from the unperturbed normals before any pass can run; add a texture_pass, which "
+                                 "carries the light, or use another on_device")
+            opts = dict(normal_map)
+            unknown = sorted(set(opts) - {"normal_map", "height", "scale", "wrap", "mipmaps", "strength", "perspective", "filter"})
+            if unknown:
+                raise ValueError("Renderer(normal_map=...) takes the keys 'normal_map', 'height', 'scale', 'wrap', 'mipmaps', "
+                                 f"'strength', 'perspective' and 'filter': {unknown} unknown")
+            self.normal_map = {k: opts.pop(k) for k in ("strength", "perspective", "filter") if k in opts}
+            if self.normal_map.get("filter") == "trilinear":
+                opts.setdefault("mipmaps", True)
+            pixel_buffer_filler.bind_normal_map(opts.pop("normal_map", None), **opts)
+            if pixel_buffer_filler.get_normal_map() is None:
+                raise ValueError("Renderer(normal_map=...) needs 'normal_map' or 'height'")
         # A PhongIllumination is a deferred pass of the filler over its winner plane (``phong_pass``): every frame
         # starts from cleared buffers (one model per frame, as "fused"); the draw, then the texture pass (unlit) if
         # asked for, then the Phong pass, then the shadow pass — AFTER the light here, since the specular term is
@@ -187,11 +217,13 @@ class Renderer:
         the passes on top of it (but the wireframe's, which follows the light: ``_draw_wire``)."""
         filler = self.pixel_buffer_filler
         if self.texture_pass is None:
-            if self.shadow is None and self.ambient_occlusion is None and self.wireframe is None and self.antialias is None:
+            if self.shadow is None and self.ambient_occlusion is None and self.wireframe is None and self.antialias is None \
+                    and self.normal_map is None:
                 return filler.render_model(model, **kw)
             if not kw.get("clear"):        # (the "fused" caller asks for the cleared frame itself: its raster kernel shades)
                 filler.set_fused_illumination(None)
             filler.render_model(model, clear=True, refresh_views=False)
+            self._bump(model)
             if self.ambient_occlusion is not None:
                 filler.ao_pass(**self.ambient_occlusion)
             if self.shadow is not None:
@@ -212,11 +244,25 @@ class Renderer:
         # kernel never shades here: the colours it stores are replaced by the texture's)
         filler.set_fused_illumination(None)
         filler.render_model(model, clear=True, refresh_views=False)
+        self._bump(model)              # before the texture pass, whose fused light reads the normal plane
         filler.texture_pass(light_direction=light, **self.texture_pass)
         if self.ambient_occlusion is not None:
             filler.ao_pass(**self.ambient_occlusion)
         if self.shadow is not None and shadows:
             self._cast_shadows(model)
+
+    def _bump(self, model):
+        """The normal-map pass over the frame just drawn, if a normal map was asked for: first of all passes."""
+        if self.normal_map is None:
+            return
+        if self._bumped is None or self._bumped() is not model:          # once per model, not per frame
+            getter = getattr(model, "get_texture_coords_by_triangles", None)
+            uv = getter() if getter is not None else None
+            if uv is None:
+                raise ValueError("Renderer(normal_map=...) needs a model with texture coordinates: this one has none")
+            self.pixel_buffer_filler.bind_normal_map_uv(uv)
+            self._bumped = weakref.ref(model)
+        self.pixel_buffer_filler.normal_map_pass(**self.normal_map)
 
     def _cast_shadows(self, model):
         """The model again, from the light, into the light's filler; then the shadow pass over the camera's frame."""
@@ -365,6 +411,7 @@ class Renderer:
         else:
             filler.set_fused_illumination(None)
             filler.render_model(model, clear=True, refresh_views=False)
+            self._bump(model)
             if self.ambient_occlusion is not None:
                 filler.ao_pass(**self.ambient_occlusion)
         self.illumination.draw_illumination_device(filler)
