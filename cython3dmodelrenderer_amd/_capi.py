@@ -94,6 +94,8 @@ WIRE_RUNS_GROUP = 256
 WIRE_RUNS_USE_WINNER = 1
 NMAP_WRAP = 1
 NMAP_PERSPECTIVE, NMAP_BILINEAR, NMAP_CHAIN = 1, 2, 4
+ENV_REFLECT, ENV_BACKGROUND = 1, 2
+ENV_MAX_SIDE = 8192
 UNIT_SIGNATURES["wire"] = {
     "crender_wire_key_bytes": (_sz, [_i32, _i32]),
     "crender_wire_draw": (_i32, [_vp, _vp, _i64, _f32p, _vp, _vp, _vp, _vp, _i32, _i32, _u32, _vp, _vp]),
@@ -125,6 +127,11 @@ UNIT_SIGNATURES["wire"] = {
     "crender_nmap_from_height": (_i32, [_vp, _i32, _i32, C.c_float, _u32, _vp, _vp]),
     "crender_nmap_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _i32, C.c_float, _vp, _i32, _i32, _i32, _i32,
                                   _u32, _vp]),
+    # environment mapping (DeferredPasses.bind_environment, environment_pass): the overlay's frame, then the normal plane,
+    # the two levels' faces and sides and the second one's weight, the orientation, reflectivity, f0, the tint, the
+    # background's gain
+    "crender_env_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _vp, _i32, C.c_float, _f32p, C.c_float, C.c_float,
+                                 _f32p, C.c_float, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
 }
 
 # the numpy filler's entry points (include/crender_py.h), bound from a table of their own

@@ -1,7 +1,7 @@
 """The deferred passes of ``AdvancedPixelBufferFiller`` over the winner plane of its last frame: texture (nearest,
 bilinear, trilinear, anisotropic), shadow, Phong, ambient occlusion and the wireframe overlay, and normal mapping (``normal_map_pass``: the one that writes the
-normal plane the others read), with the texture, normal-map and shadow-map bindings they
-read, the classification of a view's contour edges for the overlay (``contour_edges``: it reads no plane), the edges behind
+normal plane the others read) and environment mapping (``environment_pass``: reflections and a skybox from a cube map), with the
+texture, normal-map, environment and shadow-map bindings they read, the classification of a view's contour edges for the overlay (``contour_edges``: it reads no plane), the edges behind
 the surface, dashed (``hidden_line_pass``: it walks the edges, not the winner plane's pixels, and keeps a key plane), the same
 classification kept as vector segments (``line_runs``: it only reads the planes and returns a ``LineDrawing``) and geometric
 edge anti-aliasing (``edge_aa``: it reads the planes and returns a plane of its own).  A mixin
@@ -92,6 +92,7 @@ class DeferredPasses:
     _texture = None   # (uv [T, 3, 2] float32, image [th, tw, 3] uint8) device tensors: bind_texture
     _mip = None        # (chain, [(h_k, w_k)], [byte offsets]) of that image: bind_texture(mipmaps=True)
     _normal_map = None  # (uv [T, 3, 2] float32 or None, map [mh, mw, 3] uint8, its mip chain or None): bind_normal_map
+    _environment = None  # (faces [6, S, S, 3] uint8, its mip chain over the faces stacked by rows or None): bind_environment
     _shadow = None     # (the light's filler, its vertices [T, 3, 3] float32 on the device): bind_shadow_map
     _hidden_key = None  # the zeroed int32 [h, w] key plane of hidden_line_pass, which every call leaves zero
 
@@ -321,6 +322,126 @@ class DeferredPasses:
         self._run_pass("crender_nmap_shade", tri, T,
                        (uv if T else None, chain[0] if filter == "trilinear" else nmap, int(nmap.shape[0]), int(nmap.shape[1]),
                         float(strength)), flags, target=self.normals_buffer)
+
+    def bind_environment(self, faces, mipmaps=False):
+        """Keep a cube map resident for ``environment_pass``: `faces` uint8 [6, S, S, 3] with S from 1 to 8192, a numpy
+        array or a device tensor, the faces in the order +x, -x, +y, -y, +z, -z of the camera's frame (x grows with the
+        column, y with the row, z goes into the screen; ``environment.cube_from_equirect`` and ``environment.gradient_sky``
+        make one).  ``bind_environment(None)`` drops the binding.  With `mipmaps` S must be a power of two, and the chain
+        is the texture's own (``crender_mip_build``, on torch's current stream) of the faces stacked by rows, a
+        [6 S, S, 3] image: a 2 x 2 box never straddles two faces while the side is even, so of that chain the levels
+        j = 0 .. log2 S are used, level j a [6 S / 2^j, S / 2^j, 3] image at the chain's byte offset of level j, in which
+        face k starts ``k * 3 * (S / 2^j) ** 2`` bytes further on: six box-averaged faces of side S / 2^j.  (The chain's
+        levels beyond log2 S average across faces and are never read.)"""
+        if faces is None:
+            self._environment = None
+            return
+        top = _capi.ENV_MAX_SIDE
+        cube = _device_array(self, faces, torch.uint8,
+                             lambda s: len(s) == 4 and s[0] == 6 and s[1] == s[2] and 1 <= s[1] <= top and s[3] >= 3,
+                             f"faces must be uint8 [6, S, S, 3] with S from 1 to {top}", part=(..., slice(3)))
+        S = int(cube.shape[1])
+        chain = None
+        if mipmaps:
+            if S & (S - 1):
+                raise ValueError(f"bind_environment(mipmaps=True) needs a side that is a power of two, got {S}")
+            chain = self._build_mip_chain(cube.view(6 * S, S, 3))
+        self._environment = (cube, chain)
+
+    def get_environment(self):
+        """The bound cube map, a uint8 [6, S, S, 3] device tensor, or None without a binding."""
+        return None if self._environment is None else self._environment[0]
+
+    def environment_levels(self):
+        """The sides of the bound cube's levels: [S, S / 2, ..., 1] with a chain, [S] without; None without a binding."""
+        if self._environment is None:
+            return None
+        cube, chain = self._environment
+        S = int(cube.shape[1])
+        return [S] if chain is None else [S >> j for j in range(S.bit_length())]
+
+    def get_environment_level(self, j):
+        """Level `j` of the bound cube: a uint8 [6, S / 2^j, S / 2^j, 3] device tensor that views the chain (level 0 of a
+        cube without a chain is the cube)."""
+        sides = self.environment_levels()
+        if sides is None:
+            raise ValueError("no environment is bound (bind_environment)")
+        if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or not 0 <= j < len(sides):
+            raise IndexError(f"the environment has levels 0 .. {len(sides) - 1}, got {j!r}")
+        cube, chain = self._environment
+        if chain is None:
+            return cube
+        off, side = chain[2][j], sides[j]
+        return chain[0][off:off + 18 * side * side].view(6, side, side, 3)
+
+    def environment_pass(self, reflectivity=1.0, f0=0.04, tint=(1.0, 1.0, 1.0), level=0.0, orientation=None, background=None):
+        """Environment mapping of the LAST frame's colour plane (``crender_env_shade``, include/crender_wire.h) from the
+        cube bound with ``bind_environment``.  Every covered pixel mirrors the direction from the eye to the surface
+        point it shows (the perspective-correct blend of the winner's corners, as ``phong_pass`` takes it) at its stored
+        normal, looks the mirrored direction up in the cube (the face of its largest component, four texels of it,
+        nothing filtered across faces) and blends its colour c towards ``sample * tint`` by
+        ``w = reflectivity * (f0 + (1 - f0) * (1 - cos) ** 5)``, cos between the normal and the way to the eye: `f0` is
+        the share mirrored head-on (0.04 a glossy dielectric, 1 a mirror at every angle), and every surface mirrors at a
+        grazing angle.  `level` is a position in the chain of ``bind_environment(..., mipmaps=True)``, 0 to its last
+        level: the samples of the two levels around it are blended by its fraction, a blur (box averages, not a roughness
+        model).  `orientation` is None or a 3 x 3 matrix that takes a direction of the camera's frame into the cube's.
+        `background` — True, or a number, the gain — also gives every pixel of the rows that no triangle won the cube's
+        colour along its own view ray (times the gain): a skybox; None or False leaves the background alone.  With
+        ``reflectivity=0`` only the background is painted (and without one nothing is launched).  z, normals and winners
+        are only read.  Rows of the filler's ``row_strip``, on torch's current stream.
+
+        The frame is settled first (one stream synchronisation, as every getter does): a frame whose bin lists
+        overflowed is rendered again, and the pass must land on the frame that stays."""
+        number = (int, float, np.integer, np.floating)
+        for name, v in (("reflectivity", reflectivity), ("f0", f0)):
+            if isinstance(v, bool) or not isinstance(v, number) or not 0 <= float(v) <= 1:
+                raise ValueError(f"{name} must be a number from 0 to 1, got {v!r}")
+        try:
+            tint3 = [float(v) for v in tint]
+        except (TypeError, ValueError):
+            tint3 = []
+        if len(tint3) != 3 or not np.isfinite(np.float32(tint3)).all():
+            raise ValueError(f"tint must be three finite numbers, got {tint!r}")
+        if isinstance(level, bool) or not isinstance(level, number) or not float(level) >= 0:
+            raise ValueError(f"level must be a number, 0 or above, got {level!r}")
+        M = np.eye(3, dtype=np.float32) if orientation is None else np.asarray(orientation, dtype=np.float32)
+        if M.shape != (3, 3) or not np.isfinite(M).all():
+            raise ValueError(f"orientation must be None or a finite 3 x 3 matrix, got {orientation!r}")
+        if background is None or background is False:
+            gain = None
+        elif background is True:
+            gain = 1.0
+        elif isinstance(background, number) and np.isfinite(np.float32(background)) and float(background) >= 0:
+            gain = float(background)
+        else:
+            raise ValueError(f"background must be None, a bool or a finite gain, 0 or above, got {background!r}")
+        self._pass_target("environment_pass")
+        if self._environment is None:
+            raise ValueError("environment_pass: no environment is bound (bind_environment)")
+        cube, chain = self._environment
+        sides = self.environment_levels()
+        lam = float(level)
+        if lam > 0 and chain is None:
+            raise ValueError(f"level={level!r} needs a mip chain: bind_environment(..., mipmaps=True)")
+        if lam > len(sides) - 1:
+            raise ValueError(f"level must be at most {len(sides) - 1}, the last level of the bound chain, got {level!r}")
+        tri, T = self._pass_frame("environment_pass")
+        if float(reflectivity) == 0 and gain is None:
+            return
+        l0 = int(np.floor(lam))
+        f = float(np.float32(lam - l0))
+        if f >= 1.0:                    # (a fraction that rounds up to the next level)
+            l0, f = l0 + 1, 0.0
+        if l0 == len(sides) - 1:
+            f = 0.0
+        two = f != 0.0
+        faces0 = cube if chain is None else chain[0][chain[2][l0]:]
+        faces1 = chain[0][chain[2][l0 + 1]:] if two else None
+        flags = _capi.ENV_REFLECT | (_capi.ENV_BACKGROUND if gain is not None else 0)
+        self._run_pass("crender_env_shade", tri, T,
+                       (self.normals_buffer, faces0, sides[l0], faces1, sides[l0 + 1] if two else 0, f,
+                        (C.c_float * 9)(*[float(v) for v in M.reshape(9)]), float(reflectivity), float(f0),
+                        (C.c_float * 3)(*tint3), 0.0 if gain is None else gain), flags)
 
     def bind_shadow_map(self, light_filler, light_vertices):
         """Name the shadow map of ``shadow_pass``: `light_filler`, another ``AdvancedPixelBufferFiller`` on the same

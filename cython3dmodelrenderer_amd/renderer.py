@@ -22,7 +22,8 @@ def _device_form_is_the_same_shading(illumination):
 class Renderer:
     def __init__(self, pixel_buffer_filler, illumination, triangle_iterator_type=None,
                  image_height=512, image_width=512, use_tqdm=True, on_device=None, texture_pass=None,
-                 shadow=None, ambient_occlusion=None, antialias=None, normal_map=None, wireframe=None, supersample=None):
+                 shadow=None, ambient_occlusion=None, antialias=None, normal_map=None, environment=None,
+                 wireframe=None, supersample=None):
         self.pixel_buffer_filler = pixel_buffer_filler
         self.illumination = illumination
         self.triangle_iterator_type = triangle_iterator_type   # stored, unused (as in Version C)
@@ -195,6 +196,36 @@ class Renderer:
             pixel_buffer_filler.bind_normal_map(opts.pop("normal_map", None), **opts)
             if pixel_buffer_filler.get_normal_map() is None:
                 raise ValueError("Renderer(normal_map=...) needs 'normal_map' or 'height'")
+        # environment=None (default): nothing is mirrored and the background keeps the cleared colour.  A dict of ``faces``
+        # (the cube map, uint8 [6, S, S, 3]: ``environment.cube_from_equirect`` / ``gradient_sky``) and, optionally,
+        # ``mipmaps`` (AdvancedPixelBufferFiller.bind_environment's arguments) and ``reflectivity`` / ``f0`` / ``tint`` /
+        # ``level`` / ``orientation`` / ``background`` (environment_pass's; a ``level`` above 0 binds the cube with its mip
+        # chain): the cube is bound here, once.  Every frame starts from cleared buffers (one model per frame, as "fused")
+        # and the pass runs AFTER the light in whichever form — the illumination's device or host form, the fused light
+        # of the raster kernel or the texture pass, the Phong pass and its shadow pass — and immediately BEFORE the wire
+        # pass, so that the lines and ``antialias`` come after it and silhouettes blend against the sky.  (The sky cannot
+        # come before the light: the illumination multiplies the background by the factor of a zero normal.)  With
+        # ``supersample=s`` it runs on the supersampled frame and the light cannot ride in the resolve (it would shade
+        # the mirror image and the sky): as under ``wireframe``, the light runs as a pass of its own, then the
+        # environment, then the wire pass, then the plain resolve.
+        self.environment = None
+        if environment is not None:
+            if not hasattr(pixel_buffer_filler, "environment_pass"):
+                raise ValueError("Renderer(environment=...) needs a filler with an environment pass "
+                                 f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no environment_pass()")
+            opts = dict(environment)
+            known = ("faces", "mipmaps", "reflectivity", "f0", "tint", "level", "orientation", "background")
+            unknown = sorted(set(opts) - set(known))
+            if unknown:
+                raise ValueError("Renderer(environment=...) takes the keys " + ", ".join(repr(k) for k in known[:-1]) +
+                                 f" and {known[-1]!r}: {unknown} unknown")
+            if opts.get("faces") is None:
+                raise ValueError("Renderer(environment=...) needs 'faces'")
+            level = opts.get("level", 0.0)
+            if not isinstance(level, bool) and isinstance(level, (int, float, np.integer, np.floating)) and level > 0:
+                opts.setdefault("mipmaps", True)
+            pixel_buffer_filler.bind_environment(opts.pop("faces"), mipmaps=bool(opts.pop("mipmaps", False)))
+            self.environment = opts
         # A PhongIllumination is a deferred pass of the filler over its winner plane (``phong_pass``): every frame
         # starts from cleared buffers (one model per frame, as "fused"); the draw, then the texture pass (unlit) if
         # asked for, then the Phong pass, then the shadow pass — AFTER the light here, since the specular term is
@@ -213,12 +244,13 @@ class Renderer:
                                  f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no phong_pass()")
 
     def _draw(self, model, light=None, shadows=True, **kw):
-        """``render_model``; with a texture pass, ambient occlusion, a shadow map or a wireframe, a cleared frame and
-        the passes on top of it (but the wireframe's, which follows the light: ``_draw_wire``)."""
+        """``render_model``; with a texture pass, ambient occlusion, a shadow map, an environment or a wireframe, a cleared
+        frame and the passes on top of it (but the environment's and the wireframe's, which follow the light:
+        ``_draw_wire``)."""
         filler = self.pixel_buffer_filler
         if self.texture_pass is None:
             if self.shadow is None and self.ambient_occlusion is None and self.wireframe is None and self.antialias is None \
-                    and self.normal_map is None:
+                    and self.normal_map is None and self.environment is None:
                 return filler.render_model(model, **kw)
             if not kw.get("clear"):        # (the "fused" caller asks for the cleared frame itself: its raster kernel shades)
                 filler.set_fused_illumination(None)
@@ -277,7 +309,10 @@ class Renderer:
         self.pixel_buffer_filler.shadow_pass(**opts)
 
     def _draw_wire(self, model):
-        """The wire pass over the frame as it stands (host edits included), if a wireframe was asked for."""
+        """The environment pass, if one was asked for, and then the wire pass, if a wireframe was, over the frame as it
+        stands (host edits included)."""
+        if self.environment is not None:
+            self.pixel_buffer_filler.environment_pass(**self.environment)
         if self.wireframe is None:
             return
         opts = self._view_edges(model, self.wireframe, "_wired")
@@ -441,10 +476,11 @@ class Renderer:
         if self.on_device is not False and device_form is not None and light is not None:
             # the resolve carries the light: the supersampled colour plane is read once and stays unshaded
             self._draw(model, refresh_views=False)
-            if self.wireframe is None:
+            if self.wireframe is None and self.environment is None:
                 image = filler.resolve(s, light_direction=light)
             else:
-                # the lines are not lit: the light as a pass of its own over the supersampled frame, then the lines
+                # the lines, the mirror image and the sky are not lit: the light as a pass of its own over the supersampled
+                # frame, then the environment and the lines
                 if not device_form(filler):
                     self.illumination.draw_illumination(filler.get_color_buffer(), filler.get_normals_buffer())
                 self._draw_wire(model)
