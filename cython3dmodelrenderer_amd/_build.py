@@ -50,6 +50,14 @@ UNITS = {
     # only, over the pipeline handle of plan.h): it launches nothing.
     "chain": (["chain.hip"], [os.path.join(_INCLUDE, "crender_chain.h")]),
 }
+# Frame kernels that stand in for one path of the fingerprinted k_frame, in link order behind the units above:
+# name -> (sources, headers), outside source_sha16() like them.  A table of its own: UNITS and library_sources() are
+# what the feature units' tests pin, name for name; link_sources() is what the library is built from.
+#   frame32.hip  the swap chain's frame kernel for small scenes on 32-pixel tiles (include/crender_frame32.h): one
+#                path of k_frame's, over the same plans and the arithmetic of raster_math.h
+FRAME_UNITS = {
+    "frame32": (["frame32.hip"], [os.path.join(_INCLUDE, "crender_frame32.h")]),
+}
 
 # Float parity with the reference depends on these (DESIGN.md "Numerics"):
 #   -ffp-contract=off                           no FMA contraction (hipcc defaults to fast)
@@ -96,6 +104,11 @@ def library_sources() -> list:
     return SOURCES + [src for sources, _ in UNITS.values() for src in sources]
 
 
+def link_sources() -> list:
+    """Every translation unit linked into the library: library_sources(), then the frame kernels' (FRAME_UNITS)."""
+    return library_sources() + [src for sources, _ in FRAME_UNITS.values() for src in sources]
+
+
 def build_inputs() -> list:
     """Paths of everything whose change makes the library stale: the fingerprinted sources and headers, every unit's
     sources and headers, and this file (the flags).  A header that two units list is named once."""
@@ -103,11 +116,17 @@ def build_inputs() -> list:
     return [os.path.join(SRC_DIR, name) for name in dict.fromkeys(names)] + [os.path.abspath(__file__)]
 
 
-def needs_build() -> bool:
+def frame_inputs() -> list:
+    """Paths of the frame kernels' sources and headers (FRAME_UNITS): build() counts them like build_inputs()."""
+    names = [name for sources, headers in FRAME_UNITS.values() for name in sources + headers]
+    return [os.path.join(SRC_DIR, name) for name in dict.fromkeys(names)]
+
+
+def needs_build(inputs=None) -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     built = os.path.getmtime(LIB_PATH)
-    return any(os.path.getmtime(d) > built for d in build_inputs())
+    return any(os.path.getmtime(d) > built for d in (build_inputs() if inputs is None else inputs))
 
 
 def compile_library(out: str, extra_flags=(), sources=None, src_dir: str = SRC_DIR, verbose: bool = False,
@@ -116,7 +135,7 @@ def compile_library(out: str, extra_flags=(), sources=None, src_dir: str = SRC_D
     defines of diagnostic builds (-DCRENDER_STAMPS, ...)."""
     import tempfile
     from concurrent.futures import ThreadPoolExecutor
-    sources = list(sources or library_sources())
+    sources = list(sources or link_sources())
     err = subprocess.DEVNULL if quiet else None
     with tempfile.TemporaryDirectory(prefix="crender_build_") as tmp:
         objs = [os.path.join(tmp, os.path.splitext(s)[0] + ".o") for s in sources]
@@ -147,7 +166,7 @@ def compile_library(out: str, extra_flags=(), sources=None, src_dir: str = SRC_D
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Build libcrender_hip.so if missing or stale; returns its path."""
-    if not force and not needs_build():
+    if not force and not needs_build() and not needs_build(frame_inputs()):
         return LIB_PATH
     return compile_library(LIB_PATH, verbose=verbose)
 

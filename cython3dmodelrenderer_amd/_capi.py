@@ -207,6 +207,15 @@ UNIT_SIGNATURES["chain"] = {
     "crender_pipeline_owned_streams": (_i32, [_vp]),
 }
 
+# the frame kernels that stand in for one path of k_frame (_build.FRAME_UNITS, keyed alike): the swap chain's frame
+# kernel for small scenes (include/crender_frame32.h)
+FRAME_SIGNATURES = {
+    "frame32": {
+        "crender_frame32_submit": (_i32, [_vp, _vp]),
+        "crender_frame32_last": (_i32, [_vp]),
+    },
+}
+
 _lib = None
 
 
@@ -230,7 +239,7 @@ def load():
             f"{path} is missing: build it with `python -m cython3dmodelrenderer_amd._build` "
             "(or __graft_entry__.build()).  There is no CPU fallback for the rasterizer.")
     L = C.CDLL(path)
-    for table in (SIGNATURES, *UNIT_SIGNATURES.values()):
+    for table in (SIGNATURES, *UNIT_SIGNATURES.values(), *FRAME_SIGNATURES.values()):
         for name, (res, args) in table.items():
             fn = getattr(L, name)      # AttributeError if the library lacks a declared symbol
             fn.restype = res

@@ -30,7 +30,8 @@ def needs_build() -> bool:
     so = _built_path()
     if so is None:
         return True
-    deps = [SOURCE, os.path.join(_HERE, "..", "include", "crender_hip.h"), os.path.abspath(__file__)]
+    deps = [SOURCE, os.path.join(_HERE, "..", "include", "crender_hip.h"),
+            os.path.join(_HERE, "..", "include", "crender_frame32.h"), os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps)
 
 

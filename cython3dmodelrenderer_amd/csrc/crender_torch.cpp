@@ -16,6 +16,7 @@
 #include <string>
 
 #include "../../include/crender_hip.h"
+#include "../../include/crender_frame32.h"
 
 namespace {
 
@@ -103,7 +104,16 @@ void pipeline_bind(int64_t pipeline, int64_t slot, const at::Tensor &tri, const 
 
 // The per-frame call of the swap chain: the next bound frame on torch's current stream of
 // `device_index` (which must be the current device: the library launches there).
+// Frames that qualify take the small-scene kernel (crender_frame32.h); every other frame is crender_pipeline_submit's.
 void pipeline_submit(int64_t pipeline, int64_t device_index)
+{
+    check(crender_frame32_submit(reinterpret_cast<crender_pipeline *>(pipeline),
+                                 c10::hip::getCurrentHIPStreamMasqueradingAsCUDA((c10::DeviceIndex)device_index).stream()),
+          "crender_frame32_submit");
+}
+
+// ... and the general frame kernel for every frame (the filler's frame32=False)
+void pipeline_submit_general(int64_t pipeline, int64_t device_index)
 {
     check(crender_pipeline_submit(reinterpret_cast<crender_pipeline *>(pipeline),
                                   c10::hip::getCurrentHIPStreamMasqueradingAsCUDA((c10::DeviceIndex)device_index).stream()),
@@ -125,6 +135,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("abi_version", []() { return crender_abi_version(); });
     m.def("render_model", &render_model, "crender_render_model on torch's current stream");
     m.def("pipeline_bind", &pipeline_bind, "crender_pipeline_bind");
-    m.def("pipeline_submit", &pipeline_submit, "crender_pipeline_submit on torch's current stream");
+    m.def("pipeline_submit", &pipeline_submit, "crender_frame32_submit on torch's current stream");
+    m.def("pipeline_submit_general", &pipeline_submit_general, "crender_pipeline_submit on torch's current stream");
     m.def("pipeline_join", &pipeline_join, "crender_pipeline_join");
 }

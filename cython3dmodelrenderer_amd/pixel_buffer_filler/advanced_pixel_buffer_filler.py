@@ -59,6 +59,7 @@ _current_device = getattr(torch._C, "_cuda_getDevice", torch.cuda.current_device
 
 
 _DIRECT_MAX_TRIANGLES = 1 << 16      # kDirectMaxTriangles of csrc/plan.h: beyond, count / scan / fill
+_FRAME32_DEFAULT = True              # the filler's frame32=None (profiles/frame32/: the same-box A/B that decides it)
 
 # what the filler reads off a model (.pyx:94-96), and the names its errors give them
 _model_arrays = operator.attrgetter("_vertices_by_triangles", "_colors_by_triangles", "_normals_by_triangles")
@@ -161,7 +162,9 @@ class _FramePipeline:
         self.n = 0
         self.pending = False
         self._args = None          # (inputs, flags) the slots are bound to
-        self._submit = filler._ext.pipeline_submit       # (handle, device index): torch's current stream
+        # (handle, device index): torch's current stream.  Frames that qualify take the small-scene kernel
+        # (include/crender_frame32.h) unless the filler says frame32=False; the same planes either way.
+        self._submit = filler._ext.pipeline_submit if filler._frame32 else filler._ext.pipeline_submit_general
         self._handle_int = self.handle.value
         self._index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         if self.share:
@@ -182,6 +185,10 @@ class _FramePipeline:
     def owned_streams(self):
         """How many streams of its own the chain holds (depth, less the shared slot)."""
         return int(self.lib.crender_pipeline_owned_streams(self.handle))
+
+    def frame32_last(self):
+        """Did the chain's last frame take the small-scene kernel (crender_frame32_last)?"""
+        return bool(self.lib.crender_frame32_last(self.handle))
 
     def close(self):
         if self.handle:
@@ -281,7 +288,7 @@ class AdvancedPixelBufferFiller(DevicePlanes, DeferredPasses):
     def __init__(self, h, w, fov=90.0, z_near=0.1, z_far=1000.0, n_threads=1, *,
                  device=None, tile=0, row_strip=None, track_winner=False, cache_inputs=False,
                  bin_capacity=0, direct_bins=True, pipeline=False, pipeline_depth=None,
-                 presort=None, lookahead=None, raster_path=None, share_caller_stream=None):
+                 presort=None, lookahead=None, raster_path=None, share_caller_stream=None, frame32=None):
         self._lib = _capi.load()                      # raises if the HIP library is missing
         self._ext = _torch_ext.load()                 # raises if the torch extension is not built
         if not torch.cuda.is_available():
@@ -337,7 +344,10 @@ class AdvancedPixelBufferFiller(DevicePlanes, DeferredPasses):
         # by the size classes its previous frames counted; 0 / 1 = general / pixel owners.
         # Speed only: every kernel renders every tile exactly.
         self._raster_path = raster_path
-        self._order = None             # (orig_of, pos_of) int32 device tensors of the resident inputs
+        # The swap chain's frames of small scenes on 32-pixel tiles take a frame kernel of their own where they qualify
+        # (include/crender_frame32.h): None = the default (_FRAME32_DEFAULT), True / False = on / off.  Speed only.
+        self._frame32 = _FRAME32_DEFAULT if frame32 is None else bool(frame32)
+        self._order = None            # (orig_of, pos_of) int32 device tensors of the resident inputs
         self._plan_order = None        # what the single-stream plan currently holds
         self._fused_light = None       # (l0, l1, l2): illumination fused into cleared frames
         self._plan_light = None        # what the single-stream plan currently holds
