@@ -96,6 +96,7 @@ NMAP_WRAP = 1
 NMAP_PERSPECTIVE, NMAP_BILINEAR, NMAP_CHAIN = 1, 2, 4
 ENV_REFLECT, ENV_BACKGROUND = 1, 2
 ENV_MAX_SIDE = 8192
+DOF_MAX_RADIUS = 12
 UNIT_SIGNATURES["wire"] = {
     "crender_wire_key_bytes": (_sz, [_i32, _i32]),
     "crender_wire_draw": (_i32, [_vp, _vp, _i64, _f32p, _vp, _vp, _vp, _vp, _i32, _i32, _u32, _vp, _vp]),
@@ -132,6 +133,10 @@ UNIT_SIGNATURES["wire"] = {
     # background's gain
     "crender_env_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _vp, _i32, C.c_float, _f32p, C.c_float, C.c_float,
                                  _f32p, C.c_float, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
+    # depth of field (DeferredPasses.depth_of_field): the outline's frame, then the colour plane, which is only read, the
+    # focus, the band, the aperture and the largest radius, the result plane
+    "crender_dof_blur": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, C.c_float, C.c_float, C.c_float, _i32, _vp,
+                                _i32, _i32, _i32, _i32, _u32, _vp]),
 }
 
 # the numpy filler's entry points (include/crender_py.h), bound from a table of their own

@@ -4,7 +4,8 @@ normal plane the others read) and environment mapping (``environment_pass``: ref
 texture, normal-map, environment and shadow-map bindings they read, the classification of a view's contour edges for the overlay (``contour_edges``: it reads no plane), the edges behind
 the surface, dashed (``hidden_line_pass``: it walks the edges, not the winner plane's pixels, and keeps a key plane), the same
 classification kept as vector segments (``line_runs``: it only reads the planes and returns a ``LineDrawing``) and geometric
-edge anti-aliasing (``edge_aa``: it reads the planes and returns a plane of its own).  A mixin
+edge anti-aliasing (``edge_aa``: it reads the planes and returns a plane of its own) and depth of field (``depth_of_field``:
+a gather blur by the circle of confusion over the z plane, which returns a plane of its own as well).  A mixin
 beside ``_device_planes.DevicePlanes``: the filler supplies ``device, h, w, y0, y1, _lib, _P`` and its frame state (``_pipeline, _inputs, _order, _last_flags, _check_bins``).  What every pass has in common is here
 once: whom it refuses (``_pass_target``), which frame it accepts (``_pass_frame``), and how it is launched
 (``_run_pass``, whose leaf ``_launch_pass`` alone needs the GPU and the library).  A ``*_pass`` method holds its own argument checks and operands.  Also here, because the shadow
@@ -731,6 +732,40 @@ class DeferredPasses:
         new = torch.empty if (self.y0, self.y1) == (0, self.h) else torch.zeros
         out = new((self.h, self.w, 3), dtype=torch.float32, device=self.color_buffer.device)
         self._run_pass("crender_wire_edge_aa", tri, T, (edges if T else None, out), z=True, reads_only=True)
+        return out
+
+    def depth_of_field(self, focus, aperture=4.0, band=0.0, max_radius=8):
+        """Depth of field of the LAST frame (``crender_dof_blur``, include/crender_wire.h): a NEW device tensor [h, w, 3]
+        float32, as ``edge_aa`` returns one, in which every pixel is the weighted mean of the pixels around it, each
+        weighted by how far its own circle of confusion reaches.  A covered pixel at view depth zv (rebuilt from the z
+        plane; ``depth_of_field.view_depth`` gives the same number, so ``focus=view_depth(filler._P, z[y, x])`` focuses
+        on what a pixel shows) has the radius ``aperture * (|zv - focus| - band)+ / zv`` pixels — nothing within `band`
+        of `focus` is blurred, and `aperture` is the radius at infinity, which the background has — clamped to
+        `max_radius` (an int from 1 to 12), which is also how far a pixel looks.  What is in front spreads over what
+        lies behind it by its own radius; a blurred background does not bleed over something sharper in front of it.
+        ``aperture=0`` and every pixel that no blurred one reaches are copied bit for bit.  Rows of the filler's
+        ``row_strip`` (the others of the result are zero; the strip does not see across its edge), on torch's current
+        stream.
+
+        Edits made in the numpy views handed out so far are carried to the device and the frame is settled first (one
+        stream synchronisation, as every getter does).  The planes are only read: the views stay as fresh or as stale
+        as they were."""
+        self._pass_target("depth_of_field")
+        tri, T = self._pass_frame("depth_of_field")
+        number = (int, float, np.integer, np.floating)
+        top32 = float(np.finfo(np.float32).max)        # (finite as the float32 the library takes)
+        if isinstance(focus, bool) or not isinstance(focus, number) or not 0 < float(focus) <= top32 or not np.float32(focus) > 0:
+            raise ValueError(f"focus must be a finite view depth above 0, got {focus!r}")
+        for name, v in (("aperture", aperture), ("band", band)):
+            if isinstance(v, bool) or not isinstance(v, number) or not 0 <= float(v) <= top32:
+                raise ValueError(f"{name} must be a finite number, 0 or above, got {v!r}")
+        top = _capi.DOF_MAX_RADIUS
+        if isinstance(max_radius, bool) or not isinstance(max_radius, (int, np.integer)) or not 1 <= max_radius <= top:
+            raise ValueError(f"max_radius must be an int from 1 to {top}, got {max_radius!r}")
+        new = torch.empty if (self.y0, self.y1) == (0, self.h) else torch.zeros
+        out = new((self.h, self.w, 3), dtype=torch.float32, device=self.color_buffer.device)
+        self._run_pass("crender_dof_blur", tri, T, (self.color_buffer, float(focus), float(band), float(aperture),
+                                                    int(max_radius)), z=True, reads_only=True, target=out)
         return out
 
     def contour_edges(self, partners, static=None, borders=False):

@@ -22,8 +22,8 @@ def _device_form_is_the_same_shading(illumination):
 class Renderer:
     def __init__(self, pixel_buffer_filler, illumination, triangle_iterator_type=None,
                  image_height=512, image_width=512, use_tqdm=True, on_device=None, texture_pass=None,
-                 shadow=None, ambient_occlusion=None, antialias=None, normal_map=None, environment=None,
-                 wireframe=None, supersample=None):
+                 shadow=None, ambient_occlusion=None, antialias=None, depth_of_field=None, normal_map=None,
+                 environment=None, wireframe=None, supersample=None):
         self.pixel_buffer_filler = pixel_buffer_filler
         self.illumination = illumination
         self.triangle_iterator_type = triangle_iterator_type   # stored, unused (as in Version C)
@@ -166,6 +166,30 @@ class Renderer:
                 raise ValueError(f"Renderer(antialias=...) takes the keys 'edges', 'feature_angle', 'contours' and "
                                  f"'borders': {unknown} unknown")
             self.antialias = dict(antialias)
+        # depth_of_field=None (default): a pinhole image, sharp at every depth.  A dict of
+        # ``AdvancedPixelBufferFiller.depth_of_field``'s arguments (``focus``, which it needs, and ``aperture`` / ``band`` /
+        # ``max_radius``): a gather blur of the finished frame by every pixel's circle of confusion.  Every frame starts
+        # from cleared buffers (one model per frame, as "fused").  The pass runs LAST, after everything that shades and
+        # after the wire pass, reads the filler's planes and writes a tensor of its own, which ``render`` returns: the
+        # tensor for on_device=True / "fused", a fresh numpy copy otherwise.  It combines neither with ``antialias`` (each
+        # of the two reads the filler's colour plane and returns a plane of its own: the second would not see the first)
+        # nor with ``supersample`` (the radii would count the supersampled frame's pixels, and the resolve reads the
+        # filler's plane, not the pass's).
+        self.depth_of_field = None
+        if depth_of_field is not None:
+            if antialias is not None or supersample is not None:
+                raise ValueError("Renderer(depth_of_field=...) together with antialias=... or supersample=...: each of them "
+                                 "reads the filler's own colour plane and would not see the blurred one; use one of them")
+            if not hasattr(pixel_buffer_filler, "depth_of_field"):
+                raise ValueError("Renderer(depth_of_field=...) needs a filler with a depth-of-field pass "
+                                 f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no depth_of_field()")
+            unknown = sorted(set(depth_of_field) - {"focus", "aperture", "band", "max_radius"})
+            if unknown:
+                raise ValueError("Renderer(depth_of_field=...) takes the keys 'focus', 'aperture', 'band' and 'max_radius': "
+                                 f"{unknown} unknown")
+            if "focus" not in depth_of_field:
+                raise ValueError("Renderer(depth_of_field=...) needs 'focus', the view depth that stays sharp")
+            self.depth_of_field = dict(depth_of_field)
         # normal_map=None (default): the light sees the interpolated vertex normals.  A dict of
         # AdvancedPixelBufferFiller.bind_normal_map's arguments but the uv (``normal_map`` or ``height``, ``scale``, ``wrap``,
         # ``mipmaps``) and of normal_map_pass's (``strength``, ``perspective``, ``filter``; "trilinear" binds the map with
@@ -250,7 +274,7 @@ class Renderer:
         filler = self.pixel_buffer_filler
         if self.texture_pass is None:
             if self.shadow is None and self.ambient_occlusion is None and self.wireframe is None and self.antialias is None \
-                    and self.normal_map is None and self.environment is None:
+                    and self.normal_map is None and self.environment is None and self.depth_of_field is None:
                 return filler.render_model(model, **kw)
             if not kw.get("clear"):        # (the "fused" caller asks for the cleared frame itself: its raster kernel shades)
                 filler.set_fused_illumination(None)
@@ -397,6 +421,11 @@ class Renderer:
             span = min(centre)
             model.scale(span / model.get_max_span())
             model.shift(-model.get_mean_vertex() + [centre[0], centre[1], -span])
+        if self.depth_of_field is not None:
+            # the frame as ever, then the lens, last of all: the pass's own tensor is the image
+            self._render(model)
+            image = self.pixel_buffer_filler.depth_of_field(**self.depth_of_field)
+            return image if self.on_device is True or self.on_device == "fused" else image.cpu().numpy()
         if self.antialias is None:
             return self._render(model)
         # the frame as ever, then the edges smoothed, last of all: the pass's own tensor is the image
