@@ -97,6 +97,8 @@ NMAP_PERSPECTIVE, NMAP_BILINEAR, NMAP_CHAIN = 1, 2, 4
 ENV_REFLECT, ENV_BACKGROUND = 1, 2
 ENV_MAX_SIDE = 8192
 DOF_MAX_RADIUS = 12
+PEEL_FIRST, PEEL_LAST = 1, 2
+PEEL_MAX_LAYERS = 16
 UNIT_SIGNATURES["wire"] = {
     "crender_wire_key_bytes": (_sz, [_i32, _i32]),
     "crender_wire_draw": (_i32, [_vp, _vp, _i64, _f32p, _vp, _vp, _vp, _vp, _i32, _i32, _u32, _vp, _vp]),
@@ -137,6 +139,13 @@ UNIT_SIGNATURES["wire"] = {
     # focus, the band, the aperture and the largest radius, the result plane
     "crender_dof_blur": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, C.c_float, C.c_float, C.c_float, _i32, _vp,
                                 _i32, _i32, _i32, _i32, _u32, _vp]),
+    # transparency (DeferredPasses.peel_layers, transparency_pass): the outline's frame of a given layer, then the normals,
+    # the key scratch and the next layer's winner plane, its z plane in the colour plane's place
+    "crender_peel_next": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
+    # and a layer blended under what is in front of it: the overlay's frame, then the colours, normals and alpha, the
+    # light, the front colours, the background, the transmittance plane, the sum in the colour plane's place
+    "crender_peel_blend": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _vp, _f32p, _vp, _f32p, _vp, _vp, _i32, _i32, _i32,
+                                  _i32, _u32, _vp]),
 }
 
 # the numpy filler's entry points (include/crender_py.h), bound from a table of their own

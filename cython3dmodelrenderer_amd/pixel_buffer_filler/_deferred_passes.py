@@ -5,7 +5,8 @@ texture, normal-map, environment and shadow-map bindings they read, the classifi
 the surface, dashed (``hidden_line_pass``: it walks the edges, not the winner plane's pixels, and keeps a key plane), the same
 classification kept as vector segments (``line_runs``: it only reads the planes and returns a ``LineDrawing``) and geometric
 edge anti-aliasing (``edge_aa``: it reads the planes and returns a plane of its own) and depth of field (``depth_of_field``:
-a gather blur by the circle of confusion over the z plane, which returns a plane of its own as well).  A mixin
+a gather blur by the circle of confusion over the z plane, which returns a plane of its own as well) and transparency
+(``peel_layers`` and ``transparency_pass``: the frame's depth layers peeled by depth key and blended front to back, a plane of its own again).  A mixin
 beside ``_device_planes.DevicePlanes``: the filler supplies ``device, h, w, y0, y1, _lib, _P`` and its frame state (``_pipeline, _inputs, _order, _last_flags, _check_bins``).  What every pass has in common is here
 once: whom it refuses (``_pass_target``), which frame it accepts (``_pass_frame``), and how it is launched
 (``_run_pass``, whose leaf ``_launch_pass`` alone needs the GPU and the library).  A ``*_pass`` method holds its own argument checks and operands.  Also here, because the shadow
@@ -96,6 +97,7 @@ class DeferredPasses:
     _environment = None  # (faces [6, S, S, 3] uint8, its mip chain over the faces stacked by rows or None): bind_environment
     _shadow = None     # (the light's filler, its vertices [T, 3, 3] float32 on the device): bind_shadow_map
     _hidden_key = None  # the zeroed int32 [h, w] key plane of hidden_line_pass, which every call leaves zero
+    _peel_scratch = None  # (keys int64 [h, w], transmittance float32 [h, w], winners int32 [2, h, w], z float32 [2, h, w])
 
     # --------------------------------------------------- what every pass shares --
     def _pass_target(self, name):
@@ -766,6 +768,136 @@ class DeferredPasses:
         out = new((self.h, self.w, 3), dtype=torch.float32, device=self.color_buffer.device)
         self._run_pass("crender_dof_blur", tri, T, (self.color_buffer, float(focus), float(band), float(aperture),
                                                     int(max_radius)), z=True, reads_only=True, target=out)
+        return out
+
+    def _peel_frame(self, name):
+        """What the two transparency methods share: the refusals and the frame of ``edge_aa``, the edits pushed and the
+        frame settled; -> (tri, col, nrm or None each, T, pos_of, the cached scratch)."""
+        self._pass_target(name)
+        tri, T = self._pass_frame(name)
+        self._push_host_edits()
+        self._check_bins()
+        if self._peel_scratch is None:
+            device = self.color_buffer.device
+            self._peel_scratch = (
+                torch.empty((self.h, self.w), dtype=torch.int64, device=device),     # crender_atomic_scratch_bytes(h, w)
+                torch.empty((self.h, self.w), dtype=torch.float32, device=device),   # the transmittance
+                torch.empty((2, self.h, self.w), dtype=torch.int32, device=device),  # two winner planes and
+                torch.empty((2, self.h, self.w), dtype=torch.float32, device=device))  # two z planes, used in turn
+        pos_of = None if self._order is None else self._order[1]
+        arrays = tuple(self._inputs[:3]) if T else (None, None, None)
+        return arrays + (T, pos_of, self._peel_scratch)
+
+    def peel_layers(self, n):
+        """The first `n` (1 to 16) depth layers of the LAST frame (``crender_peel_next``, include/crender_wire.h):
+        ``(winner int32 [n, h, w], z float32 [n, h, w])``, device tensors.  Layer 0 is a copy of the frame's own winner and
+        z planes; layer k + 1 names, per pixel, the fragment of the frame with the least depth key strictly above layer
+        k's — the next surface behind it, coplanar duplicates one by one, the highest index first — with that fragment's
+        own z, or -1 and 1e6 where nothing lies behind.  The frame's back-face culling applies to every layer.  Rows of
+        the filler's ``row_strip`` (the others of the result are zero), on torch's current stream.
+
+        Edits made in the numpy views handed out so far are carried to the device and the frame is settled first (one
+        stream synchronisation, as every getter does).  The planes are only read: the views stay as fresh or as stale
+        as they were.  The scratch (8 bytes of key a pixel, and ``transparency_pass``'s 20) is allocated at the first call and
+        kept."""
+        top = _capi.PEEL_MAX_LAYERS
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= top:
+            raise ValueError(f"n must be an int from 1 to {top}, got {n!r}")
+        tri, _, nrm, T, pos_of, (keys, _, _, _) = self._peel_frame("peel_layers")
+        new = torch.empty if (self.y0, self.y1) == (0, self.h) else torch.zeros
+        device = self.color_buffer.device
+        winner = new((int(n), self.h, self.w), dtype=torch.int32, device=device)
+        z = new((int(n), self.h, self.w), dtype=torch.float32, device=device)
+        rows = slice(self.y0, self.y1)
+        winner[0, rows].copy_(self.winner_buffer[rows])
+        z[0, rows].copy_(self.z_buffer[rows])
+        for k in range(1, int(n)):
+            self._launch_pass("crender_peel_next", (winner[k - 1], z[k - 1], tri, T, pos_of, self._P, nrm, keys, winner[k],
+                                                    z[k], self.h, self.w, self.y0, self.y1, 0))
+        return winner, z
+
+    def transparency_pass(self, alpha, layers=4, light_direction=None, background=(0, 0, 0), front="plane"):
+        """The LAST frame with its triangles transparent (``crender_peel_next`` and ``crender_peel_blend``,
+        include/crender_wire.h): a NEW device tensor [h, w, 3] float32, as ``edge_aa`` returns one.  The first `layers` (1 to
+        16) depth layers of every pixel are peeled as ``peel_layers`` peels them and blended front to back: a layer adds
+        ``transmittance * alpha * colour`` and leaves ``transmittance * (1 - alpha)``, and what is left after the last one
+        shows `background` (three finite numbers).  `alpha` is a number, or an array [T] in the caller's triangle order,
+        numpy (checked: values outside [0, 1] and NaN raise) or a float32 device tensor (clamped on the device, a NaN is
+        0).  ``front="plane"`` takes layer 0's colours from the filler's colour plane, so whatever the other passes made
+        of the visible surface is kept; ``front="model"`` shades it from the triangle's vertex colours like the layers
+        behind it, which are lit by `light_direction` (the illumination object's own flipped, normalised vector, as
+        ``set_fused_illumination`` takes it) if it is given.  A pixel that has become opaque is not touched again.
+        ``alpha=1`` with ``front="plane"`` returns the colour plane's bits over the background.  Rows of the filler's
+        ``row_strip`` (the others of the result are zero), on torch's current stream: `layers` blends and
+        ``layers - 1`` peels over two pairs of planes used in turn, without a host synchronisation between them.
+
+        Edits made in the numpy views handed out so far are carried to the device and the frame is settled first (one
+        stream synchronisation, as every getter does).  The planes are only read: the views stay as fresh or as stale
+        as they were.  The scratch (28 bytes a pixel, shared with ``peel_layers``) is allocated at the first call and kept."""
+        top = _capi.PEEL_MAX_LAYERS
+        number = (int, float, np.integer, np.floating)
+        if isinstance(layers, bool) or not isinstance(layers, (int, np.integer)) or not 1 <= layers <= top:
+            raise ValueError(f"layers must be an int from 1 to {top}, got {layers!r}")
+        if front not in ("plane", "model"):
+            raise ValueError(f"front must be 'plane' or 'model', got {front!r}")
+        try:
+            ground = [float(v) for v in background]
+        except (TypeError, ValueError):
+            ground = []
+        top32 = float(np.finfo(np.float32).max)        # (finite as the float32 the library takes)
+        if len(ground) != 3 or not all(abs(v) <= top32 for v in ground):
+            raise ValueError(f"background must be three finite numbers, got {background!r}")
+        light = None
+        if light_direction is not None:
+            try:
+                light = [float(v) for v in light_direction]
+            except (TypeError, ValueError):
+                light = []
+            if len(light) != 3 or not all(abs(v) <= top32 for v in light):
+                raise ValueError(f"light_direction must be None or three finite numbers, got {light_direction!r}")
+            light = (C.c_float * 3)(*light)
+        host = None
+        if isinstance(alpha, torch.Tensor):
+            if alpha.dtype != torch.float32 or alpha.dim() != 1:
+                raise ValueError(f"alpha must be a number or float32 [T], got {alpha.dtype} {tuple(alpha.shape)}")
+        else:
+            if isinstance(alpha, (bool, np.bool_)) or not (isinstance(alpha, number) or isinstance(alpha, np.ndarray)):
+                raise ValueError(f"alpha must be a number or an array [T], got {alpha!r}")
+            host = np.asarray(alpha)
+            if host.dtype.kind not in "fiu" or host.ndim > 1:
+                raise ValueError(f"alpha must be a number or an array [T], got {host.dtype} {host.shape}")
+            outside = int((~((host >= 0) & (host <= 1))).sum())       # (a NaN is outside)
+            if outside:
+                raise ValueError("alpha must lie in [0, 1]" + (f", got {alpha!r}" if host.ndim == 0 else
+                                                              f": {outside} of {host.size} values do not"))
+        self._pass_target("transparency_pass")
+        T = self._pass_frame("transparency_pass")[1]
+        if (host is not None and host.ndim == 1 and host.shape[0] != T) or (host is None and alpha.shape[0] != T):
+            raise ValueError(f"transparency_pass: alpha holds {(alpha if host is None else host).shape[0]} triangles, "
+                             f"the last frame drew {T}")
+        tri, col, nrm, T, pos_of, (keys, trans, wins, zs) = self._peel_frame("transparency_pass")
+        device = self.color_buffer.device
+        if host is None:
+            alpha_t = alpha.to(device).contiguous()
+        elif host.ndim == 0:
+            alpha_t = torch.full((T,), float(host), dtype=torch.float32, device=device)
+        else:
+            alpha_t = torch.from_numpy(np.ascontiguousarray(host, dtype=np.float32)).to(device)
+        new = torch.empty if (self.y0, self.y1) == (0, self.h) else torch.zeros
+        out = new((self.h, self.w, 3), dtype=torch.float32, device=device)
+        ground3 = (C.c_float * 3)(*ground)
+        n = int(layers)
+        tail = (self.h, self.w, self.y0, self.y1)
+        winner, z = self.winner_buffer, self.z_buffer
+        for k in range(n):
+            if k:
+                self._launch_pass("crender_peel_next", (winner, z, tri, T, pos_of, self._P, nrm, keys, wins[k & 1], zs[k & 1]) +
+                                  tail + (0,))
+                winner, z = wins[k & 1], zs[k & 1]
+            flags = (_capi.PEEL_FIRST if k == 0 else 0) | (_capi.PEEL_LAST if k == n - 1 else 0)
+            self._launch_pass("crender_peel_blend", (winner, tri, T, pos_of, self._P, col, nrm, alpha_t if T else None, light,
+                                                     self.color_buffer if k == 0 and front == "plane" else None, ground3,
+                                                     trans, out) + tail + (flags,))
         return out
 
     def contour_edges(self, partners, static=None, borders=False):

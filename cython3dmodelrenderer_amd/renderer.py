@@ -23,7 +23,7 @@ class Renderer:
     def __init__(self, pixel_buffer_filler, illumination, triangle_iterator_type=None,
                  image_height=512, image_width=512, use_tqdm=True, on_device=None, texture_pass=None,
                  shadow=None, ambient_occlusion=None, antialias=None, depth_of_field=None, normal_map=None,
-                 environment=None, wireframe=None, supersample=None):
+                 environment=None, transparency=None, wireframe=None, supersample=None):
         self.pixel_buffer_filler = pixel_buffer_filler
         self.illumination = illumination
         self.triangle_iterator_type = triangle_iterator_type   # stored, unused (as in Version C)
@@ -266,6 +266,34 @@ class Renderer:
             if not hasattr(pixel_buffer_filler, "phong_pass"):
                 raise ValueError("Renderer with a PhongIllumination needs a filler with a Phong pass "
                                  f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no phong_pass()")
+        # transparency=None (default): every pixel shows its nearest surface and nothing behind it.  A dict of
+        # ``AdvancedPixelBufferFiller.transparency_pass``'s arguments (``alpha``, which it needs, and ``layers`` /
+        # ``background`` / ``front``): the frame's depth layers peeled and blended front to back.  Every frame starts from
+        # cleared buffers (one model per frame, as "fused").  The pass runs LAST, after everything that shades and after the
+        # wire pass, reads the filler's planes and writes a tensor of its own, which ``render`` returns: the tensor for
+        # on_device=True / "fused", a fresh numpy copy otherwise.  The layers behind the first are lit by the
+        # ``light_direction`` of a GuroIllumination (or the key of that name); a PhongIllumination is refused, since they would be lit by another
+        # model than the first.  It combines with none of ``antialias``, ``depth_of_field`` and ``supersample``.
+        self.transparency = None
+        if transparency is not None:
+            if antialias is not None or depth_of_field is not None or supersample is not None:
+                raise ValueError("Renderer(transparency=...) together with antialias=..., depth_of_field=... or supersample=...: "
+                                 "each of them reads the filler's own colour plane and would not see the blended one; use one "
+                                 "of them")
+            if not hasattr(pixel_buffer_filler, "transparency_pass"):
+                raise ValueError("Renderer(transparency=...) needs a filler with a transparency pass "
+                                 f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no transparency_pass()")
+            if self._phong:
+                raise ValueError("Renderer(transparency=...) with a PhongIllumination: the layers behind the first are shaded "
+                                 "with the Guro light or none and would be lit by another model than the first; use a "
+                                 "GuroIllumination")
+            unknown = sorted(set(transparency) - {"alpha", "layers", "light_direction", "background", "front"})
+            if unknown:
+                raise ValueError("Renderer(transparency=...) takes the keys 'alpha', 'layers', 'light_direction', 'background' "
+                                 f"and 'front': {unknown} unknown")
+            if "alpha" not in transparency:
+                raise ValueError("Renderer(transparency=...) needs 'alpha', a number or one value per triangle")
+            self.transparency = dict(transparency)
 
     def _draw(self, model, light=None, shadows=True, **kw):
         """``render_model``; with a texture pass, ambient occlusion, a shadow map, an environment or a wireframe, a cleared
@@ -274,7 +302,8 @@ class Renderer:
         filler = self.pixel_buffer_filler
         if self.texture_pass is None:
             if self.shadow is None and self.ambient_occlusion is None and self.wireframe is None and self.antialias is None \
-                    and self.normal_map is None and self.environment is None and self.depth_of_field is None:
+                    and self.normal_map is None and self.environment is None and self.depth_of_field is None \
+                    and self.transparency is None:
                 return filler.render_model(model, **kw)
             if not kw.get("clear"):        # (the "fused" caller asks for the cleared frame itself: its raster kernel shades)
                 filler.set_fused_illumination(None)
@@ -421,6 +450,13 @@ class Renderer:
             span = min(centre)
             model.scale(span / model.get_max_span())
             model.shift(-model.get_mean_vertex() + [centre[0], centre[1], -span])
+        if self.transparency is not None:
+            # the frame as ever, then its layers blended, last of all: the pass's own tensor is the image
+            self._render(model)
+            opts = dict(self.transparency)
+            opts.setdefault("light_direction", getattr(self.illumination, "light_direction", None))
+            image = self.pixel_buffer_filler.transparency_pass(**opts)
+            return image if self.on_device is True or self.on_device == "fused" else image.cpu().numpy()
         if self.depth_of_field is not None:
             # the frame as ever, then the lens, last of all: the pass's own tensor is the image
             self._render(model)
