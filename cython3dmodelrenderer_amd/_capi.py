@@ -99,6 +99,8 @@ ENV_MAX_SIDE = 8192
 DOF_MAX_RADIUS = 12
 PEEL_FIRST, PEEL_LAST = 1, 2
 PEEL_MAX_LAYERS = 16
+BLOOM_MAX_RADIUS = 32
+BLOOM_U8, BLOOM_FLIP, BLOOM_REINHARD, BLOOM_GAMMA2 = 1, 2, 4, 8
 UNIT_SIGNATURES["wire"] = {
     "crender_wire_key_bytes": (_sz, [_i32, _i32]),
     "crender_wire_draw": (_i32, [_vp, _vp, _i64, _f32p, _vp, _vp, _vp, _vp, _i32, _i32, _u32, _vp, _vp]),
@@ -146,6 +148,10 @@ UNIT_SIGNATURES["wire"] = {
     # light, the front colours, the background, the transmittance plane, the sum in the colour plane's place
     "crender_peel_blend": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _vp, _f32p, _vp, _f32p, _vp, _vp, _i32, _i32, _i32,
                                   _i32, _u32, _vp]),
+    # bloom and tone mapping (DevicePlanes.bloom, bloom.bloom): any float32 image, the threshold, the HOST weights and the
+    # radius, intensity, exposure, 1 / white^2 and the clamp, the scratch plane and the result, then the frame and the rows
+    "crender_bloom": (_i32, [_vp, C.c_float, _f32p, _i32, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp,
+                             _i32, _i32, _i32, _i32, _u32, _vp]),
 }
 
 # the numpy filler's entry points (include/crender_py.h), bound from a table of their own

@@ -28,6 +28,8 @@ from .. import _capi
 
 
 class DevicePlanes:
+    _bloom_scratch = None              # {(H, W): float32 [H, W, 3]}: bloom's row-blurred plane, made at the first call
+
     def __init__(self):
         self.z_buffer = self.color_buffer = self.normals_buffer = self.winner_buffer = None
         self._host = {}                # name -> numpy view handed out by a getter (of _host_pin[name])
@@ -79,6 +81,12 @@ class DevicePlanes:
                 self.color_buffer.data_ptr(), None if light is None else self.normals_buffer.data_ptr(),
                 None if light is None else (C.c_float * 3)(*light), self.h, self.w, factor, Y0, Y1,
                 out.data_ptr(), flags, self._stream()), "crender_ssaa_resolve")
+
+    def _bloom_planes(self, src, scratch, out, call, y0, y1):
+        """crender_bloom (include/crender_wire.h, "Bloom") of rows y0 .. y1 of `src` into `out`."""
+        from .. import bloom
+        with torch.cuda.device(self.device):
+            bloom.launch(self._lib, src, scratch, out, call, y0, y1, self._stream())
 
     # ----------------------------------------------------------------- protocol --
     def _planes(self):
@@ -190,6 +198,51 @@ class DevicePlanes:
         while True:
             self._resolve_planes(out, factor, light, flags, self.y0 // factor, self.y1 // factor)
             if not self._wait_planes():
+                break
+            self._ready_planes()       # (a frame was rendered again: the same planes, settled now)
+        return out
+
+    def bloom(self, threshold=255.0, radius=8, weights=None, intensity=1.0, exposure=1.0, tonemap=None, white=float("inf"),
+              gamma=1, clamp=None, dtype="float32", flip_rows=False, source=None):
+        """Bloom and tone mapping (``crender_bloom``, include/crender_wire.h "Bloom"): a NEW device tensor [H, W, 3] that
+        holds the image with a glow around its bright pixels.  A pixel whose largest channel m exceeds `threshold` is
+        bright by (m - threshold) / m of its colour; the bright values are blurred with `weights` (a table of radius + 1
+        numbers by distance; None: ``bloom.gaussian(radius)``; an explicit table fixes radius = len - 1, at most 32) along
+        the rows and then along the columns, and `intensity` times the glow is added.  A pixel no glow reaches keeps its
+        bits.  Then, only if asked for: `exposure` scales, `tonemap` "reinhard" maps a = v / 255 to
+        a (1 + a / white^2) / (1 + a), `gamma` 2 takes the square root; `clamp` cuts from above.  `dtype` "uint8"
+        stores ``present_u8``'s cast (clamped at 255 unless `clamp` says otherwise) and `flip_rows` stores the rows
+        bottom up: ``bloom(dtype="uint8", flip_rows=True)`` is the PNG's bytes.
+
+        Without `source` the image is the filler's colour plane, completed as ``present_u8`` completes it (edits made
+        in the numpy views are carried up first; a frame whose bin lists overflowed is rendered again and bloomed
+        again), over the filler's rows; the other rows of the result are zero.  The planes are only read: the views
+        stay as fresh or as stale as they were.  With `source`, a contiguous float32 [H', W', 3] tensor on the filler's
+        device, of any size — what ``edge_aa``, ``depth_of_field``, ``transparency_pass`` or ``resolve`` returned —
+        the pass runs over all of its rows.  On torch's current stream; the scratch plane is kept per shape."""
+        from .. import bloom
+        call = bloom.arguments(threshold, radius, weights, intensity, exposure, tonemap, white, gamma, clamp, dtype, flip_rows)
+        if source is None:
+            self.get_color_tensor()    # (what the filler does before it hands the plane out: it must be complete)
+            self._push_host_edits()
+            src, y0, y1 = self.color_buffer, self.y0, self.y1
+        else:
+            bloom.check_image(source, "source")
+            want = torch.device(self.device)
+            if source.device.type != want.type or (want.index is not None and source.device.index != want.index):
+                raise ValueError(f"source must be on the filler's device {want}, got {source.device}")
+            src, y0, y1 = source, 0, int(source.shape[0])
+        H, W = int(src.shape[0]), int(src.shape[1])
+        if self._bloom_scratch is None:
+            self._bloom_scratch = {}
+        scratch = self._bloom_scratch.get((H, W))
+        if scratch is None:
+            scratch = self._bloom_scratch[(H, W)] = torch.empty((H, W, 3), dtype=torch.float32, device=src.device)
+        new = torch.empty if (y0, y1) == (0, H) else torch.zeros
+        out = new((H, W, 3), dtype=getattr(torch, call.dtype), device=src.device)
+        while True:
+            self._bloom_planes(src, scratch, out, call, y0, y1)
+            if source is not None or not self._wait_planes():
                 break
             self._ready_planes()       # (a frame was rendered again: the same planes, settled now)
         return out

@@ -23,7 +23,7 @@ class Renderer:
     def __init__(self, pixel_buffer_filler, illumination, triangle_iterator_type=None,
                  image_height=512, image_width=512, use_tqdm=True, on_device=None, texture_pass=None,
                  shadow=None, ambient_occlusion=None, antialias=None, depth_of_field=None, normal_map=None,
-                 environment=None, transparency=None, wireframe=None, supersample=None):
+                 environment=None, bloom=None, transparency=None, wireframe=None, supersample=None):
         self.pixel_buffer_filler = pixel_buffer_filler
         self.illumination = illumination
         self.triangle_iterator_type = triangle_iterator_type   # stored, unused (as in Version C)
@@ -294,6 +294,24 @@ class Renderer:
             if "alpha" not in transparency:
                 raise ValueError("Renderer(transparency=...) needs 'alpha', a number or one value per triangle")
             self.transparency = dict(transparency)
+        # bloom=None (default): what is brighter than 255 stays as the frame holds it.  A dict of the filler's ``bloom``
+        # arguments but ``source`` ({} = its defaults: a glow of radius 8 around what exceeds 255): bloom and tone mapping
+        # of the finished image.  It runs after EVERYTHING else and reads a source: the tensor of ``transparency``,
+        # ``depth_of_field``, ``antialias`` or ``supersample``, whichever ran, or else the filler's colour plane — so it
+        # combines with each of the four, and alone it changes nothing about how the frame is drawn.  ``render`` returns
+        # the pass's own tensor for on_device=True / "fused", a fresh numpy copy otherwise.
+        self.bloom = None
+        if bloom is not None:
+            if not hasattr(pixel_buffer_filler, "bloom"):
+                raise ValueError("Renderer(bloom=...) needs a filler that keeps its planes on the device "
+                                 "(AdvancedPixelBufferFiller, EdgeOnlyPixelBufferFiller): "
+                                 f"{type(pixel_buffer_filler).__name__} has no bloom()")
+            from .bloom import KEYS
+            unknown = sorted(set(bloom) - set(KEYS))
+            if unknown:
+                raise ValueError("Renderer(bloom=...) takes the keys " + ", ".join(repr(k) for k in KEYS[:-1]) +
+                                 f" and {KEYS[-1]!r}: {unknown} unknown")
+            self.bloom = dict(bloom)
 
     def _draw(self, model, light=None, shadows=True, **kw):
         """``render_model``; with a texture pass, ambient occlusion, a shadow map, an environment or a wireframe, a cleared
@@ -456,17 +474,23 @@ class Renderer:
             opts = dict(self.transparency)
             opts.setdefault("light_direction", getattr(self.illumination, "light_direction", None))
             image = self.pixel_buffer_filler.transparency_pass(**opts)
-            return image if self.on_device is True or self.on_device == "fused" else image.cpu().numpy()
-        if self.depth_of_field is not None:
+        elif self.depth_of_field is not None:
             # the frame as ever, then the lens, last of all: the pass's own tensor is the image
             self._render(model)
             image = self.pixel_buffer_filler.depth_of_field(**self.depth_of_field)
-            return image if self.on_device is True or self.on_device == "fused" else image.cpu().numpy()
-        if self.antialias is None:
-            return self._render(model)
-        # the frame as ever, then the edges smoothed, last of all: the pass's own tensor is the image
-        self._render(model)
-        image = self.pixel_buffer_filler.edge_aa(**self._view_edges(model, self.antialias, "_smoothed"))
+        elif self.antialias is not None:
+            # the frame as ever, then the edges smoothed, last of all: the pass's own tensor is the image
+            self._render(model)
+            image = self.pixel_buffer_filler.edge_aa(**self._view_edges(model, self.antialias, "_smoothed"))
+        else:
+            image = self._render(model)
+            if self.bloom is None:
+                return image
+            if self.supersample is None:
+                image = None           # the filler's own colour plane, host edits included: bloom completes it itself
+        if self.bloom is not None:
+            # after everything else: over the tensor of the pass that ran last, or over the filler's plane
+            image = self.pixel_buffer_filler.bloom(source=image, **self.bloom)
         return image if self.on_device is True or self.on_device == "fused" else image.cpu().numpy()
 
     def _render(self, model):
@@ -520,7 +544,7 @@ class Renderer:
         self._draw_wire(model)
         if self.supersample is not None:
             image = filler.resolve(self.supersample)
-            return image if self.on_device is True else image.cpu().numpy()
+            return image if self.on_device is True or self.bloom is not None else image.cpu().numpy()
         return filler.get_color_tensor() if self.on_device is True else filler.get_color_buffer()
 
     def _render_supersampled(self, model):
@@ -550,11 +574,12 @@ class Renderer:
                     self.illumination.draw_illumination(filler.get_color_buffer(), filler.get_normals_buffer())
                 self._draw_wire(model)
                 image = filler.resolve(s)
-            return image if self.on_device is True else image.cpu().numpy()
+            return image if self.on_device is True or self.bloom is not None else image.cpu().numpy()
         self._draw(model)
         self.illumination.draw_illumination(filler.get_color_buffer(), filler.get_normals_buffer())
         self._draw_wire(model)
-        return filler.resolve(s).cpu().numpy()
+        image = filler.resolve(s)
+        return image if self.bloom is not None else image.cpu().numpy()      # (bloom reads the resolve's tensor)
 
     def reset_buffers(self):
         pass   # a no-op in the reference too (renderer.py:51-52): renders composite
