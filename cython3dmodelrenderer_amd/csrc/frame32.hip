@@ -26,6 +26,11 @@
 // every winner of a list of up to 256 records — takes coordinates, denominators and refined reciprocals from the
 // queue in LDS: no gather of the projected vertices and no division set-up per pixel.  Other winners go through
 // shade_and_store from global memory.
+//
+// Row stores.  Where the frame's rows are 16-byte aligned (the clear's condition, A.vec_clear) a covered rectangle of
+// full width leaves its wavefronts as whole rows in 16-byte write-through stores, like an empty tile's
+// (resolve_tile_rows); a rectangle cut at the frame's right edge, and every rectangle of any other frame, is stored
+// pixel by pixel (resolve_tile).  Same words either way.
 #include <mutex>
 #include <unordered_map>
 
@@ -41,6 +46,11 @@ constexpr int TS = 32;
 constexpr bool kSlotted = false;
 #else
 constexpr bool kSlotted = true;
+#endif
+#ifdef CRENDER_FRAME32_PLAIN_STORES        // (A/B build: every covered tile resolved by per-pixel plain stores)
+constexpr bool kRowStores = false;
+#else
+constexpr bool kRowStores = true;
 #endif
 
 // slot of tile-local pixel (dx, dy) in the key plane: each row's pairs of keys permuted by the row number
@@ -244,7 +254,8 @@ CR_DEV void sweep_runs(const Queue &q, unsigned long long *key, const uint32_t *
     }
 }
 
-// Every pixel of the rectangle is written exactly once.  A part's pixels are taken in rows of its own width.
+// The per-pixel resolve: every pixel of the rectangle is written exactly once, by plain stores of one, three and
+// three words.  A part's pixels are taken in rows of its own width.
 CR_DEV void resolve_tile(const Frame32Args &A, const Queue &q, const unsigned long long *key, int W,
                          int X0, int Y0, int X1, int Y1, int rw, int quad, uint32_t last_batch, int tid)
 {
@@ -279,6 +290,107 @@ CR_DEV void resolve_tile(const Frame32Args &A, const Queue &q, const unsigned lo
         } else {
             shade_and_store<uint32_t>(A.proj, A.col, A.nrm, 0xFFFFFFFEu - low, x, y, pix, A.zb, A.cb, A.nb);
         }
+    }
+}
+
+// The staged resolve: resolve_tile's pixels by the same operations, stored as whole rows, written through like the
+// clear's.  For a rectangle of full width (X1 - X0 == rw) in a frame of 16-byte rows (A.vec_clear) the 64 pixels of
+// one wavefront pass are whole rows of the rectangle — two of 32 pixels, four of 16 — and a row's bytes are
+// contiguous and 16-byte aligned in each plane.  A thread ends a pass holding its pixel's seven words; the wavefront
+// lays one plane's 64 pixels down in LDS in pixel order and reads them back 16 bytes per lane (take4): colour,
+// normal, z, back to back through the same 768 bytes — a wavefront's LDS operations complete in order, so nothing
+// waits between them — and only then the three 16-byte stores (st4o), 48 + 48 + 16 lanes.  (Store, then stage the
+// next plane, is one LDS round trip per plane on every covered workgroup's critical path, and lost what the
+// write-through gains: profiles/frame32/ab_writethrough.txt.)  The space is the wavefront's quarter of the queue's
+// tri / box / px_scan arrays: behind the last sweep's barrier the resolve reads the queue's coordinates,
+// denominators and reciprocals, nothing else.  No workgroup barrier.  A row at or below Y1 (a frame's cut bottom
+// tile row) is shaded by nobody and stored by nobody.
+static_assert(offsetof(Queue, box) == offsetof(Queue, tri) + 4 * kThreads &&
+              offsetof(Queue, px_scan) == offsetof(Queue, box) + 4 * kThreads && offsetof(Queue, tri) % 16 == 0 &&
+              3 * 4 * kThreads == (kThreads / 64) * 64 * 12, "64 pixels x 12 bytes of staging space per wavefront");
+
+struct Pixel7 {
+    float z, c0, c1, c2, n0, n1, n2;
+};
+
+// (base + a 32-bit byte offset, the base in scalar registers: elem()'s form of address)
+CR_DEV void st4o(float *base, uint32_t byte_off, const float4 &v)
+{
+    const cr_v4f x = {v.x, v.y, v.z, v.w};
+    asm volatile("global_store_dwordx4 %0, %1, %2 sc1" : : "v"(byte_off), "v"(x), "s"(base) : "memory");
+}
+
+// Staged words 4 * at .. 4 * at + 3: what every lane of the wavefront wrote before is read, and what is written
+// next does not overtake the read (the fences order the compiler; the hardware needs no instruction for it).
+CR_DEV float4 take4(const float *stg, int at)
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const float4 v = *reinterpret_cast<const float4 *>(stg + 4 * at);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    return v;
+}
+
+CR_DEV void resolve_tile_rows(const Frame32Args &A, Queue &q, const unsigned long long *key, int W,
+                              int X0, int Y0, int Y1, int rw, int quad, uint32_t last_batch, int tid)
+{
+    const int lane = tid & 63;
+    float *stg = reinterpret_cast<float *>(q.tri) + (tid >> 6) * (64 * 3);
+    const int npx = quad >= 0 ? rw * (TS / 2) : TS * TS;       // (a multiple of kThreads: every lane makes every pass)
+    const int wave_rows = rw == TS ? 2 : 4;
+    // lane j < 48 puts out words 4j .. 4j + 3 of a pass's colours and normals (24 or 12 lanes to a row), lane j < 16
+    // those of its depths (8 or 4 lanes to a row); the other lanes read along (word 0) and store nothing
+    const int rc = rw == TS ? lane / 24 : lane / 12, rz = rw == TS ? lane >> 3 : lane >> 2;
+    const int at_c = lane < 48 ? lane : 0, at_z = lane < 16 ? lane : 0;
+    const uint32_t uW = (uint32_t)W;
+    const uint32_t in_c = (uint32_t)rc * (uW * 12u) + (uint32_t)(lane - rc * (rw == TS ? 24 : 12)) * 16u;
+    const uint32_t in_z = (uint32_t)rz * (uW * 4u) + (uint32_t)(lane - rz * (rw == TS ? 8 : 4)) * 16u;
+    for (int p0 = tid; p0 < npx; p0 += kThreads) {
+        const int dy = rw == TS ? p0 / TS : p0 / (TS / 2), dx = p0 - dy * rw;
+        const int x = X0 + dx, y = Y0 + dy;
+        Pixel7 v{1e6f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};    // (store_background's words)
+        const uint32_t low = (uint32_t)key[key_slot(dx, dy)];
+        if (y < Y1 && low != KEY_LOW_PRIOR) {
+            // resolve_tile's three cases, operation for operation; the words stay in registers
+            const uint32_t id = kSlotted ? 0xFFFFu - (low >> 16) : 0xFFFFFFFEu - low;
+            float c[9], n[9], b1, b2, b3;
+            if (kSlotted && ((low >> 8) & 0xFFu) == last_batch) {
+                const TriSetup st = queued_setup(q, (int)(low & 0xFFu));
+                load9(elem(A.col, (uint32_t)(id * 9u)), c);
+                load9(elem(A.nrm, (uint32_t)(id * 9u)), n);
+                float n1, n2, n3;
+                numerators(st, x, y, n1, n2, n3);
+                quotients(st, n1, n2, n3, b1, b2, b3);
+                v.z = interp(st.z0, st.z1, st.z2, b1, b2, b3);
+            } else {
+                const TriXYZ t = load_tri(elem(A.proj, (uint32_t)(id * 9u)));
+                load9(elem(A.col, (uint32_t)(id * 9u)), c);
+                load9(elem(A.nrm, (uint32_t)(id * 9u)), n);
+                barycentric(t, x, y, b1, b2, b3);
+                v.z = interp(t.z0, t.z1, t.z2, b1, b2, b3);
+            }
+            const Shade s = shade_fragment(c, n, b1, b2, b3, Light{0.f, 0.f, 0.f, 0});
+            v.c0 = s.c0; v.c1 = s.c1; v.c2 = s.c2;
+            v.n0 = s.n0; v.n1 = s.n1; v.n2 = s.n2;
+        }
+        // ---- the wavefront's rows: the first is row ya of the frame, its first pixel pixel `pix0`
+        const int first = __builtin_amdgcn_readfirstlane(p0 - lane);       // (the wavefront's first pixel)
+        const int ya = Y0 + (rw == TS ? first / TS : first / (TS / 2));
+        const int rows_ok = Y1 - ya < wave_rows ? Y1 - ya : wave_rows;     // (<= 0: the whole pass is cut)
+        const uint32_t pix0 = (uint32_t)ya * (uint32_t)W + (uint32_t)X0;
+        const bool put_c = lane < 48 && rc < rows_ok, put_z = lane < 16 && rz < rows_ok;
+        stg[lane * 3] = v.c0; stg[lane * 3 + 1] = v.c1; stg[lane * 3 + 2] = v.c2;
+        const float4 c4 = take4(stg, at_c);
+        stg[lane * 3] = v.n0; stg[lane * 3 + 1] = v.n1; stg[lane * 3 + 2] = v.n2;
+        const float4 n4 = take4(stg, at_c);
+        stg[lane] = v.z;
+        const float4 z4w = take4(stg, at_z);
+        if (put_c) {
+            st4o(A.cb, pix0 * 12u + in_c, c4);
+            st4o(A.nb, pix0 * 12u + in_c, n4);
+        }
+        if (put_z) st4o(A.zb, pix0 * 4u + in_z, z4w);
     }
 }
 
@@ -343,11 +455,18 @@ void k_frame32(Frame32Args A)
     int X1 = (X0 + TS < G.W) ? (X0 + TS) : G.W;
     int Y1 = (Y0 + TS < G.y1) ? (Y0 + TS) : G.y1;
 
-    const uint32_t nlist = A.count[tile];
+    // a main workgroup's two words, the list's length and the tile's split flag, are independent: both loads are
+    // issued before either is waited for (a launch without helpers reads the length twice)
+    const bool flagged = !helper && A.heavy_flag;
+    const uint32_t *flag_at = flagged ? A.heavy_flag + tile : A.count + tile;
+    uint32_t nlist = A.count[tile], flag = *flag_at;
+    asm volatile("" : "+v"(nlist), "+v"(flag));          // (both words here: the second load is not sunk to its use)
+    nlist = (uint32_t)__builtin_amdgcn_readfirstlane((int)nlist);
+    flag = (uint32_t)__builtin_amdgcn_readfirstlane((int)flag);
     const uint32_t beg = (uint32_t)tile * A.capacity;
     const uint32_t end = beg + (nlist < A.capacity ? nlist : A.capacity);
     if (!helper) {
-        if (A.heavy_flag && A.heavy_flag[tile]) quad = 0;
+        if (flagged && flag) quad = 0;
         if (tid == 0) A.count_next[tile] = 0;            // the other parity's counter: zero for the next frame
     }
     int rw = TS;                 // width of this workgroup's rectangle in the key plane's terms
@@ -450,7 +569,11 @@ void k_frame32(Frame32Args A)
             sweep_runs(q, key, wo, (int)wo[kThreads / 64], tid, X0, Y0);
         }
         __syncthreads();
-        resolve_tile(A, q, key, G.W, X0, Y0, X1, Y1, rw, quad, ((end - beg - 1) / (uint32_t)kThreads) & 0xFFu, tid);
+        const uint32_t last_batch = ((end - beg - 1) / (uint32_t)kThreads) & 0xFFu;
+        if (kRowStores && A.vec_clear && X1 - X0 == rw)         // (uniform over the workgroup)
+            resolve_tile_rows(A, q, key, G.W, X0, Y0, Y1, rw, quad, last_batch, tid);
+        else
+            resolve_tile(A, q, key, G.W, X0, Y0, X1, Y1, rw, quad, last_batch, tid);
         // one covered tile's size class into the frame's statistics: one lane, its last memory operation
         if (tid == 0 && tile_class >= 0)
             atomicAdd(&A.stats[(((blockIdx.x >> 3) & (kStatWords / 2 - 1)) << 1) + (uint32_t)tile_class], 1u);

@@ -8,6 +8,10 @@
  * a 32-pixel plan can take.  The frames a chain renders of a small scene take one of them: direct bins, the fused
  * clear, no winner plane, no fused light, no triangle order, lists of small records swept run-wise.  This unit is
  * a kernel with that one path, launched in the general kernel's place when — and only when — a frame qualifies.
+ * Its stores: where the three planes begin on 16-byte boundaries and the width is a multiple of 4, every tile of
+ * full width — empty or covered — is stored as whole rows in 16-byte write-through stores; a tile cut at the right
+ * edge, and every tile of a frame without such rows, is stored pixel by pixel.  The planes hold the same words
+ * either way, and nothing outside the frame's rows is ever written.
  *
  * Contract.
  *   Results     Bit-identical planes: every sample goes through the same device functions (raster_math.h), the
