@@ -22,8 +22,19 @@ _INCLUDE = os.path.join("..", "..", "include")
 # but kept out of source_sha16(): that fingerprint names the kernels the committed profiles/*.json were measured on,
 # and these kernels are none of them.  _capi.UNIT_SIGNATURES is keyed alike.
 UNITS = {
-    # wireframe.hip  EdgeOnlyPixelBufferFiller, and the hidden-line overlay over the winner plane (include/crender_wire.h)
+    # wireframe.hip  EdgeOnlyPixelBufferFiller, and the line passes over the winner plane: overlay, outline, edge
+    # anti-aliasing, contours, hidden lines, runs (include/crender_wire.h)
     "wire": (["wireframe.hip"], [os.path.join(_INCLUDE, "crender_wire.h")]),
+    # bloom.hip  bloom and tone mapping over any float32 image (include/crender_bloom.h)
+    "bloom": (["bloom.hip"], [os.path.join(_INCLUDE, "crender_bloom.h")]),
+    # peel.hip  transparency: depth peeling by depth key and the blend of a layer (include/crender_peel.h)
+    "peel": (["peel.hip"], [os.path.join(_INCLUDE, "crender_peel.h")]),
+    # dof.hip  depth of field: a gather blur by the circle of confusion over the z plane (include/crender_dof.h)
+    "dof": (["dof.hip"], [os.path.join(_INCLUDE, "crender_dof.h")]),
+    # normal_map.hip  a normal map from a height map, and the pass that perturbs the normal plane (include/crender_nmap.h)
+    "nmap": (["normal_map.hip"], [os.path.join(_INCLUDE, "crender_nmap.h")]),
+    # envmap.hip  cube-map reflections and the skybox over the winner plane (include/crender_env.h)
+    "env": (["envmap.hip"], [os.path.join(_INCLUDE, "crender_env.h")]),
     # pyfill.hip  the numpy filler of crender/py (include/crender_py.h)
     "py": (["pyfill.hip"], [os.path.join(_INCLUDE, "crender_py.h")]),
     # texture.hip  the deferred texture pass over the winner plane (include/crender_tex.h)
@@ -42,9 +53,10 @@ UNITS = {
     # ao.hip  the deferred ambient-occlusion pass over the z, winner and normal planes (include/crender_ao.h)
     "ao": (["ao.hip"], [os.path.join(_INCLUDE, "crender_ao.h")]),
     # winner_pass.h  what the deferred passes over the winner plane share (texture.hip, texmip.hip, texaniso.hip,
-    # shadow.hip, phong.hip, ao.hip, wireframe.hip): the winner's triangle projected and the host's frame checks; the
-    # per-pixel frame, the store with the fused light, the texel fetches and the launch geometry; the tile frame and the
-    # tile grid; a unit of its own, without a source, so that each pass's header list stays its own.
+    # shadow.hip, phong.hip, ao.hip, wireframe.hip, bloom.hip, peel.hip, dof.hip, normal_map.hip, envmap.hip): the
+    # winner's triangle projected and the host's frame checks; the per-pixel frame, the store with the fused light, the
+    # texel fetches and the launch geometry; the tile frame and the tile grid; a unit of its own, without a source, so
+    # that each pass's header list stays its own.
     "pass": ([], ["winner_pass.h"]),
     # chain.hip  the swap chain's shared slot: one slot on the caller's stream (include/crender_chain.h; host code
     # only, over the pipeline handle of plan.h): it launches nothing.

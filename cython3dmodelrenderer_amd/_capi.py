@@ -92,15 +92,6 @@ WIRE_HIDDEN_USE_WINNER = 1
 WIRE_MAX_DASH = 64
 WIRE_RUNS_GROUP = 256
 WIRE_RUNS_USE_WINNER = 1
-NMAP_WRAP = 1
-NMAP_PERSPECTIVE, NMAP_BILINEAR, NMAP_CHAIN = 1, 2, 4
-ENV_REFLECT, ENV_BACKGROUND = 1, 2
-ENV_MAX_SIDE = 8192
-DOF_MAX_RADIUS = 12
-PEEL_FIRST, PEEL_LAST = 1, 2
-PEEL_MAX_LAYERS = 16
-BLOOM_MAX_RADIUS = 32
-BLOOM_U8, BLOOM_FLIP, BLOOM_REINHARD, BLOOM_GAMMA2 = 1, 2, 4, 8
 UNIT_SIGNATURES["wire"] = {
     "crender_wire_key_bytes": (_sz, [_i32, _i32]),
     "crender_wire_draw": (_i32, [_vp, _vp, _i64, _f32p, _vp, _vp, _vp, _vp, _i32, _i32, _u32, _vp, _vp]),
@@ -127,31 +118,60 @@ UNIT_SIGNATURES["wire"] = {
                                        _u32, _vp]),
     "crender_wire_runs_emit": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, _vp, C.c_float, _vp, _i64, _vp, _vp, _i32, _i32,
                                       _i32, _i32, _u32, _vp]),
-    # normal mapping (DeferredPasses.bind_normal_map, normal_map_pass): a tangent-space map from a height map, and the
-    # pass that perturbs the normal plane: the overlay's frame, then the uv, the map and its size, the strength, the plane
-    "crender_nmap_from_height": (_i32, [_vp, _i32, _i32, C.c_float, _u32, _vp, _vp]),
-    "crender_nmap_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _i32, C.c_float, _vp, _i32, _i32, _i32, _i32,
-                                  _u32, _vp]),
-    # environment mapping (DeferredPasses.bind_environment, environment_pass): the overlay's frame, then the normal plane,
-    # the two levels' faces and sides and the second one's weight, the orientation, reflectivity, f0, the tint, the
-    # background's gain
-    "crender_env_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _vp, _i32, C.c_float, _f32p, C.c_float, C.c_float,
-                                 _f32p, C.c_float, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
-    # depth of field (DeferredPasses.depth_of_field): the outline's frame, then the colour plane, which is only read, the
-    # focus, the band, the aperture and the largest radius, the result plane
-    "crender_dof_blur": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, C.c_float, C.c_float, C.c_float, _i32, _vp,
-                                _i32, _i32, _i32, _i32, _u32, _vp]),
-    # transparency (DeferredPasses.peel_layers, transparency_pass): the outline's frame of a given layer, then the normals,
-    # the key scratch and the next layer's winner plane, its z plane in the colour plane's place
+}
+
+# bloom and tone mapping (include/crender_bloom.h), bound from a table of its own (DevicePlanes.bloom, bloom.bloom):
+# any float32 image, the threshold, the HOST weights and the
+# radius, intensity, exposure, 1 / white^2 and the clamp, the scratch plane and the result, then the frame and the rows
+BLOOM_MAX_RADIUS = 32
+BLOOM_U8, BLOOM_FLIP, BLOOM_REINHARD, BLOOM_GAMMA2 = 1, 2, 4, 8
+UNIT_SIGNATURES["bloom"] = {
+    "crender_bloom": (_i32, [_vp, C.c_float, _f32p, _i32, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp,
+                             _i32, _i32, _i32, _i32, _u32, _vp]),
+}
+
+# transparency (include/crender_peel.h), bound from a table of its own (DeferredPasses.peel_layers,
+# transparency_pass): the outline's frame of a given layer, then the normals,
+# the key scratch and the next layer's winner plane, its z plane in the colour plane's place
+PEEL_FIRST, PEEL_LAST = 1, 2
+PEEL_MAX_LAYERS = 16
+UNIT_SIGNATURES["peel"] = {
     "crender_peel_next": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
     # and a layer blended under what is in front of it: the overlay's frame, then the colours, normals and alpha, the
     # light, the front colours, the background, the transmittance plane, the sum in the colour plane's place
     "crender_peel_blend": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _vp, _f32p, _vp, _f32p, _vp, _vp, _i32, _i32, _i32,
                                   _i32, _u32, _vp]),
-    # bloom and tone mapping (DevicePlanes.bloom, bloom.bloom): any float32 image, the threshold, the HOST weights and the
-    # radius, intensity, exposure, 1 / white^2 and the clamp, the scratch plane and the result, then the frame and the rows
-    "crender_bloom": (_i32, [_vp, C.c_float, _f32p, _i32, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp,
-                             _i32, _i32, _i32, _i32, _u32, _vp]),
+}
+
+# depth of field (include/crender_dof.h), bound from a table of its own (DeferredPasses.depth_of_field):
+# the outline's frame, then the colour plane, which is only read, the
+# focus, the band, the aperture and the largest radius, the result plane
+DOF_MAX_RADIUS = 12
+UNIT_SIGNATURES["dof"] = {
+    "crender_dof_blur": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, C.c_float, C.c_float, C.c_float, _i32, _vp,
+                                _i32, _i32, _i32, _i32, _u32, _vp]),
+}
+
+# normal mapping (include/crender_nmap.h), bound from a table of its own (DeferredPasses.bind_normal_map,
+# normal_map_pass): a tangent-space map from a height map, and the
+# pass that perturbs the normal plane: the overlay's frame, then the uv, the map and its size, the strength, the plane
+NMAP_WRAP = 1
+NMAP_PERSPECTIVE, NMAP_BILINEAR, NMAP_CHAIN = 1, 2, 4
+UNIT_SIGNATURES["nmap"] = {
+    "crender_nmap_from_height": (_i32, [_vp, _i32, _i32, C.c_float, _u32, _vp, _vp]),
+    "crender_nmap_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _i32, C.c_float, _vp, _i32, _i32, _i32, _i32,
+                                  _u32, _vp]),
+}
+
+# environment mapping (include/crender_env.h), bound from a table of its own (DeferredPasses.bind_environment,
+# environment_pass): the overlay's frame, then the normal plane,
+# the two levels' faces and sides and the second one's weight, the orientation, reflectivity, f0, the tint, the
+# background's gain
+ENV_REFLECT, ENV_BACKGROUND = 1, 2
+ENV_MAX_SIDE = 8192
+UNIT_SIGNATURES["env"] = {
+    "crender_env_shade": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _vp, _i32, C.c_float, _f32p, C.c_float, C.c_float,
+                                 _f32p, C.c_float, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
 }
 
 # the numpy filler's entry points (include/crender_py.h), bound from a table of their own

@@ -1,4 +1,4 @@
-"""Bloom and tone mapping (``crender_bloom``, include/crender_wire.h "Bloom"): a glow around what is brighter than a
+"""Bloom and tone mapping (``crender_bloom``, include/crender_bloom.h "Bloom"): a glow around what is brighter than a
 threshold — the bright values blurred along the rows, then along the columns, and added to the source — and a curve that
 brings the range back into 0 .. 255.  A post-process over any float32 image [H, W, 3] on the device.
 

@@ -1,7 +1,8 @@
 // winner_pass.h — what the deferred passes over the winner plane share (texture.hip, texmip.hip and texaniso.hip, the
-// last two also through mip_sample.h; shadow.hip, phong.hip, ao.hip, wireframe.hip): the winner's triangle projected and
-// the host's frame checks, then what the per-pixel passes share, then what the neighbourhood passes share.  Each
-// translation unit gets its own copy (anonymous namespace); include after common.h and `using namespace crender_detail;`.
+// last two also through mip_sample.h; shadow.hip, phong.hip, ao.hip, wireframe.hip, bloom.hip, peel.hip, dof.hip,
+// normal_map.hip, envmap.hip): the winner's triangle projected and the host's frame checks, then what the per-pixel
+// passes share, then what the neighbourhood passes share.  Each translation unit gets its own copy (anonymous
+// namespace); include after common.h and `using namespace crender_detail;`.
 #pragma once
 
 namespace {

@@ -1,5 +1,5 @@
 """What a caller of ``AdvancedPixelBufferFiller.depth_of_field`` needs beside the pass: the view depth a value of the z
-plane stands for, by the statement the kernel itself uses (include/crender_wire.h, "Depth of field"), so that the focus
+plane stands for, by the statement the kernel itself uses (include/crender_dof.h, "Depth of field"), so that the focus
 can be put on what a pixel shows::
 
     z = filler.get_z_tensor()

@@ -1,5 +1,5 @@
 """Cube maps for ``AdvancedPixelBufferFiller.bind_environment``: host numpy only, evaluated in float64, with no parity
-claim (what the device does with a cube is stated in include/crender_wire.h, "Environment mapping").
+claim (what the device does with a cube is stated in include/crender_env.h, "Environment mapping").
 
 A cube is uint8 [6, S, S, 3], the faces in the order +x, -x, +y, -y, +z, -z of the camera's frame under the identity
 orientation: x grows with the column, y with the ROW (so +y is down and the sky is around -y), z goes into the screen.

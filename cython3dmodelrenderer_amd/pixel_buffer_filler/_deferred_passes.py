@@ -243,7 +243,7 @@ class DeferredPasses:
         """Keep a tangent-space normal map resident for ``normal_map_pass``: `normal_map` uint8 [mh, mw, 3]
         (byte = 128 + 127 * component of a unit vector along u, along v and out of the surface; row 0 is the top of the
         image), or `height` uint8 [mh, mw], from which the map is made on the device (``crender_nmap_from_height``,
-        include/crender_wire.h, on torch's current stream): central differences times ``scale / 255``, the neighbours
+        include/crender_nmap.h, on torch's current stream): central differences times ``scale / 255``, the neighbours
         clamped to the edge or, with `wrap`, wrapped around.  Exactly one of the two, numpy arrays or device tensors; both
         None drops the binding.  `uv_by_triangles` float32 [T, 3, 2] (``bind_texture``'s) are the map's own coordinates;
         None means those of ``bind_texture`` at the time the pass runs.  With `mipmaps` the map's mip chain is built as
@@ -288,7 +288,7 @@ class DeferredPasses:
         return None if self._normal_map is None else self._normal_map[1]
 
     def normal_map_pass(self, strength=1.0, perspective=True, filter="bilinear"):
-        """Normal (bump) mapping of the LAST frame's NORMAL plane (``crender_nmap_shade``, include/crender_wire.h): every
+        """Normal (bump) mapping of the LAST frame's NORMAL plane (``crender_nmap_shade``, include/crender_nmap.h): every
         covered pixel samples the bound map at its interpolated (u, v) — the nearest texel, four of them, or
         (``"trilinear"``, which needs ``bind_normal_map(..., mipmaps=True)``) two levels of the map's mip chain picked
         from the screen-space derivatives of (u, v) —, decodes the tangent-space vector, scales its two tangent
@@ -378,7 +378,7 @@ class DeferredPasses:
         return chain[0][off:off + 18 * side * side].view(6, side, side, 3)
 
     def environment_pass(self, reflectivity=1.0, f0=0.04, tint=(1.0, 1.0, 1.0), level=0.0, orientation=None, background=None):
-        """Environment mapping of the LAST frame's colour plane (``crender_env_shade``, include/crender_wire.h) from the
+        """Environment mapping of the LAST frame's colour plane (``crender_env_shade``, include/crender_env.h) from the
         cube bound with ``bind_environment``.  Every covered pixel mirrors the direction from the eye to the surface
         point it shows (the perspective-correct blend of the winner's corners, as ``phong_pass`` takes it) at its stored
         normal, looks the mirrored direction up in the cube (the face of its largest component, four texels of it,
@@ -737,7 +737,7 @@ class DeferredPasses:
         return out
 
     def depth_of_field(self, focus, aperture=4.0, band=0.0, max_radius=8):
-        """Depth of field of the LAST frame (``crender_dof_blur``, include/crender_wire.h): a NEW device tensor [h, w, 3]
+        """Depth of field of the LAST frame (``crender_dof_blur``, include/crender_dof.h): a NEW device tensor [h, w, 3]
         float32, as ``edge_aa`` returns one, in which every pixel is the weighted mean of the pixels around it, each
         weighted by how far its own circle of confusion reaches.  A covered pixel at view depth zv (rebuilt from the z
         plane; ``depth_of_field.view_depth`` gives the same number, so ``focus=view_depth(filler._P, z[y, x])`` focuses
@@ -789,7 +789,7 @@ class DeferredPasses:
         return arrays + (T, pos_of, self._peel_scratch)
 
     def peel_layers(self, n):
-        """The first `n` (1 to 16) depth layers of the LAST frame (``crender_peel_next``, include/crender_wire.h):
+        """The first `n` (1 to 16) depth layers of the LAST frame (``crender_peel_next``, include/crender_peel.h):
         ``(winner int32 [n, h, w], z float32 [n, h, w])``, device tensors.  Layer 0 is a copy of the frame's own winner and
         z planes; layer k + 1 names, per pixel, the fragment of the frame with the least depth key strictly above layer
         k's — the next surface behind it, coplanar duplicates one by one, the highest index first — with that fragment's
@@ -818,7 +818,7 @@ class DeferredPasses:
 
     def transparency_pass(self, alpha, layers=4, light_direction=None, background=(0, 0, 0), front="plane"):
         """The LAST frame with its triangles transparent (``crender_peel_next`` and ``crender_peel_blend``,
-        include/crender_wire.h): a NEW device tensor [h, w, 3] float32, as ``edge_aa`` returns one.  The first `layers` (1 to
+        include/crender_peel.h): a NEW device tensor [h, w, 3] float32, as ``edge_aa`` returns one.  The first `layers` (1 to
         16) depth layers of every pixel are peeled as ``peel_layers`` peels them and blended front to back: a layer adds
         ``transmittance * alpha * colour`` and leaves ``transmittance * (1 - alpha)``, and what is left after the last one
         shows `background` (three finite numbers).  `alpha` is a number, or an array [T] in the caller's triangle order,

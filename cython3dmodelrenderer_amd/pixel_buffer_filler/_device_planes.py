@@ -83,7 +83,7 @@ class DevicePlanes:
                 out.data_ptr(), flags, self._stream()), "crender_ssaa_resolve")
 
     def _bloom_planes(self, src, scratch, out, call, y0, y1):
-        """crender_bloom (include/crender_wire.h, "Bloom") of rows y0 .. y1 of `src` into `out`."""
+        """crender_bloom (include/crender_bloom.h, "Bloom") of rows y0 .. y1 of `src` into `out`."""
         from .. import bloom
         with torch.cuda.device(self.device):
             bloom.launch(self._lib, src, scratch, out, call, y0, y1, self._stream())
@@ -204,7 +204,7 @@ class DevicePlanes:
 
     def bloom(self, threshold=255.0, radius=8, weights=None, intensity=1.0, exposure=1.0, tonemap=None, white=float("inf"),
               gamma=1, clamp=None, dtype="float32", flip_rows=False, source=None):
-        """Bloom and tone mapping (``crender_bloom``, include/crender_wire.h "Bloom"): a NEW device tensor [H, W, 3] that
+        """Bloom and tone mapping (``crender_bloom``, include/crender_bloom.h "Bloom"): a NEW device tensor [H, W, 3] that
         holds the image with a glow around its bright pixels.  A pixel whose largest channel m exceeds `threshold` is
         bright by (m - threshold) / m of its colour; the bright values are blurred with `weights` (a table of radius + 1
         numbers by distance; None: ``bloom.gaussian(radius)``; an explicit table fixes radius = len - 1, at most 32) along

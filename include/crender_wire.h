@@ -469,431 +469,6 @@ CRENDER_API int crender_wire_runs_emit(const int32_t *d_winner, const float *d_z
                                        int32_t *d_runs, float *d_ends, int H, int W, int y0, int y1, unsigned flags,
                                        void *stream);
 
-/*
- * ---- Normal mapping -------------------------------------------------------------------------------------------------
- * Surface detail below the size of a triangle: a deferred pass that PERTURBS THE NORMAL PLANE of the frame a raster
- * launch left, once and right after the draw.  Everything that lights a pixel afterwards reads that plane —
- * crender_guro_illumination, the fused light of crender_tex_shade / crender_mip_shade / crender_aniso_shade and of
- * crender_ssaa_resolve, crender_phong_shade, crender_ao_shade — and so shows the bumps without a change of its own.
- * The two entries live in this unit beside the other passes over the winner plane (crender_wire_edge_aa); "tex.h" and
- * "mip.h" below are include/crender_tex.h and include/crender_mip.h, whose statements are used word for word.
- *
- * A normal map is uint8 [mh][mw][3] in TANGENT SPACE: byte_i = 128 + 127 v_i of a unit vector v = (along u, along v, out
- * of the surface); (128, 128, 255) is "no bump".  Row 0 is the TOP of the image, v = 1, as for a texture.
- *
- * crender_nmap_from_height makes one from a height map, uint8 [mh][mw].  For the texel at (row r, column c), every line
- * ONE float32 operation per operator, rounded once, with IEEE division and square root, no contraction:
- *     k  = scale / 255.0f                                   (once, on the host, in float32)
- *     gx = (float)(h[r][c+1] - h[r][c-1]) * k               (the integer difference, then one conversion)
- *     gy = (float)(h[r-1][c] - h[r+1][c]) * k               (v points up: the row ABOVE minus the row below)
- *     ln = sqrtf((gx*gx + gy*gy) + 1.0f)
- *     vx = -gx / ln,   vy = -gy / ln,   vz = 1.0f / ln
- *     b_i = rintf(v_i * 127.0f + 128.0f)                    (ties to even)
- *     byte_i = !(b_i > 0) ? 0 : (b_i > 255 ? 255 : b_i)     (the clip to 0 .. 255; a NaN, which only an overflowing
- *                                                            scale makes, gives 0)
- * The four neighbours are clamped to the edge (c-1 -> max(c-1, 0), ...), so a 1 x 1 map gives the flat texel; with
- * CRENDER_NMAP_WRAP they wrap around (c-1 -> mw-1 at c = 0, ...).  A flat neighbourhood gives (128, 128, 255).
- */
-#define CRENDER_NMAP_WRAP 1u                 /* flag of crender_nmap_from_height: a tiling height map */
-
-/* Fill d_map uint8 [mh][mw][3] from d_height uint8 [mh][mw] (another buffer).
- * CRENDER_EINVAL, before anything is dereferenced or launched, checked in THIS order: a NULL d_height or d_map; mh or mw
- * outside 1 .. 65535; a scale that is not finite; any flag bit but CRENDER_NMAP_WRAP.  One launch; no synchronisation. */
-CRENDER_API int crender_nmap_from_height(const uint8_t *d_height, int mh, int mw, float scale, unsigned flags,
-                                         uint8_t *d_map, void *stream);
-
-/*
- * Result contract of crender_nmap_shade.  For every pixel (x, y) with y0 <= y < y1 and t = d_winner[y][x]:
- *
- *   Arithmetic   every step below is ONE float32 operation, rounded once, with IEEE division and square root (no
- *                contraction into fused multiply-adds, no reciprocal, denormals kept).  A dot product a.b is
- *                (a0*b0 + a1*b1) + a2*b2 and a length |a| is sqrtf(a.a).
- *   Background   t < 0, t >= T, or d_pos_of[t] >= T: the pixel is not written.  Nothing is ever read out of bounds,
- *                whatever the winner plane holds.
- *   Corners      A, B, C: the three UNPROJECTED vertices of triangle t (d_tri[t], or d_tri[d_pos_of[t]] with a d_pos_of);
- *                (u_k, v_k), k = 0, 1, 2: d_uv[t], indexed by t itself, the caller's order, as in tex.h.
- *   Position     (u, v) at the integer pixel (x, y): Barycentrics, then Affine or (CRENDER_NMAP_PERSPECTIVE) Perspective,
- *                exactly as in tex.h.
- *   Sample       s, float32 [3], of the map at (u, v):
- *                  no filter flag           the texel rule of tex.h (nearest);
- *                  CRENDER_NMAP_BILINEAR    the Bilinear statement of tex.h;
- *                  CRENDER_NMAP_CHAIN       d_map is the mip chain of the mh x mw map in mip.h's layout (crender_mip_build:
- *                                           L = 1 + floor(log2(max(mh, mw))) levels, h_k = max(1, mh >> k), packed
- *                                           tightly), and the sample is mip.h's trilinear one: Neighbours, Footprint and
- *                                           Level word for word (with (th, tw) = (mh, mw)), then a = Bilinear on level
- *                                           l0 and, where f != 0, b = Bilinear on level l0 + 1 and s = a*(1 - f) + b*f,
- *                                           left to right.  The levels are box averages of the BYTES, not re-normalised.
- *   Decode       m_i = (s_i - 128.0f) / 127.0f;  m_i = m_i < -1 ? -1 : m_i      (byte 0 decodes to -1, as byte 1 does)
- *                mx = m_0 * strength,   my = m_1 * strength,   mz = m_2
- *   Tangents     of the TRIANGLE (the frame is per triangle, not smoothed over the mesh):
- *                  e1 = B - A,   e2 = C - A
- *                  du1 = u1 - u0,  dv1 = v1 - v0,  du2 = u2 - u0,  dv2 = v2 - v0
- *                  det = du1*dv2 - du2*dv1,     sg = det < 0 ? -1 : 1
- *                  Tt_j = (e1_j*dv2 - e2_j*dv1) * sg,     Bt_j = (e2_j*du1 - e1_j*du2) * sg       (j = 0, 1, 2)
- *                Tt points along increasing u on the surface, Bt along increasing v (both up to a positive factor).
- *   Frame        around the pixel's STORED normal n = d_normal[y][x]:
- *                  nl = |n|,   Nu = n / nl
- *                  d  = Nu.Tt,   Tp = Tt - Nu*d,   tl = |Tp|,   Tu = Tp / tl
- *                  Bp = (Nu1*Tu2 - Nu2*Tu1,  Nu2*Tu0 - Nu0*Tu2,  Nu0*Tu1 - Nu1*Tu0)
- *                  if (Bp.Bt < 0) Bp = -Bp
- *                The stored normals may point either way relative to the winding: the handedness comes from the uv.
- *   Result       out_j = (Tu_j*mx + Bp_j*my) + Nu_j*mz.  Not normalised: guro_factor divides by the length.  out.Nu = mz
- *                up to rounding, so a bump never turns a normal past 90 degrees.
- *   Write        d_normal[y][x] = out iff
- *                  (det > 0 || det < 0) && nl > 0 && tl > 0 && (mx < 0 || mx > 0 || my < 0 || my > 0)
- *                Every NaN makes the condition false (the last clause is "mx != 0 || my != 0" for numbers).  A flat
- *                texel, strength = 0, a triangle whose uv are degenerate, a zero, NaN or infinite normal, a tangent
- *                parallel to the normal and a sample that is not a number therefore keep the pixel's bits, and with a
- *                finite strength no NaN is ever written.
- *   Other planes d_normal is read and written at (x, y) alone.  z, colours and the winner plane are not among the
- *                arguments; the winner plane, the triangles, the uv and the map are only read.
- *
- * Not covered: per-vertex (smoothed) tangents — a coarse mesh shows facets in the bumps; anisotropic filtering of the
- * map; re-normalised mip levels or variance-to-roughness (Toksvig); parallax or displacement; object-space maps.
- */
-enum {
-    CRENDER_NMAP_PERSPECTIVE = 1u,   /* perspective-correct uv (tex.h); default: affine                          */
-    CRENDER_NMAP_BILINEAR = 2u,      /* four texels (tex.h); default: the nearest one                            */
-    CRENDER_NMAP_CHAIN = 4u          /* d_map is a mip chain, the filter is trilinear; not with CRENDER_NMAP_BILINEAR */
-};
-
-/* Perturb rows y0 <= y < y1 of the normal plane d_normal float32 [H][W][3].
- *   d_winner, d_tri, T, d_pos_of, P16   as crender_wire_overlay takes them
- *   d_uv       float32 [T][3][2], (u, v) per corner in the CALLER's triangle order (may be NULL if T == 0)
- *   d_map      uint8 [mh][mw][3], or with CRENDER_NMAP_CHAIN the chain of crender_mip_build(map, mh, mw)
- *   mh, mw     the map's size (level 0's), 1 .. 65535
- *   strength   finite; scales the two tangent components of the decoded vector (0: nothing is written)
- * CRENDER_EINVAL, before anything is dereferenced or launched, checked in THIS order: a NULL d_winner, P16, d_map or
- * d_normal; T < 0; T > 0 without d_tri or without d_uv; H or W < 1; rows outside the frame (y0 < 0, y1 > H, y0 >= y1);
- * mh or mw outside 1 .. 65535; a strength that is not finite; an unknown flag bit; CRENDER_NMAP_CHAIN together with
- * CRENDER_NMAP_BILINEAR.  T == 0 returns CRENDER_OK without a launch.  One launch (the chain's level offsets travel in its
- * arguments); no synchronisation. */
-CRENDER_API int crender_nmap_shade(const int32_t *d_winner, const float *d_tri, int64_t T, const uint32_t *d_pos_of,
-                                   const float *P16, const float *d_uv, const uint8_t *d_map, int mh, int mw,
-                                   float strength, float *d_normal, int H, int W, int y0, int y1, unsigned flags,
-                                   void *stream);
-
-/*
- * ---- Environment mapping --------------------------------------------------------------------------------------------
- * What is around the model: a deferred pass that looks a DIRECTION up in a cube map, for the covered pixels the
- * direction in which the surface mirrors the eye (reflections), for the others the pixel's own view ray (a skybox).
- * Everything it needs is resident after a frame: the winner plane and the triangles give the surface point, exactly as
- * crender_phong_shade rebuilds it, the normal plane — perturbed by crender_nmap_shade or not — the normal, the
- * projection a background pixel's ray.  The entry lives in this unit beside the other passes over the winner plane;
- * "tex.h", "phong.h" and "ao.h" below are include/crender_tex.h, crender_phong.h and crender_ao.h, whose statements are
- * used word for word.
- *
- * Result contract of crender_env_shade.  For every pixel (x, y) with 0 <= x < W, y0 <= y < y1 and t = d_winner[y][x]:
- *
- *   Arithmetic   every step below is ONE float32 operation, rounded once, with IEEE division and square root (no
- *                contraction into fused multiply-adds, no reciprocal, denormals kept).  Constants named "host" are
- *                computed in double and rounded once to float.
- *   Frames       the camera's frame is the rasterizer's: x grows with the column, y with the row, z goes into the screen,
- *                the eye is at the origin.  The environment's frame is the camera's turned by M (below).
- *   Environment  a cube map uint8 [6][S][S][3], 1 <= S <= CRENDER_ENV_MAX_SIDE, the faces in the order +x, -x, +y, -y,
- *                +z, -z of the environment's frame.  The +z face is what the camera itself sees (under the identity);
- *                the others are that frame turned by quarter turns.  Row 0 of a face is where tc (below) is smallest.
- *   Face         of a direction d: a = (|d0|, |d1|, |d2|); the major axis is x if a0 >= a1 && a0 >= a2, else y if
- *                a1 >= a2, else z (so a NaN falls through to z); ma is that magnitude, face = 2 axis + (d_axis < 0), and
- *                    face   +x    -x    +y    -y    +z    -z
- *                    sc    -d2    d2    d0    d0    d0   -d0
- *                    tc     d1    d1   -d2    d2    d1    d1
- *                d is USABLE when ma > 0 && ma < INFINITY.  A pixel whose direction is not usable is not written.
- *   Sample       e = the Bilinear statement of tex.h, unchanged, on that face taken as an S x S texture, at
- *                    tu = (sc / ma + 1.0f) * 0.5f,     tv = (1.0f - tc / ma) * 0.5f
- *                (the row grows with tc; indices are clamped to the face: nothing is filtered across faces).
- *   Two levels   with d_faces1 (side S1) and 0 < level_frac = f < 1: e_c = e0_c * (1.0f - f) + e1_c * f, both levels
- *                sampled at the same direction.  Which two levels of a chain they are is the host's matter.
- *   Orientation  M9 is a row-major 3 x 3: d_i = (M[i][0]*r0 + M[i][1]*r1) + M[i][2]*r2.
- *
- *   CRENDER_ENV_REFLECT, for a COVERED pixel (0 <= t < T and, with a d_pos_of, d_pos_of[t] < T), unless reflectivity == 0
- *   (then no covered pixel is written):
- *     Point      p: project the winner, the rasterizer's barycentrics b_k, then phong.h's "Surface point":
- *                    q_k = b_k / z_k,   s = (q1 + q2) + q3,   p_c = ((A_c*q1 + B_c*q2) + C_c*q3) / s
- *     Mirror     n = d_normal[y][x];  nn = (n0*n0 + n1*n1) + n2*n2,  ni = (n0*p0 + n1*p1) + n2*p2,
- *                    k = (2.0f * ni) / nn,      r_c = p_c - k * n_c
- *                (not normalised: the face and the two quotients do not depend on |r|; and the same for n and -n).
- *                d = M r, e the sample.
- *     Weight     pp = (p0*p0 + p1*p1) + p2*p2,   c = fabsf(ni) / (sqrtf(nn) * sqrtf(pp)),   m = 1.0f - c,
- *                    m = m < 0 ? 0 : m,   m = m > 1 ? 1 : m;   a NaN m makes the pixel NOT written
- *                    m5 = ((m*m) * (m*m)) * m,     w = reflectivity * (f0 + one_minus_f0 * m5)
- *                with host one_minus_f0 = (float)(1.0 - (double)f0): Schlick's weight, f0 facing the eye, 1 at a
- *                grazing angle.
- *     Result     colour_c = colour_c * (1.0f - w) + (e_c * tint_c) * w
- *
- *   CRENDER_ENV_BACKGROUND, for every pixel of the rows that is NOT covered (winners that name no triangle included):
- *     Ray        with ao.h's host constants xs, ys, kx, ky: r = (((float)x - xs) * kx, ((float)y - ys) * ky, 1.0f)
- *                d = M r, e the sample.
- *     Result     colour_c = e_c * background_gain
- *
- *   Other planes z, normals and the winner plane are only read.  Nothing is ever read out of bounds, whatever the
- *                planes hold.
- *
- * Not covered: filtering across the seams of the faces; prefiltered (cosine or GGX) chains — two levels are a blur, not
- * a roughness model —; per-pixel reflectivity; refraction; diffuse irradiance; reflections that see the model itself.
- */
-#define CRENDER_ENV_REFLECT 1u               /* covered pixels mirror the environment                                   */
-#define CRENDER_ENV_BACKGROUND 2u            /* the other pixels of the rows show it                                    */
-#define CRENDER_ENV_MAX_SIDE 8192
-
-/* Shade rows y0 <= y < y1 of the colour plane d_color float32 [H][W][3].
- *   d_winner, d_tri, T, d_pos_of, P16   as crender_wire_overlay takes them; d_tri is read with REFLECT only
- *   d_normal   float32 [H][W][3], the normal plane of the frame; may be NULL without REFLECT
- *   d_faces0   uint8 [6][S0][S0][3]
- *   d_faces1   NULL, or uint8 [6][S1][S1][3]: the second level
- *   level_frac the weight of the second level, 0 < level_frac < 1; 0 without one
- *   M9         HOST float[9], finite: the orientation
- *   reflectivity, f0   0 .. 1
- *   tint3      HOST float[3], finite: a factor per channel of the reflected sample
- *   background_gain    finite, >= 0
- *   flags      CRENDER_ENV_REFLECT, CRENDER_ENV_BACKGROUND or both
- * CRENDER_EINVAL ("crender_env_shade: ..."), before anything is dereferenced or launched, checked in THIS order: a NULL
- * d_winner, P16, d_faces0, M9, tint3 or d_color, or a NULL d_normal with REFLECT; T < 0; T > 0 without d_tri; H or W < 1;
- * rows outside the frame (y0 < 0, y1 > H, y0 >= y1); S0 outside 1 .. 8192 or S1 outside 0 .. 8192; d_faces1, S1 and
- * level_frac that are neither all given (S1 >= 1, 0 < level_frac < 1) nor all absent (NULL, 0, 0); an M9, tint3 or
- * background_gain that is not finite, a reflectivity or f0 outside [0, 1], a negative background_gain; with BACKGROUND a
- * P16 whose entry 0 or 5 is zero or not finite; an unknown flag bit, or neither flag.  With REFLECT alone T == 0 and
- * reflectivity == 0 return CRENDER_OK without a launch; with BACKGROUND T == 0 paints every pixel of the rows.  One
- * launch (M9, tint3 and the coefficients travel in its arguments); no synchronisation. */
-CRENDER_API int crender_env_shade(const int32_t *d_winner, const float *d_tri, int64_t T, const uint32_t *d_pos_of,
-                                  const float *P16, const float *d_normal, const uint8_t *d_faces0, int S0,
-                                  const uint8_t *d_faces1, int S1, float level_frac, const float *M9, float reflectivity,
-                                  float f0, const float *tint3, float background_gain, float *d_color, int H, int W,
-                                  int y0, int y1, unsigned flags, void *stream);
-
-/*
- * ---- Depth of field -------------------------------------------------------------------------------------------------
- * The frame through a lens instead of a pinhole: a post-process that blurs every pixel by its CIRCLE OF CONFUSION, which
- * the z plane gives exactly.  A gather: a pixel sums the colours of the pixels around it, each weighted by how much of its
- * own disc reaches the pixel, so that what is in front spreads over what lies behind it and a blurred background does
- * not bleed over something sharper in front of it.  The colour plane is only read and the result goes to a plane of its
- * own (a pixel reads its neighbours' colours), as crender_wire_edge_aa's.  The entry lives in this unit beside the other
- * passes over the winner plane; "ao.h" below is include/crender_ao.h.
- *
- * Result contract of crender_dof_blur.  For every pixel p = (x, y) with 0 <= x < W and y0 <= y < y1:
- *
- *   Arithmetic   every step below is ONE float32 operation, rounded once, with IEEE division and square root (no
- *                contraction into fused multiply-adds, no reciprocal, denormals kept).  Rf = (float)max_radius,
- *                pi = (float)3.14159265358979323846 = 0x40490FDB.
- *   Signed circle of confusion s of a pixel q, in pixels; negative in front of the focal plane, positive behind it:
- *     covered    (t = d_winner[q] with 0 <= t < T; d_pos_of is not looked at):  with P10 = P16[10], P14 = P16[14]
- *                    zv = P14 / (z - P10)                         (the view depth, as ao.h rebuilds it)
- *                    d  = zv - focus
- *                    d  = d > band ? d - band : (d < -band ? d + band : 0.0f)     (a NaN d gives 0)
- *                    s  = aperture * (d / zv)
- *     uncovered  s = aperture                                     (the background is at infinity)
- *     clamp      s = s > Rf ? Rf : (s < -Rf ? -Rf : s)            (a NaN stays a NaN)
- *     off the frame or outside the rows:  s = NaN; such a pixel contributes nowhere, and none of its planes is read.
- *                c  = fabsf(s)                                    the blur radius
- *                ia = 1.0f / (1.0f + pi * (s * s))                the reciprocal of the footprint: one division per
- *                                                                 pixel, none per tap
- *   Taps         Sw = S_0 = S_1 = S_2 = +0.  For dy = -max_radius .. max_radius (outer) and dx = -max_radius ..
- *                max_radius (inner), both ascending, q = p + (dx, dy) and dist = sqrtf((float)(dx*dx + dy*dy)):
- *                    q LIES BEHIND p if s_q > s_p                 (s grows with the view depth)
- *                    if q lies behind p and c_p < c_q:  r = c_p, a = ia_p
- *                    otherwise:                         r = c_q, a = ia_q
- *                    k = (r + 1.0f) - dist;   the tap is TAKEN iff k > 0    (every NaN fails)
- *                    w = (k < 1.0f ? k : 1.0f) * a
- *                    Sw = Sw + w;   S_j = S_j + w * d_color[q]_j             (multiply, then add; j = 0, 1, 2)
- *                A tap that is not taken changes nothing, whatever d_color[q] holds.
- *   Result       if no tap other than (0, 0) was taken, or Sw > 0 is false:  d_out[p] = d_color[p], the bits copied
- *                (a -0 and every NaN colour are kept).  Otherwise d_out[p]_j = S_j / Sw.  Where a NaN or an infinite
- *                colour was taken, a sum or the quotient may be a NaN: WHICH NaN (sign, payload) is not stated.
- *   Other planes z, winners and colours are only read; d_tri and d_pos_of are never read.  Rows outside y0 <= y < y1 of
- *                d_out are not touched.  Nothing is ever read out of bounds, whatever the planes hold.
- *
- * Consequences.  aperture == 0 makes every c zero or NaN and the rows are copied bit for bit.  A pixel with c == 0 out
- * of reach of every blurred one (no q with r + 1 > dist) keeps its bits.  On a frame of one colour a blurred pixel
- * differs from that colour by the rounding of the sums and the quotient only.  A tap beyond ceil(the largest c around)
- * is never taken (r + 1 <= ceil + 1 <= dist, both roundings monotone): an implementation may stop there.
- *
- * Not covered: radii above CRENDER_DOF_MAX_RADIUS (the staged tile and its halo, five words a pixel, fill the 64 KB of
- * LDS at 12); what a blurred foreground hides (its colours were never rendered: the gather renormalises over what is
- * there); bokeh shapes (the disc is round and flat, with a one-pixel ramp).
- */
-#define CRENDER_DOF_MAX_RADIUS 12
-
-/* Blur rows y0 <= y < y1 of d_color float32 [H][W][3] into d_out float32 [H][W][3].
- *   d_winner   int32 [H][W]; with T it says which pixels are covered
- *   d_z        float32 [H][W], the z plane of the frame
- *   d_tri, d_pos_of   accepted (the passes' common frame) and never read; may be NULL
- *   T          the triangles of the frame: a winner outside [0, T) is background
- *   P16        HOST float[16], crender_projection_matrix's
- *   d_color    only read
- *   focus      the view depth in focus (cython3dmodelrenderer_amd.depth_of_field.view_depth of a z); finite, > 0
- *   band       the half width of the range of view depths around focus that stays sharp; finite, >= 0
- *   aperture   the blur radius in pixels at infinity; finite, >= 0
- *   max_radius 1 .. CRENDER_DOF_MAX_RADIUS: the clamp of every radius, and the reach of the taps
- *   d_out      the result; another plane than d_color
- *   flags      0
- * CRENDER_EINVAL ("crender_dof_blur: ..."), before anything is dereferenced or launched, checked in THIS order: a NULL
- * d_winner, d_z, P16, d_color or d_out; T < 0; H or W < 1; rows outside the frame (y0 < 0, y1 > H, y0 >= y1); any flag
- * bit; d_out == d_color; a P16 that is not of crender_projection_matrix's shape (ao.h's two checks, in its words); a focus
- * that is not finite and > 0; a band, then an aperture, that is not finite and >= 0; max_radius outside 1 .. 12.
- * T == 0 makes every pixel background (s = aperture).  One launch with 5 (32 + 2 max_radius)^2 + 173 words of LDS
- * (62 720 + 692 bytes at 12: below 64 KB, no launch attribute); no synchronisation. */
-CRENDER_API int crender_dof_blur(const int32_t *d_winner, const float *d_z, const float *d_tri, int64_t T,
-                                 const uint32_t *d_pos_of, const float *P16, const float *d_color, float focus, float band,
-                                 float aperture, int max_radius, float *d_out, int H, int W, int y0, int y1, unsigned flags,
-                                 void *stream);
-
-/* ---- Transparency: depth peeling by depth key, blended front to back -------------------------------------------------
- *
- * A frame keeps one fragment per pixel, the one with the least 64-bit key fragment_key(z, i) (csrc/raster_math.h: the
- * order-preserving map of z in the high word, 0xFFFFFFFE - i in the low one), and leaves the key's two halves behind:
- * the z plane and the winner plane.  crender_peel_next finds, per pixel, the fragment with the least key STRICTLY ABOVE
- * a given layer's: the next layer behind it.  No epsilon; coplanar duplicates peel one by one, the highest index first.
- * crender_peel_blend puts a layer under what is in front of it.  Every operation below is one IEEE binary32 operation,
- * nothing contracted, in the order written.
- *
- * Fragments.   THE FRAGMENTS OF THE FRAME AT pixel p = (x, y) are the pairs (i, z), i a triangle index in the caller's
- *              order (the winner plane's), for which: triangle i lies in d_tri (under d_pos_of: d_pos_of[i] < T);
- *              backface(n0z, n1z, n2z) of its three normals' z is false (n0z + n1z + n2z >= 0 is the back face); its
- *              pixel_box on the W x H frame is not empty and holds p; with the corners projected as crender_project does,
- *              the three barycentrics b1, b2, b3 at (x, y) (three correctly rounded divisions) are none of them < 0 (a
- *              NaN passes); z = z0*b1 + z1*b2 + z2*b3, left to right, is not NaN; and fragment_key(z, i) is below the
- *              cleared key make_key(zord(1e6f), 0xFFFFFFFF).
- * Next layer.  The given layer is VALID at p if its winner w satisfies 0 <= w < T (and under d_pos_of: d_pos_of[w] < T)
- *              and its z is not NaN.  Then K = fragment_key(z, w), and the result at p names the fragment of the frame
- *              at p with the least key k > K: its index, and ITS z, the value of the sum above (a -0 stays -0; not the
- *              key's word decoded).  If the layer is not valid at p or no fragment has k > K, the result is winner -1
- *              and z 1e6f: what a cleared frame holds, which is not valid again — an exhausted pixel stays exhausted.
- * Blend.       Per pixel p of the rows, with FIRST and LAST the two flags:
- *                  t = FIRST ? 1.0f : d_trans[p]
- *                  if the layer's winner w is a triangle (as above) and t > 0:
- *                      a = d_alpha[w];  a = a > 0 ? a : 0  (a NaN gives 0);  a = a > 1 ? 1 : a
- *                      c = d_front[p] if FIRST and d_front is given; otherwise the colour shade_fragment gives triangle w
- *                          at p: c_j = col0_j*b1 + col1_j*b2 + col2_j*b3, and with light3 times guro_factor of the
- *                          normal interpolated the same way — the bits a frame stores for this fragment
- *                      g = t * a
- *                      d_out[p]_j = FIRST ? g * c_j : d_out[p]_j + g * c_j          (multiply, then add)
- *                      d_trans[p] = t * (1.0f - a)
- *                  otherwise, if FIRST:  d_out[p] = (0, 0, 0), d_trans[p] = 1
- *                  otherwise nothing is written
- *                  with LAST, after that step, where d_trans[p] > 0:  d_out[p]_j = d_out[p]_j + d_trans[p] * background_j
- * Consequences. alpha == 1 everywhere gives the front layer's colours bit for bit (1 * c, a -0 kept) and the background
- *              elsewhere; alpha == 0 everywhere gives the background everywhere a colour is finite; a pixel whose
- *              transmittance has reached 0 is never written again, so a NaN behind an opaque layer does not spread.
- *
- * Not covered: back faces behind a transparent front (the frame's culling applies to every layer); an early exit when a
- * layer comes out empty; per-vertex or textured alpha; refraction.
- */
-#define CRENDER_PEEL_FIRST 1u                /* the layer is the front one: d_out and d_trans are written, not read   */
-#define CRENDER_PEEL_LAST 2u                 /* the background shows through what transmittance is left               */
-#define CRENDER_PEEL_MAX_LAYERS 16           /* what the Python layer peels at most (the entries know no limit)       */
-
-/* The layer behind a layer, rows y0 <= y < y1.
- *   d_winner, d_z   int32 / float32 [H][W]: the given layer (a frame's planes, or an earlier result)
- *   d_tri      float32 [T][3][3], unprojected, in the order d_pos_of describes;  T at most 2^31 - 1
- *   d_pos_of   NULL, or uint32 [T]: where the caller's triangle i lies in d_tri (a value >= T: nowhere)
- *   P16        HOST float[16], crender_projection_matrix's
- *   d_nrm      float32 [T][3][3], in d_tri's order
- *   d_keys     crender_atomic_scratch_bytes(H, W) bytes of scratch, 8-byte aligned; its rows are overwritten
- *   d_winner_out, d_z_out   the result; other planes than the given layer's.  Rows outside are not touched
- *   flags      0
- * CRENDER_EINVAL ("crender_peel_next: ..."), before anything is dereferenced or launched, checked in THIS order: a NULL
- * d_winner, d_z, P16, d_keys, d_winner_out or d_z_out; T < 0; d_tri or d_nrm NULL with T > 0; H or W < 1; rows outside
- * the frame; any flag bit; T > 2^31 - 1; d_winner_out == d_winner or d_z_out == d_z.
- * Three launches (two with T == 0, which makes every pixel of the rows empty); no synchronisation. */
-CRENDER_API int crender_peel_next(const int32_t *d_winner, const float *d_z, const float *d_tri, int64_t T,
-                                  const uint32_t *d_pos_of, const float *P16, const float *d_nrm, void *d_keys,
-                                  int32_t *d_winner_out, float *d_z_out, int H, int W, int y0, int y1, unsigned flags,
-                                  void *stream);
-
-/* One layer under what is in front of it, rows y0 <= y < y1.
- *   d_winner   int32 [H][W]: the layer's winner plane
- *   d_tri, d_pos_of, P16   as above
- *   d_col, d_nrm   float32 [T][3][3], in d_tri's order
- *   d_alpha    float32 [T] in the CALLER's order: indexed by the winner word
- *   light3     NULL, or HOST float[3]: the fused Guro light (crender_plan_set_light's vector)
- *   d_front    NULL, or float32 [H][W][3]: the front layer's colours as they are (only with CRENDER_PEEL_FIRST)
- *   background3   HOST float[3], finite
- *   d_trans    float32 [H][W]: the transmittance, written by FIRST, read and written otherwise
- *   d_out      float32 [H][W][3]: the sum, likewise
- * CRENDER_EINVAL ("crender_peel_blend: ..."), before anything is dereferenced or launched, checked in THIS order: a NULL
- * d_winner, P16, background3, d_trans or d_out; T < 0; d_tri, d_col, d_nrm or d_alpha NULL with T > 0; H or W < 1; rows
- * outside the frame; a flag bit other than the two; d_front without CRENDER_PEEL_FIRST; d_out == d_front; a background3,
- * then a light3, that is not finite.  One launch, no LDS; no synchronisation. */
-CRENDER_API int crender_peel_blend(const int32_t *d_winner, const float *d_tri, int64_t T, const uint32_t *d_pos_of,
-                                   const float *P16, const float *d_col, const float *d_nrm, const float *d_alpha,
-                                   const float *light3, const float *d_front, const float *background3, float *d_trans,
-                                   float *d_out, int H, int W, int y0, int y1, unsigned flags, void *stream);
-
-/*
- * ---- Bloom ----------------------------------------------------------------------------------------------------------
- * Bloom and tone mapping: a glow around what is brighter than a threshold, and a curve that brings the range back into
- * 0 .. 255.  A post-process over ANY float32 image [H][W][3] — the filler's colour plane, or the tensor of
- * crender_wire_edge_aa, crender_dof_blur, crender_peel_blend or crender_ssaa_resolve — and so the first stage that can
- * follow any of them.  The blur is SEPARABLE: the rows into a scratch plane, then the columns.  The entry lives in this
- * unit beside the other neighbourhood passes.
- *
- * Result contract of crender_bloom.  Every step below is ONE float32 operation, rounded once, with IEEE division and
- * square root (no contraction into fused multiply-adds, no reciprocal, denormals kept); no exponential, power or
- * logarithm is taken on the device: the weights w[0 .. radius] come from the host.  With src = d_src, R = radius:
- *
- *   1 Bright     per pixel (r, g, b) of src:  m = r; if (g > m) m = g; if (b > m) m = b;  k = m - threshold.
- *                If k > 0 is false (a NaN m included) bright = (+0, +0, +0).  Otherwise q = k / m and
- *                bright = (r * q, g * q, b * q): the hue is kept, at one division per bright pixel.
- *   2 Rows       hb[y][x][c] = sum over dx = -R .. R, in that order and starting from +0, of w[|dx|] * bright[y][x + dx][c]:
- *                each tap one multiply, then one add.  A column outside 0 .. W - 1 has the bright value +0, and is
- *                still added.
- *   3 Columns    g[y][x][c] = sum over dy = -R .. R of w[|dy|] * hb[y + dy][x][c], in the same manner.  A row outside
- *                y0 .. y1 - 1 has hb = +0: the strip does not see across its edge.
- *   4 Composite  t_c = intensity * g_c.  If all three t are +-0:  v = src[y][x], bit for bit (a -0 and every NaN kept).
- *                Otherwise v_c = src_c + t_c.  (The test is on t, not on g, so that an intensity of 0 keeps a -0 of
- *                the source within a glow's reach: -0 + +0 would be +0.)
- *   5 Tone       only with CRENDER_BLOOM_REINHARD, CRENDER_BLOOM_GAMMA2 or exposure != 1; otherwise o = v.
- *                    a = v * exposure;  a = a > 0 ? a : 0  (a NaN gives 0);  a = a * inv255
- *                    L = a                                             without CRENDER_BLOOM_REINHARD
- *                    L = (a * (1 + a * inv_white2)) / (1 + a)          with it
- *                    L = sqrtf(L)                                      with CRENDER_BLOOM_GAMMA2
- *                    o = L * 255
- *                inv255 = (float)(1.0 / 255.0) = 0x3B808081.  inv_white2 is the caller's (float)(1.0 / (white * white)),
- *                computed in double and rounded once; 0 is the plain operator a / (1 + a).
- *   6 Clamp      o = o > clamp ? clamp : o                             (a NaN stays a NaN; +inf clamps nothing)
- *   7 Store      d_out[Y][x][c] = o as float32, or with CRENDER_BLOOM_U8 crender_present_u8's cast of o (truncation to
- *                int32, INT_MIN for a NaN or out of range, the low byte);  Y = y, or with CRENDER_BLOOM_FLIP H - 1 - y:
- *                both as crender_ssaa_resolve stores them.
- *   Other planes d_src is only read.  Rows y0 .. y1 - 1 of d_scratch hold hb on return; its other rows, and the rows of
- *                d_out that no Y names, are not touched.  Nothing is read out of bounds, whatever the planes hold.
- *
- * Consequences.  intensity == 0 copies the source (every t is +-0 for a finite g), and so does a threshold above every
- * pixel.  A pixel out of reach of every bright pixel keeps its bits.  The weights are finite, so a neighbourhood whose
- * bright or hb values are all +-0 sums to +0 exactly: an implementation may skip it.  An infinite colour under a zero
- * weight gives a NaN; WHICH NaN (sign, payload) a step computes is not stated, copied NaNs keep every bit.
- *
- * Not covered: radii above CRENDER_BLOOM_MAX_RADIUS and mip pyramids, a soft knee, luminance-weighted keys, operators
- * other than Reinhard's, sRGB's 2.4 curve (gamma is 1 or 2), both directions fused into one launch.
- */
-#define CRENDER_BLOOM_MAX_RADIUS 32
-#define CRENDER_BLOOM_U8 1u                  /* d_out is uint8 [H][W][3]                                                */
-#define CRENDER_BLOOM_FLIP 2u                /* rows are stored bottom up                                               */
-#define CRENDER_BLOOM_REINHARD 4u            /* rule 5's operator                                                       */
-#define CRENDER_BLOOM_GAMMA2 8u              /* rule 5's square root                                                    */
-
-/* Bloom rows y0 <= y < y1 of d_src float32 [H][W][3] into d_out.
- *   d_src      only read
- *   threshold  what the largest channel must exceed to glow; >= 0 (+inf: nothing glows)
- *   weights    HOST float[radius + 1], finite: w[k] weighs the taps at distance k (cython3dmodelrenderer_amd.bloom.gaussian).
- *              Copied into the kernel arguments: the caller's array is free on return.
- *   radius     1 .. CRENDER_BLOOM_MAX_RADIUS
- *   intensity  finite, >= 0
- *   exposure   finite, >= 0
- *   inv_white2 >= 0
- *   clamp      +inf means none; not NaN
- *   d_scratch  float32 [H][W][3], the caller's: hb
- *   d_out      float32 [H][W][3], or uint8 [H][W][3] with CRENDER_BLOOM_U8; aliases neither d_src nor d_scratch
- * CRENDER_EINVAL ("crender_bloom: ..."), before anything on the device is dereferenced or launched, checked in THIS
- * order: H or W < 1; rows outside the frame (y0 < 0, y1 > H, y0 >= y1); a NULL d_src, weights, d_scratch or d_out; a radius
- * outside 1 .. 32; a weight that is not finite; a threshold that is negative or NaN; an intensity, then an exposure, that
- * is not finite and >= 0; an inv_white2 that is negative or NaN; a NaN clamp; a flag bit other than the four; d_out,
- * d_scratch and d_src that are not three planes.  Two launches, each with 3 * 32 * (32 + 2 radius) words of LDS (36 864
- * bytes at 32; the second four words more: below 64 KB, no launch attribute); no synchronisation. */
-CRENDER_API int crender_bloom(const float *d_src, float threshold, const float *weights, int radius,
-                              float intensity, float exposure, float inv_white2, float clamp,
-                              float *d_scratch, void *d_out, int H, int W, int y0, int y1,
-                              unsigned flags, void *stream);
-
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-"""Device time of bloom and tone mapping (csrc/wireframe.hip, k_bloom_rows and k_bloom_finish): crender_bloom — both
+"""Device time of bloom and tone mapping (csrc/bloom.hip, k_bloom_rows and k_bloom_finish): crender_bloom — both
 launches — between two HIP events, mean of 50 calls over the same image, for T-Rex under a Phong light with clamp=inf
 (so that its highlights exceed 255) at 1024^2 and at 4096^2, at radius 4, 12 and 32, in two cases: DARK — a threshold
 above every pixel: nothing is bright, every wavefront of the first launch and every tile of the second skips its walk,

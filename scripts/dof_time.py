@@ -1,4 +1,4 @@
-"""Device time of the depth-of-field pass (csrc/wireframe.hip, k_dof_blur): crender_dof_blur between two HIP events, mean
+"""Device time of the depth-of-field pass (csrc/dof.hip, k_dof_blur): crender_dof_blur between two HIP events, mean
 of 50 passes over the same frame, for T-Rex at 1024^2 and at 4096^2, at max_radius 4, 8 and 12, in two cases, both with
 an aperture of four times max_radius: FOCUSED — the focus on the median view depth of the model with a band that holds
 the whole model, so that every tile that sees the model alone finds nothing blurred around it and copies (`copy_tiles`

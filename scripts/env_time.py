@@ -1,4 +1,4 @@
-"""Device time of the environment pass (k_env_shade, csrc/wireframe.hip): crender_env_shade between two HIP events, mean
+"""Device time of the environment pass (k_env_shade, csrc/envmap.hip): crender_env_shade between two HIP events, mean
 of 50 passes over the same frame, for T-Rex at 1024^2 and at 4096^2 under a random 512^2 cube with its chain, for the six
 instances: reflections, the background, and both, each from one level (level 0) and from two (level 0.5).  (The pass
 rewrites the colours it blends, so the colour plane changes from pass to pass; the work per pass does not depend on the

@@ -1,4 +1,4 @@
-"""Device time of the normal-map pass (csrc/wireframe.hip, k_nmap_shade): crender_nmap_shade between two HIP events,
+"""Device time of the normal-map pass (csrc/normal_map.hip, k_nmap_shade): crender_nmap_shade between two HIP events,
 mean of 50 passes over the same frame, for T-Rex at 1024^2 and 4096^2 under the normal map of a random 709 x 709 height
 map, each filter x uv mode.  Next to every row, measured in the same run on the same frame: the texture pass with the
 same filter (crender_tex_shade, or crender_mip_shade for trilinear) under a random texture of the same size, without a

@@ -1,4 +1,4 @@
-"""Device time of transparency (csrc/wireframe.hip: k_peel_seed, k_peel_cover, k_peel_resolve, k_peel_blend): one
+"""Device time of transparency (csrc/peel.hip: k_peel_seed, k_peel_cover, k_peel_resolve, k_peel_blend): one
 crender_peel_next (the layer behind the frame's own), one crender_peel_blend (a middle layer: shaded from the model, read
 and add), and ``transparency_pass`` at 2, 4 and 8 layers, each between two HIP events, mean of 20 calls over the same
 frame, for T-Rex at 1024^2 and the bunny at 4096^2, alpha 0.5 everywhere.  Every pass only reads the frame, so every

@@ -1,5 +1,5 @@
-"""Host model of bloom and tone mapping: the statements of include/crender_wire.h ("Bloom") in vectorised numpy, one
-float32 operation per step.  The GPU tests compare csrc/wireframe.hip's k_bloom_rows and k_bloom_finish with it bit for
+"""Host model of bloom and tone mapping: the statements of include/crender_bloom.h ("Bloom") in vectorised numpy, one
+float32 operation per step.  The GPU tests compare csrc/bloom.hip's k_bloom_rows and k_bloom_finish with it bit for
 bit, the scratch plane included; tests/test_bloom_cpu.py pins it by identities and against its own float64 evaluation."""
 import numpy as np
 

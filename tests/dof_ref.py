@@ -1,4 +1,4 @@
-"""The host model of the depth-of-field pass (include/crender_wire.h, "Depth of field"): the contract's statements in
+"""The host model of the depth-of-field pass (include/crender_dof.h, "Depth of field"): the contract's statements in
 numpy, one array operation per float32 operation, in the contract's order.  The GPU tests compare the kernel with it bit
 for bit; tests/test_dof_cpu.py pins it by identities and against its own float64 evaluation (``dtype=np.float64``: the
 same statements from the same float32 inputs, every intermediate in double)."""

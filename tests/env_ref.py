@@ -1,7 +1,7 @@
-"""Host model of the environment pass: the statements of include/crender_wire.h, "Environment mapping", in vectorised
+"""Host model of the environment pass: the statements of include/crender_env.h, "Environment mapping", in vectorised
 numpy, one float32 operation per step, over (the winner plane, its unprojected triangles and projection matrix, the normal
 plane, the cube map's levels).  Built on ``tex_ref`` (the Bilinear statement, on one face) and ``phong_ref.surface_point``
-(the covered pixels and their barycentrics).  The GPU tests compare k_env_shade (csrc/wireframe.hip) with it bit for bit;
+(the covered pixels and their barycentrics).  The GPU tests compare k_env_shade (csrc/envmap.hip) with it bit for bit;
 tests/test_env_cpu.py pins it on the oracle's frames by counts, by identities and against itself in float64.
 
 A cube is uint8 [6, S, S, 3]; `levels` is a list of cubes (``chain_levels``) and `level` a position in it, as

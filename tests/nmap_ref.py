@@ -1,7 +1,7 @@
 """Host model of normal mapping: the statements of crender_nmap_from_height and crender_nmap_shade
-(include/crender_wire.h) in vectorised numpy, one float32 operation per step, on top of tests/tex_ref.py (the covered
+(include/crender_nmap.h) in vectorised numpy, one float32 operation per step, on top of tests/tex_ref.py (the covered
 pixels, projection, barycentrics, uv, the nearest and the bilinear sample) and tests/mip_ref.py (the chain, the level of
-a footprint, the trilinear sample).  The GPU tests compare csrc/wireframe.hip's k_nmap_* with it bit for bit;
+a footprint, the trilinear sample).  The GPU tests compare csrc/normal_map.hip's k_nmap_* with it bit for bit;
 tests/test_normal_map_cpu.py pins it by counts on the oracle's frames, by identities and against itself in float64.
 
 ``dtype=np.float64`` evaluates the decode, the tangent frame and the result in double precision from the same float32

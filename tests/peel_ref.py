@@ -1,9 +1,9 @@
-"""Host model of transparency: the statements of include/crender_wire.h's "Transparency" section in vectorised numpy, one
+"""Host model of transparency: the statements of include/crender_peel.h's "Transparency" section in vectorised numpy, one
 float32 operation per step.  ``fragments`` enumerates the fragments of a frame (every triangle's pixel box walked, the
 rasterizer's coverage test and z, the 64-bit depth key), ``layers`` sorts them per pixel, ``peel_next`` is
 crender_peel_next on any given layer, ``shade`` the colours a frame stores for a layer's fragments and ``blend`` one
 crender_peel_blend; ``transparency`` chains them as ``AdvancedPixelBufferFiller.transparency_pass`` does.  The GPU tests
-compare csrc/wireframe.hip with it bit for bit; tests/test_peel_cpu.py pins it on the oracle's frames.
+compare csrc/peel.hip with it bit for bit; tests/test_peel_cpu.py pins it on the oracle's frames.
 
 ``dtype=np.float64`` evaluates the blend's statements in double precision from the same float32 inputs (alpha, the
 layers' float32 colours, the background): the yardstick of the blend's rounding."""

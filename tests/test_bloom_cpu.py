@@ -1,5 +1,5 @@
-"""Bloom and tone mapping without a GPU: the header against the binding and the library, the section's place in the wire
-unit, the entry point's argument checks, the host model the GPU tests compare with (tests/bloom_ref.py) pinned by
+"""Bloom and tone mapping without a GPU: the header against the binding and the library, the unit's place in the build
+tables, the entry point's argument checks, the host model the GPU tests compare with (tests/bloom_ref.py) pinned by
 identities, against its own float64 evaluation and on the pinned scenes; ``DevicePlanes.bloom``'s protocol on CPU tensors,
 ``Renderer(bloom=...)`` through recording fillers, and ``bloom.gaussian``."""
 import ctypes as C
@@ -16,7 +16,7 @@ import torch
 import bloom_ref
 from pass_scenes import Frame, capi, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
 from ssaa_ref import present_u8
-from util import assert_bit_equal, other_symbols
+from util import assert_bit_equal, other_symbols, own_unit_source
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY = "crender_bloom"
@@ -28,11 +28,11 @@ INF, NAN = float("inf"), float("nan")
 # ---- the host side of the ABI ----------------------------------------------------------------------------------
 
 def test_bloom_symbol_is_declared_exported_and_bound(capi):
-    header = open(os.path.join(ROOT, "include", "crender_wire.h")).read()
+    header = open(os.path.join(ROOT, "include", "crender_bloom.h")).read()
     declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
-    assert ENTRY in declared and declared == set(capi.UNIT_SIGNATURES["wire"])
-    assert ENTRY not in other_symbols(capi, "wire")
-    res, args = capi.UNIT_SIGNATURES["wire"][ENTRY]
+    assert declared == set(capi.UNIT_SIGNATURES["bloom"]) == {ENTRY}
+    assert not declared & other_symbols(capi, "bloom")
+    res, args = capi.UNIT_SIGNATURES["bloom"][ENTRY]
     assert res == C.c_int and args == BLOOM_ARGTYPES == getattr(capi.load(), ENTRY).argtypes
     decl = re.search(r"CRENDER_API int " + ENTRY + r"\((.*?)\);", header, re.S).group(1)
     params = [" ".join(a.split()) for a in decl.split(",")]
@@ -53,18 +53,15 @@ def test_bloom_symbol_is_declared_exported_and_bound(capi):
     assert np.float32(1.0 / 255.0).view(np.uint32) == 0x3B808081 and "0x3B808081" in header
 
 
-def test_bloom_lives_in_the_wire_unit_between_the_runs_and_transparency():
+def test_bloom_sources_are_built_and_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert _build.UNITS["wire"] == (["wireframe.hip"], [os.path.join("..", "..", "include", "crender_wire.h")])
-    unit = open(os.path.join(_build.SRC_DIR, "wireframe.hip")).read()
+    unit = new = own_unit_source(_build, "bloom", "bloom.hip", "crender_bloom.h")
     head = "// ---- bloom (crender_bloom) ----"
     assert unit.count(head) == 1
-    assert unit.index("int crender_wire_runs_emit(") < unit.index(head) < unit.index("void k_bloom_rows") \
-        < unit.index("void k_bloom_finish") < unit.index("int crender_bloom(") < unit.index("// ---- transparency") \
-        < unit.index("// ---- depth of field") < unit.index("// ---- normal mapping")
-    new = unit[unit.index(head):unit.index("// ---- transparency")]
-    # a section of its own: its namespace and its entry point, the passes' frame from the shared header as it is
-    assert new.count("namespace {") == 1 and new.count('extern "C" {') == 1 and "#include" not in new
+    assert unit.index(head) < unit.index("void k_bloom_rows") < unit.index("void k_bloom_finish") \
+        < unit.index("int crender_bloom(")
+    # a unit of its own: its namespace and its entry point, the passes' frame from the shared header as it is
+    assert new.count("namespace {") == 1 and new.count('extern "C" {') == 1
     for name in ("tile_lane(", "tile_origin(", "tile_grid(", "frame_checks(", "rows_check(", "arg_error(", "wave_any("):
         assert name in new and not re.search(r"CR_DEV[^\n]*\b" + re.escape(name), unit), name
     assert "CR_DEV" not in new and "asm" not in new

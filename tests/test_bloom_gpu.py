@@ -1,4 +1,4 @@
-"""Bloom and tone mapping on the GPU (csrc/wireframe.hip's k_bloom_rows and k_bloom_finish through the fillers' ``bloom``,
+"""Bloom and tone mapping on the GPU (csrc/bloom.hip's k_bloom_rows and k_bloom_finish through the fillers' ``bloom``,
 the C entry, ``bloom.bloom`` and Renderer(bloom=...)), bit for bit against the host model of tests/bloom_ref.py, the
 scratch plane included, on the oracle's frames and on hand-built images (the model is pinned in tests/test_bloom_cpu.py)."""
 import ctypes as C

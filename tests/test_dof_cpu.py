@@ -1,4 +1,4 @@
-"""Depth of field without a GPU: the header against the binding and the library, the section's place in the wire unit,
+"""Depth of field without a GPU: the header against the binding and the library, the unit's place in the build tables,
 the entry point's argument checks, the host model the GPU tests compare with (tests/dof_ref.py) pinned by identities on
 the oracle's T-Rex frame and on a two-plane scene whose radii are known, and against its own float64 evaluation;
 ``AdvancedPixelBufferFiller.depth_of_field``'s protocol on CPU tensors, ``Renderer(depth_of_field=...)`` and
@@ -16,7 +16,7 @@ import torch
 
 import dof_ref
 from pass_scenes import Frame, capi, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
-from util import assert_bit_equal, other_symbols
+from util import assert_bit_equal, other_symbols, own_unit_source
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY = "crender_dof_blur"
@@ -28,11 +28,11 @@ DOF_ARGTYPES = [_vp, _vp, _vp, C.c_int64, _vp, C.POINTER(C.c_float), _vp, _f, _f
 # ---- the host side of the ABI ----------------------------------------------------------------------------------
 
 def test_dof_symbol_is_declared_exported_and_bound(capi):
-    header = open(os.path.join(ROOT, "include", "crender_wire.h")).read()
+    header = open(os.path.join(ROOT, "include", "crender_dof.h")).read()
     declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
-    assert ENTRY in declared and declared == set(capi.UNIT_SIGNATURES["wire"])
-    assert ENTRY not in other_symbols(capi, "wire")
-    res, args = capi.UNIT_SIGNATURES["wire"][ENTRY]
+    assert declared == set(capi.UNIT_SIGNATURES["dof"]) == {ENTRY}
+    assert not declared & other_symbols(capi, "dof")
+    res, args = capi.UNIT_SIGNATURES["dof"][ENTRY]
     assert res == C.c_int and args == DOF_ARGTYPES == getattr(capi.load(), ENTRY).argtypes
     decl = re.search(r"CRENDER_API int " + ENTRY + r"\((.*?)\);", header, re.S).group(1)
     params = [" ".join(a.split()) for a in decl.split(",")]
@@ -49,17 +49,14 @@ def test_dof_symbol_is_declared_exported_and_bound(capi):
     assert capi.ABI_VERSION == 6
 
 
-def test_dof_lives_in_the_wire_unit_before_normal_mapping():
+def test_dof_sources_are_built_and_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert _build.UNITS["wire"] == (["wireframe.hip"], [os.path.join("..", "..", "include", "crender_wire.h")])
-    unit = open(os.path.join(_build.SRC_DIR, "wireframe.hip")).read()
+    unit = new = own_unit_source(_build, "dof", "dof.hip", "crender_dof.h")
     head = "// ---- depth of field (crender_dof_blur) ----"
     assert unit.count(head) == 1
-    assert unit.index("int crender_wire_runs_emit(") < unit.index(head) < unit.index("void k_dof_blur") \
-        < unit.index("int crender_dof_blur(") < unit.index("// ---- normal mapping")
-    new = unit[unit.index(head):unit.index("// ---- normal mapping")]
-    # a section of its own: its namespace and its entry points, the passes' frame from the shared header as it is
-    assert new.count("namespace {") == 1 and new.count('extern "C" {') == 1 and "#include" not in new
+    assert unit.index(head) < unit.index("void k_dof_blur") < unit.index("int crender_dof_blur(")
+    # a unit of its own: its namespace and its entry points, the passes' frame from the shared header as it is
+    assert new.count("namespace {") == 1 and new.count('extern "C" {') == 1
     for name in ("tile_lane(", "tile_origin(", "tile_grid(", "tile_lds_bytes(", "frame_checks(", "rows_check(", "arg_error(",
                  "wave_any(", "wave_reduce<true>("):
         assert name in new and not re.search(r"CR_DEV[^\n]*\b" + re.escape(name), unit), name

@@ -1,4 +1,4 @@
-"""The depth-of-field pass on the GPU (csrc/wireframe.hip's k_dof_blur through AdvancedPixelBufferFiller.depth_of_field, the
+"""The depth-of-field pass on the GPU (csrc/dof.hip's k_dof_blur through AdvancedPixelBufferFiller.depth_of_field, the
 C entry and Renderer(depth_of_field=...)), bit for bit against the host model of tests/dof_ref.py evaluated on the oracle's
 frames and on hand-built planes (itself pinned in tests/test_dof_cpu.py)."""
 import ctypes as C

@@ -18,7 +18,7 @@ import edge_aa_ref
 import pass_edges
 import tex_ref
 from pass_scenes import Frame, capi, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
-from util import assert_bit_equal, other_symbols
+from util import LIBRARY_SOURCES, UNIT_KEYS, assert_bit_equal, other_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EDGE_AA_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
@@ -47,10 +47,8 @@ def test_edge_aa_symbol_is_declared_exported_and_bound(capi):
     # the feature lives in the wire unit as it was: no new unit, no new source, no new ABI, the same fingerprint
     assert capi.ABI_VERSION == 6
     assert _build.source_sha16() == "35a9bf480abfca1e"
-    assert _build.library_sources() == ["abi.hip", "binning.hip", "raster.hip", "model_ops.hip", "wireframe.hip", "pyfill.hip",
-                                        "texture.hip", "texmip.hip", "texaniso.hip", "resolve.hip", "shadow.hip", "phong.hip",
-                                        "ao.hip", "chain.hip"]
-    assert list(_build.UNITS) == ["wire", "py", "tex", "mip", "aniso", "ssaa", "shadow", "phong", "ao", "pass", "chain"]
+    assert _build.library_sources() == LIBRARY_SOURCES
+    assert list(_build.UNITS) == UNIT_KEYS
     unit = open(os.path.join(_build.SRC_DIR, "wireframe.hip")).read()
     # after the outline, before the contour kernels; the projection and the barycentrics are the rasterizer's, called
     assert unit.index("void k_wire_outline") < unit.index("void k_wire_edge_aa") < unit.index("void k_wire_facing")

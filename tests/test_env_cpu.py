@@ -1,4 +1,4 @@
-"""The environment pass without a GPU: the header against the binding and the build lists, the entry point's argument
+"""The environment pass without a GPU: the header against the binding and the build tables, the entry point's argument
 checks, the host model the GPU tests compare with (tests/env_ref.py) pinned on the oracle's frames — by counts, by
 identities and against a float64 evaluation —, the layout of the cube's chain, and the cube makers of
 ``cython3dmodelrenderer_amd.environment``."""
@@ -13,7 +13,7 @@ import pytest
 import env_ref
 import mip_ref
 from pass_scenes import Frame, Soup, capi, trex_fixture  # noqa: F401 (fixtures)
-from util import assert_bit_equal, other_symbols, random_soup
+from util import assert_bit_equal, other_symbols, own_unit_source, random_soup
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY = "crender_env_shade"
@@ -58,11 +58,11 @@ def small_soups(oracle):
 # ---- 1. the host side of the ABI -------------------------------------------------------------------------------------
 
 def test_env_symbol_is_declared_bound_and_exported(capi):
-    header = open(os.path.join(ROOT, "include", "crender_wire.h")).read()
+    header = open(os.path.join(ROOT, "include", "crender_env.h")).read()
     declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
-    assert declared == set(capi.UNIT_SIGNATURES["wire"]) and ENTRY in declared
-    assert ENTRY not in other_symbols(capi, "wire")
-    res, args = capi.UNIT_SIGNATURES["wire"][ENTRY]
+    assert declared == set(capi.UNIT_SIGNATURES["env"]) == {ENTRY}
+    assert not declared & other_symbols(capi, "env")
+    res, args = capi.UNIT_SIGNATURES["env"][ENTRY]
     L = capi.load()
     assert res == C.c_int and args == SIGNATURE == getattr(L, ENTRY).argtypes
     decl = re.search(r"CRENDER_API int " + ENTRY + r"\((.*?)\);", header, re.S).group(1).split(",")
@@ -82,23 +82,16 @@ def test_env_symbol_is_declared_bound_and_exported(capi):
     assert capi.ABI_VERSION == 6
 
 
-def test_env_lives_in_the_wire_unit_and_the_build_tables_stay():
+def test_env_sources_are_built_and_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert list(_build.UNITS) == ["wire", "py", "tex", "mip", "aniso", "ssaa", "shadow", "phong", "ao", "pass", "chain"]
-    assert _build.UNITS["wire"] == (["wireframe.hip"], [os.path.join("..", "..", "include", "crender_wire.h")])
-    assert _build.library_sources() == ["abi.hip", "binning.hip", "raster.hip", "model_ops.hip", "wireframe.hip", "pyfill.hip",
-                                        "texture.hip", "texmip.hip", "texaniso.hip", "resolve.hip", "shadow.hip", "phong.hip",
-                                        "ao.hip", "chain.hip"]
-    assert _build.source_sha16() == "35a9bf480abfca1e"
-    unit = open(os.path.join(_build.SRC_DIR, "wireframe.hip")).read()
+    unit = new = own_unit_source(_build, "env", "envmap.hip", "crender_env.h")
     head = "// ---- environment mapping (crender_env_shade) ----"
-    assert unit.count(head) == 1 and unit.index("// ---- normal mapping") < unit.index("int crender_nmap_shade(") < unit.index(head)
-    new = unit[unit.index(head):]
+    assert unit.count(head) == 1 and unit.index(head) < unit.index("void k_env_shade") < unit.index("int crender_env_shade(")
+    assert new.count("namespace {") == 1 and new.count('extern "C" {') == 1
     # the pass takes the passes' frame and the sample from the shared header, as they are
     for name in ("winner_pixel(", "winner_triangle(", "barycentric(", "bilinear(", "wave_any(", "pass_grid(", "frame_checks(",
                  "rows_check(", "make_proj("):
         assert name in new and not re.search(r"CR_DEV[^\n]*\b" + re.escape(name), unit), name
-    assert not re.search(r"#include", new)
     assert "__shared__" not in new
     # six instances
     assert len(set(re.findall(r"k_env_shade<(?:true|false), (?:true|false), (?:true|false)>", new))) == 6

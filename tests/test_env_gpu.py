@@ -1,4 +1,4 @@
-"""The environment pass on the GPU (k_env_shade of csrc/wireframe.hip through AdvancedPixelBufferFiller.environment_pass,
+"""The environment pass on the GPU (k_env_shade of csrc/envmap.hip through AdvancedPixelBufferFiller.environment_pass,
 the C entry and Renderer), bit for bit against the host model of tests/env_ref.py evaluated on the oracle's frames
 (itself pinned in tests/test_env_cpu.py)."""
 import ctypes as C

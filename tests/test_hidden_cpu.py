@@ -19,7 +19,7 @@ import pass_edges
 import tex_ref
 import wire_ref
 from pass_scenes import Frame, capi, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
-from util import assert_bit_equal, other_symbols, random_soup
+from util import UNIT_KEYS, assert_bit_equal, other_symbols, random_soup
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = C.c_float
@@ -59,7 +59,7 @@ def test_hidden_symbol_is_declared_exported_and_bound(capi):
     assert capi.ABI_VERSION == 6
     assert _build.source_sha16() == "35a9bf480abfca1e"
     assert _build.UNITS["wire"][0] == ["wireframe.hip"]
-    assert list(_build.UNITS) == ["wire", "py", "tex", "mip", "aniso", "ssaa", "shadow", "phong", "ao", "pass", "chain"]
+    assert list(_build.UNITS) == UNIT_KEYS
     unit = open(os.path.join(_build.SRC_DIR, "wireframe.hip")).read()
     # after the contour kernels; the walker and the projection are the file's and the rasterizer's own, called
     assert unit.index("void k_wire_contour_mask") < unit.index("void k_wire_hidden") < unit.index("int wire_window(")

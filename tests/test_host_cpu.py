@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from pass_scenes import capi  # noqa: F401 (fixtures)
-from util import assert_bit_equal
+from util import LIBRARY_SOURCES, UNIT_KEYS, assert_bit_equal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -33,10 +33,8 @@ def test_library_exports_every_declared_symbol(capi):
 def test_library_units_are_one_table_for_the_build_and_the_binding():
     from cython3dmodelrenderer_amd import _build, _capi
     # link order decides the library's bytes
-    assert _build.library_sources() == ["abi.hip", "binning.hip", "raster.hip", "model_ops.hip", "wireframe.hip", "pyfill.hip",
-                                        "texture.hip", "texmip.hip", "texaniso.hip", "resolve.hip", "shadow.hip", "phong.hip",
-                                        "ao.hip", "chain.hip"]
-    assert list(_build.UNITS) == ["wire", "py", "tex", "mip", "aniso", "ssaa", "shadow", "phong", "ao", "pass", "chain"]
+    assert _build.library_sources() == LIBRARY_SOURCES
+    assert list(_build.UNITS) == UNIT_KEYS
     assert set(_capi.UNIT_SIGNATURES) == {unit for unit, (sources, _) in _build.UNITS.items() if sources}
     bound = [name for table in (_capi.SIGNATURES, *_capi.UNIT_SIGNATURES.values()) for name in table]
     assert len(bound) == len(set(bound))

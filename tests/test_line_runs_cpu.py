@@ -22,7 +22,7 @@ import runs_ref
 import tex_ref
 import wire_ref
 from pass_scenes import Frame, capi, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
-from util import assert_bit_equal, other_symbols, random_soup
+from util import UNIT_KEYS, assert_bit_equal, other_symbols, random_soup
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = C.c_float
@@ -75,7 +75,7 @@ def test_runs_symbols_are_declared_exported_and_bound(capi):
     assert capi.ABI_VERSION == 6
     assert _build.source_sha16() == "35a9bf480abfca1e"
     assert _build.UNITS["wire"][0] == ["wireframe.hip"]
-    assert list(_build.UNITS) == ["wire", "py", "tex", "mip", "aniso", "ssaa", "shadow", "phong", "ao", "pass", "chain"]
+    assert list(_build.UNITS) == UNIT_KEYS
     unit = open(os.path.join(_build.SRC_DIR, "wireframe.hip")).read()
     # after the hidden pass, whose text is left alone; count and emit are ONE template, without atomics or assembly
     assert unit.index("void k_wire_hidden") < unit.index("int wire_window(") < unit.index("void k_wire_runs")

@@ -14,7 +14,7 @@ import mip_ref
 import nmap_ref
 import pass_scenes
 from pass_scenes import Frame, capi, trex_fixture, trex_uv  # noqa: F401 (fixtures)
-from util import assert_bit_equal, other_symbols
+from util import assert_bit_equal, other_symbols, own_unit_source
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("crender_nmap_from_height", "crender_nmap_shade")
@@ -23,16 +23,16 @@ ENTRIES = ("crender_nmap_from_height", "crender_nmap_shade")
 # ---- 1. the host side of the ABI -------------------------------------------------------------------------------------
 
 def test_nmap_symbols_are_declared_bound_and_exported(capi):
-    header = open(os.path.join(ROOT, "include", "crender_wire.h")).read()
+    header = open(os.path.join(ROOT, "include", "crender_nmap.h")).read()
     declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
-    assert declared == set(capi.UNIT_SIGNATURES["wire"]) and set(ENTRIES) <= declared
-    assert not set(ENTRIES) & other_symbols(capi, "wire")
+    assert declared == set(capi.UNIT_SIGNATURES["nmap"]) == set(ENTRIES)
+    assert not declared & other_symbols(capi, "nmap")
     L = capi.load()
     _vp, _i32, _i64, _u32, _f32p, _f = C.c_void_p, C.c_int, C.c_int64, C.c_uint, C.POINTER(C.c_float), C.c_float
     want = {"crender_nmap_from_height": [_vp, _i32, _i32, _f, _u32, _vp, _vp],
             "crender_nmap_shade": [_vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _i32, _f, _vp, _i32, _i32, _i32, _i32, _u32, _vp]}
     for name in ENTRIES:
-        res, args = capi.UNIT_SIGNATURES["wire"][name]
+        res, args = capi.UNIT_SIGNATURES["nmap"][name]
         assert res == C.c_int and args == want[name] == getattr(L, name).argtypes, name
         decl = re.search(r"CRENDER_API int " + name + r"\((.*?)\);", header, re.S).group(1).split(",")
         assert len(decl) == len(args), name
@@ -48,23 +48,16 @@ def test_nmap_symbols_are_declared_bound_and_exported(capi):
     assert capi.ABI_VERSION == 6
 
 
-def test_nmap_lives_in_the_wire_unit_and_the_build_tables_stay():
+def test_nmap_sources_are_built_and_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert list(_build.UNITS) == ["wire", "py", "tex", "mip", "aniso", "ssaa", "shadow", "phong", "ao", "pass", "chain"]
-    assert _build.UNITS["wire"][0] == ["wireframe.hip"]
-    assert _build.library_sources() == ["abi.hip", "binning.hip", "raster.hip", "model_ops.hip", "wireframe.hip", "pyfill.hip",
-                                        "texture.hip", "texmip.hip", "texaniso.hip", "resolve.hip", "shadow.hip", "phong.hip",
-                                        "ao.hip", "chain.hip"]
-    assert _build.source_sha16() == "35a9bf480abfca1e"
-    unit = open(os.path.join(_build.SRC_DIR, "wireframe.hip")).read()
+    unit = new = own_unit_source(_build, "nmap", "normal_map.hip", "crender_nmap.h")
+    assert unit.count("// ---- normal mapping") == 1 and new.count("namespace {") == 1 and new.count('extern "C" {') == 1
     # the mip unit's headers stay its own: what the pass needs of them is restated
     assert "mip_sample.h\"" not in unit and "crender_mip.h\"" not in unit
     assert not re.search(r"#include[^\n]*(mip_sample|crender_mip)", unit)
-    # the kernels come after everything the unit had, and take the passes' frame from the shared header
+    # the kernels take the passes' frame from the shared header
     for name in ("k_nmap_shade", "k_nmap_from_height"):
-        assert unit.index("int runs_checks(") < unit.index("void " + name), name
-    assert unit.index("int crender_wire_runs_emit(") < unit.index("int crender_nmap_from_height(")
-    new = unit[unit.index("// ---- normal mapping"):]
+        assert unit.index("// ---- normal mapping") < unit.index("void " + name) < unit.index("int crender_nmap_from_height("), name
     for name in ("winner_triangle(", "winner_pixel(", "barycentric(", "bilinear(", "make_proj(", "wave_any(", "pass_grid(",
                  "frame_checks(", "rows_check(", "arg_error("):
         assert name in new and not re.search(r"CR_DEV[^\n]*\b" + re.escape(name), unit), name

@@ -1,4 +1,4 @@
-"""Normal mapping on the GPU (csrc/wireframe.hip's k_nmap_shade and k_nmap_from_height through
+"""Normal mapping on the GPU (csrc/normal_map.hip's k_nmap_shade and k_nmap_from_height through
 AdvancedPixelBufferFiller.bind_normal_map / normal_map_pass, the C entries and Renderer), bit for bit against the host
 model of tests/nmap_ref.py evaluated on the oracle's frames (itself pinned in tests/test_normal_map_cpu.py)."""
 import ctypes as C

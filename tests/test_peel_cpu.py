@@ -1,4 +1,4 @@
-"""Transparency without a GPU: the header against the binding and the library, the section's place in the wire unit, the
+"""Transparency without a GPU: the header against the binding and the library, the unit's place in the build tables, the
 two entry points' argument checks and their order; the host model the GPU tests compare with (tests/peel_ref.py) pinned
 on the oracle's frames — layer 0 is the oracle's frame, every triangle's fragments are what the oracle draws of it alone,
 the counts per layer — and on an analytic scene, its blend against its own float64 evaluation;
@@ -17,7 +17,7 @@ import torch
 
 import peel_ref
 from pass_scenes import LIGHT, Frame, Soup, capi, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
-from util import assert_bit_equal, other_symbols, random_soup
+from util import assert_bit_equal, other_symbols, own_unit_source, random_soup
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEXT, BLEND = "crender_peel_next", "crender_peel_blend"
@@ -37,14 +37,15 @@ BLEND_PARAMS = ["const int32_t *d_winner", "const float *d_tri", "int64_t T", "c
 # ---- the host side of the ABI ----------------------------------------------------------------------------------
 
 def test_peel_symbols_are_declared_exported_and_bound(capi):
-    header = open(os.path.join(ROOT, "include", "crender_wire.h")).read()
+    header = open(os.path.join(ROOT, "include", "crender_peel.h")).read()
     declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
-    assert {NEXT, BLEND} <= declared and declared == set(capi.UNIT_SIGNATURES["wire"])
+    assert declared == set(capi.UNIT_SIGNATURES["peel"]) == {NEXT, BLEND}
+    assert not declared & other_symbols(capi, "peel")
     out = subprocess.check_output(["nm", "-D", "--defined-only", capi.lib_path()], text=True)
     exported = set(re.findall(r" T (crender_\w+)", out))
     for entry, argtypes, params in ((NEXT, NEXT_ARGTYPES, NEXT_PARAMS), (BLEND, BLEND_ARGTYPES, BLEND_PARAMS)):
-        assert entry not in other_symbols(capi, "wire") and entry in exported
-        res, args = capi.UNIT_SIGNATURES["wire"][entry]
+        assert entry in exported
+        res, args = capi.UNIT_SIGNATURES["peel"][entry]
         assert res == C.c_int and args == argtypes == getattr(capi.load(), entry).argtypes
         decl = re.search(r"CRENDER_API int " + entry + r"\((.*?)\);", header, re.S).group(1)
         assert [" ".join(a.split()) for a in decl.split(",")] == params and len(params) == len(args)
@@ -56,24 +57,16 @@ def test_peel_symbols_are_declared_exported_and_bound(capi):
     assert capi.ABI_VERSION == 6 and capi.load().crender_abi_version() == 6
 
 
-def test_peel_lives_in_the_wire_unit_before_depth_of_field_and_the_build_tables_stay():
+def test_peel_sources_are_built_and_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert list(_build.UNITS) == ["wire", "py", "tex", "mip", "aniso", "ssaa", "shadow", "phong", "ao", "pass", "chain"]
-    assert _build.UNITS["wire"] == (["wireframe.hip"], [os.path.join("..", "..", "include", "crender_wire.h")])
-    assert _build.library_sources() == ["abi.hip", "binning.hip", "raster.hip", "model_ops.hip", "wireframe.hip", "pyfill.hip",
-                                        "texture.hip", "texmip.hip", "texaniso.hip", "resolve.hip", "shadow.hip", "phong.hip",
-                                        "ao.hip", "chain.hip"]
-    assert _build.source_sha16() == "35a9bf480abfca1e"
-    unit = open(os.path.join(_build.SRC_DIR, "wireframe.hip")).read()
+    unit = new = own_unit_source(_build, "peel", "peel.hip", "crender_peel.h")
     head = "// ---- transparency (crender_peel_next, crender_peel_blend) ----"
-    dof = "// ---- depth of field (crender_dof_blur) ----"
     assert unit.count(head) == 1
-    assert unit.index("int crender_wire_runs_emit(") < unit.index(head) < unit.index("void k_peel_seed") \
-        < unit.index("void k_peel_cover") < unit.index("void k_peel_resolve") < unit.index("void k_peel_blend") \
-        < unit.index("int crender_peel_next(") < unit.index("int crender_peel_blend(") < unit.index(dof)
-    new = unit[unit.index(head):unit.index(dof)]
-    # a section of its own: its namespace and its entry points, the passes' frame from the shared header as it is
-    assert new.count("namespace {") == 1 and new.count('extern "C" {') == 1 and "#include" not in new
+    assert unit.index(head) < unit.index("void k_peel_seed") < unit.index("void k_peel_cover") \
+        < unit.index("void k_peel_resolve") < unit.index("void k_peel_blend") < unit.index("int crender_peel_next(") \
+        < unit.index("int crender_peel_blend(")
+    # a unit of its own: its namespace and its entry points, the passes' frame from the shared header as it is
+    assert new.count("namespace {") == 1 and new.count('extern "C" {') == 1
     for name in ("winner_triangle(", "winner_pixel(", "barycentric(", "make_proj(", "wave_any(", "pass_grid(", "frame_checks(",
                  "rows_check(", "arg_error("):
         assert name in new and not re.search(r"CR_DEV[^\n]*\b" + re.escape(name), unit), name

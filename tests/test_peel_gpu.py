@@ -1,4 +1,4 @@
-"""Transparency on the GPU (csrc/wireframe.hip's k_peel_seed, k_peel_cover, k_peel_resolve and k_peel_blend through
+"""Transparency on the GPU (csrc/peel.hip's k_peel_seed, k_peel_cover, k_peel_resolve and k_peel_blend through
 AdvancedPixelBufferFiller.peel_layers and transparency_pass, the two C entries and Renderer(transparency=...)), bit for bit
 against the host model of tests/peel_ref.py (itself pinned in tests/test_peel_cpu.py)."""
 import ctypes as C

@@ -14,7 +14,7 @@ import pytest
 import contour_ref
 import outline_ref
 from pass_scenes import Frame, capi, trex_fixture  # noqa: F401 (fixtures)
-from util import other_symbols, sha
+from util import LIBRARY_SOURCES, UNIT_KEYS, other_symbols, sha
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONTOUR_ARGTYPES = [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -46,10 +46,8 @@ def test_contours_symbol_is_declared_exported_and_bound(capi):
     # the feature lives in the wire unit as it was: no new unit, no new source, no new ABI, the same fingerprint
     assert capi.ABI_VERSION == 6
     assert _build.source_sha16() == "35a9bf480abfca1e"
-    assert _build.library_sources() == ["abi.hip", "binning.hip", "raster.hip", "model_ops.hip", "wireframe.hip", "pyfill.hip",
-                                        "texture.hip", "texmip.hip", "texaniso.hip", "resolve.hip", "shadow.hip", "phong.hip",
-                                        "ao.hip", "chain.hip"]
-    assert list(_build.UNITS) == ["wire", "py", "tex", "mip", "aniso", "ssaa", "shadow", "phong", "ao", "pass", "chain"]
+    assert _build.library_sources() == LIBRARY_SOURCES
+    assert list(_build.UNITS) == UNIT_KEYS
     assert _build.UNITS["wire"][0] == ["wireframe.hip"]
     unit = open(os.path.join(_build.SRC_DIR, "wireframe.hip")).read()
     assert "k_wire_facing" in unit and "k_wire_contour_mask" in unit

@@ -13,7 +13,7 @@ import pytest
 
 import overlay_ref
 from pass_scenes import Frame, capi, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
-from util import assert_bit_equal, other_symbols, unit_inputs
+from util import LIBRARY_SOURCES, UNIT_KEYS, assert_bit_equal, other_symbols, unit_inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OVERLAY_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.POINTER(C.c_float),
@@ -45,10 +45,8 @@ def test_overlay_symbol_is_declared_exported_and_bound(capi):
 def test_the_build_lists_are_unchanged():
     from cython3dmodelrenderer_amd import _build
     assert _build.source_sha16() == "35a9bf480abfca1e"
-    assert _build.library_sources() == ["abi.hip", "binning.hip", "raster.hip", "model_ops.hip", "wireframe.hip", "pyfill.hip",
-                                        "texture.hip", "texmip.hip", "texaniso.hip", "resolve.hip", "shadow.hip", "phong.hip",
-                                        "ao.hip", "chain.hip"]
-    assert list(_build.UNITS) == ["wire", "py", "tex", "mip", "aniso", "ssaa", "shadow", "phong", "ao", "pass", "chain"]
+    assert _build.library_sources() == LIBRARY_SOURCES
+    assert list(_build.UNITS) == UNIT_KEYS
     assert _build.UNITS["wire"][0] == ["wireframe.hip"]
     # the overlay's kernel takes the passes' frame from the shared header, which a unit of its own watches
     inputs = _build.build_inputs()

@@ -126,6 +126,8 @@ def test_wire_header_symbols_are_exported_and_bound(capi):
     header = open(os.path.join(ROOT, "include", "crender_wire.h")).read()
     declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
     assert declared == set(capi.UNIT_SIGNATURES["wire"]), declared ^ set(capi.UNIT_SIGNATURES["wire"])
+    assert declared == {"crender_wire_" + name for name in ("key_bytes", "draw", "overlay", "outline", "edge_aa", "contours",
+                                                            "hidden", "runs_groups", "runs_count", "runs_emit")}
     assert not declared & other_symbols(capi, "wire")
     L = capi.load()
     for name in declared:

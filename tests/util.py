@@ -40,6 +40,36 @@ def unit_inputs(_build, unit):
     return {os.path.join(_build.SRC_DIR, name) for name in sources + headers}
 
 
+# The library's units and its translation units in link order, name for name: what the units' tests pin _build.UNITS and
+# _build.library_sources() against.  A new unit is one name in each.
+UNIT_KEYS = ["wire", "bloom", "peel", "dof", "nmap", "env", "py", "tex", "mip", "aniso", "ssaa", "shadow", "phong", "ao",
+             "pass", "chain"]
+LIBRARY_SOURCES = ["abi.hip", "binning.hip", "raster.hip", "model_ops.hip", "wireframe.hip", "bloom.hip", "peel.hip",
+                   "dof.hip", "normal_map.hip", "envmap.hip", "pyfill.hip", "texture.hip", "texmip.hip", "texaniso.hip",
+                   "resolve.hip", "shadow.hip", "phong.hip", "ao.hip", "chain.hip"]
+
+
+def own_unit_source(_build, unit, source, header):
+    """Asserts that `unit` is built from exactly its one source and its one public header, outside the profile
+    fingerprint, and that the source opens with the four includes of a pass; returns the source's text."""
+    assert list(_build.UNITS) == UNIT_KEYS and _build.library_sources() == LIBRARY_SOURCES
+    assert _build.UNITS[unit] == ([source], [os.path.join("..", "..", "include", header)])
+    fingerprinted = _build.SOURCES + _build.HEADERS
+    assert not set(_build.UNITS[unit][0] + _build.UNITS[unit][1]) & set(fingerprinted)
+    assert not any(os.path.splitext(source)[0] in name or os.path.splitext(header)[0] in name for name in fingerprinted)
+    assert _build.source_sha16() == "35a9bf480abfca1e"
+    for path in unit_inputs(_build, unit):
+        assert os.path.exists(path), path
+    # the default build compiles the unit, and a change of it makes the library stale
+    assert source in _build.library_sources()
+    assert unit_inputs(_build, unit) <= set(_build.build_inputs())
+    text = open(os.path.join(_build.SRC_DIR, source)).read()
+    includes = [line.split()[1] for line in text.splitlines() if line.startswith("#include")]
+    assert includes == ["<math.h>", '"common.h"', f'"../../include/{header}"', '"winner_pass.h"'], includes
+    assert text.index('"common.h"') < text.index("using namespace crender_detail;") < text.index('"winner_pass.h"')
+    return text
+
+
 def random_soup(rng, T, res, size_px=(1.0, 40.0), z=(0.5, 3.0), frac_backface=0.2, margin=0.3):
     """Random projected-space-friendly triangles in MODEL space for a fov-45 filler:
     centres spread a bit beyond the frustum, sizes in pixels at resolution `res`."""
