@@ -70,6 +70,13 @@ UNITS = {
 FRAME_UNITS = {
     "frame32": (["frame32.hip"], [os.path.join(_INCLUDE, "crender_frame32.h")]),
 }
+# The feature units added since the two tables above were pinned by their tests, in link order behind them:
+# name -> (sources, headers), outside source_sha16() like them.  all_sources() is what the library is built from.
+#   motion.hip  per-pixel motion vectors against an earlier pose, and the motion blur that gathers along them
+#               (include/crender_motion.h)
+MORE_UNITS = {
+    "motion": (["motion.hip"], [os.path.join(_INCLUDE, "crender_motion.h")]),
+}
 
 # Float parity with the reference depends on these (DESIGN.md "Numerics"):
 #   -ffp-contract=off                           no FMA contraction (hipcc defaults to fast)
@@ -121,6 +128,11 @@ def link_sources() -> list:
     return library_sources() + [src for sources, _ in FRAME_UNITS.values() for src in sources]
 
 
+def all_sources() -> list:
+    """Everything linked into the library: link_sources(), then the later feature units' (MORE_UNITS)."""
+    return link_sources() + [src for sources, _ in MORE_UNITS.values() for src in sources]
+
+
 def build_inputs() -> list:
     """Paths of everything whose change makes the library stale: the fingerprinted sources and headers, every unit's
     sources and headers, and this file (the flags).  A header that two units list is named once."""
@@ -131,6 +143,12 @@ def build_inputs() -> list:
 def frame_inputs() -> list:
     """Paths of the frame kernels' sources and headers (FRAME_UNITS): build() counts them like build_inputs()."""
     names = [name for sources, headers in FRAME_UNITS.values() for name in sources + headers]
+    return [os.path.join(SRC_DIR, name) for name in dict.fromkeys(names)]
+
+
+def more_inputs() -> list:
+    """Paths of the later feature units' sources and headers (MORE_UNITS): build() counts them like build_inputs()."""
+    names = [name for sources, headers in MORE_UNITS.values() for name in sources + headers]
     return [os.path.join(SRC_DIR, name) for name in dict.fromkeys(names)]
 
 
@@ -147,7 +165,7 @@ def compile_library(out: str, extra_flags=(), sources=None, src_dir: str = SRC_D
     defines of diagnostic builds (-DCRENDER_STAMPS, ...)."""
     import tempfile
     from concurrent.futures import ThreadPoolExecutor
-    sources = list(sources or link_sources())
+    sources = list(sources or all_sources())
     err = subprocess.DEVNULL if quiet else None
     with tempfile.TemporaryDirectory(prefix="crender_build_") as tmp:
         objs = [os.path.join(tmp, os.path.splitext(s)[0] + ".o") for s in sources]
@@ -178,7 +196,7 @@ def compile_library(out: str, extra_flags=(), sources=None, src_dir: str = SRC_D
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Build libcrender_hip.so if missing or stale; returns its path."""
-    if not force and not needs_build() and not needs_build(frame_inputs()):
+    if not force and not needs_build() and not needs_build(frame_inputs()) and not needs_build(more_inputs()):
         return LIB_PATH
     return compile_library(LIB_PATH, verbose=verbose)
 

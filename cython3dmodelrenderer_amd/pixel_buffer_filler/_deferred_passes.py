@@ -5,7 +5,9 @@ texture, normal-map, environment and shadow-map bindings they read, the classifi
 the surface, dashed (``hidden_line_pass``: it walks the edges, not the winner plane's pixels, and keeps a key plane), the same
 classification kept as vector segments (``line_runs``: it only reads the planes and returns a ``LineDrawing``) and geometric
 edge anti-aliasing (``edge_aa``: it reads the planes and returns a plane of its own) and depth of field (``depth_of_field``:
-a gather blur by the circle of confusion over the z plane, which returns a plane of its own as well) and transparency
+a gather blur by the circle of confusion over the z plane, which returns a plane of its own as well), motion vectors and
+motion blur (``motion_vectors`` and ``motion_blur``: where every pixel's surface point was in an earlier pose, and a gather
+along that, two planes of their own) and transparency
 (``peel_layers`` and ``transparency_pass``: the frame's depth layers peeled by depth key and blended front to back, a plane of its own again).  A mixin
 beside ``_device_planes.DevicePlanes``: the filler supplies ``device, h, w, y0, y1, _lib, _P`` and its frame state (``_pipeline, _inputs, _order, _last_flags, _check_bins``).  What every pass has in common is here
 once: whom it refuses (``_pass_target``), which frame it accepts (``_pass_frame``), and how it is launched
@@ -768,6 +770,92 @@ class DeferredPasses:
         out = new((self.h, self.w, 3), dtype=torch.float32, device=self.color_buffer.device)
         self._run_pass("crender_dof_blur", tri, T, (self.color_buffer, float(focus), float(band), float(aperture),
                                                     int(max_radius)), z=True, reads_only=True, target=out)
+        return out
+
+    def _previous_pose(self, name, previous_vertices, T):
+        """`previous_vertices` as ``bind_shadow_map`` converts ``light_vertices``; it must hold the last frame's T triangles."""
+        if previous_vertices is None:
+            raise ValueError(f"{name}: previous_vertices is None: the vertex array of the earlier pose is needed")
+        prev = _as_device_f32(previous_vertices, "previous_vertices", self.device)
+        if prev.shape[0] != T:
+            raise ValueError(f"{name}: previous_vertices holds {prev.shape[0]} triangles, the last frame drew {T}")
+        return prev
+
+    @staticmethod
+    def _check_exposure(exposure):
+        if isinstance(exposure, bool) or not isinstance(exposure, (int, float, np.integer, np.floating)) \
+                or not 0 <= float(exposure) <= float(np.finfo(np.float32).max):
+            raise ValueError(f"exposure must be a finite number, 0 or above, got {exposure!r}")
+
+    def motion_vectors(self, previous_vertices, exposure=1.0):
+        """The motion vectors of the LAST frame against an earlier pose (``crender_motion_vectors``,
+        include/crender_motion.h): a NEW device tensor [h, w, 2] float32 in which a covered pixel holds (vx, vy), the
+        pixels the surface point it shows moved on the screen between the pose of `previous_vertices` and the frame's,
+        times `exposure` — pointing from where it was to where it is.  The point is the perspective-correct blend of the
+        winner's three PREVIOUS corners with the rasterizer's own barycentrics, projected with the filler's own matrix,
+        as ``shadow_pass`` carries it into the light's frame: exact per pixel, no finite differences.
+        `previous_vertices` is float32 [T, 3, 3], numpy or a device tensor, in the caller's triangle order and in the
+        camera's frame: the vertex array of the earlier pose, T the triangles of the last frame.  The background, a
+        point that was behind the camera and a velocity that is not finite give (0, 0).  Rows of the filler's
+        ``row_strip`` (the others of the result are zero), on torch's current stream.
+
+        Edits made in the numpy views handed out so far are carried to the device and the frame is settled first (one
+        stream synchronisation, as every getter does).  The planes are only read: the views stay as fresh or as stale
+        as they were."""
+        self._pass_target("motion_vectors")
+        tri, T = self._pass_frame("motion_vectors")
+        prev = self._previous_pose("motion_vectors", previous_vertices, T)
+        self._check_exposure(exposure)
+        return self._motion_vectors(tri, T, prev, exposure)
+
+    def _motion_vectors(self, tri, T, prev, exposure):
+        new = torch.empty if (self.y0, self.y1) == (0, self.h) else torch.zeros
+        out = new((self.h, self.w, 2), dtype=torch.float32, device=self.color_buffer.device)
+        self._run_pass("crender_motion_vectors", tri, T, (prev if T else None, float(exposure)), reads_only=True, target=out)
+        return out
+
+    def motion_blur(self, previous_vertices=None, *, velocity=None, exposure=1.0, max_radius=8, taps=16, soft=0.02):
+        """Motion blur of the LAST frame (``crender_motion_blur``, include/crender_motion.h): a NEW device tensor
+        [h, w, 3] float32, as ``depth_of_field`` returns one, in which every pixel is the weighted mean of `taps` pixels
+        on a line through it: the reconstruction filter of McGuire et al. 2012.  The line is the DOMINANT half velocity
+        of the pixel's tile of 32 x 32 and of `max_radius` pixels around it (an int from 1 to 12: every half velocity is
+        clamped to it), and a tap counts by the two pixels' velocities and view depths: what moves spreads over what
+        lies behind it, what stands still in front of something moving keeps its bits, and depths closer than `soft`
+        blend.  The velocities come from `previous_vertices` (``motion_vectors``' argument, with `exposure`) or from
+        `velocity`, a float32 [h, w, 2] array or tensor such as an edited result of ``motion_vectors``: exactly one of
+        the two.  A tile in which nothing moves by more than a pixel, and every pixel that takes no tap, is copied bit
+        for bit.  Rows of the filler's ``row_strip`` (the others of the result are zero; the strip does not see across
+        its edge), on torch's current stream.
+
+        Edits made in the numpy views handed out so far are carried to the device and the frame is settled first (one
+        stream synchronisation, as every getter does).  The planes are only read: the views stay as fresh or as stale
+        as they were."""
+        self._pass_target("motion_blur")
+        tri, T = self._pass_frame("motion_blur")
+        if (previous_vertices is None) == (velocity is None):
+            raise ValueError("motion_blur takes exactly one of previous_vertices and velocity")
+        self._check_exposure(exposure)
+        top = _capi.MOTION_MAX_RADIUS
+        if isinstance(max_radius, bool) or not isinstance(max_radius, (int, np.integer)) or not 1 <= max_radius <= top:
+            raise ValueError(f"max_radius must be an int from 1 to {top}, got {max_radius!r}")
+        top = _capi.MOTION_MAX_TAPS
+        if isinstance(taps, bool) or not isinstance(taps, (int, np.integer)) or not 1 <= taps <= top:
+            raise ValueError(f"taps must be an int from 1 to {top}, got {taps!r}")
+        if isinstance(soft, bool) or not isinstance(soft, (int, float, np.integer, np.floating)) \
+                or not 0 < float(soft) <= float(np.finfo(np.float32).max) or not np.float32(soft) > 0:
+            raise ValueError(f"soft must be a finite range of view depths above 0, got {soft!r}")
+        if velocity is not None:
+            if float(exposure) != 1.0:
+                raise ValueError(f"exposure={exposure!r} with velocity=...: the exposure scales the velocities "
+                                 "motion_vectors computes; scale the plane itself")
+            velocity = _device_array(self, velocity, torch.float32, lambda s: s == (self.h, self.w, 2),
+                                     f"velocity must be float32 [{self.h}, {self.w}, 2], the frame's")
+        else:
+            velocity = self._motion_vectors(tri, T, self._previous_pose("motion_blur", previous_vertices, T), exposure)
+        new = torch.empty if (self.y0, self.y1) == (0, self.h) else torch.zeros
+        out = new((self.h, self.w, 3), dtype=torch.float32, device=self.color_buffer.device)
+        self._run_pass("crender_motion_blur", tri, T, (self.color_buffer, velocity, int(max_radius), int(taps), float(soft)),
+                       z=True, reads_only=True, target=out)
         return out
 
     def _peel_frame(self, name):

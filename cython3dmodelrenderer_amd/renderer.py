@@ -22,7 +22,7 @@ def _device_form_is_the_same_shading(illumination):
 class Renderer:
     def __init__(self, pixel_buffer_filler, illumination, triangle_iterator_type=None,
                  image_height=512, image_width=512, use_tqdm=True, on_device=None, texture_pass=None,
-                 shadow=None, ambient_occlusion=None, antialias=None, depth_of_field=None, normal_map=None,
+                 shadow=None, ambient_occlusion=None, antialias=None, depth_of_field=None, motion_blur=None, normal_map=None,
                  environment=None, bloom=None, transparency=None, wireframe=None, supersample=None):
         self.pixel_buffer_filler = pixel_buffer_filler
         self.illumination = illumination
@@ -190,6 +190,32 @@ class Renderer:
             if "focus" not in depth_of_field:
                 raise ValueError("Renderer(depth_of_field=...) needs 'focus', the view depth that stays sharp")
             self.depth_of_field = dict(depth_of_field)
+        # motion_blur=None (default): every frame is an instant.  A dict of ``exposure`` / ``max_radius`` / ``taps`` / ``soft``
+        # (``AdvancedPixelBufferFiller.motion_blur``'s arguments; {} = its defaults): the finished frame blurred along the
+        # motion vectors of the model between the pose of the ``render`` call before and this one's.  At every ``render``
+        # the renderer keeps a device COPY of the vertex array the frame was drawn from (a DeviceModel is transformed in
+        # place) and uses the copy of the call before as the previous pose; on the first call, after ``reset_motion()``
+        # and when the triangle count changed, the previous pose is the current one and the image is the frame, copied.
+        # Every frame starts from cleared buffers (one model per frame, as "fused").  The pass runs LAST, after everything
+        # that shades and after the wire pass, reads the filler's planes and writes a tensor of its own, which ``render``
+        # returns (``bloom`` reads it): the tensor for on_device=True / "fused", a fresh numpy copy otherwise.  It combines
+        # with none of ``antialias``, ``depth_of_field``, ``supersample`` and ``transparency``: each of them reads the
+        # filler's own colour plane and would not see the blurred one.
+        self.motion_blur = None
+        self._previous_pose = None     # the device copy of the vertices the last frame was drawn from
+        if motion_blur is not None:
+            if antialias is not None or depth_of_field is not None or supersample is not None or transparency is not None:
+                raise ValueError("Renderer(motion_blur=...) together with antialias=..., depth_of_field=..., supersample=... or "
+                                 "transparency=...: each of them reads the filler's own colour plane and would not see the "
+                                 "blurred one; use one of them")
+            if not hasattr(pixel_buffer_filler, "motion_blur"):
+                raise ValueError("Renderer(motion_blur=...) needs a filler with a motion-blur pass "
+                                 f"(AdvancedPixelBufferFiller): {type(pixel_buffer_filler).__name__} has no motion_blur()")
+            unknown = sorted(set(motion_blur) - {"exposure", "max_radius", "taps", "soft"})
+            if unknown:
+                raise ValueError("Renderer(motion_blur=...) takes the keys 'exposure', 'max_radius', 'taps' and 'soft': "
+                                 f"{unknown} unknown")
+            self.motion_blur = dict(motion_blur)
         # normal_map=None (default): the light sees the interpolated vertex normals.  A dict of
         # AdvancedPixelBufferFiller.bind_normal_map's arguments but the uv (``normal_map`` or ``height``, ``scale``, ``wrap``,
         # ``mipmaps``) and of normal_map_pass's (``strength``, ``perspective``, ``filter``; "trilinear" binds the map with
@@ -321,7 +347,7 @@ class Renderer:
         if self.texture_pass is None:
             if self.shadow is None and self.ambient_occlusion is None and self.wireframe is None and self.antialias is None \
                     and self.normal_map is None and self.environment is None and self.depth_of_field is None \
-                    and self.transparency is None:
+                    and self.transparency is None and self.motion_blur is None:
                 return filler.render_model(model, **kw)
             if not kw.get("clear"):        # (the "fused" caller asks for the cleared frame itself: its raster kernel shades)
                 filler.set_fused_illumination(None)
@@ -478,6 +504,10 @@ class Renderer:
             # the frame as ever, then the lens, last of all: the pass's own tensor is the image
             self._render(model)
             image = self.pixel_buffer_filler.depth_of_field(**self.depth_of_field)
+        elif self.motion_blur is not None:
+            # the frame as ever, then the shutter, last of all: the pass's own tensor is the image
+            self._render(model)
+            image = self._shutter(model)
         elif self.antialias is not None:
             # the frame as ever, then the edges smoothed, last of all: the pass's own tensor is the image
             self._render(model)
@@ -580,6 +610,27 @@ class Renderer:
         self._draw_wire(model)
         image = filler.resolve(s)
         return image if self.bloom is not None else image.cpu().numpy()      # (bloom reads the resolve's tensor)
+
+    def _shutter(self, model):
+        """The motion-blur pass over the frame just drawn, against the pose of the call before; keeps this call's pose."""
+        import torch
+        v = model._vertices_by_triangles
+        device = getattr(self.pixel_buffer_filler, "device", None)
+        if isinstance(v, torch.Tensor):
+            current = v.detach().to(device=v.device if device is None else device, copy=True)
+        else:
+            current = torch.from_numpy(np.array(v, copy=True))
+            if device is not None:
+                current = current.to(device)
+        previous = self._previous_pose
+        if previous is None or previous.shape[0] != current.shape[0]:
+            previous = current         # a static pose: the frame, copied
+        self._previous_pose = current
+        return self.pixel_buffer_filler.motion_blur(previous, **self.motion_blur)
+
+    def reset_motion(self):
+        """Forget the previous pose: the next ``render`` under ``motion_blur`` returns its frame unblurred (a camera cut)."""
+        self._previous_pose = None
 
     def reset_buffers(self):
         pass   # a no-op in the reference too (renderer.py:51-52): renders composite
