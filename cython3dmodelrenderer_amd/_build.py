@@ -18,9 +18,9 @@ LIB_PATH = os.path.join(_HERE, "libcrender_hip.so")
 SOURCES = ["abi.hip", "binning.hip", "raster.hip", "model_ops.hip"]
 HEADERS = ["common.h", "binning.h", "plan.h", "raster_math.h", os.path.join("..", "..", "include", "crender_hip.h")]
 _INCLUDE = os.path.join("..", "..", "include")
-# The other units of the library, in link order: name -> (sources, headers).  All are linked into the same library
-# but kept out of source_sha16(): that fingerprint names the kernels the committed profiles/*.json were measured on,
-# and these kernels are none of them.  _capi.UNIT_SIGNATURES is keyed alike.
+# The other units of the library, in link order (which decides the library's bytes): name -> (sources, headers).  All are
+# linked into the same library but kept out of source_sha16(): that fingerprint names the kernels the committed
+# profiles/*.json were measured on, and these kernels are none of them.  _capi.UNIT_SIGNATURES is keyed alike.
 UNITS = {
     # wireframe.hip  EdgeOnlyPixelBufferFiller, and the line passes over the winner plane: overlay, outline, edge
     # anti-aliasing, contours, hidden lines, runs (include/crender_wire.h)
@@ -53,28 +53,19 @@ UNITS = {
     # ao.hip  the deferred ambient-occlusion pass over the z, winner and normal planes (include/crender_ao.h)
     "ao": (["ao.hip"], [os.path.join(_INCLUDE, "crender_ao.h")]),
     # winner_pass.h  what the deferred passes over the winner plane share (texture.hip, texmip.hip, texaniso.hip,
-    # shadow.hip, phong.hip, ao.hip, wireframe.hip, bloom.hip, peel.hip, dof.hip, normal_map.hip, envmap.hip): the
-    # winner's triangle projected and the host's frame checks; the per-pixel frame, the store with the fused light, the
-    # texel fetches and the launch geometry; the tile frame and the tile grid; a unit of its own, without a source, so
-    # that each pass's header list stays its own.
+    # shadow.hip, phong.hip, ao.hip, wireframe.hip, bloom.hip, peel.hip, dof.hip, normal_map.hip, envmap.hip,
+    # motion.hip): the winner's triangle projected and the host's frame checks; the per-pixel frame, the store with the
+    # fused light, the texel fetches and the launch geometry; the tile frame and the tile grid; a unit of its own,
+    # without a source, so that each pass's header list stays its own.
     "pass": ([], ["winner_pass.h"]),
     # chain.hip  the swap chain's shared slot: one slot on the caller's stream (include/crender_chain.h; host code
     # only, over the pipeline handle of plan.h): it launches nothing.
     "chain": (["chain.hip"], [os.path.join(_INCLUDE, "crender_chain.h")]),
-}
-# Frame kernels that stand in for one path of the fingerprinted k_frame, in link order behind the units above:
-# name -> (sources, headers), outside source_sha16() like them.  A table of its own: UNITS and library_sources() are
-# what the feature units' tests pin, name for name; link_sources() is what the library is built from.
-#   frame32.hip  the swap chain's frame kernel for small scenes on 32-pixel tiles (include/crender_frame32.h): one
-#                path of k_frame's, over the same plans and the arithmetic of raster_math.h
-FRAME_UNITS = {
+    # frame32.hip  the swap chain's frame kernel for small scenes on 32-pixel tiles (include/crender_frame32.h): it stands
+    # in for one path of the fingerprinted k_frame, over the same plans and the arithmetic of raster_math.h
     "frame32": (["frame32.hip"], [os.path.join(_INCLUDE, "crender_frame32.h")]),
-}
-# The feature units added since the two tables above were pinned by their tests, in link order behind them:
-# name -> (sources, headers), outside source_sha16() like them.  all_sources() is what the library is built from.
-#   motion.hip  per-pixel motion vectors against an earlier pose, and the motion blur that gathers along them
-#               (include/crender_motion.h)
-MORE_UNITS = {
+    # motion.hip  per-pixel motion vectors against an earlier pose, and the motion blur that gathers along them
+    # (include/crender_motion.h)
     "motion": (["motion.hip"], [os.path.join(_INCLUDE, "crender_motion.h")]),
 }
 
@@ -123,16 +114,6 @@ def library_sources() -> list:
     return SOURCES + [src for sources, _ in UNITS.values() for src in sources]
 
 
-def link_sources() -> list:
-    """Every translation unit linked into the library: library_sources(), then the frame kernels' (FRAME_UNITS)."""
-    return library_sources() + [src for sources, _ in FRAME_UNITS.values() for src in sources]
-
-
-def all_sources() -> list:
-    """Everything linked into the library: link_sources(), then the later feature units' (MORE_UNITS)."""
-    return link_sources() + [src for sources, _ in MORE_UNITS.values() for src in sources]
-
-
 def build_inputs() -> list:
     """Paths of everything whose change makes the library stale: the fingerprinted sources and headers, every unit's
     sources and headers, and this file (the flags).  A header that two units list is named once."""
@@ -140,23 +121,11 @@ def build_inputs() -> list:
     return [os.path.join(SRC_DIR, name) for name in dict.fromkeys(names)] + [os.path.abspath(__file__)]
 
 
-def frame_inputs() -> list:
-    """Paths of the frame kernels' sources and headers (FRAME_UNITS): build() counts them like build_inputs()."""
-    names = [name for sources, headers in FRAME_UNITS.values() for name in sources + headers]
-    return [os.path.join(SRC_DIR, name) for name in dict.fromkeys(names)]
-
-
-def more_inputs() -> list:
-    """Paths of the later feature units' sources and headers (MORE_UNITS): build() counts them like build_inputs()."""
-    names = [name for sources, headers in MORE_UNITS.values() for name in sources + headers]
-    return [os.path.join(SRC_DIR, name) for name in dict.fromkeys(names)]
-
-
-def needs_build(inputs=None) -> bool:
+def needs_build() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     built = os.path.getmtime(LIB_PATH)
-    return any(os.path.getmtime(d) > built for d in (build_inputs() if inputs is None else inputs))
+    return any(os.path.getmtime(d) > built for d in build_inputs())
 
 
 def compile_library(out: str, extra_flags=(), sources=None, src_dir: str = SRC_DIR, verbose: bool = False,
@@ -165,7 +134,7 @@ def compile_library(out: str, extra_flags=(), sources=None, src_dir: str = SRC_D
     defines of diagnostic builds (-DCRENDER_STAMPS, ...)."""
     import tempfile
     from concurrent.futures import ThreadPoolExecutor
-    sources = list(sources or all_sources())
+    sources = list(sources or library_sources())
     err = subprocess.DEVNULL if quiet else None
     with tempfile.TemporaryDirectory(prefix="crender_build_") as tmp:
         objs = [os.path.join(tmp, os.path.splitext(s)[0] + ".o") for s in sources]
@@ -196,7 +165,7 @@ def compile_library(out: str, extra_flags=(), sources=None, src_dir: str = SRC_D
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Build libcrender_hip.so if missing or stale; returns its path."""
-    if not force and not needs_build() and not needs_build(frame_inputs()) and not needs_build(more_inputs()):
+    if not force and not needs_build():
         return LIB_PATH
     return compile_library(LIB_PATH, verbose=verbose)
 

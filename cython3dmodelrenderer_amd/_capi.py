@@ -247,26 +247,22 @@ UNIT_SIGNATURES["chain"] = {
     "crender_pipeline_owned_streams": (_i32, [_vp]),
 }
 
-# the frame kernels that stand in for one path of k_frame (_build.FRAME_UNITS, keyed alike): the swap chain's frame
-# kernel for small scenes (include/crender_frame32.h)
-FRAME_SIGNATURES = {
-    "frame32": {
-        "crender_frame32_submit": (_i32, [_vp, _vp]),
-        "crender_frame32_last": (_i32, [_vp]),
-    },
+# the swap chain's frame kernel for small scenes (include/crender_frame32.h), bound from a table of its own: it stands in
+# for one path of k_frame
+UNIT_SIGNATURES["frame32"] = {
+    "crender_frame32_submit": (_i32, [_vp, _vp]),
+    "crender_frame32_last": (_i32, [_vp]),
 }
 
-# the feature units of _build.MORE_UNITS, keyed alike: motion vectors and motion blur (include/crender_motion.h;
-# DeferredPasses.motion_vectors, motion_blur): the overlay's frame, then the previous pose, the exposure and the velocity
+# motion vectors and motion blur (include/crender_motion.h), bound from a table of their own
+# (DeferredPasses.motion_vectors, motion_blur): the overlay's frame, then the previous pose, the exposure and the velocity
 # plane; and the lens's frame, then the colour and the velocity planes, the largest radius, the taps, the depth range, the result
 MOTION_MAX_RADIUS = 12
 MOTION_MAX_TAPS = 32
-MORE_SIGNATURES = {
-    "motion": {
-        "crender_motion_vectors": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, C.c_float, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
-        "crender_motion_blur": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _i32, C.c_float, _vp,
-                                       _i32, _i32, _i32, _i32, _u32, _vp]),
-    },
+UNIT_SIGNATURES["motion"] = {
+    "crender_motion_vectors": (_i32, [_vp, _vp, _i64, _vp, _f32p, _vp, C.c_float, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
+    "crender_motion_blur": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32p, _vp, _vp, _i32, _i32, C.c_float, _vp,
+                                   _i32, _i32, _i32, _i32, _u32, _vp]),
 }
 
 _lib = None
@@ -292,7 +288,7 @@ def load():
             f"{path} is missing: build it with `python -m cython3dmodelrenderer_amd._build` "
             "(or __graft_entry__.build()).  There is no CPU fallback for the rasterizer.")
     L = C.CDLL(path)
-    for table in (SIGNATURES, *UNIT_SIGNATURES.values(), *FRAME_SIGNATURES.values(), *MORE_SIGNATURES.values()):
+    for table in (SIGNATURES, *UNIT_SIGNATURES.values()):
         for name, (res, args) in table.items():
             fn = getattr(L, name)      # AttributeError if the library lacks a declared symbol
             fn.restype = res

@@ -171,12 +171,7 @@ int crender_ao_shade(const int32_t *d_winner, const float *d_z, const float *d_t
         return arg_error(E, "min_cos, strength or floor is not finite");
     if (strength < 0.0f) return arg_error(E, "strength is negative");
     if (floor < 0.0f || floor > 1.0f) return arg_error(E, "floor is not 0 .. 1");
-    for (int i : {1, 2, 4, 6, 8, 9, 12, 13})
-        if (!(P16[i] == 0.0f))
-            return arg_error(E, "P16 is not of crender_projection_matrix's shape (an entry that must be 0 is not)");
-    for (int i : {0, 5, 14})
-        if (!isfinite(P16[i]) || P16[i] == 0.0f)
-            return arg_error(E, "P16 is not of crender_projection_matrix's shape (entry 0, 5 or 14 is 0 or not finite)");
+    if (int rc = projection_shape_check(E, P16)) return rc;
     if (T == 0) return CRENDER_OK;
     const ProjConst P = make_proj(P16, W, H);
     AoParams A{};

@@ -289,12 +289,7 @@ int crender_motion_blur(const int32_t *d_winner, const float *d_z, const float *
     if (int rc = rows_check(E, H, y0, y1)) return rc;
     if (flags) return arg_error(E, "unknown flag bits");
     if (d_out == d_color) return arg_error(E, "d_out is d_color (the pass cannot run in place)");
-    for (int i : {1, 2, 4, 6, 8, 9, 12, 13})
-        if (!(P16[i] == 0.0f))
-            return arg_error(E, "P16 is not of crender_projection_matrix's shape (an entry that must be 0 is not)");
-    for (int i : {0, 5, 14})
-        if (!isfinite(P16[i]) || P16[i] == 0.0f)
-            return arg_error(E, "P16 is not of crender_projection_matrix's shape (entry 0, 5 or 14 is 0 or not finite)");
+    if (int rc = projection_shape_check(E, P16)) return rc;
     if (max_radius < 1 || max_radius > CRENDER_MOTION_MAX_RADIUS) return arg_error(E, "max_radius is not 1 .. 12");
     if (taps < 1 || taps > CRENDER_MOTION_MAX_TAPS) return arg_error(E, "taps is not 1 .. 32");
     if (!isfinite(soft) || !(soft > 0.0f)) return arg_error(E, "soft is not finite and positive");

@@ -1,6 +1,6 @@
 // winner_pass.h — what the deferred passes over the winner plane share (texture.hip, texmip.hip and texaniso.hip, the
 // last two also through mip_sample.h; shadow.hip, phong.hip, ao.hip, wireframe.hip, bloom.hip, peel.hip, dof.hip,
-// normal_map.hip, envmap.hip): the winner's triangle projected and the host's frame checks, then what the per-pixel
+// normal_map.hip, envmap.hip, motion.hip): the winner's triangle projected and the host's frame checks, then what the per-pixel
 // passes share, then what the neighbourhood passes share.  Each translation unit gets its own copy (anonymous
 // namespace); include after common.h and `using namespace crender_detail;`.
 #pragma once
@@ -53,6 +53,18 @@ inline int frame_checks(const char *entry, int64_t T, bool have_tri, int H, int 
 inline int rows_check(const char *entry, int H, int y0, int y1)
 {
     return (y0 < 0 || y1 > H || y0 >= y1) ? arg_error(entry, "rows outside the frame") : CRENDER_OK;
+}
+
+// P16 has crender_projection_matrix's shape: what a pass that rebuilds view depths from the z plane relies on.
+inline int projection_shape_check(const char *entry, const float *P16)
+{
+    for (int i : {1, 2, 4, 6, 8, 9, 12, 13})
+        if (!(P16[i] == 0.0f))
+            return arg_error(entry, "P16 is not of crender_projection_matrix's shape (an entry that must be 0 is not)");
+    for (int i : {0, 5, 14})
+        if (!std::isfinite(P16[i]) || P16[i] == 0.0f)       // <cmath>'s, which common.h brings to every unit
+            return arg_error(entry, "P16 is not of crender_projection_matrix's shape (entry 0, 5 or 14 is 0 or not finite)");
+    return CRENDER_OK;
 }
 
 // ---- per-pixel passes ---------------------------------------------------------------------------------------------

@@ -14,7 +14,7 @@ import pytest
 import aniso_ref
 import mip_ref
 from pass_scenes import capi, trex_textured  # noqa: F401 (fixtures)
-from util import assert_bit_equal, other_symbols
+from util import INCLUDE, assert_bit_equal, other_symbols, unit_in_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -54,17 +54,13 @@ def test_aniso_header_symbol_is_exported_and_bound(capi):
 
 def test_aniso_sources_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert _build.UNITS["aniso"][0] == ["texaniso.hip"] and _build.UNITS["mip"][0] == ["texmip.hip"]
-    fingerprinted = _build.SOURCES + _build.HEADERS
-    assert not set(_build.UNITS["aniso"][0] + _build.UNITS["aniso"][1]) & set(fingerprinted)
-    assert not any("aniso" in name or "mip" in name for name in fingerprinted)
-    assert any(h.endswith("crender_aniso.h") for h in _build.UNITS["aniso"][1])
+    unit_in_build(_build, "aniso", ["texaniso.hip"], [os.path.join(INCLUDE, "crender_aniso.h"), "mip_sample.h"])
+    assert _build.UNITS["mip"][0] == ["texmip.hip"]
+    assert not any("mip" in name for name in _build.SOURCES + _build.HEADERS)
     # what the pass shares with texmip.hip is watched by both and by nothing else
     shared = set(_build.UNITS["aniso"][1]) & set(_build.UNITS["mip"][1])
     assert shared == {"mip_sample.h"}
     assert not shared & set(_build.UNITS["wire"][1] + _build.UNITS["py"][1] + _build.UNITS["tex"][1])
-    for name in _build.UNITS["aniso"][0] + _build.UNITS["aniso"][1]:
-        assert os.path.exists(os.path.join(_build.SRC_DIR, name)), name
 
 
 def test_aniso_argument_errors_without_a_gpu(capi):

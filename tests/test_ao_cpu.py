@@ -13,7 +13,7 @@ import pytest
 
 import ao_ref
 from pass_scenes import Frame, capi, trex_fixture  # noqa: F401 (fixtures)
-from util import assert_bit_equal, other_symbols, unit_inputs
+from util import INCLUDE, assert_bit_equal, other_symbols, unit_in_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TABLE = [(1, 0), (-2, 2), (0, -3), (2, 3), (-4, -1), (4, -3), (-1, 5), (-3, -5), (5, 2), (-6, 2), (3, -6), (2, 6), (-6, -4),
@@ -49,17 +49,7 @@ def test_ao_header_symbol_is_exported_and_bound(capi):
 
 def test_ao_sources_are_built_and_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert _build.UNITS["ao"][0] == ["ao.hip"]
-    assert len(_build.UNITS["ao"][1]) == 1 and _build.UNITS["ao"][1][0].endswith("crender_ao.h")
-    fingerprinted = _build.SOURCES + _build.HEADERS
-    assert not set(_build.UNITS["ao"][0] + _build.UNITS["ao"][1]) & set(fingerprinted)
-    assert not any("ao." in name for name in fingerprinted)
-    assert _build.source_sha16() == "35a9bf480abfca1e"
-    for name in _build.UNITS["ao"][0] + _build.UNITS["ao"][1]:
-        assert os.path.exists(os.path.join(_build.SRC_DIR, name)), name
-    # the default build compiles the unit, and a change of it makes the library stale
-    assert set(_build.UNITS["ao"][0]) <= set(_build.library_sources())
-    assert unit_inputs(_build, "ao") <= set(_build.build_inputs())
+    unit_in_build(_build, "ao", ["ao.hip"], [os.path.join(INCLUDE, "crender_ao.h")])
     # the kernel takes the shared pieces by inclusion, stages in LDS behind barriers and has no inline assembly
     unit = open(os.path.join(_build.SRC_DIR, "ao.hip")).read()
     for name in ("make_proj(", "wave_any(", "gather_corners("):

@@ -7,7 +7,7 @@ import re
 import subprocess
 
 from pass_scenes import capi  # noqa: F401 (fixtures)
-from util import other_symbols, unit_inputs
+from util import INCLUDE, other_symbols, unit_in_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -36,17 +36,7 @@ def test_chain_header_symbols_are_exported_and_bound(capi):
 
 def test_chain_sources_are_built_and_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert _build.UNITS["chain"][0] == ["chain.hip"]
-    assert len(_build.UNITS["chain"][1]) == 1 and _build.UNITS["chain"][1][0].endswith("crender_chain.h")
-    fingerprinted = _build.SOURCES + _build.HEADERS
-    assert not set(_build.UNITS["chain"][0] + _build.UNITS["chain"][1]) & set(fingerprinted)
-    assert not any("chain" in name for name in fingerprinted)
-    assert _build.source_sha16() == "35a9bf480abfca1e"
-    for name in _build.UNITS["chain"][0] + _build.UNITS["chain"][1]:
-        assert os.path.exists(os.path.join(_build.SRC_DIR, name)), name
-    # the default build compiles the unit, and a change of it makes the library stale
-    assert set(_build.UNITS["chain"][0]) <= set(_build.library_sources())
-    assert unit_inputs(_build, "chain") <= set(_build.build_inputs())
+    unit_in_build(_build, "chain", ["chain.hip"], [os.path.join(INCLUDE, "crender_chain.h")])
     # host code over the pipeline handle of plan.h: no kernel, no launch
     unit = open(os.path.join(_build.SRC_DIR, "chain.hip")).read()
     assert '#include "plan.h"' in unit

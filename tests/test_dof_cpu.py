@@ -67,7 +67,8 @@ def test_dof_sources_are_built_and_stay_out_of_the_profile_fingerprint():
     taps = body[body.index("for (int dy = -Rt"):body.index("if (!inside) continue;")]
     code = "".join(line.split("//")[0] for line in taps.splitlines())
     assert "/" not in code and "sqrtf" not in code and "wave_any(take[0]" in code
-    assert new.index("frame_checks(E") < new.index("rows_check(E") < new.index("P16[i]") < new.index("focus is not")
+    shape = new.index("projection_shape_check(E, P16)")          # winner_pass.h's, shared with ao.hip and motion.hip
+    assert new.index("frame_checks(E") < new.index("rows_check(E") < shape < new.index("focus is not")
 
 
 def test_dof_argument_errors_without_a_gpu(capi):

@@ -44,22 +44,30 @@ def test_library_units_are_one_table_for_the_build_and_the_binding():
         assert os.path.isfile(path), path
     want = _build.SOURCES + _build.HEADERS + [name for unit in _build.UNITS.values() for name in unit[0] + unit[1]]
     assert set(inputs) == {os.path.join(_build.SRC_DIR, name) for name in want} | {os.path.abspath(_build.__file__)}
+    # ... and the only one: a unit kept in a table beside these fails here
+    for mod, tables in ((_build, {"UNITS"}), (_capi, {"SIGNATURES", "UNIT_SIGNATURES"})):
+        public = {name for name in vars(mod) if not name.startswith("_")}
+        assert {name for name in public if name.endswith(("UNITS", "SIGNATURES"))} == tables, mod.__name__
 
 
 def test_the_library_is_stale_when_any_build_input_is_newer(tmp_path, monkeypatch):
     from cython3dmodelrenderer_amd import _build
     lib = tmp_path / "libcrender_hip.so"
     monkeypatch.setattr(_build, "LIB_PATH", str(lib))
+    built = []
+    monkeypatch.setattr(_build, "compile_library", lambda out, **kw: built.append(out) or out)
     assert _build.needs_build()                    # no library at all
     lib.write_bytes(b"")
     inputs = _build.build_inputs()
     newest = max(os.path.getmtime(path) for path in inputs)
     os.utime(lib, (newest + 1, newest + 1))
     assert not _build.needs_build()
+    assert _build.build() == str(lib) and built == []                 # a fresh library is not compiled again
     for path in inputs:
         then = os.path.getmtime(path) - 1
         os.utime(lib, (then, then))
         assert _build.needs_build(), path
+    assert _build.build() == str(lib) and built == [str(lib)]         # a stale one is, and build() returns its path
 
 
 def test_torch_extension_is_built_and_bound():

@@ -1,5 +1,5 @@
 """Motion vectors and motion blur without a GPU: the header against the binding and the library, the unit's place in the
-build (a third table beside the two the other tests pin), the entry points' argument checks, the host model the GPU tests
+build, the entry points' argument checks, the host model the GPU tests
 compare with (tests/motion_ref.py) pinned by hand-made scenes, against its own float64 evaluation and against the oracle's
 frame of the previous pose; ``AdvancedPixelBufferFiller.motion_vectors`` / ``motion_blur``'s protocol on CPU tensors and
 ``Renderer(motion_blur=...)``."""
@@ -16,7 +16,7 @@ import torch
 
 import motion_ref
 from pass_scenes import Frame, capi, oracle_frame, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
-from util import LIBRARY_SOURCES, UNIT_KEYS, assert_bit_equal, other_symbols
+from util import assert_bit_equal, other_symbols, own_unit_source
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VECTORS, BLUR = "crender_motion_vectors", "crender_motion_blur"
@@ -31,12 +31,11 @@ BLUR_ARGTYPES = [_vp, _vp, _vp, C.c_int64, _vp, _f32p, _vp, _vp, _i32, _i32, _f,
 def test_motion_symbols_are_declared_exported_and_bound(capi):
     header = open(os.path.join(ROOT, "include", "crender_motion.h")).read()
     declared = set(re.findall(r"CRENDER_API[^;(]*?\b(crender_\w+)\s*\(", header))
-    assert declared == set(capi.MORE_SIGNATURES["motion"]) == {VECTORS, BLUR}
-    assert not declared & other_symbols(capi, None)
-    assert not declared & {n for table in capi.FRAME_SIGNATURES.values() for n in table}
+    assert declared == set(capi.UNIT_SIGNATURES["motion"]) == {VECTORS, BLUR}
+    assert not declared & other_symbols(capi, "motion")
     L = capi.load()
     for name, want in ((VECTORS, VECTORS_ARGTYPES), (BLUR, BLUR_ARGTYPES)):
-        res, args = capi.MORE_SIGNATURES["motion"][name]
+        res, args = capi.UNIT_SIGNATURES["motion"][name]
         assert res == C.c_int and args == want == getattr(L, name).argtypes, name
     decl = {n: [" ".join(a.split()) for a in re.search(r"CRENDER_API int " + n + r"\((.*?)\);", header, re.S).group(1).split(",")]
             for n in (VECTORS, BLUR)}
@@ -61,29 +60,10 @@ def test_motion_symbols_are_declared_exported_and_bound(capi):
     assert capi.ABI_VERSION == 6                                  # the change is additive
 
 
-def test_motion_unit_is_built_from_a_third_table_and_the_pinned_ones_are_as_they_were():
-    from cython3dmodelrenderer_amd import _build, _capi
-    inc = os.path.join("..", "..", "include")
-    assert _build.MORE_UNITS == {"motion": (["motion.hip"], [os.path.join(inc, "crender_motion.h")])}
-    assert list(_capi.MORE_SIGNATURES) == list(_build.MORE_UNITS)
-    # what the other tests pin, name for name
-    assert list(_build.UNITS) == UNIT_KEYS and _build.library_sources() == LIBRARY_SOURCES
-    assert list(_build.FRAME_UNITS) == ["frame32"] and _build.link_sources() == LIBRARY_SOURCES + ["frame32.hip"]
-    assert _build.source_sha16() == "35a9bf480abfca1e"
-    assert "motion" not in _build.UNITS and "motion" not in _capi.UNIT_SIGNATURES and "motion" not in _capi.FRAME_SIGNATURES
-    # everything linked, and the default of compile_library
-    assert _build.all_sources() == _build.link_sources() + ["motion.hip"]
-    assert "sources or all_sources()" in inspect.getsource(_build.compile_library)
-    paths = {os.path.join(_build.SRC_DIR, n) for n in ("motion.hip", os.path.join(inc, "crender_motion.h"))}
-    assert set(_build.more_inputs()) == paths and all(os.path.exists(p) for p in paths)
-    assert not paths & set(_build.build_inputs()) and not paths & set(_build.frame_inputs())
-    fingerprinted = _build.SOURCES + _build.HEADERS
-    assert not any("motion" in name for name in fingerprinted)
-    # the four includes of a pass, in dof.hip's order
-    text = open(os.path.join(_build.SRC_DIR, "motion.hip")).read()
-    includes = [line.split()[1] for line in text.splitlines() if line.startswith("#include")]
-    assert includes == ["<math.h>", '"common.h"', '"../../include/crender_motion.h"', '"winner_pass.h"'], includes
-    assert text.index('"common.h"') < text.index("using namespace crender_detail;") < text.index('"winner_pass.h"')
+def test_motion_sources_are_built_and_stay_out_of_the_profile_fingerprint():
+    from cython3dmodelrenderer_amd import _build
+    # the unit's place in the build, and the four includes of a pass, in dof.hip's order
+    text = own_unit_source(_build, "motion", "motion.hip", "crender_motion.h")
     assert text.count("namespace {") == 1 and text.count('extern "C" {') == 1 and "asm" not in text
     assert text.index("void k_motion_vectors") < text.index("void k_motion_blur") < text.index("int crender_motion_vectors(")
     # the blur: one staging barrier, one behind the tap table and one at the end of a tile; no tap divides or takes a root
@@ -95,22 +75,6 @@ def test_motion_unit_is_built_from_a_third_table_and_the_pinned_ones_are_as_they
     # the host checks R, N and the LDS size before the launch
     entry = text[text.index("int crender_motion_blur("):]
     assert entry.index("max_radius is not") < entry.index("taps is not") < entry.index("lds > 65536") < entry.index("hipLaunchKernelGGL")
-
-
-def test_the_library_is_stale_when_the_unit_is_newer(capi):
-    from cython3dmodelrenderer_amd import _build
-    assert "needs_build(more_inputs())" in inspect.getsource(_build.build)
-    assert not _build.needs_build(_build.more_inputs())
-    built = os.path.getmtime(_build.LIB_PATH)
-    for path in _build.more_inputs():
-        keep = os.stat(path)
-        try:
-            os.utime(path, (built + 10, built + 10))
-            assert _build.needs_build(_build.more_inputs()), path
-            assert not _build.needs_build() and not _build.needs_build(_build.frame_inputs())
-        finally:
-            os.utime(path, ns=(keep.st_atime_ns, keep.st_mtime_ns))
-    assert not _build.needs_build(_build.more_inputs())
 
 
 def _matrix(capi):

@@ -12,7 +12,7 @@ import pytest
 
 import phong_ref
 from pass_scenes import Frame, capi, trex_fixture  # noqa: F401 (fixtures)
-from util import assert_bit_equal, other_symbols, unit_inputs
+from util import INCLUDE, assert_bit_equal, other_symbols, unit_in_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GURO = (0.3, -0.2, 1.0)              # what GuroIllumination is constructed with
@@ -47,17 +47,7 @@ def test_phong_header_symbol_is_exported_and_bound(capi):
 
 def test_phong_sources_are_built_and_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert _build.UNITS["phong"][0] == ["phong.hip"]
-    assert len(_build.UNITS["phong"][1]) == 1 and _build.UNITS["phong"][1][0].endswith("crender_phong.h")
-    fingerprinted = _build.SOURCES + _build.HEADERS
-    assert not set(_build.UNITS["phong"][0] + _build.UNITS["phong"][1]) & set(fingerprinted)
-    assert not any("phong" in name for name in fingerprinted)
-    assert _build.source_sha16() == "35a9bf480abfca1e"
-    for name in _build.UNITS["phong"][0] + _build.UNITS["phong"][1]:
-        assert os.path.exists(os.path.join(_build.SRC_DIR, name)), name
-    # the default build compiles the unit, and a change of it makes the library stale
-    assert set(_build.UNITS["phong"][0]) <= set(_build.library_sources())
-    assert unit_inputs(_build, "phong") <= set(_build.build_inputs())
+    unit_in_build(_build, "phong", ["phong.hip"], [os.path.join(INCLUDE, "crender_phong.h")])
     # the kernel takes the rasterizer's arithmetic and the passes' frame from the shared headers by inclusion
     unit = open(os.path.join(_build.SRC_DIR, "phong.hip")).read()
     # (the gather and the projection of the winner's corners are the header's winner_triangle)

@@ -11,7 +11,7 @@ import pytest
 
 import shadow_ref
 from pass_scenes import capi  # noqa: F401 (fixtures)
-from util import assert_bit_equal, other_symbols, unit_inputs
+from util import INCLUDE, assert_bit_equal, other_symbols, unit_in_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -40,17 +40,7 @@ def test_shadow_header_symbol_is_exported_and_bound(capi):
 
 def test_shadow_sources_are_built_and_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert _build.UNITS["shadow"][0] == ["shadow.hip"]
-    assert len(_build.UNITS["shadow"][1]) == 1 and _build.UNITS["shadow"][1][0].endswith("crender_shadow.h")
-    fingerprinted = _build.SOURCES + _build.HEADERS
-    assert not set(_build.UNITS["shadow"][0] + _build.UNITS["shadow"][1]) & set(fingerprinted)
-    assert not any("shadow" in name for name in fingerprinted)
-    assert _build.source_sha16() == "35a9bf480abfca1e"
-    for name in _build.UNITS["shadow"][0] + _build.UNITS["shadow"][1]:
-        assert os.path.exists(os.path.join(_build.SRC_DIR, name)), name
-    # the default build compiles the unit, and a change of it makes the library stale
-    assert set(_build.UNITS["shadow"][0]) <= set(_build.library_sources())
-    assert unit_inputs(_build, "shadow") <= set(_build.build_inputs())
+    unit_in_build(_build, "shadow", ["shadow.hip"], [os.path.join(INCLUDE, "crender_shadow.h")])
     # the kernel takes the rasterizer's arithmetic from the fingerprinted headers by inclusion
     unit = open(os.path.join(_build.SRC_DIR, "shadow.hip")).read()
     for name in ("project_vertex(", "barycentric(", "make_proj(", "wave_any("):

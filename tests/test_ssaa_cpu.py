@@ -15,7 +15,7 @@ import torch
 
 import ssaa_ref
 from pass_scenes import capi  # noqa: F401 (fixtures)
-from util import assert_bit_equal, other_symbols, unit_inputs
+from util import INCLUDE, assert_bit_equal, other_symbols, unit_in_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -45,17 +45,7 @@ def test_ssaa_header_symbol_is_exported_and_bound(capi):
 
 def test_ssaa_sources_are_built_and_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert _build.UNITS["ssaa"][0] == ["resolve.hip"]
-    assert len(_build.UNITS["ssaa"][1]) == 1 and _build.UNITS["ssaa"][1][0].endswith("crender_ssaa.h")
-    fingerprinted = _build.SOURCES + _build.HEADERS
-    assert not set(_build.UNITS["ssaa"][0] + _build.UNITS["ssaa"][1]) & set(fingerprinted)
-    assert not any("ssaa" in name or "resolve" in name for name in fingerprinted)
-    assert _build.source_sha16() == "35a9bf480abfca1e"
-    for name in _build.UNITS["ssaa"][0] + _build.UNITS["ssaa"][1]:
-        assert os.path.exists(os.path.join(_build.SRC_DIR, name)), name
-    # the default build compiles the unit, and a change of it makes the library stale
-    assert set(_build.UNITS["ssaa"][0]) <= set(_build.library_sources())
-    assert unit_inputs(_build, "ssaa") <= set(_build.build_inputs())
+    unit_in_build(_build, "ssaa", ["resolve.hip"], [os.path.join(INCLUDE, "crender_ssaa.h")])
     # the units the other passes pin stay as they were
     assert _build.UNITS["aniso"][0] == ["texaniso.hip"] and _build.UNITS["mip"][0] == ["texmip.hip"]
     # the kernel takes the light's factor from raster_math.h by inclusion

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from pass_scenes import capi, wire_golden  # noqa: F401 (fixtures)
-from util import other_symbols, sha
+from util import INCLUDE, other_symbols, sha, unit_in_build
 from wire_ref import HostImage, line_pixels, wire_plane
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -141,8 +141,7 @@ def test_wire_header_symbols_are_exported_and_bound(capi):
 
 def test_wire_sources_stay_out_of_the_profile_fingerprint():
     from cython3dmodelrenderer_amd import _build
-    assert "wireframe.hip" in _build.UNITS["wire"][0] and "wireframe.hip" not in _build.SOURCES
-    assert not any("crender_wire" in h for h in _build.HEADERS)
+    unit_in_build(_build, "wire", ["wireframe.hip"], [os.path.join(INCLUDE, "crender_wire.h")])
 
 
 def test_wire_argument_errors_without_a_gpu(capi):

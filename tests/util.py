@@ -43,26 +43,35 @@ def unit_inputs(_build, unit):
 # The library's units and its translation units in link order, name for name: what the units' tests pin _build.UNITS and
 # _build.library_sources() against.  A new unit is one name in each.
 UNIT_KEYS = ["wire", "bloom", "peel", "dof", "nmap", "env", "py", "tex", "mip", "aniso", "ssaa", "shadow", "phong", "ao",
-             "pass", "chain"]
+             "pass", "chain", "frame32", "motion"]
 LIBRARY_SOURCES = ["abi.hip", "binning.hip", "raster.hip", "model_ops.hip", "wireframe.hip", "bloom.hip", "peel.hip",
                    "dof.hip", "normal_map.hip", "envmap.hip", "pyfill.hip", "texture.hip", "texmip.hip", "texaniso.hip",
-                   "resolve.hip", "shadow.hip", "phong.hip", "ao.hip", "chain.hip"]
+                   "resolve.hip", "shadow.hip", "phong.hip", "ao.hip", "chain.hip", "frame32.hip", "motion.hip"]
+INCLUDE = os.path.join("..", "..", "include")          # the public headers, as _build.UNITS names them from csrc/
+
+
+def unit_in_build(_build, unit, sources, headers):
+    """Asserts `unit`'s place in the build: exactly these sources and headers (as _build.UNITS names them), all of them
+    there; none of it, by path or by stem (a header's without its crender_), in the profile fingerprint, which is the
+    committed profiles'; compiled by the default build, and a change of any of it makes the library stale."""
+    assert list(_build.UNITS) == UNIT_KEYS and _build.library_sources() == LIBRARY_SOURCES
+    assert _build.UNITS[unit] == (sources, headers)
+    fingerprinted = _build.SOURCES + _build.HEADERS
+    assert not set(sources + headers) & set(fingerprinted)
+    stems = {os.path.splitext(os.path.basename(name))[0] for name in sources + headers}
+    stems |= {stem[len("crender_"):] for stem in stems if stem.startswith("crender_")}
+    assert not any(stem in name for stem in stems for name in fingerprinted)
+    assert _build.source_sha16() == "35a9bf480abfca1e"
+    for path in unit_inputs(_build, unit):
+        assert os.path.exists(path), path
+    assert set(sources) <= set(_build.library_sources())
+    assert unit_inputs(_build, unit) <= set(_build.build_inputs())
 
 
 def own_unit_source(_build, unit, source, header):
     """Asserts that `unit` is built from exactly its one source and its one public header, outside the profile
     fingerprint, and that the source opens with the four includes of a pass; returns the source's text."""
-    assert list(_build.UNITS) == UNIT_KEYS and _build.library_sources() == LIBRARY_SOURCES
-    assert _build.UNITS[unit] == ([source], [os.path.join("..", "..", "include", header)])
-    fingerprinted = _build.SOURCES + _build.HEADERS
-    assert not set(_build.UNITS[unit][0] + _build.UNITS[unit][1]) & set(fingerprinted)
-    assert not any(os.path.splitext(source)[0] in name or os.path.splitext(header)[0] in name for name in fingerprinted)
-    assert _build.source_sha16() == "35a9bf480abfca1e"
-    for path in unit_inputs(_build, unit):
-        assert os.path.exists(path), path
-    # the default build compiles the unit, and a change of it makes the library stale
-    assert source in _build.library_sources()
-    assert unit_inputs(_build, unit) <= set(_build.build_inputs())
+    unit_in_build(_build, unit, [source], [os.path.join(INCLUDE, header)])
     text = open(os.path.join(_build.SRC_DIR, source)).read()
     includes = [line.split()[1] for line in text.splitlines() if line.startswith("#include")]
     assert includes == ["<math.h>", '"common.h"', f'"../../include/{header}"', '"winner_pass.h"'], includes
