@@ -1,5 +1,6 @@
 """What the per-pass tests share: the scenes (T-Rex, the random soups, their textured forms), the fillers, the oracle's
-frame of a scene with the comparison of the planes a pass only reads, and the module-scoped fixtures built from them.
+frame of a scene with the comparison of the planes a pass only reads, the test doubles of a filler (``recording_filler``,
+``fake_filler_base``), and the module-scoped fixtures built from them.
 Imported by name by the CPU and the GPU files alike, so torch and the package are imported inside the functions.
 
 A fixture defined here is shared by importing it into the test module (``from pass_scenes import capi  # noqa: F401``):
@@ -150,6 +151,100 @@ class Scene(Frame):
         changed = (want.view(np.uint32) != self.cam.color_buffer.view(np.uint32)).any(2)
         assert changed.any(), (what, "the pass changed nothing")
         return changed
+
+
+# ---- the test doubles: a filler that records, a filler of the two mixins on CPU tensors ----------------------------
+
+class RecordingFiller:
+    """A filler that records what the Renderer asks of it, as (name, args, kwargs) in ``calls``.  It has the methods
+    that ``recording_filler`` is given and no others: the Renderer's constructor asks ``hasattr``."""
+    device = None
+    returns = {}
+    copies = ()
+
+    def __init__(self, h=8, w=8):
+        self.calls = []
+        self.h, self.w = h, w
+
+    def names(self):
+        return [c[0] for c in self.calls]
+
+    def _answer(self, name, a, kw):
+        """What the method `name` returns: ``returns[name]``, called with the filler and the arguments if it is a
+        function; else a fresh zero plane for the two host views, "colour" for the colour tensor, and None."""
+        if name in self.returns:
+            r = self.returns[name]
+            return r(self, *a, **kw) if callable(r) else r
+        if name in ("get_color_buffer", "get_normals_buffer"):
+            return np.zeros((self.h, self.w, 3), np.float32)
+        return "colour" if name == "get_color_tensor" else None
+
+
+def recording_filler(methods, returns=None, quiet=(), copies=(), **attributes):
+    """-> a RecordingFiller class with the methods named in `methods` and `quiet` (lists, or one string of names).  A
+    call of a method in `methods` is recorded, one in `quiet` is not.  `returns` is {name: what the method returns, or a
+    function of the filler and the call's arguments that returns it}.  The methods in `copies` record a clone of each
+    tensor among their positional arguments (for a caller that edits it in place afterwards).  `attributes` become
+    class attributes, such as the tensor that the tests expect back."""
+    def method(name, noted):
+        def call(self, *a, **kw):
+            if noted:
+                seen = tuple(v.clone() if hasattr(v, "clone") else v for v in a) if name in self.copies else a
+                self.calls.append((name, seen, kw))
+            return self._answer(name, a, kw)
+        call.__name__ = name
+        return call
+    methods, quiet = [m.split() if isinstance(m, str) else list(m) for m in (methods, quiet)]
+    body = dict(attributes, returns=dict(returns or {}), copies=tuple(copies))
+    body.update({n: method(n, True) for n in methods})
+    body.update({n: method(n, False) for n in quiet})
+    return type("RecordingFiller", (RecordingFiller,), body)
+
+
+def fake_filler_base():
+    """-> the base of a file's ``FakeFiller``: the protocol of the two mixins (DevicePlanes, DeferredPasses) on CPU
+    tensors, with the planes of a ``Frame``.  ``events`` lists what happened: "push" for the host edits carried up,
+    "settle" for the wait for the frame, and whatever the file's own ``_launch_pass``, the host model, appends."""
+    import torch
+    from cython3dmodelrenderer_amd.pixel_buffer_filler._deferred_passes import DeferredPasses
+    from cython3dmodelrenderer_amd.pixel_buffer_filler._device_planes import DevicePlanes
+
+    class FakeFillerBase(DevicePlanes, DeferredPasses):
+        device = "cpu"
+        _pipeline = None
+        _order = None
+        inputs = ("tri",)                  # the arrays of the frame that the last draw left resident
+
+        def __init__(self, frame, row_strip=None, track_winner=True):
+            super().__init__()
+            self.frame = frame
+            self.h, self.w = frame.cam.winner.shape
+            self.y0, self.y1 = (0, self.h) if row_strip is None else row_strip
+            self._P = frame.cam.proj_mat
+            self.z_buffer = torch.from_numpy(frame.cam.z_buffer.copy())
+            self.color_buffer = torch.from_numpy(frame.cam.color_buffer.copy())
+            self.normals_buffer = torch.from_numpy(frame.cam.normals_buffer.copy())
+            self.winner_buffer = torch.from_numpy(frame.cam.winner.copy()) if track_winner else None
+            self._inputs = tuple(torch.from_numpy(np.ascontiguousarray(getattr(frame, n))) for n in self.inputs)
+            self._last_flags = 1               # FUSED_CLEAR
+            self.events = []
+
+        def _ready_planes(self):
+            pass
+
+        def _wait_planes(self):
+            return False
+
+        def _check_bins(self):
+            self.events.append("settle")
+
+        def _push_host_edits(self):
+            self.events.append("push")
+            super()._push_host_edits()
+
+        def _pinned_like(self, buf):
+            return torch.empty(tuple(buf.shape), dtype=buf.dtype)
+    return FakeFillerBase
 
 
 # ---- fixtures: import them into the test module, or build them there from its own class ----------------------------

@@ -14,7 +14,7 @@ import pytest
 import torch
 
 import bloom_ref
-from pass_scenes import Frame, capi, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
+from pass_scenes import Frame, capi, recording_filler, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
 from ssaa_ref import present_u8
 from util import assert_bit_equal, other_symbols, own_unit_source
 
@@ -562,45 +562,13 @@ def test_the_free_function_checks_its_image():
 
 # ---- the Renderer ----------------------------------------------------------------------------------------------
 
-class _Recorder:
-    """A filler that records what the Renderer asks of it; each last pass returns a tensor of its own."""
-    device = None
-
-    def __init__(self, h=8, w=8):
-        self.calls = []
-        self.h, self.w = h, w
-        self.images = {n: torch.full((h, w, 3), float(i + 1)) for i, n in
-                       enumerate(("depth_of_field", "edge_aa", "transparency_pass", "resolve", "bloom"))}
-
-    def _note(name):
-        def method(self, *a, **kw):
-            self.calls.append((name, a, kw))
-            return self.images.get(name, {"draw_illumination_device": True}.get(name))
-        return method
-    for _n in ("render_model", "set_fused_illumination", "wire_pass", "phong_pass", "ao_pass", "shade_guro", "depth_of_field",
-               "edge_aa", "transparency_pass", "resolve", "bloom"):
-        locals()[_n] = _note(_n)
-    del _n
-
-    def _push_host_edits(self):
-        pass
-
-    def synchronize(self):
-        pass
-
-    def get_color_tensor(self):
-        self.calls.append(("get_color_tensor", (), {}))
-        return "colour"
-
-    def get_color_buffer(self):
-        self.calls.append(("get_color_buffer", (), {}))
-        return np.zeros((self.h, self.w, 3), np.float32)
-
-    def get_normals_buffer(self):
-        return np.zeros((self.h, self.w, 3), np.float32)
-
-    def names(self):
-        return [c[0] for c in self.calls]
+# a filler that records what the Renderer asks of it; each last pass returns a tensor of its own
+IMAGES = {n: torch.full((8, 8, 3), float(i + 1)) for i, n in
+          enumerate(("depth_of_field", "edge_aa", "transparency_pass", "resolve", "bloom"))}
+_Recorder = recording_filler(
+    "render_model set_fused_illumination wire_pass phong_pass ao_pass shade_guro depth_of_field edge_aa transparency_pass resolve bloom "
+    "get_color_tensor get_color_buffer",
+    returns=IMAGES, quiet="_push_host_edits synchronize get_normals_buffer", images=IMAGES)
 
 
 def test_renderer_construction():

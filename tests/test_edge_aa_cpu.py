@@ -17,7 +17,7 @@ import torch
 import edge_aa_ref
 import pass_edges
 import tex_ref
-from pass_scenes import Frame, capi, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
+from pass_scenes import Frame, capi, fake_filler_base, recording_filler, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
 from util import LIBRARY_SOURCES, UNIT_KEYS, assert_bit_equal, other_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -500,43 +500,10 @@ def test_the_model_is_nearer_to_the_exact_coverage_than_the_frame(oracle, name):
 # ---- the Python layer, on CPU tensors --------------------------------------------------------------------------
 
 from cython3dmodelrenderer_amd.pixel_buffer_filler._deferred_passes import DeferredPasses  # noqa: E402
-from cython3dmodelrenderer_amd.pixel_buffer_filler._device_planes import DevicePlanes  # noqa: E402
 
 
-class FakeFiller(DevicePlanes, DeferredPasses):
+class FakeFiller(fake_filler_base()):
     """The protocol of the two mixins on CPU tensors; the launch is the host model."""
-    device = "cpu"
-    _pipeline = None
-    _order = None
-
-    def __init__(self, frame, row_strip=None, track_winner=True):
-        super().__init__()
-        self.h, self.w = frame.cam.winner.shape
-        self.y0, self.y1 = (0, self.h) if row_strip is None else row_strip
-        self._P = frame.cam.proj_mat
-        self.z_buffer = torch.from_numpy(frame.cam.z_buffer.copy())
-        self.color_buffer = torch.from_numpy(frame.cam.color_buffer.copy())
-        self.normals_buffer = torch.from_numpy(frame.cam.normals_buffer.copy())
-        self.winner_buffer = torch.from_numpy(frame.cam.winner.copy()) if track_winner else None
-        self._inputs = (torch.from_numpy(np.ascontiguousarray(frame.tri)),)
-        self._last_flags = 1               # FUSED_CLEAR
-        self.events = []
-
-    def _ready_planes(self):
-        pass
-
-    def _wait_planes(self):
-        return False
-
-    def _check_bins(self):
-        self.events.append("settle")
-
-    def _push_host_edits(self):
-        self.events.append("push")
-        super()._push_host_edits()
-
-    def _pinned_like(self, buf):
-        return torch.empty(tuple(buf.shape), dtype=buf.dtype)
 
     def _launch_pass(self, entry, args):
         winner, z, tri, T, pos_of, P, edges, out, color, h, w, y0, y1, flags = args
@@ -620,48 +587,11 @@ class _Mesh:
         self._vertices_by_triangles = tri
 
 
-class _Recorder:
-    """A filler that records what the Renderer asks of it."""
-    device = None
-
-    def __init__(self, h=8, w=8):
-        self.calls = []
-        self.h, self.w = h, w
-        self.image = torch.arange(h * w * 3, dtype=torch.float32).reshape(h, w, 3)
-
-    def _note(name):
-        def method(self, *a, **kw):
-            self.calls.append((name, a, kw))
-            return {"draw_illumination_device": True, "contour_edges": "view mask"}.get(name)
-        return method
-    render_model = _note("render_model")
-    set_fused_illumination = _note("set_fused_illumination")
-    wire_pass = _note("wire_pass")
-    contour_edges = _note("contour_edges")
-    phong_pass = _note("phong_pass")
-    ao_pass = _note("ao_pass")
-    shade_guro = _note("shade_guro")
-
-    def _push_host_edits(self):
-        pass
-
-    def synchronize(self):
-        pass
-
-    def get_color_tensor(self):
-        self.calls.append(("get_color_tensor", (), {}))
-        return "colour"
-
-    def get_color_buffer(self):
-        self.calls.append(("get_color_buffer", (), {}))
-        return np.zeros((self.h, self.w, 3), np.float32)
-
-    def get_normals_buffer(self):
-        return np.zeros((self.h, self.w, 3), np.float32)
-
-    def edge_aa(self, **kw):
-        self.calls.append(("edge_aa", (), kw))
-        return self.image
+# a filler that records what the Renderer asks of it; ``image`` is what its pass returns
+IMAGE = torch.arange(8 * 8 * 3, dtype=torch.float32).reshape(8, 8, 3)
+_Recorder = recording_filler(
+    "render_model set_fused_illumination wire_pass contour_edges phong_pass ao_pass shade_guro get_color_tensor get_color_buffer edge_aa",
+    returns=dict(contour_edges="view mask", edge_aa=IMAGE), quiet="_push_host_edits synchronize get_normals_buffer", image=IMAGE)
 
 
 def test_renderer_construction():

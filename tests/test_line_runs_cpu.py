@@ -21,7 +21,7 @@ import pass_edges
 import runs_ref
 import tex_ref
 import wire_ref
-from pass_scenes import Frame, capi, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
+from pass_scenes import Frame, capi, fake_filler_base, recording_filler, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
 from util import UNIT_KEYS, assert_bit_equal, other_symbols, random_soup
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -489,43 +489,10 @@ def test_a_closed_visible_loop_closes_exactly(oracle):
 # ---- the Python layer, on CPU tensors --------------------------------------------------------------------------
 
 from cython3dmodelrenderer_amd.pixel_buffer_filler._deferred_passes import DeferredPasses, LineDrawing  # noqa: E402
-from cython3dmodelrenderer_amd.pixel_buffer_filler._device_planes import DevicePlanes  # noqa: E402
 
 
-class FakeFiller(DevicePlanes, DeferredPasses):
+class FakeFiller(fake_filler_base()):
     """The protocol of the two mixins on CPU tensors; the launches are the host model."""
-    device = "cpu"
-    _pipeline = None
-    _order = None
-
-    def __init__(self, frame, row_strip=None, track_winner=True):
-        super().__init__()
-        self.h, self.w = frame.cam.winner.shape
-        self.y0, self.y1 = (0, self.h) if row_strip is None else row_strip
-        self._P = frame.cam.proj_mat
-        self.z_buffer = torch.from_numpy(frame.cam.z_buffer.copy())
-        self.color_buffer = torch.from_numpy(frame.cam.color_buffer.copy())
-        self.normals_buffer = torch.from_numpy(frame.cam.normals_buffer.copy())
-        self.winner_buffer = torch.from_numpy(frame.cam.winner.copy()) if track_winner else None
-        self._inputs = (torch.from_numpy(np.ascontiguousarray(frame.tri)),)
-        self._last_flags = 1               # FUSED_CLEAR
-        self.events = []
-
-    def _ready_planes(self):
-        pass
-
-    def _wait_planes(self):
-        return False
-
-    def _check_bins(self):
-        self.events.append("settle")
-
-    def _push_host_edits(self):
-        self.events.append("push")
-        super()._push_host_edits()
-
-    def _pinned_like(self, buf):
-        return torch.empty(tuple(buf.shape), dtype=buf.dtype)
 
     def _model(self, winner, z, tri, T, pos_of, P, edges, partners, bias, y0, y1, flags):
         return runs_ref.line_runs(winner.numpy(), z.numpy(), tri.numpy()[:T], pos_of, P, edges=None if edges is None else edges.numpy(),
@@ -630,39 +597,11 @@ class _Mesh:
         self._vertices_by_triangles = tri
 
 
-class _Recorder:
-    """A filler that records what the Renderer asks of it."""
-    device = None
-
-    def __init__(self):
-        self.calls = []
-
-    def _note(name):
-        def method(self, *a, **kw):
-            self.calls.append((name, a, kw))
-            return {"draw_illumination_device": True, "line_runs": "drawing", "resolve": "resolved"}.get(name)
-        return method
-    render_model = _note("render_model")
-    set_fused_illumination = _note("set_fused_illumination")
-    wire_pass = _note("wire_pass")
-    hidden_line_pass = _note("hidden_line_pass")
-    line_runs = _note("line_runs")
-    shade_guro = _note("shade_guro")
-    resolve = _note("resolve")
-
-    def contour_edges(self, partners, static=None, borders=False):
-        self.calls.append(("contour_edges", (partners,), dict(static=static, borders=borders)))
-        return np.full(len(partners), 5, np.uint8)
-
-    def _push_host_edits(self):
-        pass
-
-    def synchronize(self):
-        pass
-
-    def get_color_tensor(self):
-        self.calls.append(("get_color_tensor", (), {}))
-        return "colour"
+# a filler that records what the Renderer asks of it
+_Recorder = recording_filler(
+    "render_model set_fused_illumination wire_pass hidden_line_pass line_runs shade_guro resolve contour_edges get_color_tensor",
+    returns=dict(line_runs="drawing", resolve="resolved", contour_edges=lambda f, partners, **kw: np.full(len(partners), 5, np.uint8)),
+    quiet="_push_host_edits synchronize")
 
 
 def test_renderer_takes_the_drawing_after_the_wire_and_hidden_passes():

@@ -15,7 +15,7 @@ import pytest
 import torch
 
 import motion_ref
-from pass_scenes import Frame, capi, oracle_frame, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
+from pass_scenes import Frame, capi, fake_filler_base, oracle_frame, recording_filler, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
 from util import assert_bit_equal, other_symbols, own_unit_source
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -462,43 +462,10 @@ def test_the_vectors_lead_to_the_same_triangle_in_the_previous_frame(oracle, tre
 # ---- the Python layer, on CPU tensors --------------------------------------------------------------------------
 
 from cython3dmodelrenderer_amd.pixel_buffer_filler._deferred_passes import DeferredPasses  # noqa: E402
-from cython3dmodelrenderer_amd.pixel_buffer_filler._device_planes import DevicePlanes  # noqa: E402
 
 
-class FakeFiller(DevicePlanes, DeferredPasses):
+class FakeFiller(fake_filler_base()):
     """The protocol of the two mixins on CPU tensors; the launch is the host model."""
-    device = "cpu"
-    _pipeline = None
-    _order = None
-
-    def __init__(self, frame, row_strip=None, track_winner=True):
-        super().__init__()
-        self.h, self.w = frame.cam.winner.shape
-        self.y0, self.y1 = (0, self.h) if row_strip is None else row_strip
-        self._P = frame.cam.proj_mat
-        self.z_buffer = torch.from_numpy(frame.cam.z_buffer.copy())
-        self.color_buffer = torch.from_numpy(frame.cam.color_buffer.copy())
-        self.normals_buffer = torch.from_numpy(frame.cam.normals_buffer.copy())
-        self.winner_buffer = torch.from_numpy(frame.cam.winner.copy()) if track_winner else None
-        self._inputs = (torch.from_numpy(np.ascontiguousarray(frame.tri)),)
-        self._last_flags = 1               # FUSED_CLEAR
-        self.events = []
-
-    def _ready_planes(self):
-        pass
-
-    def _wait_planes(self):
-        return False
-
-    def _check_bins(self):
-        self.events.append("settle")
-
-    def _push_host_edits(self):
-        self.events.append("push")
-        super()._push_host_edits()
-
-    def _pinned_like(self, buf):
-        return torch.empty(tuple(buf.shape), dtype=buf.dtype)
 
     def _launch_pass(self, entry, args):
         if entry == VECTORS:
@@ -628,47 +595,13 @@ def test_the_two_methods_refuse_what_depth_of_field_refuses_and_name_bad_argumen
 
 # ---- the Renderer ----------------------------------------------------------------------------------------------
 
-class _Recorder:
-    """A filler that records what the Renderer asks of it."""
-    device = None
-
-    def __init__(self, h=8, w=8):
-        self.calls = []
-        self.h, self.w = h, w
-        self.image = torch.arange(h * w * 3, dtype=torch.float32).reshape(h, w, 3)
-
-    def _note(name):
-        def method(self, *a, **kw):
-            self.calls.append((name, a, kw))
-            return {"draw_illumination_device": True, "bloom": "bloomed"}.get(name)
-        return method
-    render_model = _note("render_model")
-    set_fused_illumination = _note("set_fused_illumination")
-    wire_pass = _note("wire_pass")
-    phong_pass = _note("phong_pass")
-    shade_guro = _note("shade_guro")
-    bloom = _note("bloom")
-
-    def _push_host_edits(self):
-        pass
-
-    def synchronize(self):
-        pass
-
-    def get_color_tensor(self):
-        self.calls.append(("get_color_tensor", (), {}))
-        return "colour"
-
-    def get_color_buffer(self):
-        self.calls.append(("get_color_buffer", (), {}))
-        return np.zeros((self.h, self.w, 3), np.float32)
-
-    def get_normals_buffer(self):
-        return np.zeros((self.h, self.w, 3), np.float32)
-
-    def motion_blur(self, previous, **kw):
-        self.calls.append(("motion_blur", (previous.clone(),), kw))
-        return self.image
+# a filler that records what the Renderer asks of it (the pose as it was at the call: the model moves in place); ``image`` is
+# what its pass returns
+IMAGE = torch.arange(8 * 8 * 3, dtype=torch.float32).reshape(8, 8, 3)
+_Recorder = recording_filler(
+    "render_model set_fused_illumination wire_pass phong_pass shade_guro bloom get_color_tensor get_color_buffer motion_blur",
+    returns=dict(bloom="bloomed", motion_blur=IMAGE), quiet="_push_host_edits synchronize get_normals_buffer",
+    copies=("motion_blur",), image=IMAGE)
 
 
 def test_renderer_construction():

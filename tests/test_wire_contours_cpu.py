@@ -13,7 +13,7 @@ import pytest
 
 import contour_ref
 import outline_ref
-from pass_scenes import Frame, capi, trex_fixture  # noqa: F401 (fixtures)
+from pass_scenes import Frame, capi, recording_filler, trex_fixture  # noqa: F401 (fixtures)
 from util import LIBRARY_SOURCES, UNIT_KEYS, other_symbols, sha
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -331,31 +331,9 @@ class _Mesh:
         self._vertices_by_triangles = tri
 
 
-class _Recorder:
-    """A filler that records what the Renderer asks of it."""
-    device = None
-
-    def __init__(self, h=8, w=8):
-        self.calls = []
-        self.h, self.w = h, w
-
-    def _note(name):
-        def method(self, *a, **kw):
-            self.calls.append((name, a, kw))
-            return {"draw_illumination_device": True, "contour_edges": "view mask"}.get(name)
-        return method
-    render_model = _note("render_model")
-    set_fused_illumination = _note("set_fused_illumination")
-    wire_pass = _note("wire_pass")
-    contour_edges = _note("contour_edges")
-    phong_pass = _note("phong_pass")
-
-    def get_color_tensor(self):
-        return "colour"
-
-    def resolve(self, s, **kw):
-        self.calls.append(("resolve", (s,), kw))
-        return "resolved"
+# a filler that records what the Renderer asks of it
+_Recorder = recording_filler("render_model set_fused_illumination wire_pass contour_edges phong_pass resolve",
+                             returns=dict(contour_edges="view mask", resolve="resolved"), quiet="get_color_tensor")
 
 
 def test_renderer_builds_the_table_once_and_the_mask_every_frame():

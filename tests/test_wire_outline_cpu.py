@@ -14,7 +14,7 @@ import pytest
 import outline_ref
 import overlay_ref
 import tex_ref
-from pass_scenes import Frame, capi, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
+from pass_scenes import Frame, capi, recording_filler, soups_fixture, trex_fixture  # noqa: F401 (fixtures)
 from util import assert_bit_equal, other_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -346,33 +346,10 @@ def test_wire_pass_refuses_bad_outline_arguments_before_it_looks_at_the_device()
         DeferredPasses.wire_pass(chain, outline=True)
 
 
-class _Recorder:
-    """A filler that records what the Renderer asks of it."""
-    device = None
-
-    def __init__(self, h=8, w=8):
-        self.calls = []
-        self.h, self.w = h, w
-
-    def _note(name):
-        def method(self, *a, **kw):
-            self.calls.append((name, a, kw))
-            return True if name == "draw_illumination_device" else None
-        return method
-    render_model = _note("render_model")
-    set_fused_illumination = _note("set_fused_illumination")
-    wire_pass = _note("wire_pass")
-    phong_pass = _note("phong_pass")
-    shadow_pass = _note("shadow_pass")
-    bind_shadow_map = _note("bind_shadow_map")
-
-    def get_color_tensor(self):
-        self.calls.append(("get_color_tensor", (), {}))
-        return "colour"
-
-    def resolve(self, s, **kw):
-        self.calls.append(("resolve", (s,), kw))
-        return "resolved"
+# a filler that records what the Renderer asks of it
+_Recorder = recording_filler(
+    "render_model set_fused_illumination wire_pass phong_pass shadow_pass bind_shadow_map get_color_tensor resolve",
+    returns=dict(resolve="resolved"))
 
 
 def test_renderer_forwards_the_outline_options():
