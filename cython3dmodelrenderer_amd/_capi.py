@@ -265,6 +265,16 @@ UNIT_SIGNATURES["motion"] = {
                                    _i32, _i32, _i32, _i32, _u32, _vp]),
 }
 
+# Provisional, keyed like _build.PENDING: the next refactor folds this table into UNIT_SIGNATURES, together with
+# tests/util.py's two lists.  Temporal anti-aliasing (include/crender_taa.h; DeferredPasses.temporal_resolve): the frame's
+# colour, the history, the velocity and the z plane or NULL, the blend, the result, then the frame, the rows and the flags
+TAA_NO_CLAMP = 1
+PENDING = {
+    "taa": {
+        "crender_taa_resolve": (_i32, [_vp, _vp, _vp, _vp, C.c_float, _vp, _i32, _i32, _i32, _i32, _u32, _vp]),
+    },
+}
+
 _lib = None
 
 
@@ -288,7 +298,7 @@ def load():
             f"{path} is missing: build it with `python -m cython3dmodelrenderer_amd._build` "
             "(or __graft_entry__.build()).  There is no CPU fallback for the rasterizer.")
     L = C.CDLL(path)
-    for table in (SIGNATURES, *UNIT_SIGNATURES.values()):
+    for table in (SIGNATURES, *UNIT_SIGNATURES.values(), *PENDING.values()):
         for name, (res, args) in table.items():
             fn = getattr(L, name)      # AttributeError if the library lacks a declared symbol
             fn.restype = res

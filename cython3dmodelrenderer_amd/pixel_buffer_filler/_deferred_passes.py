@@ -7,7 +7,8 @@ classification kept as vector segments (``line_runs``: it only reads the planes 
 edge anti-aliasing (``edge_aa``: it reads the planes and returns a plane of its own) and depth of field (``depth_of_field``:
 a gather blur by the circle of confusion over the z plane, which returns a plane of its own as well), motion vectors and
 motion blur (``motion_vectors`` and ``motion_blur``: where every pixel's surface point was in an earlier pose, and a gather
-along that, two planes of their own) and transparency
+along that, two planes of their own), temporal anti-aliasing (``temporal_resolve``: the frame blended into a history
+image that follows the surface, a plane of its own too) and transparency
 (``peel_layers`` and ``transparency_pass``: the frame's depth layers peeled by depth key and blended front to back, a plane of its own again).  A mixin
 beside ``_device_planes.DevicePlanes``: the filler supplies ``device, h, w, y0, y1, _lib, _P`` and its frame state (``_pipeline, _inputs, _order, _last_flags, _check_bins``).  What every pass has in common is here
 once: whom it refuses (``_pass_target``), which frame it accepts (``_pass_frame``), and how it is launched
@@ -856,6 +857,59 @@ class DeferredPasses:
         out = new((self.h, self.w, 3), dtype=torch.float32, device=self.color_buffer.device)
         self._run_pass("crender_motion_blur", tri, T, (self.color_buffer, velocity, int(max_radius), int(taps), float(soft)),
                        z=True, reads_only=True, target=out)
+        return out
+
+    def temporal_resolve(self, history, previous_vertices=None, *, velocity=None, blend=0.1, dilate=True, clamp=True):
+        """Temporal anti-aliasing of the LAST frame (``crender_taa_resolve``, include/crender_taa.h): a NEW device tensor
+        [h, w, 3] float32, as ``edge_aa`` returns one, in which every pixel is ``c + (hist - c) * (1 - blend)``: its own
+        colour c blended towards `history` (float32 [h, w, 3], numpy or a device tensor: the image this method returned
+        for the frame before) sampled bilinearly where the surface point the pixel shows WAS, and, with `clamp`, clamped
+        per channel to the range of the frame's colours in the pixel's 3 x 3 first, which keeps a stale history from
+        ghosting.  Where it was comes from `previous_vertices` (``motion_vectors``' argument, at exposure 1) or from
+        `velocity`, a float32 [h, w, 2] array or tensor such as an edited result of ``motion_vectors``: at most one of
+        the two, and neither means a static view (no velocity plane is made or read).  With `dilate` the velocity is
+        taken from the nearest pixel of the 3 x 3 by the z plane, so that a silhouette carries its own motion over the
+        background pixels it is blended into; it is ignored without a velocity.  `blend` is the new frame's share, in
+        (0, 1]; 1 returns the frame's rows, copied, and so does ``history=None``.  A pixel whose previous position is off
+        the frame (or outside the strip) keeps its own colour.  Rows of the filler's ``row_strip`` (the others of the
+        result are zero; the strip does not see across its edge), on torch's current stream.  Draw the frames with a
+        sub-pixel offset each (``temporal.jitter_offsets``, ``view_shear``, ``sheared``) and the image converges towards
+        the supersampled one; ``Renderer(temporal_aa=...)`` does both.
+
+        Edits made in the numpy views handed out so far are carried to the device and the frame is settled first (one
+        stream synchronisation, as every getter does).  The planes and the history are only read: the views stay as fresh
+        or as stale as they were."""
+        self._pass_target("temporal_resolve")
+        tri, T = self._pass_frame("temporal_resolve")
+        if previous_vertices is not None and velocity is not None:
+            raise ValueError("temporal_resolve takes at most one of previous_vertices and velocity")
+        if isinstance(blend, bool) or not isinstance(blend, (int, float, np.integer, np.floating)) \
+                or not 0 < float(blend) <= 1 or not np.float32(blend) > 0:
+            raise ValueError(f"blend must be a number above 0 and at most 1, got {blend!r}")
+        for name, v in (("dilate", dilate), ("clamp", clamp)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"{name} must be a bool, got {v!r}")
+        if history is not None:
+            history = _device_array(self, history, torch.float32, lambda s: s == (self.h, self.w, 3),
+                                    f"history must be None or float32 [{self.h}, {self.w}, 3], the frame's")
+        if velocity is not None:
+            velocity = _device_array(self, velocity, torch.float32, lambda s: s == (self.h, self.w, 2),
+                                     f"velocity must be float32 [{self.h}, {self.w}, 2], the frame's")
+        elif previous_vertices is not None:
+            prev = self._previous_pose("temporal_resolve", previous_vertices, T)
+            if history is not None:
+                velocity = self._motion_vectors(tri, T, prev, 1.0)
+        self._push_host_edits()
+        self._check_bins()
+        whole = (self.y0, self.y1) == (0, self.h)
+        out = (torch.empty if whole else torch.zeros)((self.h, self.w, 3), dtype=torch.float32, device=self.color_buffer.device)
+        if history is None:
+            out[self.y0:self.y1].copy_(self.color_buffer[self.y0:self.y1])
+            return out
+        flags = 0 if clamp else _capi.TAA_NO_CLAMP
+        self._launch_pass("crender_taa_resolve", (self.color_buffer, history, velocity,
+                                                  self.z_buffer if dilate and velocity is not None else None,
+                                                  float(np.float32(blend)), out, self.h, self.w, self.y0, self.y1, flags))
         return out
 
     def _peel_frame(self, name):

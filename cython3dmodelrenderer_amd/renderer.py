@@ -124,6 +124,26 @@ _OPTIONS = (
             excludes=("antialias", "depth_of_field", "supersample", "transparency"),
             clash="together with antialias=..., depth_of_field=..., supersample=... or transparency=...: " + _OWN_PLANE +
             "blurred one; use one of them"),
+    # temporal_aa=None (default): every frame stands alone.  A dict of ``blend`` (default 0.1), ``jitter`` (an int from 0 to
+    # 64, default 8: the length of the cycle of sub-pixel offsets, ``temporal.jitter_offsets``; 0 draws every frame
+    # without an offset), ``dilate`` and ``clamp`` (``AdvancedPixelBufferFiller.temporal_resolve``'s arguments): temporal
+    # anti-aliasing.  Frame n since the first ``render`` (or ``reset_motion()``, or a change of the triangle count) is
+    # drawn from a stand-in for the model whose vertices are sheared by offset ``n mod jitter`` (``temporal.view_shear``,
+    # ``sheared``: the image moves by that fraction of a pixel; texture, normal-map, shadow and edge helpers keep
+    # receiving the caller's model), and the finished frame is blended into the image returned for the frame before,
+    # reprojected along the motion vectors against the pose of the call before (a device COPY of every frame's
+    # unjittered vertices is kept, as under ``motion_blur``; it is sheared by THIS frame's offset, so that the jitter
+    # cancels in the velocity) with ``blend = max(blend, 1 / (n + 1))``: a still model averages its frames evenly until
+    # the floor is reached.  Frame 0 is the jittered frame, copied.  Every frame starts from cleared buffers (one model
+    # per frame, as "fused").  The pass runs LAST, after everything that shades and after the wire pass, reads the
+    # filler's planes and writes a tensor of its own, which ``render`` returns (``bloom`` reads it) AND keeps as the next
+    # history: clone it before editing it.  The tensor for on_device=True / "fused", a fresh numpy copy otherwise.  It
+    # combines with none of ``antialias``, ``depth_of_field``, ``motion_blur``, ``supersample`` and ``transparency``:
+    # each of them reads the filler's own colour plane and would not see the resolved one.
+    _Option("temporal_aa", "temporal_resolve", "with a temporal resolve pass " + _PASS, ("blend", "jitter", "dilate", "clamp"),
+            excludes=("antialias", "depth_of_field", "motion_blur", "supersample", "transparency"),
+            clash="together with antialias=..., depth_of_field=..., motion_blur=..., supersample=... or transparency=...: " +
+            _OWN_PLANE + "resolved one; use one of them"),
     # normal_map=None (default): the light sees the interpolated vertex normals.  A dict of
     # AdvancedPixelBufferFiller.bind_normal_map's arguments but the uv (``normal_map`` or ``height``, ``scale``, ``wrap``,
     # ``mipmaps``) and of normal_map_pass's (``strength``, ``perspective``, ``filter``; "trilinear" binds the map with
@@ -178,13 +198,14 @@ class Renderer:
     above, each with its comment; a frame runs in this order (``_frame``): the draw, the normal map, the texture pass,
     the ambient occlusion, the shadow pass, the light, the environment, the wire pass (with its hidden lines and
     vectors), the resolve; under a PhongIllumination the shadow pass follows the light.  ``render`` then runs the one
-    pass that reads the finished frame (``transparency``, ``depth_of_field``, ``motion_blur`` or ``antialias``) and
+    pass that reads the finished frame (``transparency``, ``depth_of_field``, ``motion_blur``, ``temporal_aa`` or
+    ``antialias``) and
     ``bloom`` after everything else."""
 
     def __init__(self, pixel_buffer_filler, illumination, triangle_iterator_type=None,
                  image_height=512, image_width=512, use_tqdm=True, on_device=None, texture_pass=None,
-                 shadow=None, ambient_occlusion=None, antialias=None, depth_of_field=None, motion_blur=None, normal_map=None,
-                 environment=None, bloom=None, transparency=None, wireframe=None, supersample=None):
+                 shadow=None, ambient_occlusion=None, antialias=None, temporal_aa=None, depth_of_field=None, motion_blur=None,
+                 normal_map=None, environment=None, bloom=None, transparency=None, wireframe=None, supersample=None):
         self.pixel_buffer_filler = pixel_buffer_filler
         self.illumination = illumination
         self.triangle_iterator_type = triangle_iterator_type   # stored, unused (as in Version C)
@@ -206,7 +227,9 @@ class Renderer:
         self._wired = None             # (weak reference to the model, its feature-edge mask, its partner table, the angle)
         self._smoothed = None          # as _wired, for the edges of ``antialias``
         self._paired = None            # (weak reference to the model, its partner table) where the contours keep none
-        self._previous_pose = None     # the device copy of the vertices the last frame was drawn from
+        self._previous_pose = None     # the device copy of the (unjittered) vertices the last frame was drawn from
+        self._history = None           # under temporal_aa: the tensor the last ``render`` resolved, the next history
+        self._frame_number = 0         # under temporal_aa: n, the frames since the history began
         self.line_drawing = None       # the last frame's LineDrawing under wireframe={"vector": ...}
         # A PhongIllumination is a deferred pass of the filler over its winner plane (``phong_pass``): every frame
         # starts from cleared buffers (one model per frame, as "fused"); the draw, then the texture pass (unlit) if
@@ -217,12 +240,13 @@ class Renderer:
         from .illumination.phong_illumination import PhongIllumination
         self._phong = isinstance(illumination, PhongIllumination)
         given = dict(texture_pass=texture_pass, shadow=shadow, ambient_occlusion=ambient_occlusion, antialias=antialias,
-                     depth_of_field=depth_of_field, motion_blur=motion_blur, normal_map=normal_map, environment=environment,
+                     depth_of_field=depth_of_field, motion_blur=motion_blur, temporal_aa=temporal_aa, normal_map=normal_map,
+                     environment=environment,
                      bloom=bloom, transparency=transparency, wireframe=wireframe, supersample=supersample)
         # what is one option's own: checked between the method and the keys, and how its dict is kept
         own_checks = {"wireframe": self._check_wireframe, "antialias": lambda v: self._check_contours("antialias", v),
                       "normal_map": lambda v: self._check_fused_normal_map(texture_pass),
-                      "transparency": self._check_transparency}
+                      "transparency": self._check_transparency, "temporal_aa": self._check_temporal}
         keep = {"normal_map": self._bind_normal_map, "environment": self._bind_environment, "supersample": lambda v: v}
         for o in _OPTIONS:
             if o.name == "transparency":
@@ -336,10 +360,21 @@ class Renderer:
                              "with the Guro light or none and would be lit by another model than the first; use a "
                              "GuroIllumination")
 
-    def _frame(self, model):
+    @staticmethod
+    def _check_temporal(temporal_aa):
+        jitter = temporal_aa.get("jitter", 8)
+        if isinstance(jitter, bool) or not isinstance(jitter, (int, np.integer)) or not 0 <= jitter <= 64:
+            raise ValueError(f"Renderer(temporal_aa=...): jitter must be an int from 0 to 64, got {jitter!r}")
+        blend = temporal_aa.get("blend", 0.1)
+        if isinstance(blend, bool) or not isinstance(blend, (int, float, np.integer, np.floating)) or not 0 < float(blend) <= 1:
+            raise ValueError(f"Renderer(temporal_aa=...): blend must be a number above 0 and at most 1, got {blend!r}")
+
+    def _frame(self, model, drawn=None):
         """One frame after the model fit, in the order the class documents -> (the image: the resolve's tensor, the
-        colour tensor or the colour view; whether a resolve's tensor is handed out as it is, not as a numpy copy)."""
+        colour tensor or the colour view; whether a resolve's tensor is handed out as it is, not as a numpy copy).
+        `drawn`: the stand-in the filler draws in the model's place (``temporal_aa``); the helpers get the model."""
         filler, shading, s = self.pixel_buffer_filler, self.illumination, self.supersample
+        drawn = model if drawn is None else drawn
         # where the light comes from: the raster kernel, the texture pass, the resolve, the illumination's device form,
         # its host form ("host" also where a device form is tried first), or the Phong pass
         device_form = None
@@ -373,13 +408,13 @@ class Renderer:
             # shades only for the "fused" caller without a texture pass, whose colours would replace what it stores)
             if source != "raster":
                 filler.set_fused_illumination(None)
-            filler.render_model(model, clear=True, refresh_views=False)
+            filler.render_model(drawn, clear=True, refresh_views=False)
         elif source == "raster":
-            filler.render_model(model, clear=True)
+            filler.render_model(drawn, clear=True)
         elif device_form is not None:
-            filler.render_model(model, refresh_views=False)      # (the getter below refreshes the views, after the shading)
+            filler.render_model(drawn, refresh_views=False)      # (the getter below refreshes the views, after the shading)
         else:
-            filler.render_model(model)     # without ``clear``: renders composite, as in the reference
+            filler.render_model(drawn)     # without ``clear``: renders composite, as in the reference
         # the passes before the light
         self._bump(model)                  # before the texture pass, whose fused light reads the normal plane
         if self.texture_pass is not None:
@@ -528,7 +563,12 @@ class Renderer:
             model.scale(span / model.get_max_span())
             model.shift(-model.get_mean_vertex() + [centre[0], centre[1], -span])
         filler = self.pixel_buffer_filler
-        image, as_it_is = self._frame(model)
+        shear = self._jitter(model) if self.temporal_aa is not None else None
+        if shear is None:
+            image, as_it_is = self._frame(model)
+        else:
+            from .temporal import JitteredModel
+            image, as_it_is = self._frame(model, JitteredModel(model, *shear))
         # the frame as ever, then the one pass that reads the finished frame, last of all: its own tensor is the image
         last = None
         if self.transparency is not None:
@@ -539,6 +579,8 @@ class Renderer:
             last = filler.depth_of_field(**self.depth_of_field)
         elif self.motion_blur is not None:
             last = self._shutter(model)
+        elif self.temporal_aa is not None:
+            last = self._accumulate(model, shear)
         elif self.antialias is not None:
             last = filler.edge_aa(**self._view_edges(model, self.antialias, "_smoothed"))
         if self.bloom is not None:
@@ -549,17 +591,52 @@ class Renderer:
             image, as_it_is = last, self.on_device is True or self.on_device == "fused"
         return image if as_it_is else image.cpu().numpy()
 
-    def _shutter(self, model):
-        """The motion-blur pass over the frame just drawn, against the pose of the call before; keeps this call's pose."""
+    def _pose_copy(self, model):
+        """A device copy of the vertex array of `model` as it is now (a DeviceModel is transformed in place)."""
         import torch
         v = model._vertices_by_triangles
         device = getattr(self.pixel_buffer_filler, "device", None)
         if isinstance(v, torch.Tensor):
-            current = v.detach().to(device=v.device if device is None else device, copy=True)
+            return v.detach().to(device=v.device if device is None else device, copy=True)
+        current = torch.from_numpy(np.array(v, copy=True))
+        return current if device is None else current.to(device)
+
+    def _jitter(self, model):
+        """(kx, ky), the view shear of this frame under ``temporal_aa``, or None where it is drawn without an offset.  A
+        first frame, and one whose triangle count is not the kept pose's, is frame 0."""
+        previous = self._previous_pose
+        if previous is None or self._history is None or previous.shape[0] != len(model._vertices_by_triangles):
+            self._frame_number = 0
+        J = int(self.temporal_aa.get("jitter", 8))
+        if J == 0:
+            return None
+        from .temporal import jitter_offsets, view_shear
+        filler = self.pixel_buffer_filler
+        jx, jy = jitter_offsets(J)[self._frame_number % J]
+        return view_shear(filler._P, filler.h, filler.w, jx, jy)
+
+    def _accumulate(self, model, shear):
+        """The temporal resolve over the frame just drawn, against the image and the pose of the call before; keeps this
+        call's unjittered pose and the resolved image."""
+        opts = dict(self.temporal_aa)
+        opts.pop("jitter", None)
+        n, floor = self._frame_number, float(opts.pop("blend", 0.1))
+        current = self._pose_copy(model)
+        if n == 0:
+            image = self.pixel_buffer_filler.temporal_resolve(None)         # the frame, copied
         else:
-            current = torch.from_numpy(np.array(v, copy=True))
-            if device is not None:
-                current = current.to(device)
+            previous = self._previous_pose
+            if shear is not None:
+                from .temporal import sheared
+                previous = sheared(previous, *shear)
+            image = self.pixel_buffer_filler.temporal_resolve(self._history, previous_vertices=previous,
+                                                              blend=max(floor, 1.0 / (n + 1)), **opts)
+        self._previous_pose, self._history, self._frame_number = current, image, n + 1
+        return image
+
+    def _shutter(self, model):
+        """The motion-blur pass over the frame just drawn, against the pose of the call before; keeps this call's pose."""
+        current = self._pose_copy(model)
         previous = self._previous_pose
         if previous is None or previous.shape[0] != current.shape[0]:
             previous = current         # a static pose: the frame, copied
@@ -567,8 +644,11 @@ class Renderer:
         return self.pixel_buffer_filler.motion_blur(previous, **self.motion_blur)
 
     def reset_motion(self):
-        """Forget the previous pose: the next ``render`` under ``motion_blur`` returns its frame unblurred (a camera cut)."""
+        """Forget the previous pose: the next ``render`` under ``motion_blur`` returns its frame unblurred (a camera cut).
+        Under ``temporal_aa`` the history is forgotten with it and the frames are counted from 0 again."""
         self._previous_pose = None
+        self._history = None
+        self._frame_number = 0
 
     def reset_buffers(self):
         pass   # a no-op in the reference too (renderer.py:51-52): renders composite

@@ -23,7 +23,7 @@ def main():
     args, extra = ap.parse_known_args()
     flags = [f for f in _build.HIPCC_FLAGS if f not in ("-shared", "-fPIC") and not f.startswith("-Wl,")]
     text = ""
-    for src in _build.library_sources():           # (chain.hip is host code: no kernels, no rows)
+    for src in _build.library_sources() + _build.pending_sources():    # (chain.hip is host code: no kernels, no rows)
         asm = args.asm + "." + os.path.splitext(src)[0]
         cmd = [_build._hipcc()] + flags + extra + ["--offload-device-only", "-S", "-o", asm, os.path.join(_build.SRC_DIR, src)]
         subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
